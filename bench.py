@@ -81,7 +81,39 @@ def parse():
                          "weak / strong split, the timing reduction and the JSON fields on a box without GPUs")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="per-launch HBM bytes from the PMC passes (tools/pmc_traffic.py)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (the fused image) as DIR/<name>.npy in "
+                         "float32: the whole array if it fits in 64 MB, else a fixed, seeded sample of its values")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: bytes written in all
+DUMP_SAMPLE = 4 << 20         # values kept of an output that does not fit (16 MB of float32)
+DUMP_SEED = 20250824
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (the 8- / 16-bit images are exact in it).  One that would
+    not fit in DUMP_MAX_BYTES is written as DIR/<name>_sample.npy: its values at DUMP_SAMPLE flat positions drawn with a
+    fixed seed from its shape alone, in increasing order -- the same positions on every run with the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    files, total = {}, 0
+    for name, a in arrays.items():
+        v = np.ascontiguousarray(a, dtype=np.float32)
+        entry = {"shape": list(v.shape), "dtype": str(np.asarray(a).dtype)}
+        if total + v.nbytes > DUMP_MAX_BYTES:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(v.size, min(DUMP_SAMPLE, v.size), replace=False))
+            v = v.ravel()[idx]
+            name += "_sample"
+            entry["sample"] = f"{v.size} of {a.size} values, flat positions from default_rng({DUMP_SEED}).choice, sorted"
+        assert total + v.nbytes <= DUMP_MAX_BYTES, "--dump-outputs: over the 64 MB budget"
+        np.save(os.path.join(dirname, name + ".npy"), v)
+        total += v.nbytes
+        files[name] = entry
+    return {"dir": os.path.abspath(dirname), "files": files, "bytes": total}
 
 
 def kernel_source_sha():
@@ -411,6 +443,8 @@ def dry_run(args, rank, world):
                 "roofline": None,
                 "breakdown_ms_per_step": {f"{k}_ms_host": v / args.steps * 1e3 for k, v in phase.items()},
                 "verified": bool(np.array_equal(out, whole.finish())), "dry_run": True}
+        if args.dump_outputs:
+            line["dump_outputs"] = dump_outputs(args.dump_outputs, {"fused": out})
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -657,7 +691,11 @@ def main():
             line["verified"] = v.pop("ok")
             line["verify"] = v
     do_other = world == 1 and not force_dist and not args.no_other_mode and args.source == "device"
-    fused_main = st.finish() if do_other and not args.no_verify else None   # outside the timed region
+    # outside the timed region: the fused image of the last timed step (finish re-runs the same collapse on the same state)
+    fused = st.finish() if rank == 0 and (args.dump_outputs or (do_other and not args.no_verify)) else None
+    fused_main = fused if do_other and not args.no_verify else None
+    if rank == 0 and args.dump_outputs:
+        line["dump_outputs"] = dump_outputs(args.dump_outputs, {"fused": fused})
     st.close()
     if do_other:
         other = "exact" if args.arith == "separable" else "separable"
