@@ -14,10 +14,15 @@ frames, 6 Laplacian levels + 63x94 base.
   --arith separable (default) north_star's LDS-staged 5-tap separable / polyphase form (MI_ARITH_SEPARABLE,
                     tolerance-tested against float64, bit-exact against oracle/separable_oracle.c);
   --arith exact     the reference-order 25-tap form, bit-identical to the oracle of the reference's own run.
-At N=1 the other mode is measured too (same K and W) and reported under "other_mode".
-After the timed region the last step's result is verified (outside the timing): level-0 arg-max against the
-generator's known band structure, and the level-0 state of a 128x128 corner against the CPU oracle fed the same
-frames cropped -> "verified".
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if given and prints its line: the headline and
+what the timed steps themselves recorded (roofline, breakdown).  Everything else runs only with --full, after the timed
+region:
+  the last step's result is verified: level-0 arg-max against the generator's known band structure, and levels 0-2 of
+  six 512x512 windows against the CPU oracle fed the same frames cropped -> "verified";
+  at N=1 the other mode is measured too (same K and W) and reported under "other_mode" (+ its parity report), the
+  same stack as the other input types under "other_dtypes", the PROJECTED 2 / 4 / 8-GPU lines and the measured shard
+  steps, and the CPU baseline.
+(--no-verify, --no-other-mode, ... switch single parts of a --full run off.  --dry-run always verifies: its stack is tiny.)
 
 One JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
 """
@@ -57,6 +62,10 @@ def parse():
     ap.add_argument("--source", default="device", choices=["device", "host", "host-pinned"],
                     help="host: frames are pushed from host memory one by one (PCIe-inclusive rate; "
                          "never the headline value)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also verify the result and take the side measurements (other arithmetic "
+                         "mode + parity, other input types, projected scaling + shard steps, CPU baseline); a plain run "
+                         "does only what the headline figure needs")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-other-mode", action="store_true", help="do not also measure the other arithmetic mode")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -87,6 +96,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run: every part after the timed region that the headline does not need is off
+        args.no_verify = args.no_other_mode = args.no_other_dtypes = args.no_projection = args.no_cpu_baseline = True
     return args
 
 

@@ -53,12 +53,50 @@ def test_dump_of_a_large_output_is_a_fixed_sample(tmp_path, monkeypatch):
     assert np.array_equal(s0, a.ravel()[idx].astype(np.float32))
 
 
+SIDE_PARTS = ("no_verify", "no_other_mode", "no_other_dtypes", "no_projection", "no_cpu_baseline")
+
+
+def test_plain_run_leaves_the_side_parts_to_full(monkeypatch):
+    """a plain run does only what the headline needs; --full switches every side part on, and --no-* still picks parts off"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and all(getattr(a, k) for k in SIDE_PARTS)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not any(getattr(a, k) for k in SIDE_PARTS)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.no_cpu_baseline and not any(getattr(a, k) for k in SIDE_PARTS if k != "no_cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline(tmp_path, oracle):
+    """without --full the line carries the headline and what the timed steps recorded, no side measurement; the dumped
+    image is the same one --full verifies"""
+    H, W, N = 600, 900, 8
+    d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", str(N), "--height", str(H), "--width", str(W),
+                "--dump-outputs", str(tmp_path)], 600)
+    assert d["metric"] == "Mpixels/s fused (pyramid build+select+collapse)" and d["unit"] == "Mpixels/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and abs(d["value"] - N * H * W / d["ms_per_step"] / 1e3) <= 1e-6 * d["value"]
+    assert d["roofline"]["launches"] > 0 and d["breakdown_ms_per_step"]
+    for k in ("verified", "verify", "other_mode", "other_dtypes", "projected_scaling", "shard_step", "cpu_baseline", "cv2"):
+        assert k not in d, k
+    got = np.load(tmp_path / "fused.npy")
+    so = oracle.StreamingOracle(H, W, np.uint8, arith="separable")
+    for f in range(N):
+        so.push_frame(oracle.synth_frame_numpy(H, W, f, N))
+    assert np.array_equal(got, so.finish().astype(np.float32))
+
+
 @pytest.mark.gpu
 def test_bench_dump_on_gpu_equals_the_oracle(tmp_path, oracle):
     """the timed path's own result (separable arithmetic, float-32 frames resident in HBM) == its CPU oracle"""
     H, W, N = 600, 900, 8
-    d = _bench(["--steps", "2", "--warmup", "1", "--frames", str(N), "--height", str(H), "--width", str(W), "--no-other-mode",
-                "--no-cpu-baseline", "--no-projection", "--no-other-dtypes", "--dump-outputs", str(tmp_path)], 600)
+    d = _bench(["--full", "--steps", "2", "--warmup", "1", "--frames", str(N), "--height", str(H), "--width", str(W),
+                "--no-other-mode", "--no-cpu-baseline", "--no-projection", "--no-other-dtypes", "--dump-outputs", str(tmp_path)], 600)
     assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["verified"] is True
     got = np.load(tmp_path / "fused.npy")
     so = oracle.StreamingOracle(H, W, np.uint8, arith="separable")

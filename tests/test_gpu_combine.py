@@ -228,7 +228,7 @@ def test_bench_flow_with_two_ranks_on_one_gpu(scaling):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MI_BENCH_ONE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--frames", "8", "--height", "600",
-                        "--width", "900", "--steps", "1", "--warmup", "1", "--scaling", scaling, "--no-cpu-baseline"],
+                        "--width", "900", "--steps", "1", "--warmup", "1", "--scaling", scaling, "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=root)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert lines, r.stdout[-2000:] + r.stderr[-3000:]

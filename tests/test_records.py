@@ -36,7 +36,7 @@ def test_round_profiles_are_tracked():
 
 def test_cpu_baseline_leg_runs_for_every_input_type():
     """bench.py's cpu_baseline on a tiny sample (CPU only): the streaming port on the GPU leg's own frame type (float-32 frames are
-    level 0 as they are), the reference-shaped leg on the integer frames the reference reads -- the default line must not
+    level 0 as they are), the reference-shaped leg on the integer frames the reference reads -- the --full line must not
     die in its side measurements"""
     import types
     import bench

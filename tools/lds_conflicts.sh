@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 for ab in 0 1 4 8 13; do
   out=gpurun_out/lds_$ab
-  MI_ABLATE=$((ab+256)) rocprofv3 --kernel-trace --output-format csv --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS -d $out -o pmc -- python bench.py --frames 32 --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
+  MI_ABLATE=$((ab+256)) rocprofv3 --kernel-trace --output-format csv --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS -d $out -o pmc -- python bench.py --full --frames 32 --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
   python - "$out" "$ab" <<'PY'
 import csv,glob,sys,collections
 d=collections.defaultdict(list)
