@@ -30,7 +30,8 @@ def test_config2_256_frames_24mp_fp32(L, oracle, arith):
     combination -- exact: 8 batches with double-buffered Gaussians and the tapered tail; separable: one batch, level
     after level, launches of 16 frames and frame chunks -- verified exactly as bench.py verifies its last step (band
     structure of the level-0 arg-max; level-0 energy / arg-max / fused Laplacian of the top-left corner == oracle on
-    the cropped frames)."""
+    the cropped frames) and then whole: every tap of every level, the base level and the final image == the streaming
+    oracle over the 256 full frames; the separable run proves from the profiler that the automatic level pair ran."""
     if ROOT not in sys.path:
         sys.path.insert(0, ROOT)
     import bench
@@ -38,8 +39,10 @@ def test_config2_256_frames_24mp_fp32(L, oracle, arith):
     per = H * W * 3 * 4
     buf = L.DeviceBuffer(per * N)
     L.synth_frames_device(buf.ptr, np.float32, H, W, 0, N, N)
-    st = L.Stack(H, W, in_dtype=np.float32, out_dtype=np.uint8, arith=arith)
+    st = L.Stack(H, W, in_dtype=np.float32, out_dtype=np.uint8, arith=arith, pair_levels=0)
     assert st.levels == 6 and st.shapes[-1] == (63, 94)
+    if arith == "separable":
+        st.profile()
     st.push_frames_device(buf.ptr, N)
     out = st.finish()
     args = types.SimpleNamespace(height=H, width=W, dtype="f32", arith=arith)
@@ -50,9 +53,29 @@ def test_config2_256_frames_24mp_fp32(L, oracle, arith):
     assert all(sorted(c["levels"]) == ["0", "1", "2"] for c in v["crops"]), v
     # the fused image: every frame is sharp in its own band around the same 64..191 ramp, so the result stays in range
     assert out.shape == (H, W, 3) and out.dtype == np.uint8 and 40 < out.mean() < 215
+    buf.free()
+    if arith == "separable":   # one batch of 256 frames, levels (0, 1) as the automatic pair (tests/test_gpu_auto_pair.py)
+        from test_gpu_auto_pair import assert_plan
+        assert_plan(L, st, [(N, True)])
+    # ... and the whole stack against the oracle: every level, the base twins, the fused base, the last frame's Gaussians, the
+    # collapsed and the final image (the streaming oracle holds one frame's pyramid and the running state: ~2 GB)
+    so = oracle.StreamingOracle(H, W, np.uint8, arith=arith, keep_gauss=False)
+    for f in range(N):
+        frame = oracle.synth_frame_u8(H, W, f, N)
+        so.push_frame(frame)
+    for lv in range(st.levels):
+        assert np.array_equal(st.tap(L.TAP_ENERGY, lv), so.best_e[lv]), f"energy {lv}"
+        assert np.array_equal(st.tap(L.TAP_INDEX, lv), so.best_idx[lv]), f"index {lv}"
+        assert np.array_equal(st.tap(L.TAP_FUSED_LAP, lv), so.best_lap[lv]), f"lap {lv}"
+    assert np.array_equal(st.tap(L.TAP_BASE_IDX_E), so.idx_e) and np.array_equal(st.tap(L.TAP_BASE_IDX_D), so.idx_d)
+    assert np.array_equal(st.tap(L.TAP_FUSED_BASE), so.fused_base())
+    for lv, g in enumerate(so.gaussians(frame)):
+        if lv >= 1:
+            assert np.array_equal(st.tap(L.TAP_GAUSS, lv), g), f"gauss {lv}"
+    assert np.array_equal(st.tap(L.TAP_COLLAPSED), np.clip(np.abs(so.collapse()), 0, 255))
+    assert np.array_equal(out, so.finish())
     _FUSED[arith] = out
     st.close()
-    buf.free()
 
 
 def test_config2_parity_report_between_the_arithmetics_at_full_size(L):

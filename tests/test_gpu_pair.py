@@ -4,7 +4,8 @@ recompute the winners' G_{l+1}; the three-channel G_{l+1} of the batch never rea
 dependency of algorithms/pyramid.py:27-46, :125-139).  A pair must give the SAME BITS as the level-by-level kernels, i.e. equal
 oracle/separable_oracle.c on every tap: the cases of tests/test_gpu_separable.py with the pair plans forced (pair_levels = 1:
 (0, 1), (2, 3), ...; 3: (1, 2), (3, 4), ... -- small test stacks stay below the automatic plan's threshold), frame chunks, batch
-boundaries, the automatic choice, the kept-frame tap, and the tile-by-tile payload pass."""
+boundaries, the kept-frame tap, and the tile-by-tile payload pass.  The stacks here are too short for the automatic plan
+(pair_levels = 0) to pair anything: tests/test_gpu_auto_pair.py covers it."""
 import numpy as np
 import pytest
 
@@ -67,7 +68,8 @@ def test_pair_sizes_and_types(L, oracle, dt, h, w, pl):
 @pytest.mark.parametrize("dt", [np.uint8, np.float32])
 def test_pair_frame_chunks(L, oracle, dt):
     """small frames, long resident pushes: both levels of the pair run in frame chunks whose partial maxima the pair's payload
-    passes fold; duplicates in different chunks and pushes; the automatic choice (50 and 20 frames: pair, then not)"""
+    passes fold; duplicates in different chunks and pushes.  (pl = 0: pushes of 50 and 20 frames are below the automatic
+    plan's threshold -- both run unpaired, as pl = 2 would.)"""
     h, w, n = 133, 201, 70
     rng = np.random.default_rng(5)
     frames = [rng.integers(0, 256, (h, w, 3)).astype(np.uint8) for _ in range(n)]

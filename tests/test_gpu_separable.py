@@ -22,16 +22,25 @@ def run_oracle(oracle, frames, **kw):
     return so, gs
 
 
-def compare(L, st, so, last_gauss=None):
+def compare(L, st, so, last_gauss=None, index=lambda i: i, base=False):
+    """every tap of `st` == the oracle `so`: each level's energy / arg-max / fused Laplacian, the last frame's Gaussians
+    (`last_gauss`, when given), the collapsed and the final image; `base`: also the base level's two arg-max twins and the
+    fused base.
+    `index`: the global frame number of the oracle's k-th frame (interleaved shards: set_first_index(r, W) -> r + W * k)."""
     for lv in range(st.levels):
         assert np.array_equal(st.tap(L.TAP_ENERGY, lv), so.best_e[lv]), f"energy {lv}"
-        assert np.array_equal(st.tap(L.TAP_INDEX, lv), so.best_idx[lv]), f"index {lv}"
+        assert np.array_equal(st.tap(L.TAP_INDEX, lv), index(so.best_idx[lv])), f"index {lv}"
         assert np.array_equal(st.tap(L.TAP_FUSED_LAP, lv), so.best_lap[lv]), f"lap {lv}"
+    if base:
+        assert np.array_equal(st.tap(L.TAP_BASE_IDX_E), index(so.idx_e)), "base index (entropy)"
+        assert np.array_equal(st.tap(L.TAP_BASE_IDX_D), index(so.idx_d)), "base index (deviation)"
     if last_gauss is not None:
         for lv in range(1, st.levels + 1):
             assert np.array_equal(st.tap(L.TAP_GAUSS, lv), last_gauss[lv]), f"gauss {lv}"
     want = so.finish()
     got = st.finish()
+    if base:
+        assert np.array_equal(st.tap(L.TAP_FUSED_BASE), so.fused_base()), "fused base"
     assert np.array_equal(st.tap(L.TAP_COLLAPSED), np.clip(np.abs(so.collapse()), 0, 255 if got.dtype == np.uint8 else 65535))
     assert got.dtype == want.dtype and np.array_equal(got, want)
 
