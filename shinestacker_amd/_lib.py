@@ -11,7 +11,7 @@ import numpy as np
 from .errors import DeviceError, InvalidOptionError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# MI355STACK_LIB: another build of the same library (tools/study_build.sh puts its -DMI_STUDY variant there)
+# MI355STACK_LIB: another build of the same library (tools/variants_build.sh puts its variants there)
 LIB_PATH = os.environ.get("MI355STACK_LIB") or os.path.join(_HERE, "csrc", "libmi355stack.so")
 
 # enums of mi355stack.h

@@ -74,7 +74,6 @@ struct mi_stack {
     K25 K{};
     float k1d[3] = {0.f, 0.f, 0.f};   // MI_ARITH_SEPARABLE: float32 of the 1-D generating kernel (k0, k1, k2)
     float rk[4] = {0.f, 0.f, 0.f, 1.f};   // MI_ARITH_SEPARABLE, reduce: taps (w0, w1, w2) and final scale (red_taps)
-    bool mfma_ok = false;             // integer taps small enough for the MFMA form of the level-0 reduce
     bool sep = false;         // p.arith == MI_ARITH_SEPARABLE
     K25d Kd{};                // float-64 mode: the float64 generating kernel (np.outer, pyramid.py:21)
     bool f64 = false;         // float_type == MI_F64: float buffers below hold doubles (allocated twice as large)
@@ -1047,14 +1046,12 @@ int aligner_solve(mi_aligner* al, hipStream_t st, int n, int max_iters, double e
         // sample every `step`-th pixel in both directions: a third of a million samples and more are plenty for 4 parameters
         // (6 MP level: step 4 = 375 K samples, 1.5 MP level: step 2; rounds 3-4 kept half a million -- 667 K and all 1.5 M --:
         // the recovered transforms of config 4 stay ten times inside the tolerances either way, profiles/r05)
-        static const int ecc_step = study_env("MI_ECC_STEP", 0);   // -DMI_STUDY: force a step
-        int step = ecc_sample_step(np);
-        if (ecc_step > 0) step = ecc_step;
+        const int step = ecc_sample_step(np);
         // ~48 samples per thread (the 28 double sums cost a thread ~500 instructions to reduce, as much as 5 samples),
         // at most ECC_MAX_BLOCKS blocks (4 per CU).  Measured (round 3, config 4 / the estimate of a 16-frame batch alone):
         // 3072 -> 0.054 s / 6.6 ms, 6144 -> 0.047 / 5.5, 12288 -> 0.042 / 5.5, 24576 -> 0.041 / 6.7: fewer, longer
         // workgroups leave more of the GPU to the warps and the fuse that run beside the estimate
-        static const size_t per_blk = (size_t)study_env("MI_ECC_PER_BLOCK", 12288);   // study knob
+        constexpr size_t per_blk = 12288;
         const size_t work = (np / ((size_t)step * step) + per_blk - 1) / per_blk;
         const unsigned nblk = (unsigned)(work < 1 ? 1 : (work > (size_t)ECC_MAX_BLOCKS ? ECC_MAX_BLOCKS : work));
         hipLaunchKernelGGL(ecc_level_begin, dim3(cdiv(n, 64)), dim3(64), 0, st, al->dstate, n, cx, cy);
@@ -1384,7 +1381,7 @@ int mi_stack_create(mi_stack_t** out, const mi_stack_params_t* params) {
             }
         for (int i = 0; i < 3; ++i) s->k1d[i] = (float)k[i];
         s->sep = p.arith == MI_ARITH_SEPARABLE;
-        s->mfma_ok = red_taps(a, s->rk);
+        red_taps(a, s->rk);
     }
     s->pad = (p.kernel_size - 1) / 2;
     s->nlevels_hist = p.out_dtype == MI_U8 ? 256 : 65536;

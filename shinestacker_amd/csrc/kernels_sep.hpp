@@ -11,8 +11,8 @@
 //            when 20 k is integral -- the reference's default 0.4 gives (1, 5, 8) -- the taps are those INTEGERS and
 //            rs = float32(1 / 400): every product and every partial sum of integer-valued input (8 / 16-bit frames, fp32
 //            frames holding such values) is exact, the one rounding of the sum is that of the exact integer sum S, and
-//            G_{l+1} = fl(fl(S) * rs) -- two roundings instead of ten, and an integer pipeline (level_sep's MFMA form for
-//            8-bit frames) reproduces it bit for bit.  Otherwise (w0, w1, w2) = float32(k) and rs = 1 (round 5).
+//            G_{l+1} = fl(fl(S) * rs) -- two roundings instead of ten, and an integer pipeline (a matrix-pipe form for
+//            8-bit frames, measured and retired in round 5) reproduces it bit for bit.  Otherwise (w0, w1, w2) = float32(k) and rs = 1 (round 5).
 //   expand   X = along the rows:  even column  fma(2k0, N[j-1] + N[j+1], 2k2 * N[j]),  odd  2k1 * (N[j] + N[j+1])
 //            then the same down the rows (the zero-stuffed grid's zero taps skipped)           (pyramid.py:34-46)
 //   lap      G_l - expand(G_{l+1})                                                             (pyramid.py:133-138)
@@ -49,9 +49,6 @@ namespace mi {
 #endif
 // threads per workgroup for fp32 input (all levels >= 1 and fp32 frames): 512 = one quad per lane; 576 adds a ninth wave so
 // that the 18 x 32 items of P2 fit one round (with 512 the last two rows are a second round on wave 0 alone)
-#ifndef MI_SEP_PF_SPLIT
-#define MI_SEP_PF_SPLIT 0
-#endif
 #ifndef MI_SEP_NT_F32
 #define MI_SEP_NT_F32 ((MI_SEP_TH / 2 + 2) * 32)
 #endif
@@ -64,23 +61,10 @@ template <typename TIn> constexpr int sep_nt() { return sizeof(TIn) == 4 ? MI_SE
 #define MI_SEP_NT_STORE 1
 #endif
 
-// fp32 interior tiles: stage the G_l patch by LDS-DMA (`buffer_load_dwordx4 ... lds`: HBM -> LDS without a VGPR round trip,
-// 1 KB per wave instruction) instead of prefetching into registers and writing them out.  The lane's quad takes its gray
-// of G_l in P1 (registers), so the staged patch is dead after P1 and the next frame's DMA runs beside P2-P4.
-// Bit-identical (all parity tests pass with it), 60 instead of 73 VGPRs -- and NOT faster: interleaved A/B on three boxes
-// gave +1.0 %, -1.1 %, -1.4 % on the job (docs/studies.md, round 4): the kernel moves its bytes at the fabric's rate
-// either way.  Off by default; -DMI_SEP_DMA=1 builds it.
-// study knobs for the 8 / 16-bit instantiations (VALU-bound): waves per SIMD the compiler must leave room for (8 = 64
-// VGPRs, 4 workgroups per CU; 6 = 85 VGPRs, 3 workgroups) and whether the per-frame addresses are laundered (rebuilt every
-// frame) or may be hoisted into registers
+// study knob for the 8 / 16-bit instantiations (VALU-bound): waves per SIMD the compiler must leave room for (8 = 64
+// VGPRs, 4 workgroups per CU; 6 = 85 VGPRs, 3 workgroups)
 #ifndef MI_SEP_INT_WAVES
 #define MI_SEP_INT_WAVES 8
-#endif
-// MI_SEP_TOUCH n (study): touch one dword of every 128-byte line of the patch of frame b + n while frame b is worked on -- a
-// software prefetch into L2 / the Infinity Cache that costs one register, so that the real loads of that frame (issued
-// one frame ahead, 16 registers) find their lines on the way instead of in DRAM.  0 = off.
-#ifndef MI_SEP_TOUCH
-#define MI_SEP_TOUCH 0
 #endif
 // V rows a lane of P1 produces for 8 / 16-bit interior tiles (one float4 column group each): R rows read 2 R + 3 patch rows
 // -- 3.5 conversions and LDS reads per output at R = 2, 2.75 at 4, 2.5 at 6 -- on correspondingly fewer lanes (the integer
@@ -90,36 +74,9 @@ template <typename TIn> constexpr int sep_nt() { return sizeof(TIn) == 4 ? MI_SE
 #ifndef MI_SEP_P1_ROWS
 #define MI_SEP_P1_ROWS 4
 #endif
-#ifndef MI_SEP_LAUNDER
-#define MI_SEP_LAUNDER 1
-#endif
-// MF: interior tiles fetch their patch rows as 16-byte pieces (one / two loads per lane instead of four).  Measured slower
-// (u8 level-0 launch 0.854 -> 0.901 ms: the pieces start 2 bytes off a dword boundary); off.
-#ifndef MI_SEP_MF_WIDE
-#define MI_SEP_MF_WIDE 0
-#endif
-#ifndef MI_SEP_MF_LAUNDER
-#define MI_SEP_MF_LAUNDER 1
-#endif
-#ifndef MI_SEP_DMA
-#define MI_SEP_DMA 0
-#endif
-// Level 0 of 8-bit frames with integer reduce taps (red_taps: the default generating kernel): the 5 x 5 reduce as exact
-// integer arithmetic on the matrix pipe (v_mfma_i32_16x16x64_i8 on the staged bytes) instead of P1 + P2's VALU work -- see
-// level_sep_body, "MF".  Bit-identical to the VALU form (all of tests/test_gpu_separable.py and test_gpu_parity.py pass with
-// it) and NOT faster (round 5, docs/studies.md): 154 instead of 197 VALU instructions per wave and frame and one barrier
-// less, but more LDS bank conflicts, and the kernel is bound by the sum of its phases (ablating the matrix instructions
-// themselves changes nothing; the phase around them costs what P1 + P2 cost).  8-bit level-0 launch, interleaved A/B:
-// 0.833 ms (VALU form) vs 0.853 ms (tile height 28, wave 0 takes a ninth row pair) and 0.854 ms (tile height 24, 17 % more
-// workgroups; the VALU form at that height: 0.936 ms).  16-bit frames (two byte planes, ten matrix instructions per row
-// pair): 0.962 -> 1.154 ms, never dispatched.  Off; -DMI_SEP_MFMA=1 builds it.
-#ifndef MI_SEP_MFMA
-#define MI_SEP_MFMA 0
-#endif
-#ifndef MI_SEP_MF_TH
-#define MI_SEP_MF_TH 28
-#endif
-constexpr int SEP_MF_TH = MI_SEP_MF_TH, SEP_MF_NT = (MI_SEP_MF_TH / 2 + 2) * 32;
+// Measured and retired (docs/studies.md; the code is in the history): staging the fp32 patch by LDS-DMA (bit-identical,
+// not faster, round 4), the level-0 reduce of 8 / 16-bit frames on the matrix pipe (bit-identical, not faster, round 5),
+// an L2 "touch" prefetch a few frames ahead, splitting the next frame's loads over the phases, and 16-byte patch loads.
 
 // the pair's tile-by-tile payload pass walks at most this many distinct winners per tile (level_sep_body, "PL")
 constexpr int SEP_PL_MAXF = 32;
@@ -143,18 +100,12 @@ struct SepGeom {
     static constexpr int lds_floats(int esize, bool interior) {
         return (interior && esize <= 2 ? GH * (GD / 4) * esize : GH * GS) + NH * VS + NH * XS;
     }
-    // MF (integer reduce on the matrix pipe): the staged patch as BYTE PLANES at a 208-byte row pitch (52 dwords: the MFMA
-    // operand reads want 8-byte alignment) -- one plane for 8-bit frames, low bytes | high bytes for 16-bit frames --, then X,
-    // HB (its own array: V does not exist) and the three weight operands (64 lanes x 16 bytes each)
-    static constexpr int MF_CPR = 52, MF_PLANE = GH * MF_CPR;   // dwords
-    static constexpr int lds_floats_mf(int esize) { return esize * MF_PLANE + NH * XS + HBH * HBS + 3 * 64 * 4; }
     static_assert(GD % 4 == 0 && NW == 32, "tile width is fixed by the 32-lane quad rows");
     static_assert(QY * QL <= NT, "one quad per lane (a ninth wave, if any, only stages, reduces and carries P2 items)");
     static_assert(HBH * HBS <= NH * VS, "HB aliases V");
     static_assert((NH / 2) * (GD / 4) <= NT && NH % 2 == 0 && NT % 64 == 0, "phase items");
 };
 
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 struct __attribute__((packed, aligned(4))) Px3 { float v[3]; };   // one pixel: a 12-byte load / store
 
@@ -240,20 +191,6 @@ __device__ __forceinline__ v2f lds_load2s(const float* p) {
     return *(lds_ptr)(size_t)(uint32_t)(uintptr_t)p;                                 // generic LDS address: low 32 bits = offset
 }
 
-// ---- LDS-DMA (gfx950: 16 bytes per lane).  Inline assembly on purpose: with the builtin the compiler drains vmcnt at every
-// workgroup barrier behind it (it cannot tell which LDS reads the transfer feeds); here the kernel places the wait itself.
-__device__ __forceinline__ v4u make_rsrc_words(const void* base, uint32_t bytes) {   // raw buffer, as make_rsrc
-    const uint64_t ad = (uint64_t)(uintptr_t)base;
-    return v4u{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ad),
-               (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ad >> 32)) & 0xffffu, bytes, 0x00020000u};
-}
-// lane i of the wave: 16 bytes from buffer offset `voff` to LDS byte address lds_base + 16 i (lds_base wave-uniform)
-__device__ __forceinline__ void lds_dma16(v4u rsrc, uint32_t voff, uint32_t lds_base) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-                 :: "s"(lds_base), "v"(voff), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ void wait_vmem_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 // value of lane-1 / lane+1 across the wave; lanes without a source get 0
 __device__ __forceinline__ float dpp_wave_prev(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
@@ -280,10 +217,6 @@ template <> struct PreChunk<float> {
     static __device__ __forceinline__ v4f cvt_raw(raw_t) { return v4f{}; }
     static __device__ __forceinline__ v4f unpack_raw(const uint32_t*) { return v4f{}; }
     static __device__ __forceinline__ void unpack6(const uint32_t*, int, v2f*) {}
-    __device__ __forceinline__ void store_mf(uint32_t*, int) const {}
-    __device__ __forceinline__ void set_raw(v4u, int) {}
-    static __device__ __forceinline__ void store_mf16(const PreChunk*, uint32_t*, int) {}
-    static __device__ __forceinline__ void unpack6_mf(const uint32_t*, int, int, v2f*) {}
     __device__ __forceinline__ void load(const char* p) { __builtin_memcpy(&v, p, 16); }
     __device__ __forceinline__ void load(BufRsrc r, uint32_t off) {
         v = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
@@ -310,22 +243,6 @@ template <> struct PreChunk<uint8_t> {
         const uint32_t* q = row + (e0 >> 2);
         const uint32_t q0 = q[0], q1 = q[1];
         const uint32_t lo = __builtin_amdgcn_alignbyte(q1, q0, (uint32_t)e0), hi = __builtin_amdgcn_alignbyte(0u, q1, (uint32_t)e0);
-        out[0] = v2f{(float)(lo & 0xffu), (float)(lo >> 24)};
-        out[1] = v2f{(float)((lo >> 8) & 0xffu), (float)(hi & 0xffu)};
-        out[2] = v2f{(float)((lo >> 16) & 0xffu), (float)((hi >> 8) & 0xffu)};
-    }
-    // MF form: the chunk's dword in the (single) byte plane, every byte as x ^ 0x80 = the signed byte x - 128 the MFMA takes
-    __device__ __forceinline__ void store_mf(uint32_t* q, int) const { *q = v ^ 0x80808080u; }
-    __device__ __forceinline__ void set_raw(v4u t, int i) { v = t[i]; }   // dword i of a 16-byte piece
-    // four chunks = one 16-byte piece, one ds_write_b128
-    static __device__ __forceinline__ void store_mf16(const PreChunk* c, uint32_t* q, int) {
-        *reinterpret_cast<v4u*>(q) = v4u{c[0].v ^ 0x80808080u, c[1].v ^ 0x80808080u, c[2].v ^ 0x80808080u, c[3].v ^ 0x80808080u};
-    }
-    static __device__ __forceinline__ void unpack6_mf(const uint32_t* row, int, int e0, v2f* out) {
-        const uint32_t* q = row + (e0 >> 2);
-        const uint32_t q0 = q[0], q1 = q[1];
-        const uint32_t lo = __builtin_amdgcn_alignbyte(q1, q0, (uint32_t)e0) ^ 0x80808080u;
-        const uint32_t hi = __builtin_amdgcn_alignbyte(0u, q1, (uint32_t)e0) ^ 0x00008080u;
         out[0] = v2f{(float)(lo & 0xffu), (float)(lo >> 24)};
         out[1] = v2f{(float)((lo >> 8) & 0xffu), (float)(hi & 0xffu)};
         out[2] = v2f{(float)((lo >> 16) & 0xffu), (float)((hi >> 8) & 0xffu)};
@@ -360,33 +277,6 @@ template <> struct PreChunk<uint16_t> {
         out[1] = v2f{(float)(q0 >> 16), (float)(q2 & 0xffffu)};
         out[2] = v2f{(float)(q1 & 0xffffu), (float)(q2 >> 16)};
     }
-    // MF form: the four low bytes -> plane 0, the four high bytes -> plane 1 (`plane` dwords further), each as x ^ 0x80
-    __device__ __forceinline__ void store_mf(uint32_t* q, int plane) const {
-        q[0] = __builtin_amdgcn_perm(v1, v0, 0x06040200u) ^ 0x80808080u;
-        q[plane] = __builtin_amdgcn_perm(v1, v0, 0x07050301u) ^ 0x80808080u;
-    }
-    __device__ __forceinline__ void set_raw(v4u t, int i) { v0 = t[2 * i]; v1 = t[2 * i + 1]; }   // chunk i of a 16-byte piece
-    // two chunks = one 16-byte piece: 8 bytes into each plane
-    static __device__ __forceinline__ void store_mf16(const PreChunk* c, uint32_t* q, int plane) {
-        *reinterpret_cast<v2u*>(q) = v2u{__builtin_amdgcn_perm(c[0].v1, c[0].v0, 0x06040200u) ^ 0x80808080u,
-                                         __builtin_amdgcn_perm(c[1].v1, c[1].v0, 0x06040200u) ^ 0x80808080u};
-        *reinterpret_cast<v2u*>(q + plane) = v2u{__builtin_amdgcn_perm(c[0].v1, c[0].v0, 0x07050301u) ^ 0x80808080u,
-                                                 __builtin_amdgcn_perm(c[1].v1, c[1].v0, 0x07050301u) ^ 0x80808080u};
-    }
-    // six consecutive elements from the two byte planes: bytes realigned per plane, re-paired into 16-bit values
-    static __device__ __forceinline__ void unpack6_mf(const uint32_t* row, int plane, int e0, v2f* out) {
-        const uint32_t* q = row + (e0 >> 2);
-        const uint32_t l0 = q[0], l1 = q[1], h0 = q[plane], h1 = q[plane + 1];
-        const uint32_t La = __builtin_amdgcn_alignbyte(l1, l0, (uint32_t)e0) ^ 0x80808080u;
-        const uint32_t Lb = __builtin_amdgcn_alignbyte(0u, l1, (uint32_t)e0) ^ 0x00008080u;
-        const uint32_t Ha = __builtin_amdgcn_alignbyte(h1, h0, (uint32_t)e0) ^ 0x80808080u;
-        const uint32_t Hb = __builtin_amdgcn_alignbyte(0u, h1, (uint32_t)e0) ^ 0x00008080u;
-        const uint32_t p01 = __builtin_amdgcn_perm(Ha, La, 0x05010400u), p23 = __builtin_amdgcn_perm(Ha, La, 0x07030602u);
-        const uint32_t p45 = __builtin_amdgcn_perm(Hb, Lb, 0x05010400u);
-        out[0] = v2f{(float)(p01 & 0xffffu), (float)(p23 >> 16)};
-        out[1] = v2f{(float)(p01 >> 16), (float)(p45 & 0xffffu)};
-        out[2] = v2f{(float)(p23 & 0xffffu), (float)(p45 >> 16)};
-    }
     __device__ __forceinline__ void load(const char* p) {
         uint64_t t;
         __builtin_memcpy(&t, p, 8);
@@ -407,8 +297,6 @@ template <> struct PreChunk<uint16_t> {
         return v4f{(float)(v0 & 0xffffu), (float)(v0 >> 16), (float)(v1 & 0xffffu), (float)(v1 >> 16)};
     }
 };
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 // Which tile does this workgroup own?  (interior: 8x8-tile super-blocks, one per XCD at a time -- see kernels_tiled.hpp;
 // border: every tile of the TH x TW grid outside the interior rectangle.)  false: none.
@@ -465,13 +353,12 @@ __device__ __forceinline__ bool sep_tile_origin(const LevelArgs& a, int& y0, int
 }
 
 
-template <typename TIn, bool INTERIOR, int TH, int NT, bool MF_ = false, bool PAIR_ = false, bool PL_ = false>
+template <typename TIn, bool INTERIOR, int TH, int NT, bool PAIR_ = false, bool PL_ = false>
 __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
     using G = SepGeom<TH, NT>;
     constexpr int TW = G::TW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr bool RAW = INTERIOR && sizeof(TIn) <= 2;   // staged patch kept in the input type (see SepGeom::lds_floats)
-    constexpr bool DMA = MI_SEP_DMA && INTERIOR && sizeof(TIn) == 4;   // patch staged by LDS-DMA (see MI_SEP_DMA)
     // PAIR (round 6): levels l and l + 1 as a pair.  The 18 x 32 patch of G_{l+1} this tile computes anyway is exactly the
     // support of the tile's 7 x 14 pixels of G_{l+2} (rows 2m - 2 .. 2m + 2 of the patch's 17 leading rows), and the energy
     // path of level l + 1 needs gray(G_{l+1}) only: the kernel keeps the three-channel patch in LDS (planar, sN -- where the
@@ -481,40 +368,26 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
     // gray(G_{l+1}) -- 4 bytes per pixel instead of 12 -- for level_sep_e.  G_{l+1} itself never reaches HBM (one frame per
     // launch excepted: LevelArgs::g1_keep, the debug tap); the payload passes recompute the winners' (sep_payload_pair).
     constexpr bool PAIR = PAIR_;
-    static_assert(!PAIR || (!MF_ && !DMA && TH % 4 == 0 && G::NH * G::NW * 3 <= G::GH * (G::GD / 4)), "PAIR geometry");
+    static_assert(!PAIR || (TH % 4 == 0 && G::NH * G::NW * 3 <= G::GH * (G::GD / 4)), "PAIR geometry");
     // PL (round 6): the PAYLOAD pass of a pair, tile by tile.  The workgroup collects the distinct winners of its tile (level
     // l: the tile's pixels; level l + 1: the tile's 14 x 28 pixels of it) -- at most SEP_PL_MAXF, else the tile is flagged and
     // left to the per-quad kernels (sep_payload_pair0 / 1) -- and walks THOSE frames: P0 - P2 as ever give the frame's
     // G_{l+1} patch (sN), from which the lanes fill in lap_l = G_l - expand(G_{l+1}) of the pixels that frame won and
     // lap_{l+1} = G_{l+1} - expand(G_{l+2}) likewise.  A tile whose pixels have one winner costs one tile-frame of P0 - P2.
     constexpr bool PL = PL_;
-    static_assert(!PL || (!PAIR && !MF_ && !DMA), "PL geometry");
+    static_assert(!PL || !PAIR, "PL geometry");
     constexpr int N2H = TH / 4, N2W = TW / 4, NPL1 = G::NH * G::NW;   // G_{l+2} pixels of the tile; floats per plane of sN
     // fp32 interior tiles: the G_{l+1} patch goes where the staged G_l patch was, whose last reader -- the gray of the lane's quad
     // of G_l -- moves from P3 to P1 (registers).  8 / 16-bit tiles keep that gray in P3 (their P1 runs on half the waves: it is
     // the critical path of its phase) and give the patch its own LDS (8-bit: 34.4 KB, still four workgroups per CU).
     constexpr bool SN_ALIAS = PAIR && INTERIOR && sizeof(TIn) == 4;
-    constexpr bool GQ1 = DMA || SN_ALIAS;   // gray of the lane's quad of G_l taken in P1 (registers)
+    constexpr bool GQ1 = SN_ALIAS;   // gray of the lane's quad of G_l taken in P1 (registers)
     constexpr int RD = (int)sizeof(TIn);                 // dwords per 4-element chunk in that form
-    // MF: the reduce of 8 / 16-bit frames on the matrix pipe.  P1 + P2 become one phase: wave v computes the G_{l+1} patch
-    // rows 2v, 2v + 1 (16 rows = 8 waves) with five v_mfma_i32_16x16x64_i8 per byte plane -- one per tap row -- whose DATA
-    // operand (B, 64 x 16) is read straight from the staged bytes: column n = a 64-byte window of a patch row, 24 bytes (four
-    // output pixels) further along the row per window, 8 windows per row, two rows; and whose WEIGHT operand (A, 16 x 64)
-    // holds kv[t] * kh[tau] at byte 6 p + 3 tau + c of the window in row 4 p + c (output pixel p of the window, channel c;
-    // row 4 p + 3 is empty).  The result layout then hands lane 16 p + n the three channel sums of ONE G_{l+1} pixel.  The
-    // staged bytes carry x ^ 0x80 (= x - 128 as the signed byte the instruction takes) and the accumulator starts at
-    // 128 * 400.  16-bit frames: the same on the plane of low bytes and on the plane of high bytes, S = 256 S_hi + S_lo.
-    // S is the exact integer sum and G_{l+1} = float(S) * rs: bit-identical to the float evaluation of red_taps' integer
-    // taps (header; float(S) rounds once, to nearest even, exactly where the float chain's last fma does).
-    static_assert(!MF_ || (INTERIOR && sizeof(TIn) <= 2 && G::NH % 2 == 0 && NT % 64 == 0), "MF geometry");
-    constexpr bool MF = MF_;
-    constexpr int NPL = MF ? (int)sizeof(TIn) : 0;    // byte planes
     float* sG = smem;
     uint32_t* sGr = reinterpret_cast<uint32_t*>(smem);
-    float* sV = smem + (MF ? 0 : G::lds_floats((int)sizeof(TIn), INTERIOR) - G::NH * G::VS - G::NH * G::XS);
-    float* sX = MF ? smem + NPL * G::MF_PLANE : sV + G::NH * G::VS;
-    float* sHB = MF ? sX + G::NH * G::XS : sV;         // (not MF: V is dead once P2 has read it)
-    uint32_t* sW = reinterpret_cast<uint32_t*>(sHB + G::HBH * G::HBS);   // MF: weight operands, [3][64] x 16 bytes
+    float* sV = smem + (G::lds_floats((int)sizeof(TIn), INTERIOR) - G::NH * G::VS - G::NH * G::XS);
+    float* sX = sV + G::NH * G::VS;
+    float* sHB = sV;         // (V is dead once P2 has read it)
     // PAIR: G_{l+1} patch, [3][NH][NW] (interior tiles: over the dead G_l patch; border tiles and PL: their own array)
     float* sN = (SN_ALIAS || (PL && INTERIOR)) ? smem : smem + (INTERIOR ? G::lds_floats((int)sizeof(TIn), true) : G::LDS_FLOATS);
     // PL: [0..7] winner bit map, [8] count, [16..] frame list -- behind everything else (interior tiles: the patch is over G_l's)
@@ -530,27 +403,6 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
     const float k0 = a.k1d[0], k1 = a.k1d[1], k2 = a.k1d[2];
     const float w0 = a.rk[0], w1 = a.rk[1], w2 = a.rk[2], rs = a.rk[3];   // reduce taps and final scale (red_taps)
     const float ce = 2.0f * k0, cc = 2.0f * k2, co = 2.0f * k1;   // expand taps (the reference's 4 * K, per dimension)
-    if constexpr (MF) {
-        // weight operands: class 0 = tap rows 0 and 4 (kv = w0), 1 = rows 1 and 3 (w1), 2 = row 2 (w2); lane (row s = lane & 15,
-        // k-group g = lane >> 4) holds the bytes k = 16 g .. 16 g + 15 of row s.  Visible after the first frame's barrier.
-        if (tid < 192) {
-            const int cls = tid >> 6, ln = tid & 63, sl = ln & 15, kg = ln >> 4, p = sl >> 2, c = sl & 3;
-            const int wi[3] = {(int)w0, (int)w1, (int)w2};
-            const int kv = wi[cls];
-            uint32_t wd[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int d = 16 * kg + i - 6 * p - c;
-                int wt = 0;
-#pragma unroll
-                for (int tau = 0; tau < 5; ++tau)
-                    if (c < 3 && d == 3 * tau) wt = kv * wi[tau < 3 ? tau : 4 - tau];
-                wd[i >> 2] |= (uint32_t)(wt & 0xff) << (8 * (i & 3));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) sW[4 * tid + i] = wd[i];
-        }
-    }
 
     // ---- which frames?  (levels with few tiles split the batch into chunks along blockIdx.y, see LevelArgs)
     const int ck = blockIdx.y, f_lo = ck * a.chunk_frames;
@@ -649,10 +501,8 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
     // inside LDS after the staging barrier (6 columns per side; edge tiles pay one more barrier per frame).  Patch rows
     // start 2 elements off the 4-element chunk grid of an image row, so the chunk that straddles an image edge holds 2
     // in-image elements: it is loaded 2 elements further inside the row and stored rotated by 2.
-    constexpr int CPR = MF ? G::MF_CPR : G::GD / 4;   // chunks per patch row (MF: one more, for a 208-byte LDS row pitch)
+    constexpr int CPR = G::GD / 4;   // chunks per patch row
     constexpr int NCH = G::GH * CPR, NPRE = (NCH + NT - 1) / NT;
-    constexpr int W16 = 13 * (int)sizeof(TIn), NW16 = G::GH * W16, NPW = (NW16 + NT - 1) / NT;   // MF: 16-byte pieces (row, patch, per lane)
-    constexpr int CP16 = 4 / (int)sizeof(TIn);                                                     // chunks per piece
     PreChunk<TIn> pre[NPRE];
     uint32_t goff[NPRE];          // interior / edge: byte offset of the chunk inside a frame
     bool edge = false;
@@ -665,15 +515,6 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
             if (x0 < 6) colL = 4;                          // elements 16 .. 19: columns -1 | 0
             if (rel < G::GD) { peR = w - 1 - (x0 - 6); if ((rel & 3) == 2) colR = (rel - 2) >> 2; }
         }
-        if (MF && MI_SEP_MF_WIDE && !edge) {
-            // MF, tiles that mirror nothing: the patch row as 16-byte pieces (four / two chunks), one / two loads per lane
-            // instead of four (the 208-byte row pitch makes the pieces 16-byte aligned in LDS)
-#pragma unroll
-            for (int m = 0; m < NPW; ++m) {
-                const int id = tid + m * NT, row = id / W16, c16 = id - row * W16;
-                goff[m] = (uint32_t)(((y0 - 6 + row) * w + (x0 - 6)) * 3 * (int)sizeof(TIn) + 16 * c16);
-            }
-        } else
 #pragma unroll
         for (int n = 0; n < NPRE; ++n) {
             const int id = tid + n * NT, row = id / CPR, col = id - row * CPR;
@@ -692,26 +533,12 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
     // outside its image)?  Uniform per workgroup; the tiles that do not take the unmapped fast paths of V2 / H2.
     const bool e2 = !INTERIOR || y0 < 4 || x0 < 4 || y0 / 2 + TH / 2 >= hn || x0 / 2 + TW / 2 >= wn;
     const uint32_t frame_bytes = (uint32_t)h * (uint32_t)w * 3u * (uint32_t)sizeof(TIn);
-    // chunks [n0, n1) of frame b
-    auto prefetch = [&](int b, int n0, int n1) {
+    // all chunks of frame b
+    auto prefetch = [&](int b) {
         const char* frb = src0 + (size_t)fid(b) * a.src_stride;
         const BufRsrc rs = make_rsrc(frb, frame_bytes);
-        if constexpr (MF) {
-            if (MI_SEP_MF_WIDE && !edge) {
-#pragma unroll
-                for (int m = 0; m < NPW; ++m) {
-                    if ((m + 1) * NT > NW16 && tid + m * NT >= NW16) continue;
-                    const v4u t = __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rs, goff[m], 0, 0));
-                    pre[CP16 * m].set_raw(t, 0);
-                    if constexpr (CP16 >= 2) pre[CP16 * m + 1].set_raw(t, 1);
-                    if constexpr (CP16 == 4) { pre[4 * m + 2].set_raw(t, 2); pre[4 * m + 3].set_raw(t, 3); }
-                }
-                return;
-            }
-        }
 #pragma unroll
         for (int n = 0; n < NPRE; ++n) {
-            if (n < n0 || n >= n1) continue;
             const int id = tid + n * NT;
             if ((n + 1) * NT > NCH && id >= NCH) continue;
             if constexpr (INTERIOR) {
@@ -735,65 +562,14 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
             }
         }
     };
-    // LDS-DMA form of the same: chunk id = tid + n * NT lands at sG + 4 * id, i.e. wave-uniform base + 16 * lane
-    const uint32_t dma_base = (uint32_t)(uintptr_t)sG + 1024u * (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
-    auto dma_issue = [&](int b) {
-        if constexpr (DMA) {
-            const v4u rs = make_rsrc_words(src0 + (size_t)b * a.src_stride, frame_bytes);
-#pragma unroll
-            for (int n = 0; n < NPRE; ++n) {
-                if ((n + 1) * NT > NCH && tid + n * NT >= NCH) continue;
-                lds_dma16(rs, goff[n], dma_base + 16u * (uint32_t)(n * NT));
-            }
-        }
-    };
-    if constexpr (DMA) dma_issue(0);
-    else prefetch(0, 0, NPRE);
-    constexpr bool TOUCH = MI_SEP_TOUCH > 0 && INTERIOR && !DMA;
-    constexpr int TOUCH_PER_ROW = (G::GD * (int)sizeof(TIn) + 127) / 128 + 1;   // lines a patch row can straddle
-    uint32_t touch_off = 0, touch_val = 0, touch_acc = 0;
-    const bool touch_on = TOUCH && !edge && tid < G::GH * TOUCH_PER_ROW;
-    if (touch_on) {
-        const int row = tid / TOUCH_PER_ROW, j = tid - row * TOUCH_PER_ROW;
-        touch_off = (uint32_t)(((y0 - 6 + row) * w + (x0 - 6)) * 3) * (uint32_t)sizeof(TIn) +
-                    (uint32_t)min(128 * j, G::GD * (int)sizeof(TIn) - 4);
-        touch_off &= ~3u;
-    }
-    v2f gq_e = {0.f, 0.f}, gq_o = {0.f, 0.f};   // DMA: gray of the lane's quad (rows 2qy+4, +5 of the patch), taken in P1
-#ifdef MI_PHASE_CLOCK
-    unsigned int pc_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pc_last = (unsigned int)clock64();
-#endif
+    prefetch(0);
+    v2f gq_e = {0.f, 0.f}, gq_o = {0.f, 0.f};   // GQ1: gray of the lane's quad (rows 2qy+4, +5 of the patch), taken in P1
 
     for (int b = 0; b < nfr; ++b) {
         int lt = tid;
-#if MI_SEP_LAUNDER
-        if (!MF || MI_SEP_MF_LAUNDER) asm volatile("" : "+v"(lt));   // per-frame addresses are rebuilt from this, not hoisted out of the loop
-#endif
+        asm volatile("" : "+v"(lt));   // per-frame addresses are rebuilt from this, not hoisted out of the loop
         // ---------------- P0: stage
-        if constexpr (DMA) {
-            wait_vmem_all();   // this wave's share of the patch has landed (and the previous frame's G_{l+1} stores)
-            if (edge) {
-                // the chunk that straddles an image edge was fetched 2 elements further in: rotate it in place, then the
-                // mirrored columns as below
-#pragma unroll
-                for (int n = 0; n < NPRE; ++n) {
-                    const int id = lt + n * NT;
-                    if ((n + 1) * NT > NCH && id >= NCH) continue;
-                    const int col = id - (id / CPR) * CPR;
-                    if (col == colL || col == colR) {
-                        const v4f c = lds_load4(sG + 4 * id);
-                        lds_store4(sG + 4 * id, c.z, c.w, c.x, c.y);
-                    }
-                }
-                __syncthreads();
-                for (int e = lt; e < G::GH * 18; e += NT) {
-                    const int r = e / 18, k = e - r * 18, pc = k / 3, c = k - pc * 3;
-                    float* rowp = sG + mul24(r, G::GS);
-                    if (colL >= 0) rowp[3 * pc + c] = rowp[3 * (12 - pc) + c];
-                    if (peR >= 0 && peR + 1 + pc < G::GW) rowp[3 * (peR + 1 + pc) + c] = rowp[3 * (peR - 1 - pc) + c];
-                }
-            }
-        } else if (INTERIOR && edge) {
+        if (INTERIOR && edge) {
 #pragma unroll
             for (int n = 0; n < NPRE; ++n) {
                 const int id = lt + n * NT;
@@ -801,22 +577,14 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
                 const int col = id - (id / CPR) * CPR;
                 PreChunk<TIn> c = pre[n];
                 if (col == colL || col == colR) c.rot2();
-                if constexpr (MF) c.store_mf(sGr + id, G::MF_PLANE);
-                else if constexpr (RAW) c.store_raw(sGr + RD * id);
+                if constexpr (RAW) c.store_raw(sGr + RD * id);
                 else *reinterpret_cast<v4f*>(sG + 4 * id) = c.get();
             }
             __syncthreads();
             // mirrored columns: patch column pc <- 12 - pc on the left, pc <- 2 peR - pc on the right (6 columns each)
             for (int e = lt; e < G::GH * 18; e += NT) {
                 const int r = e / 18, k = e - r * 18, pc = k / 3, c = k - pc * 3;
-                if constexpr (MF) {
-#pragma unroll
-                    for (int pl = 0; pl < NPL; ++pl) {   // byte planes: an element is one byte of each
-                        uint8_t* rowp = reinterpret_cast<uint8_t*>(sGr + pl * G::MF_PLANE) + mul24(r, 4 * CPR);
-                        if (colL >= 0) rowp[3 * pc + c] = rowp[3 * (12 - pc) + c];
-                        if (peR >= 0 && peR + 1 + pc < G::GW) rowp[3 * (peR + 1 + pc) + c] = rowp[3 * (peR - 1 - pc) + c];
-                    }
-                } else if constexpr (RAW) {
+                if constexpr (RAW) {
                     TIn* rowp = reinterpret_cast<TIn*>(sGr) + mul24(r, 4 * CPR);   // a raw row = CPR chunks of 4 elements
                     if (colL >= 0) rowp[3 * pc + c] = rowp[3 * (12 - pc) + c];
                     if (peR >= 0 && peR + 1 + pc < G::GW) rowp[3 * (peR + 1 + pc) + c] = rowp[3 * (peR - 1 - pc) + c];
@@ -826,47 +594,27 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
                     if (peR >= 0 && peR + 1 + pc < G::GW) rowp[3 * (peR + 1 + pc) + c] = rowp[3 * (peR - 1 - pc) + c];
                 }
             }
-        } else if (MF && MI_SEP_MF_WIDE && !edge) {
-#pragma unroll
-            for (int m = 0; m < NPW; ++m) {
-                const int id = lt + m * NT;
-                if ((m + 1) * NT > NW16 && id >= NW16) continue;
-                PreChunk<TIn>::store_mf16(pre + CP16 * m, sGr + CP16 * id, G::MF_PLANE);   // piece id = chunks CP16 id ..
-            }
         } else {
 #pragma unroll
             for (int n = 0; n < NPRE; ++n) {
                 if ((n + 1) * NT > NCH && lt + n * NT >= NCH) continue;
-                if constexpr (MF) pre[n].store_mf(sGr + (lt + n * NT), G::MF_PLANE);
-                else if constexpr (RAW) pre[n].store_raw(sGr + RD * (lt + n * NT));
+                if constexpr (RAW) pre[n].store_raw(sGr + RD * (lt + n * NT));
                 else *reinterpret_cast<v4f*>(sG + 4 * (lt + n * NT)) = pre[n].get();
             }
         }
-        MI_TICK(0);   // stage (waits for the prefetched loads)
         __syncthreads();
-        MI_TICK(1);   // barrier 1
-        // the next frame's loads: all here (0), or spread over the phases (MI_SEP_PF_SPLIT) so that the eight waves do
-        // not queue up at the texture-address unit together (an issue stalls while its queue is full)
-        constexpr int PF_A = MI_SEP_PF_SPLIT == 0 ? NPRE : MI_SEP_PF_SPLIT == 1 ? (NPRE + 1) / 2 : 1;
-        if (!DMA && b + 1 < nfr && !MI_ABL(16)) prefetch(b + 1, 0, PF_A);
-        if constexpr (TOUCH) {
-            touch_acc ^= touch_val;   // last frame's touch has long returned: keeps the load alive for the compiler
-            if (touch_on && b + MI_SEP_TOUCH < nfr)
-                touch_val = __builtin_amdgcn_raw_buffer_load_b32(make_rsrc(src0 + (size_t)(b + MI_SEP_TOUCH) * a.src_stride, frame_bytes),
-                                                                 touch_off, 0, 0);
-        }
-        MI_TICK(2);   // prefetch issue
+        // the next frame's loads, all of them here
+        if (b + 1 < nfr) prefetch(b + 1);
         const BufRsrc gn_rs = make_rsrc(PAIR ? gnext0 : gnext0 + (size_t)b * a.gnext_stride, (uint32_t)hn * (uint32_t)wn * 12u);
         const BufRsrc gy_rs = make_rsrc(PAIR ? gray1_0 + (size_t)b * a.gray1_stride : nullptr, (uint32_t)hn * (uint32_t)wn * 4u);
         const BufRsrc g2_rs = make_rsrc(PAIR ? g2_0 + (size_t)b * a.g2_stride : nullptr, (uint32_t)a.hn2 * (uint32_t)a.wn2 * 12u);
         const bool keep3 = PAIR && f_lo + b == a.g1_keep;   // this frame's three-channel G_{l+1} goes to `gnext` (the tap)
 
-        if constexpr (!MF) {
         // ---------------- P1: vertical reduce, P1R V rows x one float4 column group per lane
         constexpr int P1R = (RAW && MI_SEP_P1_ROWS > 2 && G::NH >= MI_SEP_P1_ROWS) ? MI_SEP_P1_ROWS : 2;
         if constexpr (P1R > 2) {
             constexpr int P1G = (G::NH + P1R - 1) / P1R;
-            if (lt < P1G * CPR && !MI_ABL(1)) {
+            if (lt < P1G * CPR) {
                 const int rg = SmallDiv<CPR, NT>::div(lt), g = lt - mul24(rg, CPR);
                 const int v0 = min(P1R * rg, G::NH - P1R);
                 const uint32_t* p = sGr + RD * (mul24(2 * v0, CPR) + g);
@@ -891,7 +639,7 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
                 }
             }
         } else
-        if (lt < (G::NH / 2) * CPR && !MI_ABL(1)) {
+        if (lt < (G::NH / 2) * CPR) {
             const int rp = SmallDiv<CPR, NT>::div(lt), g = lt - mul24(rp, CPR);
             v2f a0, a1, b0, b1;   // (row 2rp | 2rp+1) x (floats 4g, 4g+1 | 4g+2, 4g+3)
             if constexpr (INTERIOR) {
@@ -951,74 +699,14 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
                 }
             }
         }
-        if (!DMA && MI_SEP_PF_SPLIT == 1 && b + 1 < nfr && !MI_ABL(16)) prefetch(b + 1, PF_A, NPRE);
-        if (!DMA && MI_SEP_PF_SPLIT == 2 && b + 1 < nfr && !MI_ABL(16)) prefetch(b + 1, 1, 2);
-        MI_TICK(3);   // P1
         __syncthreads();
-        MI_TICK(4);   // barrier 2
-        }   // !MF
-        if (DMA && b + 1 < nfr && !MI_ABL(16)) dma_issue(b + 1);   // the patch is dead: the next frame streams in beside P2-P4
 
         // ---------------- P2: horizontal reduce (one G_{l+1} pixel per lane, 32 lanes per patch row), G_{l+1} store, gray,
         // horizontal expand of the gray -> X.  18 rows x 32 = 576 items: the last two rows are a second round on wave 0.
-        if constexpr (MF) { if (!MI_ABL(2)) {
-            // ---------------- MF: the whole reduce of this wave's two G_{l+1} rows on the matrix pipe (see the top of the function)
-            // (a task = two rows; tile height 28 has nine of them for eight waves: wave 0 takes the last one too)
-            const int ln = lt & 63, n = ln & 15, kg = ln >> 4;
-            for (int task = lt >> 6; task < G::NH / 2; task += NT / 64) {
-            const int r = 2 * task + (n >> 3), jp = 4 * (n & 7) + kg;    // the pixel this lane ends up with
-            typedef const volatile v4i __attribute__((address_space(3))) * lds_v4i;
-            typedef const volatile v2u __attribute__((address_space(3))) * lds_v2u;
-            const uint32_t wbase = (uint32_t)(uintptr_t)sW + 16u * (uint32_t)ln;
-            const v4i A0 = *(lds_v4i)(size_t)wbase, A1 = *(lds_v4i)(size_t)(wbase + 1024u), A2 = *(lds_v4i)(size_t)(wbase + 2048u);
-            // data: window n of patch row 2 r + t, bytes 16 kg .. 16 kg + 15 (two 8-byte reads: windows are 8-byte aligned)
-            const uint32_t dbase = (uint32_t)(uintptr_t)sGr + (uint32_t)(mul24(2 * r, 4 * CPR) + 24 * (n & 7) + 16 * kg);
-            v4i S4 = {0, 0, 0, 0};
-#pragma unroll
-            for (int pl = NPL - 1; pl >= 0; --pl) {
-                v4i acc = {128 * 400, 128 * 400, 128 * 400, 128 * 400};
-#pragma unroll
-                for (int t = 0; t < 5; ++t) {
-                    const uint32_t ad = dbase + (uint32_t)(4 * (pl * G::MF_PLANE + t * CPR));
-                    const v2u d0 = *(lds_v2u)(size_t)ad, d1 = *(lds_v2u)(size_t)(ad + 8u);
-                    const v4i B = {(int)d0.x, (int)d0.y, (int)d1.x, (int)d1.y};
-                    if (MI_ABL(64)) acc += B;   // study: the data reads without the matrix instruction
-                    else acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(t == 2 ? A2 : (t == 1 || t == 3) ? A1 : A0, B, acc, 0, 0, 0);
-                }
-                S4 = pl == NPL - 1 ? acc : (S4 << 8) + acc;   // 16-bit frames: 256 * (high-byte sum) + low-byte sum
-            }
-            float nn[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) nn[c] = (float)S4[c] * rs;
-            {
-                const int i = y0 / 2 - 2 + r, j = x0 / 2 - 2 + jp;
-                bool st = r >= 2 && r < G::NH - 2 && jp >= 2 && jp < G::NW - 2 && !MI_ABL(32);
-                st = st && i < hn && j < wn;   // edge tiles overhang the image
-                if (st) {
-                    typedef uint32_t v3u __attribute__((ext_vector_type(3)));
-                    const v3u pv = {__builtin_bit_cast(uint32_t, nn[0]), __builtin_bit_cast(uint32_t, nn[1]),
-                                    __builtin_bit_cast(uint32_t, nn[2])};
-                    __builtin_amdgcn_raw_buffer_store_b96(pv, gn_rs, times12((uint32_t)(mul24(i, wn) + j)), 0, MI_SEP_NT_STORE ? 2 : 0);
-                }
-            }
-            // gray of the pixel; its neighbours along the row sit 16 lanes away (next pixel of the window) or in the
-            // neighbouring window's lane group: two bpermutes (LDS crossbar, no memory).  Pixels 0 / 31 of a row get a wrong
-            // neighbour: X columns 0, 1, 62, 63 feed only the quads nobody owns or blurs from.
-            const float g = gray_of<true>(nn[0], nn[1], nn[2]);
-            const int lprev = kg > 0 ? ln - 16 : ln + 47, lnext = kg < 3 ? ln + 16 : ln - 47;
-            float gl, gr;
-            if (MI_ABL(128)) { gl = dpp_wave_prev(g); gr = dpp_wave_next(g); }   // study: (wrong) neighbours without the bpermutes
-            else {
-                gl = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * lprev, __builtin_bit_cast(int, g)));
-                gr = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * lnext, __builtin_bit_cast(int, g)));
-            }
-            lds_store2(sX + mul24(r, G::XS) + 2 * jp, ex_even(gl, g, gr, ce, cc), ex_odd(g, gr, co));
-            }   // task
-        } } else {
 #pragma unroll
         for (int rnd = 0; rnd < (G::NH * 32 + NT - 1) / NT; ++rnd) {
             const int it = lt + rnd * NT;
-            if (it >= G::NH * 32 || MI_ABL(2)) break;   // uniform per wave: NT and the item count are multiples of 64
+            if (it >= G::NH * 32) break;   // uniform per wave: NT and the item count are multiples of 64
             const int r = it >> 5, jp = it & 31;
             float n[3];
             if constexpr (INTERIOR) {
@@ -1054,7 +742,7 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
             // tile centre of G_{l+1} -> global (input of the next level; PAIR: its gray, and the pixel into the LDS patch)
             {
                 const int i = y0 / 2 - 2 + r, j = x0 / 2 - 2 + jp;
-                bool st = r >= 2 && r < G::NH - 2 && jp >= 2 && jp < G::NW - 2 && !MI_ABL(32);
+                bool st = r >= 2 && r < G::NH - 2 && jp >= 2 && jp < G::NW - 2;
                 st = st && i < hn && j < wn;   // edge / border tiles overhang the image
                 if constexpr (PAIR) {
                     float* np = sN + it;       // planar [3][NH][NW]: item `it` = pixel (r, jp)
@@ -1076,11 +764,7 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
             const float gl = dpp_wave_prev(g), gr = dpp_wave_next(g);
             lds_store2(sX + mul24(r, G::XS) + 2 * jp, ex_even(gl, g, gr, ce, cc), ex_odd(g, gr, co));
         }
-        }   // !MF
-        if (!DMA && MI_SEP_PF_SPLIT == 2 && b + 1 < nfr && !MI_ABL(16)) prefetch(b + 1, 2, 3);
-        MI_TICK(5);   // P2
         __syncthreads();
-        MI_TICK(6);   // barrier 3
 
         if constexpr (PL) {
             // ---------------- PL: the Laplacians of the pixels this frame won, from the G_{l+1} patch
@@ -1135,7 +819,7 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
         }
 
         // ---------------- P3: vertical expand of the gray, gray Laplacian, Q, row blur of Q -> HB
-        if (lt < G::QY * G::QL && !MI_ABL(4)) {   // (uniform per wave)
+        if (lt < G::QY * G::QL) {   // (uniform per wave)
             const int qy3 = lt >> 5, ql3 = lt & 31;
             float q[4];
             if constexpr (INTERIOR) {
@@ -1146,13 +830,6 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
                 if constexpr (GQ1) {
                     gge = gq_e;
                     ggo = gq_o;
-                } else if constexpr (MF) {
-                    v2f ge[3], go[3];
-                    const uint32_t* rowp = sGr + mul24(2 * qy3 + 4, CPR);
-                    PreChunk<TIn>::unpack6_mf(rowp, G::MF_PLANE, 6 * ql3 + 6, ge);
-                    PreChunk<TIn>::unpack6_mf(rowp + CPR, G::MF_PLANE, 6 * ql3 + 6, go);
-                    gge = gray_of2(ge[0], ge[1], ge[2]);
-                    ggo = gray_of2(go[0], go[1], go[2]);
                 } else if constexpr (RAW) {
                     // unpacked channel by channel ((pixel, pixel) pairs: the conversions write where they like), so the
                     // two grays of a row are one packed chain
@@ -1228,13 +905,10 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
                 lds_store4(sV2 + (c * N2H + m) * G::NW + 4 * ch, lo.x, lo.y, hi.x, hi.y);
             }
         }
-        if (!DMA && MI_SEP_PF_SPLIT == 2 && b + 1 < nfr && !MI_ABL(16)) prefetch(b + 1, 3, NPRE);
-        MI_TICK(7);   // P3
         __syncthreads();
-        MI_TICK(8);   // barrier 4
 
         // ---------------- P4: column blur of HB for the own quad + running first-max
-        if (own_tile && !MI_ABL(8)) {
+        if (own_tile) {
             const int qy4 = lt >> 5, ql4 = lt & 31;
             const float* hp = sHB + mul24(2 * qy4 - 2, G::HBS) + 2 * ql4;
             v2f hb[6];
@@ -1289,17 +963,9 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
                 }
             }
         }
-        MI_TICK(9);   // P4
         // no barrier here: sG is rewritten after P3's reads (barrier above), V/HB after the next frame's first
         // barrier, X after its second
     }
-#ifdef MI_PHASE_CLOCK
-    if (INTERIOR && a.dbg && (tid & 63) == 0 && blockIdx.y == 0) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) atomicAdd(a.dbg + (tid >> 6) * 16 + i, (unsigned long long)pc_acc[i]);
-        atomicAdd(a.dbg + (tid >> 6) * 16 + 15, 1ull);
-    }
-#endif
 
     // ---- write the running maxima back
     if constexpr (PL) return;
@@ -1314,9 +980,6 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
             }
         }
     }
-    if constexpr (TOUCH) {   // never true: the touched dwords have a use
-        if ((touch_acc ^ touch_val) == 0x9e3779b9u && a.nframes < 0) st_i[0] = (int32_t)touch_acc;
-    }
 }
 
 // The kernels proper; the coarser levels get their own name so that profiles (rocprofv3 --stats aggregates by
@@ -1329,11 +992,6 @@ template <typename TIn, bool INTERIOR, int TH, int NT>
 __global__ __launch_bounds__(NT, INTERIOR ? (sizeof(TIn) <= 2 ? MI_SEP_INT_WAVES : (NT > 512 ? 7 : 1)) : MI_SEP_BD_WAVES) void level_sep(LevelArgs a) {
     level_sep_body<TIn, INTERIOR, TH, NT>(a);
 }
-// level 0 of 8 / 16-bit frames, reduce on the matrix pipe (MI_SEP_MFMA; tile height SEP_MF_TH)
-template <typename TIn, int TH, int NT>
-__global__ __launch_bounds__(NT, MI_SEP_INT_WAVES) void level_sep_mf(LevelArgs a) {
-    level_sep_body<TIn, true, TH, NT, true>(a);
-}
 template <typename TIn, bool INTERIOR, int TH, int NT>
 __global__ __launch_bounds__(NT, INTERIOR && NT > 512 ? 7 : 1) void level_sep_coarse(LevelArgs a) {
     level_sep_body<TIn, INTERIOR, TH, NT>(a);
@@ -1342,13 +1000,13 @@ __global__ __launch_bounds__(NT, INTERIOR && NT > 512 ? 7 : 1) void level_sep_co
 // level pairs (level_sep_body, "PAIR"): the first level of a pair
 template <typename TIn, bool INTERIOR, int TH, int NT>
 __global__ __launch_bounds__(NT, INTERIOR ? (sizeof(TIn) <= 2 ? MI_SEP_INT_WAVES : 1) : MI_SEP_BD_WAVES) void level_sep_pair(LevelArgs a) {
-    level_sep_body<TIn, INTERIOR, TH, NT, false, true>(a);
+    level_sep_body<TIn, INTERIOR, TH, NT, true>(a);
 }
 
 // the pair's payload pass, tile by tile (level_sep_body, "PL")
 template <typename TIn, bool INTERIOR, int TH, int NT>
 __global__ __launch_bounds__(NT, 1) void level_sep_pl(LevelArgs a) {
-    level_sep_body<TIn, INTERIOR, TH, NT, false, false, true>(a);
+    level_sep_body<TIn, INTERIOR, TH, NT, false, true>(a);
 }
 template <typename TIn, int TH, int NT>
 constexpr int sep_pl_lds_floats(bool interior) {
@@ -1448,9 +1106,7 @@ __device__ __forceinline__ void level_sep_e_body(const LevelArgs& a) {
 
     for (int b = 0; b < nfr; ++b) {
         int lt = tid;
-#if MI_SEP_LAUNDER
         asm volatile("" : "+v"(lt));
-#endif
         // ---------------- P0: the gray patch, and X from the G_{l+1} pixels (one per lane; rows 16, 17: a second round on wave 0)
         *reinterpret_cast<v4f*>(sY + 4 * lt) = preY;
 #pragma unroll

@@ -63,14 +63,11 @@ struct LevelArgs {
     int32_t* best_idx;
     int first;              // state holds nothing yet
     int frame_idx0;         // global index of the batch's first frame
-    int ablate;             // debug: bit mask of phases to skip (timing studies only)
-#ifdef MI_PHASE_CLOCK
-    unsigned long long* dbg;  // [16 intervals] cycle sums over all waves (timing studies only)
-#endif
+    int ablate;             // unused (was: phases to skip in timing studies); kept so that the later offsets stay put
     K6 K;
     float k1d[3];           // MI_ARITH_SEPARABLE: float32 of the 1-D generating kernel (k0, k1, k2)
     float rk[4];            // MI_ARITH_SEPARABLE, reduce: taps (w0, w1, w2) and the final scale (red_taps, kernels_sep.hpp)
-    int mfma_ok;            // the integer (MFMA) form of the level-0 reduce may be used: small non-negative integer taps
+    int mfma_ok;            // unused (was: the retired MFMA form of the level-0 reduce applies); kept, as `ablate` is
     // MI_ARITH_SEPARABLE, frame chunks: blockIdx.y = c works on frames [c * chunk_frames, (c + 1) * chunk_frames) of the
     // batch.  Chunk 0 continues the running state; chunk c > 0 starts from nothing and leaves its (max, arg-max) in
     // part_e / part_idx [(c - 1) * part_stride + pixel]; merge_chunks folds them into the running state in chunk order.
@@ -329,17 +326,6 @@ __device__ __forceinline__ v2f mac2_shared(v2f k, v2f x, int sel, v2f acc) {
 }
 __device__ __forceinline__ float half_of(v2f x, int sel) { return sel ? x.y : x.x; }
 
-#ifdef MI_PHASE_CLOCK
-#define MI_TICK(i)                                                   \
-    do {                                                             \
-        const unsigned int _t = (unsigned int)clock64();             \
-        pc_acc[i] += _t - pc_last;                                   \
-        pc_last = _t;                                                \
-    } while (0)
-#else
-#define MI_TICK(i) do { } while (0)
-#endif
-
 template <typename TIn, bool FMA, bool INTERIOR, int TH, int TW, int NT, bool PAD>
 __device__ __forceinline__ void level_fused_body(const LevelArgs& a) {
     using G = TileGeom<TH, TW, NT, PAD>;
@@ -506,7 +492,7 @@ __device__ __forceinline__ void level_fused_body(const LevelArgs& a) {
         if constexpr (INTERIOR && G::TABLE_REDUCE && RED_RU == 2 && RED_ITEMS == 1) {
             static_assert(RED_BX == 18 && G::NH / RED_RU == 10, "the reduce item table is for the 32x64 tile");
             const int e = it < 192 ? RED_MAP_32x64[it] : 0xFFFF;   // (row pair << 8) | column pair
-            if (!MI_ABL(1024)) c_red[k] = e != 0xFFFF ? ((e >> 8) << 16) | (e & 0xff) : -1;
+            c_red[k] = e != 0xFFFF ? ((e >> 8) << 16) | (e & 0xff) : -1;
         }
     }
     // waves that own reduce items (lanes below RED_N, or the table's 192 lanes)
@@ -535,9 +521,6 @@ __device__ __forceinline__ void level_fused_body(const LevelArgs& a) {
         const int e = tid + k * G::NT, r = e / GN_C4;
         c_gn[k] = e < GN_N4 ? (r << 16) | ((e - r * GN_C4) * 4) : -1;
     }
-#ifdef MI_PHASE_CLOCK
-    unsigned int pc_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, pc_last = (unsigned int)clock64();
-#endif
     for (int b = 0; b < nfr; ++b) {
         int ltid = tid;
         asm volatile("" : "+v"(ltid));  // used by the border variants only
@@ -569,113 +552,138 @@ __device__ __forceinline__ void level_fused_body(const LevelArgs& a) {
                     else lds_store2(d, pre[n][0], pre[n][1]);
                 }
         }
-        MI_TICK(0);   // stage (waits for the prefetched loads)
         __syncthreads();
-        MI_TICK(1);   // barrier 1
         // Issuing the next frame's loads stalls a wave for about as long as a stencil phase takes (the memory
         // pipeline is kept full), so the waves that own reduce items -- the critical path to the next barrier --
         // issue theirs after it; the others, idle until then, issue now.
         const bool pf_late = MI_SCHED && INTERIOR && red_wave;
-        if (!pf_late && b + 1 < nfr && !MI_ABL(16)) prefetch(b + 1);
-        MI_TICK(2);   // prefetch issue
+        if (!pf_late && b + 1 < nfr) prefetch(b + 1);
 
         // ---------------- reduce: items of RU output rows x 2 output pixels x 3 channels
-        if (!MI_ABL(1)) {
-            constexpr int RU = RED_RU;  // output rows per item
-            static_assert(G::NH % RU == 0, "reduce rows per item must divide the patch height");
+        constexpr int RU = RED_RU;  // output rows per item
+        static_assert(G::NH % RU == 0, "reduce rows per item must divide the patch height");
 #pragma unroll
-            for (int kk = 0; kk < RED_ITEMS; ++kk) {
-                if (c_red[kk] < 0) continue;
-                const int rb = c_red[kk] >> 16, bx = c_red[kk] & 0xffff, ri = rb * RU, rj = 2 * bx;
-                float acc[RU][2][3];
+        for (int kk = 0; kk < RED_ITEMS; ++kk) {
+            if (c_red[kk] < 0) continue;
+            const int rb = c_red[kk] >> 16, bx = c_red[kk] & 0xffff, ri = rb * RU, rj = 2 * bx;
+            float acc[RU][2][3];
 #pragma unroll
-                for (int u = 0; u < RU; ++u)
+            for (int u = 0; u < RU; ++u)
 #pragma unroll
-                    for (int vv = 0; vv < 2; ++vv) acc[u][vv][0] = acc[u][vv][1] = acc[u][vv][2] = 0.f;
-                if constexpr (INTERIOR && RU == 2) {
-                    // input rows 2ri .. 2ri+6, pixels 2rj .. 2rj+6: 21 floats (+1 spare), 16-byte aligned.
-                    // Row rr+1 is loaded while row rr is consumed (two register sets).  Input row rr is tap row rr of
-                    // output row 0 and tap row rr-2 of output row 1: rows 2..4 feed both, with one packed instruction
-                    // per (tap column, pixel, channel) -- 35 instead of 50 instructions per chain pair.
-                    constexpr int NR = 7;
-                    const float* p0 = sG + mul24(2 * ri, G::GS) + 2 * rj * 3;
-                    v4f rq[2][5];
-                    v2f rl[2];
-                    auto load_row = [&](int rr, int s) {
+                for (int vv = 0; vv < 2; ++vv) acc[u][vv][0] = acc[u][vv][1] = acc[u][vv][2] = 0.f;
+            if constexpr (INTERIOR && RU == 2) {
+                // input rows 2ri .. 2ri+6, pixels 2rj .. 2rj+6: 21 floats (+1 spare), 16-byte aligned.
+                // Row rr+1 is loaded while row rr is consumed (two register sets).  Input row rr is tap row rr of
+                // output row 0 and tap row rr-2 of output row 1: rows 2..4 feed both, with one packed instruction
+                // per (tap column, pixel, channel) -- 35 instead of 50 instructions per chain pair.
+                constexpr int NR = 7;
+                const float* p0 = sG + mul24(2 * ri, G::GS) + 2 * rj * 3;
+                v4f rq[2][5];
+                v2f rl[2];
+                auto load_row = [&](int rr, int s) {
 #pragma unroll
-                        for (int t = 0; t < 5; ++t) rq[s][t] = lds_load4(p0 + rr * G::GS + 4 * t);
-                        rl[s] = lds_load2(p0 + rr * G::GS + 20);
-                    };
-                    v2f acc2[2][3];   // [pixel][channel] = (output row 0, output row 1)
+                    for (int t = 0; t < 5; ++t) rq[s][t] = lds_load4(p0 + rr * G::GS + 4 * t);
+                    rl[s] = lds_load2(p0 + rr * G::GS + 20);
+                };
+                v2f acc2[2][3];   // [pixel][channel] = (output row 0, output row 1)
+#pragma unroll
+                for (int vv = 0; vv < 2; ++vv)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) acc2[vv][c] = v2f{0.f, 0.f};
+                load_row(0, 0);
+#pragma unroll
+                for (int rr = 0; rr < NR; ++rr) {
+                    const int s = rr & 1;
+                    if (rr + 1 < NR) load_row(rr + 1, s ^ 1);
+                    MI_LDS_FENCE();
+                    v2f P[11];
+#pragma unroll
+                    for (int t = 0; t < 5; ++t) {
+                        P[2 * t] = rq[s][t].xy;
+                        P[2 * t + 1] = rq[s][t].zw;
+                    }
+                    P[10] = rl[s];
 #pragma unroll
                     for (int vv = 0; vv < 2; ++vv)
 #pragma unroll
-                        for (int c = 0; c < 3; ++c) acc2[vv][c] = v2f{0.f, 0.f};
-                    load_row(0, 0);
+                        for (int tx = 0; tx < 5; ++tx)
 #pragma unroll
-                    for (int rr = 0; rr < NR; ++rr) {
-                        const int s = rr & 1;
-                        if (rr + 1 < NR) load_row(rr + 1, s ^ 1);
-                        MI_LDS_FENCE();
-                        v2f P[11];
+                            for (int c = 0; c < 3; ++c) {
+                                const int e = (2 * vv + tx) * 3 + c;
+                                if (rr >= 2 && rr <= 4)
+                                    acc2[vv][c] = mac2_shared<FMA>(v2f{K(rr, tx), K(rr - 2, tx)}, P[e >> 1], e & 1, acc2[vv][c]);
+                                else if (rr < 2)
+                                    acc2[vv][c].x = mac<FMA>(K(rr, tx), half_of(P[e >> 1], e & 1), acc2[vv][c].x);
+                                else
+                                    acc2[vv][c].y = mac<FMA>(K(rr - 2, tx), half_of(P[e >> 1], e & 1), acc2[vv][c].y);
+                            }
+                }
 #pragma unroll
-                        for (int t = 0; t < 5; ++t) {
-                            P[2 * t] = rq[s][t].xy;
-                            P[2 * t + 1] = rq[s][t].zw;
-                        }
-                        P[10] = rl[s];
+                for (int vv = 0; vv < 2; ++vv)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        acc[0][vv][c] = acc2[vv][c].x;
+                        acc[1][vv][c] = acc2[vv][c].y;
+                    }
+            } else if constexpr (INTERIOR) {
+                // input rows 2ri .. 2ri+2RU+2, pixels 2rj .. 2rj+6: 21 floats, 16-byte aligned.
+                // Row rr+1 is loaded while row rr is consumed (two register sets); input row
+                // rr is tap row rr-2u of output row u.
+                constexpr int NR = 2 * RU + 3;
+                const float* p0 = sG + mul24(2 * ri, G::GS) + 2 * rj * 3;
+                v4f rq[2][5];
+                float rl[2];
+                auto load_row = [&](int rr, int s) {
+#pragma unroll
+                    for (int t = 0; t < 5; ++t) rq[s][t] = lds_load4(p0 + rr * G::GS + 4 * t);
+                    rl[s] = p0[rr * G::GS + 20];
+                };
+                load_row(0, 0);
+#pragma unroll
+                for (int rr = 0; rr < NR; ++rr) {
+                    const int s = rr & 1;
+                    if (rr + 1 < NR) load_row(rr + 1, s ^ 1);
+                    MI_LDS_FENCE();
+                    float v[21];
+#pragma unroll
+                    for (int t = 0; t < 5; ++t) {
+                        v[4 * t] = rq[s][t].x; v[4 * t + 1] = rq[s][t].y;
+                        v[4 * t + 2] = rq[s][t].z; v[4 * t + 3] = rq[s][t].w;
+                    }
+                    v[20] = rl[s];
+#pragma unroll
+                    for (int u = 0; u < RU; ++u) {
+                        const int ty = rr - 2 * u;
+                        if (ty < 0 || ty > 4) continue;
 #pragma unroll
                         for (int vv = 0; vv < 2; ++vv)
 #pragma unroll
-                            for (int tx = 0; tx < 5; ++tx)
+                            for (int tx = 0; tx < 5; ++tx) {
+                                const float k = K(ty, tx);
 #pragma unroll
-                                for (int c = 0; c < 3; ++c) {
-                                    const int e = (2 * vv + tx) * 3 + c;
-                                    if (rr >= 2 && rr <= 4)
-                                        acc2[vv][c] = mac2_shared<FMA>(v2f{K(rr, tx), K(rr - 2, tx)}, P[e >> 1], e & 1, acc2[vv][c]);
-                                    else if (rr < 2)
-                                        acc2[vv][c].x = mac<FMA>(K(rr, tx), half_of(P[e >> 1], e & 1), acc2[vv][c].x);
-                                    else
-                                        acc2[vv][c].y = mac<FMA>(K(rr - 2, tx), half_of(P[e >> 1], e & 1), acc2[vv][c].y);
-                                }
+                                for (int c = 0; c < 3; ++c)
+                                    acc[u][vv][c] = mac<FMA>(k, v[(2 * vv + tx) * 3 + c], acc[u][vv][c]);
+                            }
                     }
+                }
+            } else {
+                const int im = map_expand_src(y0 / 2 - 2 + ri, hn);
+                {
+                    // the common case: both cells of the item map to neighbouring columns and their
+                    // joint 5 x 7 pixel window lies inside the patch -- read it like the interior
+                    // path does, 8 bytes at a time (rows and windows start on even floats)
+                    const int jm0 = map_expand_src(x0 / 2 - 2 + rj, wn), jm1 = map_expand_src(x0 / 2 - 2 + rj + 1, wn);
+                    const int r0 = 2 * im - 2 - (y0 - 6), c0 = 2 * jm0 - 2 - (x0 - 6);
+                    if ((G::GS & 1) == 0 && jm1 == jm0 + 1 && r0 >= 0 && r0 + 4 < G::GH && c0 >= 0 && c0 + 6 < G::GW) {
+                        const float* p = sG + mul24(r0, G::GS) + c0 * 3;
 #pragma unroll
-                    for (int vv = 0; vv < 2; ++vv)
+                        for (int ty = 0; ty < 5; ++ty) {
+                            float v[22];
 #pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            acc[0][vv][c] = acc2[vv][c].x;
-                            acc[1][vv][c] = acc2[vv][c].y;
-                        }
-                } else if constexpr (INTERIOR) {
-                    // input rows 2ri .. 2ri+2RU+2, pixels 2rj .. 2rj+6: 21 floats, 16-byte aligned.
-                    // Row rr+1 is loaded while row rr is consumed (two register sets); input row
-                    // rr is tap row rr-2u of output row u.
-                    constexpr int NR = 2 * RU + 3;
-                    const float* p0 = sG + mul24(2 * ri, G::GS) + 2 * rj * 3;
-                    v4f rq[2][5];
-                    float rl[2];
-                    auto load_row = [&](int rr, int s) {
-#pragma unroll
-                        for (int t = 0; t < 5; ++t) rq[s][t] = lds_load4(p0 + rr * G::GS + 4 * t);
-                        rl[s] = p0[rr * G::GS + 20];
-                    };
-                    load_row(0, 0);
-#pragma unroll
-                    for (int rr = 0; rr < NR; ++rr) {
-                        const int s = rr & 1;
-                        if (rr + 1 < NR) load_row(rr + 1, s ^ 1);
-                        MI_LDS_FENCE();
-                        float v[21];
-#pragma unroll
-                        for (int t = 0; t < 5; ++t) {
-                            v[4 * t] = rq[s][t].x; v[4 * t + 1] = rq[s][t].y;
-                            v[4 * t + 2] = rq[s][t].z; v[4 * t + 3] = rq[s][t].w;
-                        }
-                        v[20] = rl[s];
-#pragma unroll
-                        for (int u = 0; u < RU; ++u) {
-                            const int ty = rr - 2 * u;
-                            if (ty < 0 || ty > 4) continue;
+                            for (int t = 0; t < 11; ++t) {
+                                const v2f q = lds_load2(p + ty * G::GS + 2 * t);   // 21 floats + 1 spare
+                                v[2 * t] = q.x; v[2 * t + 1] = q.y;
+                            }
 #pragma unroll
                             for (int vv = 0; vv < 2; ++vv)
 #pragma unroll
@@ -683,302 +691,253 @@ __device__ __forceinline__ void level_fused_body(const LevelArgs& a) {
                                     const float k = K(ty, tx);
 #pragma unroll
                                     for (int c = 0; c < 3; ++c)
-                                        acc[u][vv][c] = mac<FMA>(k, v[(2 * vv + tx) * 3 + c], acc[u][vv][c]);
+                                        acc[0][vv][c] = mac<FMA>(k, v[(2 * vv + tx) * 3 + c], acc[0][vv][c]);
                                 }
                         }
+                        goto reduce_store;
                     }
-                } else {
-                    const int im = map_expand_src(y0 / 2 - 2 + ri, hn);
-                    {
-                        // the common case: both cells of the item map to neighbouring columns and their
-                        // joint 5 x 7 pixel window lies inside the patch -- read it like the interior
-                        // path does, 8 bytes at a time (rows and windows start on even floats)
-                        const int jm0 = map_expand_src(x0 / 2 - 2 + rj, wn), jm1 = map_expand_src(x0 / 2 - 2 + rj + 1, wn);
-                        const int r0 = 2 * im - 2 - (y0 - 6), c0 = 2 * jm0 - 2 - (x0 - 6);
-                        if ((G::GS & 1) == 0 && jm1 == jm0 + 1 && r0 >= 0 && r0 + 4 < G::GH && c0 >= 0 && c0 + 6 < G::GW) {
-                            const float* p = sG + mul24(r0, G::GS) + c0 * 3;
+                }
 #pragma unroll
-                            for (int ty = 0; ty < 5; ++ty) {
-                                float v[22];
+                for (int vv = 0; vv < 2; ++vv) {
+                    const int jm = map_expand_src(x0 / 2 - 2 + rj + vv, wn);
+                    // window of the (mapped) cell in patch coordinates; the patch already holds
+                    // reflected data, so a window that lies inside it needs no per-tap mapping
+                    const int r0 = 2 * im - 2 - (y0 - 6), c0 = 2 * jm - 2 - (x0 - 6);
+                    if (r0 >= 0 && r0 + 4 < G::GH && c0 >= 0 && c0 + 4 < G::GW) {
+                        const float* p = sG + mul24(r0, G::GS) + c0 * 3;
 #pragma unroll
-                                for (int t = 0; t < 11; ++t) {
-                                    const v2f q = lds_load2(p + ty * G::GS + 2 * t);   // 21 floats + 1 spare
-                                    v[2 * t] = q.x; v[2 * t + 1] = q.y;
-                                }
-#pragma unroll
-                                for (int vv = 0; vv < 2; ++vv)
-#pragma unroll
-                                    for (int tx = 0; tx < 5; ++tx) {
-                                        const float k = K(ty, tx);
-#pragma unroll
-                                        for (int c = 0; c < 3; ++c)
-                                            acc[0][vv][c] = mac<FMA>(k, v[(2 * vv + tx) * 3 + c], acc[0][vv][c]);
-                                    }
-                            }
-                            goto reduce_store;
-                        }
-                    }
-#pragma unroll
-                    for (int vv = 0; vv < 2; ++vv) {
-                        const int jm = map_expand_src(x0 / 2 - 2 + rj + vv, wn);
-                        // window of the (mapped) cell in patch coordinates; the patch already holds
-                        // reflected data, so a window that lies inside it needs no per-tap mapping
-                        const int r0 = 2 * im - 2 - (y0 - 6), c0 = 2 * jm - 2 - (x0 - 6);
-                        if (r0 >= 0 && r0 + 4 < G::GH && c0 >= 0 && c0 + 4 < G::GW) {
-                            const float* p = sG + mul24(r0, G::GS) + c0 * 3;
-#pragma unroll
-                            for (int ty = 0; ty < 5; ++ty)
-#pragma unroll
-                                for (int tx = 0; tx < 5; ++tx) {
-                                    const float k = K(ty, tx);
-#pragma unroll
-                                    for (int c = 0; c < 3; ++c)
-                                        acc[0][vv][c] = mac<FMA>(k, p[ty * G::GS + tx * 3 + c], acc[0][vv][c]);
-                                }
-                            continue;
-                        }
-                        for (int ty = 0; ty < 5; ++ty) {
-                            // rows/cols beyond the image already hold reflected data (staging)
-                            const int r = clampi(2 * im - 2 + ty - (y0 - 6), 0, G::GH - 1);
+                        for (int ty = 0; ty < 5; ++ty)
 #pragma unroll
                             for (int tx = 0; tx < 5; ++tx) {
-                                const int cc = clampi(2 * jm - 2 + tx - (x0 - 6), 0, G::GW - 1);
                                 const float k = K(ty, tx);
-                                const float* p = sG + r * G::GS + cc * 3;
 #pragma unroll
-                                for (int c = 0; c < 3; ++c) acc[0][vv][c] = mac<FMA>(k, p[c], acc[0][vv][c]);
+                                for (int c = 0; c < 3; ++c)
+                                    acc[0][vv][c] = mac<FMA>(k, p[ty * G::GS + tx * 3 + c], acc[0][vv][c]);
                             }
-                        }
+                        continue;
                     }
-                }
-            reduce_store:
-#pragma unroll
-                for (int u = 0; u < RU; ++u) {
-                    float* o = sN + mul24(ri + u, G::NS) + rj * 3;  // 6 floats, 8-byte aligned
-                    lds_store2(o, acc[u][0][0], acc[u][0][1]);
-                    lds_store2(o + 2, acc[u][0][2], acc[u][1][0]);
-                    lds_store2(o + 4, acc[u][1][1], acc[u][1][2]);
-                }
-            }
-        }
-        MI_TICK(3);   // reduce
-        __syncthreads();
-        MI_TICK(4);   // barrier 2
-        if (pf_late && b + 1 < nfr && !MI_ABL(16)) prefetch(b + 1);
-
-        // ---------------- store the tile centre of G_{l+1}: (TH/2) rows of (TW/2)*3 floats
-        if (!MI_ABL(2)) {
-            float* gout = gnext0 + (size_t)b * a.gnext_stride;
-            const int i0 = y0 / 2, j0 = x0 / 2;
-            constexpr int CW = (TW / 2) * 3;
-            // whole tile centre inside G_{l+1} (always so for interior tiles, mostly so for border ones)
-            const bool whole = INTERIOR || (i0 + TH / 2 <= hn && j0 + TW / 2 <= wn);
-            if (whole && (wn & 3) == 0 && (CW & 3) == 0) {
-                // rows start 16-byte aligned in global memory: one float4 per lane
-#pragma unroll
-                for (int kk = 0; kk < GN_ITEMS4; ++kk) {
-                    if (c_gn[kk] < 0) continue;
-                    const int r = c_gn[kk] >> 16, k = c_gn[kk] & 0xffff;
-                    const float* sp = sN + mul24(r + 2, G::NS) + 6 + k;  // 8-byte aligned
-                    const v2f lo = lds_load2(sp), hi = lds_load2(sp + 2);
-                    v4f v = {lo.x, lo.y, hi.x, hi.y};
-                    *reinterpret_cast<v4f*>(reinterpret_cast<char*>(gout) +
-                                            ((uint32_t)(mul24(i0 + r, wn) + j0) * 3u + (uint32_t)k) * 4u) = v;
-                }
-            } else {
-                for (int e = ltid; e < (TH / 2) * CW; e += G::NT) {
-                    const int r = e / CW, k = e - r * CW;
-                    const int i = i0 + r, j = j0 + k / 3;
-                    if (INTERIOR || (i < hn && j < wn))
-                        gstore32(gout, ((uint32_t)(mul24(i, wn) + j0) * 3u + (uint32_t)k) * 4u,
-                                 sN[mul24(r + 2, G::NS) + 6 + k]);
-                }
-            }
-        }
-
-        MI_TICK(5);   // G_{l+1} store
-        // ---------------- laplacian + Q on (TH+4) x (TW+4), as 2x2 quads
-        if (!MI_ABL(4)) {
-            auto do_quad = [&](int qy, int qx) {
-                // local sN rows/cols of the expand source, local sG rows/cols of the cells
-                int re, ro, ce, co, gre, gro, gce, gco;
-                if constexpr (INTERIOR) {
-                    re = ro = qy + 1;
-                    ce = co = qx + 1;
-                    gre = 2 * qy + 4; gro = gre + 1;
-                    gce = 2 * qx + 4; gco = gce + 1;
-                } else {
-                    const int ye = map_clamp(y0 - 2 + 2 * qy, h), yo = map_clamp(y0 - 1 + 2 * qy, h);
-                    const int xe = map_clamp(x0 - 2 + 2 * qx, w), xo = map_clamp(x0 - 1 + 2 * qx, w);
-                    re = clampi((ye >> 1) - (y0 / 2 - 2), 1, G::NH - 2);
-                    ro = clampi(((yo - 1) >> 1) - (y0 / 2 - 2), 0, G::NH - 2);
-                    ce = clampi((xe >> 1) - (x0 / 2 - 2), 1, G::NW - 2);
-                    co = clampi(((xo - 1) >> 1) - (x0 / 2 - 2), 0, G::NW - 2);
-                    gre = clampi(ye - (y0 - 6), 0, G::GH - 1); gro = clampi(yo - (y0 - 6), 0, G::GH - 1);
-                    gce = clampi(xe - (x0 - 6), 0, G::GW - 1); gco = clampi(xo - (x0 - 6), 0, G::GW - 1);
-                }
-                float see[3] = {0, 0, 0}, seo[3] = {0, 0, 0}, soe[3] = {0, 0, 0}, soo[3] = {0, 0, 0};
-                if constexpr (INTERIOR) {
-                    // The even output row takes tap rows 0, 2, 4 from G_{l+1} rows qy, qy+1, qy+2; the odd one tap rows
-                    // 1, 3 from rows qy+1, qy+2: on those two rows one packed instruction advances the even-row and
-                    // the odd-row chain of the same column phase (15 instead of 25 instructions per channel).  A row's
-                    // window (pixels qx .. qx+2: nine floats, 4-byte aligned) comes in as five register pairs.
-                    v2f A[3], B[3];   // (see, soe) and (seo, soo) per channel
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) A[c] = B[c] = v2f{0.f, 0.f};
-#pragma unroll
-                    for (int ar = 0; ar < 3; ++ar) {
-                        const float* wp = sN + mul24(qy + ar, G::NS) + 3 * qx;
-                        v2f W[5];
-#pragma unroll
-                        for (int t = 0; t < 5; ++t) W[t] = lds_load2u(wp + 2 * t);   // the tenth float is not used
-#pragma unroll
-                        for (int ac = 0; ac < 3; ++ac)
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) {
-                                const int e = 3 * ac + c;
-                                if (ar == 0) A[c].x = mac<FMA>(K(0, 2 * ac), half_of(W[e >> 1], e & 1), A[c].x);
-                                else A[c] = mac2_shared<FMA>(v2f{K(2 * ar, 2 * ac), K(2 * ar - 1, 2 * ac)}, W[e >> 1], e & 1, A[c]);
-                            }
-#pragma unroll
-                        for (int ac = 0; ac < 2; ++ac)
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) {
-                                const int e = 3 * (1 + ac) + c;
-                                if (ar == 0) B[c].x = mac<FMA>(K(0, 2 * ac + 1), half_of(W[e >> 1], e & 1), B[c].x);
-                                else B[c] = mac2_shared<FMA>(v2f{K(2 * ar, 2 * ac + 1), K(2 * ar - 1, 2 * ac + 1)}, W[e >> 1], e & 1, B[c]);
-                            }
-                    }
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        see[c] = A[c].x; soe[c] = A[c].y;
-                        seo[c] = B[c].x; soo[c] = B[c].y;
-                    }
-                } else {
-                // (even row, even col): taps ty in {0,2,4} x tx in {0,2,4};  (even, odd): tx in {1,3}
-#pragma unroll
-                for (int ar = 0; ar < 3; ++ar) {
-                    const float* nrow = sN + mul24(re - 1 + ar, G::NS);
-#pragma unroll
-                    for (int ac = 0; ac < 3; ++ac) {
-                        const float k = K(2 * ar, 2 * ac);
-                        const float* p = nrow + (ce - 1 + ac) * 3;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) see[c] = mac<FMA>(k, p[c], see[c]);
-                    }
-#pragma unroll
-                    for (int ac = 0; ac < 2; ++ac) {
-                        const float k = K(2 * ar, 2 * ac + 1);
-                        const float* p = nrow + (co + ac) * 3;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) seo[c] = mac<FMA>(k, p[c], seo[c]);
-                    }
-                }
-                // (odd row, *): ty in {1,3}
-#pragma unroll
-                for (int ar = 0; ar < 2; ++ar) {
-                    const float* nrow = sN + mul24(ro + ar, G::NS);
-#pragma unroll
-                    for (int ac = 0; ac < 3; ++ac) {
-                        const float k = K(2 * ar + 1, 2 * ac);
-                        const float* p = nrow + (ce - 1 + ac) * 3;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) soe[c] = mac<FMA>(k, p[c], soe[c]);
-                    }
-#pragma unroll
-                    for (int ac = 0; ac < 2; ++ac) {
-                        const float k = K(2 * ar + 1, 2 * ac + 1);
-                        const float* p = nrow + (co + ac) * 3;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) soo[c] = mac<FMA>(k, p[c], soo[c]);
-                    }
-                }
-                }
-                const float* gee = sG + mul24(gre, G::GS) + gce * 3;
-                const float* geo = sG + mul24(gre, G::GS) + gco * 3;
-                const float* goe = sG + mul24(gro, G::GS) + gce * 3;
-                const float* goo = sG + mul24(gro, G::GS) + gco * 3;
-                float l[4][3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    // g - 4*s: the product is exact, so one fused op rounds identically
-                    l[0][c] = __builtin_fmaf(-4.0f, see[c], gee[c]);
-                    l[1][c] = __builtin_fmaf(-4.0f, seo[c], geo[c]);
-                    l[2][c] = __builtin_fmaf(-4.0f, soe[c], goe[c]);
-                    l[3][c] = __builtin_fmaf(-4.0f, soo[c], goo[c]);
-                }
-                float qv[4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    float gr = gray_of<FMA>(l[p][0], l[p][1], l[p][2]);
-                    qv[p] = gr * gr;
-                }
-                float* qo = sQ + mul24(2 * qy, G::QS) + 2 * qx;
-                lds_store2(qo, qv[0], qv[1]);
-                lds_store2(qo + G::QS, qv[2], qv[3]);
-            };
-            // own quads (tile interior) ...
-#pragma unroll
-            for (int q = 0; q < G::NQ; ++q)
-                do_quad((c_own[q] >> 16) + 1, (c_own[q] & 0xffff) + 1);
-            // ... and the halo ring, spread over the first threads
-#pragma unroll
-            for (int kk = 0; kk < RING_ITEMS; ++kk)
-                if (c_ring[kk] >= 0) do_quad(c_ring[kk] >> 16, c_ring[kk] & 0xffff);
-        }
-        MI_TICK(6);   // laplacian + Q
-        __syncthreads();
-        MI_TICK(7);   // barrier 3
-
-        // ---------------- energy of the own quads + running first-max
-        if (!MI_ABL(8)) {
-            const int fidx = a.frame_idx0 + f_lo + b;
-#pragma unroll
-            for (int q = 0; q < G::NQ; ++q) {
-                const int oy = c_own[q] >> 16, ox = c_own[q] & 0xffff;
-                const float* base = sQ + mul24(2 * oy, G::QS) + 2 * ox;  // 8-byte aligned
-                // Q row rr is tap row rr of the quad's upper pixels and tap row rr-1 of its lower ones: rows 1..4 advance
-                // both chains of a column with one packed instruction (60 instead of 100 per quad)
-                v2f E[2] = {v2f{0.f, 0.f}, v2f{0.f, 0.f}};   // [dx] = (upper, lower)
-#pragma unroll
-                for (int rr = 0; rr < 6; ++rr) {
-                    const float* rp = base + rr * G::QS;
-                    v2f V[3];
-                    V[0] = lds_load2(rp);
-                    if MI_ABL(2048) { V[1] = V[0]; V[2] = V[0]; }   // probe: a third of the energy phase's LDS reads
-                    else { V[1] = lds_load2(rp + 2); V[2] = lds_load2(rp + 4); }
-#pragma unroll
-                    for (int dx = 0; dx < 2; ++dx)
+                    for (int ty = 0; ty < 5; ++ty) {
+                        // rows/cols beyond the image already hold reflected data (staging)
+                        const int r = clampi(2 * im - 2 + ty - (y0 - 6), 0, G::GH - 1);
 #pragma unroll
                         for (int tx = 0; tx < 5; ++tx) {
-                            const int e1 = dx + tx;
-                            if (rr == 0) E[dx].x = mac<FMA>(K(0, tx), half_of(V[e1 >> 1], e1 & 1), E[dx].x);
-                            else if (rr == 5) E[dx].y = mac<FMA>(K(4, tx), half_of(V[e1 >> 1], e1 & 1), E[dx].y);
-                            else E[dx] = mac2_shared<FMA>(v2f{K(rr, tx), K(rr - 1, tx)}, V[e1 >> 1], e1 & 1, E[dx]);
-                        }
-                }
-                const float e[4] = {E[0].x, E[1].x, E[0].y, E[1].y};
+                            const int cc = clampi(2 * jm - 2 + tx - (x0 - 6), 0, G::GW - 1);
+                            const float k = K(ty, tx);
+                            const float* p = sG + r * G::GS + cc * 3;
 #pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const bool win = e[p] > bE[q][p];
-                    bE[q][p] = win ? e[p] : bE[q][p];
-                    bI[q][p] = win ? fidx : bI[q][p];
+                            for (int c = 0; c < 3; ++c) acc[0][vv][c] = mac<FMA>(k, p[c], acc[0][vv][c]);
+                        }
+                    }
                 }
             }
+        reduce_store:
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+                float* o = sN + mul24(ri + u, G::NS) + rj * 3;  // 6 floats, 8-byte aligned
+                lds_store2(o, acc[u][0][0], acc[u][0][1]);
+                lds_store2(o + 2, acc[u][0][2], acc[u][1][0]);
+                lds_store2(o + 4, acc[u][1][1], acc[u][1][2]);
+            }
         }
-        MI_TICK(8);   // energy + select
+        __syncthreads();
+        if (pf_late && b + 1 < nfr) prefetch(b + 1);
+
+        // ---------------- store the tile centre of G_{l+1}: (TH/2) rows of (TW/2)*3 floats
+        float* gout = gnext0 + (size_t)b * a.gnext_stride;
+        const int i0 = y0 / 2, j0 = x0 / 2;
+        constexpr int CW = (TW / 2) * 3;
+        // whole tile centre inside G_{l+1} (always so for interior tiles, mostly so for border ones)
+        const bool whole = INTERIOR || (i0 + TH / 2 <= hn && j0 + TW / 2 <= wn);
+        if (whole && (wn & 3) == 0 && (CW & 3) == 0) {
+            // rows start 16-byte aligned in global memory: one float4 per lane
+#pragma unroll
+            for (int kk = 0; kk < GN_ITEMS4; ++kk) {
+                if (c_gn[kk] < 0) continue;
+                const int r = c_gn[kk] >> 16, k = c_gn[kk] & 0xffff;
+                const float* sp = sN + mul24(r + 2, G::NS) + 6 + k;  // 8-byte aligned
+                const v2f lo = lds_load2(sp), hi = lds_load2(sp + 2);
+                v4f v = {lo.x, lo.y, hi.x, hi.y};
+                *reinterpret_cast<v4f*>(reinterpret_cast<char*>(gout) +
+                                        ((uint32_t)(mul24(i0 + r, wn) + j0) * 3u + (uint32_t)k) * 4u) = v;
+            }
+        } else {
+            for (int e = ltid; e < (TH / 2) * CW; e += G::NT) {
+                const int r = e / CW, k = e - r * CW;
+                const int i = i0 + r, j = j0 + k / 3;
+                if (INTERIOR || (i < hn && j < wn))
+                    gstore32(gout, ((uint32_t)(mul24(i, wn) + j0) * 3u + (uint32_t)k) * 4u,
+                             sN[mul24(r + 2, G::NS) + 6 + k]);
+            }
+        }
+
+        // ---------------- laplacian + Q on (TH+4) x (TW+4), as 2x2 quads
+        auto do_quad = [&](int qy, int qx) {
+            // local sN rows/cols of the expand source, local sG rows/cols of the cells
+            int re, ro, ce, co, gre, gro, gce, gco;
+            if constexpr (INTERIOR) {
+                re = ro = qy + 1;
+                ce = co = qx + 1;
+                gre = 2 * qy + 4; gro = gre + 1;
+                gce = 2 * qx + 4; gco = gce + 1;
+            } else {
+                const int ye = map_clamp(y0 - 2 + 2 * qy, h), yo = map_clamp(y0 - 1 + 2 * qy, h);
+                const int xe = map_clamp(x0 - 2 + 2 * qx, w), xo = map_clamp(x0 - 1 + 2 * qx, w);
+                re = clampi((ye >> 1) - (y0 / 2 - 2), 1, G::NH - 2);
+                ro = clampi(((yo - 1) >> 1) - (y0 / 2 - 2), 0, G::NH - 2);
+                ce = clampi((xe >> 1) - (x0 / 2 - 2), 1, G::NW - 2);
+                co = clampi(((xo - 1) >> 1) - (x0 / 2 - 2), 0, G::NW - 2);
+                gre = clampi(ye - (y0 - 6), 0, G::GH - 1); gro = clampi(yo - (y0 - 6), 0, G::GH - 1);
+                gce = clampi(xe - (x0 - 6), 0, G::GW - 1); gco = clampi(xo - (x0 - 6), 0, G::GW - 1);
+            }
+            float see[3] = {0, 0, 0}, seo[3] = {0, 0, 0}, soe[3] = {0, 0, 0}, soo[3] = {0, 0, 0};
+            if constexpr (INTERIOR) {
+                // The even output row takes tap rows 0, 2, 4 from G_{l+1} rows qy, qy+1, qy+2; the odd one tap rows
+                // 1, 3 from rows qy+1, qy+2: on those two rows one packed instruction advances the even-row and
+                // the odd-row chain of the same column phase (15 instead of 25 instructions per channel).  A row's
+                // window (pixels qx .. qx+2: nine floats, 4-byte aligned) comes in as five register pairs.
+                v2f A[3], B[3];   // (see, soe) and (seo, soo) per channel
+#pragma unroll
+                for (int c = 0; c < 3; ++c) A[c] = B[c] = v2f{0.f, 0.f};
+#pragma unroll
+                for (int ar = 0; ar < 3; ++ar) {
+                    const float* wp = sN + mul24(qy + ar, G::NS) + 3 * qx;
+                    v2f W[5];
+#pragma unroll
+                    for (int t = 0; t < 5; ++t) W[t] = lds_load2u(wp + 2 * t);   // the tenth float is not used
+#pragma unroll
+                    for (int ac = 0; ac < 3; ++ac)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const int e = 3 * ac + c;
+                            if (ar == 0) A[c].x = mac<FMA>(K(0, 2 * ac), half_of(W[e >> 1], e & 1), A[c].x);
+                            else A[c] = mac2_shared<FMA>(v2f{K(2 * ar, 2 * ac), K(2 * ar - 1, 2 * ac)}, W[e >> 1], e & 1, A[c]);
+                        }
+#pragma unroll
+                    for (int ac = 0; ac < 2; ++ac)
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const int e = 3 * (1 + ac) + c;
+                            if (ar == 0) B[c].x = mac<FMA>(K(0, 2 * ac + 1), half_of(W[e >> 1], e & 1), B[c].x);
+                            else B[c] = mac2_shared<FMA>(v2f{K(2 * ar, 2 * ac + 1), K(2 * ar - 1, 2 * ac + 1)}, W[e >> 1], e & 1, B[c]);
+                        }
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    see[c] = A[c].x; soe[c] = A[c].y;
+                    seo[c] = B[c].x; soo[c] = B[c].y;
+                }
+            } else {
+            // (even row, even col): taps ty in {0,2,4} x tx in {0,2,4};  (even, odd): tx in {1,3}
+#pragma unroll
+            for (int ar = 0; ar < 3; ++ar) {
+                const float* nrow = sN + mul24(re - 1 + ar, G::NS);
+#pragma unroll
+                for (int ac = 0; ac < 3; ++ac) {
+                    const float k = K(2 * ar, 2 * ac);
+                    const float* p = nrow + (ce - 1 + ac) * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) see[c] = mac<FMA>(k, p[c], see[c]);
+                }
+#pragma unroll
+                for (int ac = 0; ac < 2; ++ac) {
+                    const float k = K(2 * ar, 2 * ac + 1);
+                    const float* p = nrow + (co + ac) * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) seo[c] = mac<FMA>(k, p[c], seo[c]);
+                }
+            }
+            // (odd row, *): ty in {1,3}
+#pragma unroll
+            for (int ar = 0; ar < 2; ++ar) {
+                const float* nrow = sN + mul24(ro + ar, G::NS);
+#pragma unroll
+                for (int ac = 0; ac < 3; ++ac) {
+                    const float k = K(2 * ar + 1, 2 * ac);
+                    const float* p = nrow + (ce - 1 + ac) * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) soe[c] = mac<FMA>(k, p[c], soe[c]);
+                }
+#pragma unroll
+                for (int ac = 0; ac < 2; ++ac) {
+                    const float k = K(2 * ar + 1, 2 * ac + 1);
+                    const float* p = nrow + (co + ac) * 3;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) soo[c] = mac<FMA>(k, p[c], soo[c]);
+                }
+            }
+            }
+            const float* gee = sG + mul24(gre, G::GS) + gce * 3;
+            const float* geo = sG + mul24(gre, G::GS) + gco * 3;
+            const float* goe = sG + mul24(gro, G::GS) + gce * 3;
+            const float* goo = sG + mul24(gro, G::GS) + gco * 3;
+            float l[4][3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                // g - 4*s: the product is exact, so one fused op rounds identically
+                l[0][c] = __builtin_fmaf(-4.0f, see[c], gee[c]);
+                l[1][c] = __builtin_fmaf(-4.0f, seo[c], geo[c]);
+                l[2][c] = __builtin_fmaf(-4.0f, soe[c], goe[c]);
+                l[3][c] = __builtin_fmaf(-4.0f, soo[c], goo[c]);
+            }
+            float qv[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                float gr = gray_of<FMA>(l[p][0], l[p][1], l[p][2]);
+                qv[p] = gr * gr;
+            }
+            float* qo = sQ + mul24(2 * qy, G::QS) + 2 * qx;
+            lds_store2(qo, qv[0], qv[1]);
+            lds_store2(qo + G::QS, qv[2], qv[3]);
+        };
+        // own quads (tile interior) ...
+#pragma unroll
+        for (int q = 0; q < G::NQ; ++q)
+            do_quad((c_own[q] >> 16) + 1, (c_own[q] & 0xffff) + 1);
+        // ... and the halo ring, spread over the first threads
+#pragma unroll
+        for (int kk = 0; kk < RING_ITEMS; ++kk)
+            if (c_ring[kk] >= 0) do_quad(c_ring[kk] >> 16, c_ring[kk] & 0xffff);
+        __syncthreads();
+
+        // ---------------- energy of the own quads + running first-max
+        const int fidx = a.frame_idx0 + f_lo + b;
+#pragma unroll
+        for (int q = 0; q < G::NQ; ++q) {
+            const int oy = c_own[q] >> 16, ox = c_own[q] & 0xffff;
+            const float* base = sQ + mul24(2 * oy, G::QS) + 2 * ox;  // 8-byte aligned
+            // Q row rr is tap row rr of the quad's upper pixels and tap row rr-1 of its lower ones: rows 1..4 advance
+            // both chains of a column with one packed instruction (60 instead of 100 per quad)
+            v2f E[2] = {v2f{0.f, 0.f}, v2f{0.f, 0.f}};   // [dx] = (upper, lower)
+#pragma unroll
+            for (int rr = 0; rr < 6; ++rr) {
+                const float* rp = base + rr * G::QS;
+                v2f V[3];
+                V[0] = lds_load2(rp);
+                V[1] = lds_load2(rp + 2);
+                V[2] = lds_load2(rp + 4);
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx)
+#pragma unroll
+                    for (int tx = 0; tx < 5; ++tx) {
+                        const int e1 = dx + tx;
+                        if (rr == 0) E[dx].x = mac<FMA>(K(0, tx), half_of(V[e1 >> 1], e1 & 1), E[dx].x);
+                        else if (rr == 5) E[dx].y = mac<FMA>(K(4, tx), half_of(V[e1 >> 1], e1 & 1), E[dx].y);
+                        else E[dx] = mac2_shared<FMA>(v2f{K(rr, tx), K(rr - 1, tx)}, V[e1 >> 1], e1 & 1, E[dx]);
+                    }
+            }
+            const float e[4] = {E[0].x, E[1].x, E[0].y, E[1].y};
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const bool win = e[p] > bE[q][p];
+                bE[q][p] = win ? e[p] : bE[q][p];
+                bI[q][p] = win ? fidx : bI[q][p];
+            }
+        }
         // no barrier needed here: the next writes to sG happen after every thread
         // passed the barrier above (sG/sN are only read before it), and sQ is
         // rewritten only after the next iteration's two barriers.
     }
 
-#ifdef MI_PHASE_CLOCK
-    if (INTERIOR && a.dbg && (tid & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) atomicAdd(a.dbg + (tid >> 6) * 16 + i, (unsigned long long)pc_acc[i]);
-        atomicAdd(a.dbg + (tid >> 6) * 16 + 15, 1ull);
-    }
-#endif
     // ---- write the running maxima back: only pixels a frame of this launch won (a fresh state: all of them)
 #pragma unroll
     for (int q = 0; q < G::NQ; ++q) {

@@ -58,7 +58,6 @@ struct TiledState {
     hipStream_t st3 = nullptr;
     std::vector<hipEvent_t> evPayIn;   // [set][level]: the level's energy pass (all streams) is through
     hipEvent_t evPay[2] = {nullptr, nullptr};   // the batch's payload passes are through
-    std::vector<hipEvent_t> evGrp;     // pair, piped: level 0's launch of frame group g is through (level 1's energy launch of g waits)
     hipEvent_t evL0i[2] = {nullptr, nullptr}, evL0b[2] = {nullptr, nullptr}, evRest[2] = {nullptr, nullptr};
     hipEvent_t evL0done[2] = {nullptr, nullptr};   // level-0 state of the batch is final (separable: after its payload pass)
     std::vector<hipEvent_t> evLvl;  // [set][level][interior|border]: per-level joins of st2 and st1
@@ -144,16 +143,9 @@ int tiled_create(mi_stack* s) {
     // they run beside; otherwise they starve and become the critical path.
     int prio_lo = 0, prio_hi = 0;
     MI_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    if (study_env("MI_SERIAL", 0)) t->st1 = t->st2 = t->st3 = s->stream;   // -DMI_STUDY: every kernel alone on the GPU
-    else {
-        const int bd = study_env("MI_BD_PRIO", 0), co = study_env("MI_CO_PRIO", 0);   // 0 high, 1 normal, 2 low
-        MI_HIP(hipStreamCreateWithPriority(&t->st1, hipStreamNonBlocking, bd == 0 ? prio_hi : bd == 1 ? 0 : prio_lo));
-        MI_HIP(hipStreamCreateWithPriority(&t->st2, hipStreamNonBlocking, co == 0 ? prio_hi : co == 1 ? 0 : prio_lo));
-        const int ps = study_env("MI_PAYLOAD_STREAM", 2);   // -DMI_STUDY: 0 = in line with the levels (rounds 2-5), 1 = a stream of their own
-        if (ps == 1) MI_HIP(hipStreamCreateWithPriority(&t->st3, hipStreamNonBlocking, co == 0 ? prio_hi : co == 1 ? 0 : prio_lo));
-        else t->st3 = ps == 2 ? t->st1 : t->st2;
-        if (study_env("MI_BD_PRIO", 0)) fprintf(stderr, "priority range lo=%d hi=%d\n", prio_lo, prio_hi);
-    }
+    MI_HIP(hipStreamCreateWithPriority(&t->st1, hipStreamNonBlocking, prio_hi));
+    MI_HIP(hipStreamCreateWithPriority(&t->st2, hipStreamNonBlocking, prio_hi));
+    t->st3 = t->st1;
     t->gstride.assign(L + 1, 0);
     MI_HIP(hipEventCreateWithFlags(&t->evInput, hipEventDisableTiming));
     for (int set = 0; set < 2; ++set) {
@@ -197,7 +189,6 @@ int tiled_sync_all(mi_stack* s) {
     if (t->stc) MI_HIP(hipStreamSynchronize(t->stc));
     if (t->st1) MI_HIP(hipStreamSynchronize(t->st1));
     if (t->st2) MI_HIP(hipStreamSynchronize(t->st2));
-    if (t->st3 && t->st3 != t->st2 && t->st3 != t->st1) MI_HIP(hipStreamSynchronize(t->st3));
     t->streams_dirty = false;
     return MI_OK;
 }
@@ -214,7 +205,6 @@ void tiled_destroy(mi_stack* s) {
     }
     for (auto e : t->evLvl) (void)hipEventDestroy(e);
     for (auto e : t->evPayIn) (void)hipEventDestroy(e);
-    for (auto e : t->evGrp) (void)hipEventDestroy(e);
     for (int i = 0; i < TiledState::NUP; ++i)
         if (t->evUp[i]) (void)hipEventDestroy(t->evUp[i]);
     for (int i = 0; i < TiledState::NPIN; ++i) {
@@ -226,7 +216,6 @@ void tiled_destroy(mi_stack* s) {
     if (t->evInput) (void)hipEventDestroy(t->evInput);
     if (t->stc) (void)hipStreamDestroy(t->stc);
     if (t->st1 && t->st1 != s->stream) (void)hipStreamDestroy(t->st1);
-    if (t->st3 && t->st3 != s->stream && t->st3 != t->st2 && t->st3 != t->st1) (void)hipStreamDestroy(t->st3);
     if (t->st2 && t->st2 != s->stream) (void)hipStreamDestroy(t->st2);
     delete t;
     tstate(s) = nullptr;
@@ -279,14 +268,12 @@ constexpr int ilcm(int a, int b) {
 // (measured on 24 MP frames: 256 frames in one launch cost 3.1 ms per 32 frames, launches of 32 frames 2.9 ms, of 16
 // frames 2.7 ms, of 8 frames 2.75 ms), so a level with many tiles runs as consecutive launches of 16 frames.  Returns the frames per chunk / per launch.
 constexpr int SEP_LAUNCH_FRAMES = 16;
+constexpr int SEP_PAR_TILES = 3072;   // tile count below which a level's frame chunks run side by side
 inline int level_chunk_frames(int nb, int tiles, bool* parallel) {
-    static const int on = study_env("MI_CHUNK", 1);           // -DMI_STUDY: 0 = never in parallel chunks
-    static const int lf = study_env("MI_LAUNCH_FRAMES", SEP_LAUNCH_FRAMES);
-    static const int par = study_env("MI_PAR_TILES", 3072);   // -DMI_STUDY: tile count below which chunks run side by side
-    const int c = par / std::max(tiles, 1);
-    *parallel = on && c > 1 && nb >= 32;
-    if (!*parallel) return std::min(nb, lf);
-    return std::min(lf, std::max(16, cdiv(cdiv(nb, c), 4) * 4));
+    const int c = SEP_PAR_TILES / std::max(tiles, 1);
+    *parallel = c > 1 && nb >= 32;
+    if (!*parallel) return std::min(nb, SEP_LAUNCH_FRAMES);
+    return std::min(SEP_LAUNCH_FRAMES, std::max(16, cdiv(cdiv(nb, c), 4) * 4));
 }
 
 // Super-block order of an interior launch: longest-processing-time-first assignment of the super-blocks (weight = tiles
@@ -372,29 +359,6 @@ int launch_level(mi_stack* s, int l, int set, const void* src, size_t src_stride
     a.frame_idx0 = s->first_index + s->n_pushed;
     for (int i = 0; i < 3; ++i)
         for (int j = i; j < 3; ++j) a.K.c[i == 0 ? j : (i == 1 ? 2 + j : 5)] = s->K.k[i * 5 + j];
-    a.ablate = study_env("MI_ABLATE", 0);   // -DMI_STUDY builds only (results are wrong when set)
-#ifdef MI_PHASE_CLOCK
-    static unsigned long long* dbg_dev = nullptr;
-    if (l == 0) {
-        if (!dbg_dev) {
-            MI_HIP(hipMalloc(&dbg_dev, 16 * 16 * 8));
-            MI_HIP(hipMemset(dbg_dev, 0, 16 * 16 * 8));
-        } else {   // print the previous launch's numbers
-            unsigned long long hbuf[16 * 16];
-            MI_HIP(hipMemcpy(hbuf, dbg_dev, sizeof hbuf, hipMemcpyDeviceToHost));
-            MI_HIP(hipMemset(dbg_dev, 0, 16 * 16 * 8));
-            static const char* nm[9] = {"stage", "bar1", "prefetch", "reduce", "bar2", "gnstore", "lapq", "bar3", "energy"};
-            for (int wv = 0; wv < NT / 64; ++wv) {
-                if (!hbuf[wv * 16 + 15]) continue;
-                fprintf(stderr, "wave %d:", wv);
-                for (int i = 0; i < 9; ++i)
-                    fprintf(stderr, " %s %.0f", nm[i], (double)hbuf[wv * 16 + i] / (double)hbuf[wv * 16 + 15] / nb);
-                fprintf(stderr, "  (cycles per frame)\n");
-            }
-        }
-        a.dbg = dbg_dev;
-    } else a.dbg = nullptr;
-#endif
     const size_t ldsA = (size_t)GA::LDS_FLOATS * sizeof(float), ldsB = (size_t)GB::LDS_FLOATS * sizeof(float);
     auto kin = COARSE_NAME ? level_fused_coarse<TIn, FMA, true, TH, TW, NT, PADA> : level_fused<TIn, FMA, true, TH, TW, NT, PADA>;
     auto kbd = level_fused<TIn, FMA, false, BH, BW, BNT, false>;
@@ -447,7 +411,7 @@ int launch_level(mi_stack* s, int l, int set, const void* src, size_t src_stride
         a.first = first && f0 == 0;
         a.frame_idx0 = idx0 + f0;
     };
-    if (nborder > 0 && !MI_ABL(256)) {   // border first: its few, latency-bound workgroups should claim their slots early
+    if (nborder > 0) {   // border first: its few, latency-bound workgroups should claim their slots early
         ProfScope ps(s, MI_PROF_LEVEL, bytes * (1.0 - frac_in), st_bd);
         ps.r.launches = nlaunch;
         for (int f0 = 0; f0 < nb; f0 += step) {
@@ -455,7 +419,7 @@ int launch_level(mi_stack* s, int l, int set, const void* src, size_t src_stride
             hipLaunchKernelGGL(kbd, dim3(nborder, nchunks), dim3(BNT), ldsB, st_bd, a);
         }
     }
-    if (!MI_ABL(512) && nyi > 0) {
+    if (nyi > 0) {
         const int nsb = cdiv(nxi, SB) * cdiv(nyi, SB);
         ProfScope ps(s, l == 0 ? MI_PROF_LEVEL0 : MI_PROF_LEVEL, bytes * frac_in, st_in);
         ps.r.launches = nlaunch;
@@ -475,10 +439,6 @@ int launch_level(mi_stack* s, int l, int set, const void* src, size_t src_stride
 }
 
 // `ev_bd`: recorded on st_bd behind the border kernel when the level ran in chunks (the merge on st_in waits for it).
-// `f_begin`, `f_end`: launch the frames [f_begin, f_end) of the batch only (levels that run as consecutive launches; the
-// interleaved level-0 / level-1 schedule of run_batch) -- the whole batch by default.
-// `MF`: level 0 of 8 / 16-bit frames with the reduce on the matrix pipe (kernels_sep.hpp, MI_SEP_MFMA): its own tile height,
-// for the interior and the border launch alike.
 // `info` (optional): what run_batch needs to finish the level -- how many chunk partials sep_payload has to fold (it then takes
 // merge_chunks' place) and whether border tiles were launched on st_bd (only then the streams have to join).  `ev_sync`
 // (optional): recorded on st_in and waited for on st_bd in front of a border launch (everything st_in has done so far).
@@ -488,20 +448,17 @@ int launch_level(mi_stack* s, int l, int set, const void* src, size_t src_stride
 // 3 = the pair's payload pass tile by tile (level_sep_pl, one launch over the whole batch: fills bestLap[l] and bestLap[l+1]
 // of the tiles with few distinct winners, flags the others in tileFlag).
 struct SepLevelInfo { int nparts = 0; bool border = false; };
-template <typename TIn, bool L0_NAME, bool MF = false, int PM = 0>
+template <typename TIn, bool L0_NAME, int PM = 0>
 int launch_level_sep(mi_stack* s, int l, int set, const void* src, size_t src_stride, int nb, hipStream_t st_in,
-                     hipStream_t st_bd, hipEvent_t ev_bd, int f_begin = 0, int f_end = -1, SepLevelInfo* info = nullptr,
+                     hipStream_t st_bd, hipEvent_t ev_bd, SepLevelInfo* info = nullptr,
                      hipEvent_t ev_sync = nullptr) {
-    constexpr int TH = MF ? SEP_MF_TH : MI_SEP_TH, NT = MF ? SEP_MF_NT : sep_nt<TIn>();
+    constexpr int TH = MI_SEP_TH, NT = sep_nt<TIn>();
     using SG = SepGeom<TH, NT>;
     constexpr int TW = SG::TW;
     TiledState* t = tstate(s);
     LevelArgs a{};
     a.src = src;
     a.src_stride = src_stride;
-#ifdef MI_STUDY_SAME_FRAME   // study: every frame of a level-0 launch reads frame 0's addresses (L2 / Infinity Cache instead of HBM)
-    if (l == 0) a.src_stride = 0;
-#endif
     a.gnext = t->Gb[set][l + 1];
     a.gnext_stride = t->gstride[l + 1];
     a.nframes = nb;
@@ -512,7 +469,6 @@ int launch_level_sep(mi_stack* s, int l, int set, const void* src, size_t src_st
     a.g1_keep = -1;
     const size_t gray_stride = (size_t)a.hn * a.wn;
     if constexpr (PM == 1 || PM == 3) {
-        static_assert(!MF, "the matrix-pipe reduce has no pair form");
         if (l + 2 > s->L) return fail(MI_ERR_INVALID, "level pair at level %d of %d", l, s->L);
         if (!t->Gkeep[set][l + 1]) {   // (first pair batch of this level and set: one image)
             int rc = dev_alloc_t(s, &t->Gkeep[set][l + 1], t->gstride[l + 1]);
@@ -534,8 +490,7 @@ int launch_level_sep(mi_stack* s, int l, int set, const void* src, size_t src_st
     // The "interior" launch covers every tile whose staged patch may be mirrored into place (kernels_sep.hpp, edge tiles):
     // all of the grid, except the tile rows / columns that reach an ODD far edge (those stay with the border kernel), and
     // nothing at all on levels too small for a single reflection per side.
-    static const int edge_fold = study_env("MI_EDGE_FOLD", 1);   // -DMI_STUDY: 0 = the round-2 interior / border split
-    if (edge_fold && a.h >= 16 && a.w >= 16) {
+    if (a.h >= 16 && a.w >= 16) {
         a.iy0 = a.ix0 = 0;
         a.iy1 = (a.h & 1) ? std::max(0, (a.h - 6) / TH * TH) : cdiv(a.h, TH) * TH;
         a.ix1 = (a.w & 1) ? std::max(0, (a.w - 6) / TW * TW) : cdiv(a.w, TW) * TW;
@@ -554,47 +509,17 @@ int launch_level_sep(mi_stack* s, int l, int set, const void* src, size_t src_st
     a.frame_idx0 = s->first_index + s->n_pushed;
     for (int i = 0; i < 3; ++i) a.k1d[i] = s->k1d[i];
     for (int i = 0; i < 4; ++i) a.rk[i] = s->rk[i];
-    a.mfma_ok = s->mfma_ok;
-    a.ablate = study_env("MI_ABLATE", 0);   // -DMI_STUDY builds only (results are wrong when set)
-#ifdef MI_PHASE_CLOCK
-    static unsigned long long* dbg_dev = nullptr;
-    if (l == 0) {
-        if (!dbg_dev) {
-            MI_HIP(hipMalloc(&dbg_dev, 16 * 16 * 8));
-            MI_HIP(hipMemset(dbg_dev, 0, 16 * 16 * 8));
-        } else {   // print the previous level-0 pass's numbers (cycles per wave and frame)
-            unsigned long long hbuf[16 * 16];
-            MI_HIP(hipMemcpy(hbuf, dbg_dev, sizeof hbuf, hipMemcpyDeviceToHost));
-            MI_HIP(hipMemset(dbg_dev, 0, 16 * 16 * 8));
-            static const char* nm[10] = {"stage", "bar1", "pfissue", "P1", "bar2", "P2", "bar3", "P3", "bar4", "P4"};
-            for (int wv = 0; wv < NT / 64; ++wv) {
-                if (!hbuf[wv * 16 + 15]) continue;
-                fprintf(stderr, "wave %d:", wv);
-                double tot = 0;
-                for (int i = 0; i < 10; ++i) {
-                    const double v = (double)hbuf[wv * 16 + i] / (double)hbuf[wv * 16 + 15] / std::min(nb, SEP_LAUNCH_FRAMES);
-                    tot += v;
-                    fprintf(stderr, " %s %.0f", nm[i], v);
-                }
-                fprintf(stderr, "  total %.0f (clock ticks per frame)\n", tot);
-            }
-        }
-        a.dbg = dbg_dev;
-    } else a.dbg = nullptr;
-#endif
     const size_t lds = (size_t)(PM == 3 ? sep_pl_lds_floats<TIn, TH, NT>(false) : PM == 2 ? sep_e_lds_floats<TH, NT>()
                                         : SG::LDS_FLOATS + (PM == 1 ? 3 * SG::NH * SG::NW : 0)) * sizeof(float);   // border tiles
     const size_t lds_in = (size_t)(PM == 3 ? sep_pl_lds_floats<TIn, TH, NT>(true) : PM == 2 ? sep_e_lds_floats<TH, NT>()
-                                           : MF ? SG::lds_floats_mf((int)sizeof(TIn))
-                                                : SG::lds_floats((int)sizeof(TIn), true) + (PM == 1 && sizeof(TIn) <= 2 ? 3 * SG::NH * SG::NW : 0)) * sizeof(float);   // interior tiles
+                                           : SG::lds_floats((int)sizeof(TIn), true) + (PM == 1 && sizeof(TIn) <= 2 ? 3 * SG::NH * SG::NW : 0)) * sizeof(float);   // interior tiles
     void (*kin)(LevelArgs);
     void (*kbd)(LevelArgs);
     if constexpr (PM == 1) { kin = level_sep_pair<TIn, true, TH, NT>; kbd = level_sep_pair<TIn, false, TH, NT>; }
     else if constexpr (PM == 2) { kin = level_sep_e<true, TH, NT>; kbd = level_sep_e<false, TH, NT>; }
     else if constexpr (PM == 3) { kin = level_sep_pl<TIn, true, TH, NT>; kbd = level_sep_pl<TIn, false, TH, NT>; }
     else {
-        if constexpr (MF) kin = level_sep_mf<TIn, TH, NT>;
-        else kin = L0_NAME ? level_sep<TIn, true, TH, NT> : level_sep_coarse<TIn, true, TH, NT>;
+        kin = L0_NAME ? level_sep<TIn, true, TH, NT> : level_sep_coarse<TIn, true, TH, NT>;
         kbd = level_sep<TIn, false, TH, NT>;
     }
     static thread_local bool attr_set = false;
@@ -634,21 +559,16 @@ int launch_level_sep(mi_stack* s, int l, int set, const void* src, size_t src_st
     const int nborder = ntiles - nyi * nxi;
     const int nsb = cdiv(nxi, SEP_SBW) * cdiv(nyi, SEP_SBH);
     int ngroups = cdiv(nsb, 8) * 8;   // super-block-sized groups of workgroups of the interior launch
-    if (nyi > 0 && !MI_ABL(4096)) {
+    if (nyi > 0) {
         int rc = build_sb_order(s, l, nyi, nxi, SEP_SBW, SEP_SBH);
         if (rc) return rc;
         if (t->sbOrder[l]) { a.sb_order = t->sbOrder[l]; ngroups = t->sbGroups[l]; }
     }
     const int first = a.first, idx0 = a.frame_idx0;
-    if (f_end < 0 || parallel) { f_begin = 0; f_end = nb; }
-    const int step = parallel ? nb : fc, nlaunch = cdiv(f_end - f_begin, step);
-    const double part = (double)(f_end - f_begin) / (double)nb;   // share of the batch's bytes this call launches
+    const int step = parallel ? nb : fc, nlaunch = cdiv(nb, step);
     auto frames_of = [&](int f0) {
-        const int nf = parallel ? nb : std::min(fc, f_end - f0);
+        const int nf = parallel ? nb : std::min(fc, nb - f0);
         a.src = (const char*)src + (size_t)f0 * src_stride;
-#ifdef MI_STUDY_SAME_FRAME
-        if (l == 0) a.src = src;
-#endif
         if constexpr (PM == 3) {
         } else if constexpr (PM == 1) {
             a.gray1 = t->Gb[set][l + 1] + (size_t)f0 * gray_stride;
@@ -663,22 +583,22 @@ int launch_level_sep(mi_stack* s, int l, int set, const void* src, size_t src_st
     // one timing-event pair around each stream's sequence of launches (an event record between two kernels of a stream
     // costs a few microseconds of idle GPU: 30 launches per level pass)
     if (info) { info->nparts = nchunks - 1; info->border = nborder > 0; }
-    if (nborder > 0 && !MI_ABL(256)) {
+    if (nborder > 0) {
         if (ev_sync) {
             MI_HIP(hipEventRecord(ev_sync, st_in));
             MI_HIP(hipStreamWaitEvent(st_bd, ev_sync, 0));
         }
-        ProfScope ps(s, MI_PROF_LEVEL, bytes * (1.0 - frac_in) * part, st_bd);
+        ProfScope ps(s, MI_PROF_LEVEL, bytes * (1.0 - frac_in), st_bd);
         ps.r.launches = nlaunch;
-        for (int f0 = f_begin; f0 < f_end; f0 += step) {
+        for (int f0 = 0; f0 < nb; f0 += step) {
             frames_of(f0);
             hipLaunchKernelGGL(kbd, dim3(nborder, nchunks), dim3(NT), lds, st_bd, a);
         }
     }
     if (nyi > 0) {
-        ProfScope ps(s, l == 0 && PM != 3 ? MI_PROF_LEVEL0 : MI_PROF_LEVEL, bytes * frac_in * part, st_in);
+        ProfScope ps(s, l == 0 && PM != 3 ? MI_PROF_LEVEL0 : MI_PROF_LEVEL, bytes * frac_in, st_in);
         ps.r.launches = nlaunch;
-        for (int f0 = f_begin; f0 < f_end; f0 += step) {
+        for (int f0 = 0; f0 < nb; f0 += step) {
             frames_of(f0);
             hipLaunchKernelGGL(kin, dim3(ngroups * SEP_SBW * SEP_SBH, nchunks), dim3(NT), lds_in, st_in, a);
         }
@@ -750,7 +670,7 @@ int launch_payload_pair_tiles(mi_stack* s, int l, int set, const void* src, size
     int rc;
     if (!t->tileFlag[l] && (rc = dev_alloc_t(s, &t->tileFlag[l], ntiles))) return rc;
     MI_HIP(hipMemsetAsync(t->tileFlag[l], 0, ntiles, st));
-    if ((rc = launch_level_sep<TIn, false, false, 3>(s, l, set, src, src_stride, nb, st, st, nullptr))) return rc;
+    if ((rc = launch_level_sep<TIn, false, 3>(s, l, set, src, src_stride, nb, st, st, nullptr))) return rc;
     if ((rc = launch_payload_pair0<TIn>(s, l, set, src, src_stride, nb, st, 0, t->tileFlag[l]))) return rc;
     return launch_payload_pair1<TIn>(s, l, set, src, src_stride, nb, st, 0, t->tileFlag[l]);
 }
@@ -768,19 +688,10 @@ int launch_payload_pair_tiles(mi_stack* s, int l, int set, const void* src, size
 //    payload is the per-quad recomputation, and it ends up as the tail of the batch.
 //  * short batches: the once-per-batch payload recomputation outweighs level 1's gain (a 64-frame shard: 11.0 against 8.1 ms).
 constexpr int SEP_PAIR_MIN_FRAMES = 192;
-#ifndef MI_L1E_PIPE_DEFAULT
-#define MI_L1E_PIPE_DEFAULT 0
-#endif
 inline void sep_pair_plan(const mi_stack* s, int nb, std::vector<int>& pm) {
     pm.assign(std::max(s->L, 1), 0);
     if (!s->sep || s->p.pair_levels == 2) return;
-    static const int plan = study_env("MI_PAIR_PLAN", -1);   // -DMI_STUDY: bit l = level l is the first level of a pair
     int l0;
-    if (plan >= 0) {
-        for (int l = 0; l + 2 <= s->L; ++l)
-            if (((plan >> l) & 1) && pm[l] == 0) { pm[l] = 1; pm[l + 1] = 2; }
-        return;
-    }
     if (s->p.pair_levels == 1) l0 = 0;
     else if (s->p.pair_levels == 3) l0 = 1;
     else {
@@ -804,18 +715,6 @@ int launch_payload_exact(mi_stack* s, int l, int set, const void* src, size_t sr
                        t->gstride[l + 1], nb, s->lh[l], s->lw[l], s->lh[l + 1], s->lw[l + 1], (const int32_t*)s->bestIdx[l],
                        s->first_index + s->n_pushed, s->bestLap[l], K);
     return MI_OK;
-}
-
-// level 0 of the separable arithmetic: the matrix-pipe form of the reduce for 8 / 16-bit frames when the taps allow it
-template <typename TIn>
-int launch_level0_sep(mi_stack* s, int set, const void* src, size_t src_stride, int nb, hipStream_t st_in, hipStream_t st_bd,
-                      hipEvent_t ev_bd, int f_begin = 0, int f_end = -1, SepLevelInfo* info = nullptr) {
-    if constexpr (MI_SEP_MFMA && sizeof(TIn) == 1) {   // (16-bit frames: two byte planes, ten matrix instructions per task -- measured slower)
-        static const int mf_off = study_env("MI_NO_MFMA", 0);   // -DMI_STUDY: the VALU form, for A/B runs
-        if (s->mfma_ok && !mf_off)
-            return launch_level_sep<TIn, true, true>(s, 0, set, src, src_stride, nb, st_in, st_bd, ev_bd, f_begin, f_end, info);
-    }
-    return launch_level_sep<TIn, true, false>(s, 0, set, src, src_stride, nb, st_in, st_bd, ev_bd, f_begin, f_end, info);
 }
 
 template <typename TIn, bool FMA>
@@ -849,60 +748,12 @@ int run_batch(mi_stack* s, const void* frames, size_t stride, int nb) {
     // before the level-0 interior kernel by the stream itself; the border kernel runs on st1 and needs the event
     MI_HIP(hipEventRecord(t->evInput, st0));
     MI_HIP(hipStreamWaitEvent(st1, t->evInput, 0));
-    // -DMI_STUDY, MI_INTERLEAVE01=1: level 1 of frame group g right behind level 0 of the same group, on the same stream (the
-    // G_1 images level 0 just wrote are the freshest lines of the 256 MB Infinity Cache when level 1 reads them), instead of
-    // all of level 0, then all of level 1.  Only when both levels run as consecutive launches without border tiles.
-    static const int interleave01 = study_env("MI_INTERLEAVE01", 0);
-    bool il = false;
     SepLevelInfo li0;
     std::vector<int> pm;   // the batch's pair plan (sep_pair_plan): 1 = first level of a pair, 2 = second
     sep_pair_plan(s, nb, pm);
     const bool pair = pm[0] == 1;
-    // pair: pipe level 1's energy pass behind level 0's launches, group by group -- when both levels run as consecutive
-    // launches and have no border tiles (even sizes)
-    bool l1e_pipe = false;
-    if (pair) {
-        static const int pipe_on = study_env("MI_L1E_PIPE", MI_L1E_PIPE_DEFAULT);
-        bool p0 = false, p1 = false;
-        level_chunk_frames(nb, cdiv(s->lw[0], 56) * cdiv(s->lh[0], MI_SEP_TH), &p0);
-        level_chunk_frames(nb, cdiv(s->lw[1], 56) * cdiv(s->lh[1], MI_SEP_TH), &p1);
-        l1e_pipe = pipe_on && !p0 && !p1 && !(s->lh[0] & 1) && !(s->lw[0] & 1) && !(s->lh[1] & 1) && !(s->lw[1] & 1);
-    }
-    if (s->sep && !pair && interleave01 && L >= 2 && nb > SEP_LAUNCH_FRAMES) {
-        bool p0 = false, p1 = false;
-        const int nt0 = cdiv(s->lw[0], 56) * cdiv(s->lh[0], MI_SEP_TH), nt1 = cdiv(s->lw[1], 56) * cdiv(s->lh[1], MI_SEP_TH);
-        level_chunk_frames(nb, nt0, &p0);
-        level_chunk_frames(nb, nt1, &p1);
-        il = !p0 && !p1 && !(s->lh[0] & 1) && !(s->lw[0] & 1) && !(s->lh[1] & 1) && !(s->lw[1] & 1);
-    }
-    if (il) {
-        for (int f0 = 0; f0 < nb && !rc; f0 += SEP_LAUNCH_FRAMES) {
-            const int f1 = std::min(nb, f0 + SEP_LAUNCH_FRAMES);
-            rc = launch_level0_sep<TIn>(s, set, frames, stride, nb, st0, st1, t->evL0b[set], f0, f1);
-            if (!rc) rc = launch_level_sep<float, false>(s, 1, set, t->Gb[set][1], t->gstride[1] * sizeof(float), nb, st0, st1,
-                                                         t->evLvl[(set * (L + 1) + 1) * 2 + 1], f0, f1);
-        }
-    } else if (pair && l1e_pipe) {
-        // level 1's energy launch of a frame group right behind level 0's launch of that group, on st2 (it needs the group's
-        // gray(G_1) and G_2 only): the light kernel beside the heavy one
-        const int ngrp = cdiv(nb, SEP_LAUNCH_FRAMES);
-        while ((int)t->evGrp.size() < ngrp) {
-            hipEvent_t e;
-            MI_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            t->evGrp.push_back(e);
-        }
-        for (int g = 0; g < ngrp && !rc; ++g) {
-            const int f0 = g * SEP_LAUNCH_FRAMES, f1 = std::min(nb, f0 + SEP_LAUNCH_FRAMES);
-            rc = launch_level_sep<TIn, true, false, 1>(s, 0, set, frames, stride, nb, st0, st1, t->evL0b[set], f0, f1, &li0);
-            if (rc) break;
-            MI_HIP(hipEventRecord(t->evGrp[g], st0));
-            MI_HIP(hipStreamWaitEvent(st2, t->evGrp[g], 0));
-            SepLevelInfo li1;
-            rc = launch_level_sep<float, false, false, 2>(s, 1, set, t->Gb[set][1], (size_t)s->lh[1] * s->lw[1] * sizeof(float), nb,
-                                                          st2, st1, t->evLvl[(set * (L + 1) + 1) * 2 + 1], f0, f1, &li1);
-        }
-    } else if (pair) rc = launch_level_sep<TIn, true, false, 1>(s, 0, set, frames, stride, nb, st0, st1, t->evL0b[set], 0, -1, &li0);
-    else if (s->sep) rc = launch_level0_sep<TIn>(s, set, frames, stride, nb, st0, st1, t->evL0b[set], 0, -1, &li0);
+    if (pair) rc = launch_level_sep<TIn, true, 1>(s, 0, set, frames, stride, nb, st0, st1, t->evL0b[set], &li0);
+    else if (s->sep) rc = launch_level_sep<TIn, true>(s, 0, set, frames, stride, nb, st0, st1, t->evL0b[set], &li0);
     else
         rc = launch_level<TIn, FMA, MI_TILE0_H, MI_TILE0_W, MI_TILE0_NT, MI_TILE_PAD != 0, MI_TILE_H, MI_TILE_W, MI_TILE_NT>(
             s, 0, set, frames, stride, nb, st0, st1, t->evL0b[set]);
@@ -938,20 +789,17 @@ int run_batch(mi_stack* s, const void* frames, size_t stride, int nb) {
     };
     // coarser levels: interior tiles on st2, border tiles on st1 (disjoint tiles of one level run
     // side by side); both streams join after every level because level l+1 reads all of G_{l+1}
-    static const int only_l0 = study_env("MI_ONLY_L0", 0);   // -DMI_STUDY: level 0 alone on the GPU (results are wrong)
-    for (int l = 1; l < L && !only_l0; ++l) {
+    for (int l = 1; l < L; ++l) {
         // coarser levels that still have thousands of tiles (4 MP and more: level 1 of a 24 MP frame) run on
-        // level 0's tile configuration -- less halo per tile: +2 % on the 256 x 24 MP job; MI_WIDE_LEVELS overrides
-        static const int wide_levels = study_env("MI_WIDE_LEVELS", -1);
-        const bool wide = wide_levels >= 0 ? l <= wide_levels : (size_t)s->lh[l] * s->lw[l] >= ((size_t)4 << 20);
+        // level 0's tile configuration -- less halo per tile: +2 % on the 256 x 24 MP job
+        const bool wide = (size_t)s->lh[l] * s->lw[l] >= ((size_t)4 << 20);
         hipEvent_t ei = t->evLvl[(set * (L + 1) + l) * 2], eb = t->evLvl[(set * (L + 1) + l) * 2 + 1];
         if (pm[l] == 2) {
             // the second level of a pair: energy only, from gray(G_l) and G_{l+1} (both written by level l - 1's kernel);
             // the pair's payload pass recomputes the winners' G_l from level l - 1's images
             SepLevelInfo li;
-            if (l == 1 && l1e_pipe) ;   // (launched group by group behind level 0, above: no chunks, no border tiles)
-            else if ((rc = launch_level_sep<float, false, false, 2>(s, l, set, t->Gb[set][l], (size_t)s->lh[l] * s->lw[l] * sizeof(float), nb,
-                                                                    st2, st1, eb, 0, -1, &li, ei)))
+            if ((rc = launch_level_sep<float, false, 2>(s, l, set, t->Gb[set][l], (size_t)s->lh[l] * s->lw[l] * sizeof(float), nb,
+                                                        st2, st1, eb, &li, ei)))
                 return rc;
             if (li.border) {
                 MI_HIP(hipEventRecord(eb, st1));
@@ -967,8 +815,8 @@ int run_batch(mi_stack* s, const void* frames, size_t stride, int nb) {
             // the first level of a pair beyond level 0: level_sep_pair on the float images of level l (gray(G_{l+1}) and G_{l+2}
             // out); its payload waits for level l + 1
             SepLevelInfo li;
-            if ((rc = launch_level_sep<float, false, false, 1>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, eb,
-                                                               0, -1, &li, ei)))
+            if ((rc = launch_level_sep<float, false, 1>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, eb,
+                                                        &li, ei)))
                 return rc;
             if (li.border) {
                 MI_HIP(hipEventRecord(eb, st1));
@@ -977,12 +825,12 @@ int run_batch(mi_stack* s, const void* frames, size_t stride, int nb) {
             nparts_first = li.nparts;
             continue;
         }
-        if (s->sep && !(il && l == 1)) {
+        if (s->sep) {
             // interior tiles on st2; border tiles, if the level has any, on st1 behind everything st2 has done so far (`ei`);
             // the streams join again (`eb`) in front of the payload pass, which also folds the frame chunks' partial maxima
             SepLevelInfo li;
-            if ((rc = launch_level_sep<float, false>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, eb, 0, -1,
-                                                     &li, ei)))
+            if ((rc = launch_level_sep<float, false>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, eb, &li,
+                                                     ei)))
                 return rc;
             if (li.border) {
                 MI_HIP(hipEventRecord(eb, st1));
@@ -992,9 +840,7 @@ int run_batch(mi_stack* s, const void* frames, size_t stride, int nb) {
             if ((rc = launch_payload_sep<float>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st3, li.nparts))) return rc;
             continue;
         }
-        if (s->sep && il && l == 1)
-            rc = MI_OK;   // level 1 ran interleaved with level 0 on st0 (st2 waited for evL0i, recorded behind both)
-        else if (wide)
+        if (wide)
             rc = launch_level<float, FMA, MI_TILE0_H, MI_TILE0_W, MI_TILE0_NT, MI_TILE_PAD != 0, MI_TILE_H, MI_TILE_W, MI_TILE_NT, true>(
                 s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, t->evLvl[(set * (L + 1) + l) * 2 + 1]);
         else
@@ -1012,7 +858,7 @@ int run_batch(mi_stack* s, const void* frames, size_t stride, int nb) {
             return rc;
     }
     MI_HIP(hipGetLastError());
-    if (!only_l0) {   // base level of the whole batch
+    {   // base level of the whole batch
         ProfScope ps(s, MI_PROF_BASE, 0.0, st2);
         const int hb = s->lh[L], wb = s->lw[L], npix = hb * wb;
         MI_HIP(hipMemsetAsync(t->cnt[set], 0, sizeof(uint32_t) * s->nlevels_hist * nb, st2));
@@ -1103,9 +949,7 @@ int tiled_push(mi_stack* s, const void* dev_frames, int n, size_t stride) {
         // levels, which is latency-bound and scales with the batch length.
         const int left = n - f0;
         int nb = left > t->bcap ? t->bcap : left;
-        static const int taper = study_env("MI_TAPER", 1);   // 0 / 2: timing studies (-DMI_STUDY)
-        if (taper == 1 && left <= t->bcap && left >= 16 && n > t->bcap) nb = (left / 2 + 3) & ~3;
-        if (taper == 2 && left == t->bcap && n > t->bcap) nb = t->bcap / 2;
+        if (left <= t->bcap && left >= 16 && n > t->bcap) nb = (left / 2 + 3) & ~3;
         if (sep_nb) nb = std::min(left, sep_nb);
         const void* fr = (const char*)dev_frames + (size_t)f0 * stride;
         switch (s->p.in_dtype) {

@@ -111,9 +111,8 @@ def test_product_does_not_import_oracle():
 
 
 def test_release_library_reads_no_environment_variable():
-    """The timing-study knobs (MI_ABLATE, MI_TAPER, MI_SERIAL, MI_CHUNK, MI_LAUNCH_FRAMES, ...) exist only in the -DMI_STUDY
-    build: the shipped library neither imports getenv nor contains their names, so a stray environment variable cannot
-    change a user's stack."""
+    """The retired timing-study knobs (MI_ABLATE, MI_TAPER, MI_SERIAL, MI_CHUNK, MI_LAUNCH_FRAMES, ...) stay out: the shipped
+    library neither imports getenv nor contains their names, so a stray environment variable cannot change a user's stack."""
     import re
     import subprocess
     from shinestacker_amd import build as b

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build named variants of the library HERE (hipcc cross-compiles; the .so files travel to the GPU box with gpurun):
-#   tools/variants_build.sh base "" dma "-DMI_SEP_DMA=1" th44 "-DMI_SEP_TH=44"
+#   tools/variants_build.sh base "" th44 "-DMI_SEP_TH=44"
 # -> shinestacker_amd/csrc/variants/libmi355stack_<name>.so ; run them with tools/variants_run.sh
 cd "$(dirname "$0")/.."
 mkdir -p shinestacker_amd/csrc/variants
