@@ -30,7 +30,6 @@ using namespace mi;
 struct mi_stack;
 namespace mi {
 // LDS-tiled production path + host-frame staging (tiled_host.hpp)
-bool tiled_available();
 int tiled_create(mi_stack* s);
 void tiled_destroy(mi_stack* s);
 int tiled_reset(mi_stack* s);
@@ -168,6 +167,19 @@ struct ProfScope {
         s->recs.push_back(r);
     }
 };
+
+// fn(TIn{}, std::integral_constant<bool, FMA>{}) for the handle's input type and FMA switch: the one place that turns
+// them into template arguments
+template <typename Fn>
+int dispatch_input(const mi_stack* s, Fn&& fn) {
+    const bool fma = s->p.use_fma != 0;
+    switch (s->p.in_dtype) {
+        case MI_U8: return fma ? fn(uint8_t{}, std::true_type{}) : fn(uint8_t{}, std::false_type{});
+        case MI_U16: return fma ? fn(uint16_t{}, std::true_type{}) : fn(uint16_t{}, std::false_type{});
+        case MI_F32: return fma ? fn(float{}, std::true_type{}) : fn(float{}, std::false_type{});
+    }
+    return fail(MI_ERR_INVALID, "bad in_dtype %d", s->p.in_dtype);
+}
 
 int prof_drain(mi_stack* s) {
     if (s->recs.empty()) return MI_OK;
@@ -418,34 +430,14 @@ int push_device_frames(mi_stack* s, const void* dev_frames, int n, size_t stride
 
 }  // namespace
 int mi::dispatch_push(mi_stack* s, const void* dev_frames, int n, size_t stride) {
-    const bool fma = s->p.use_fma != 0;
     if (s->p.impl == MI_IMPL_TILED) return tiled_push(s, dev_frames, n, stride);
-    if (s->f64) {
-        switch (s->p.in_dtype) {
-            case MI_U8:
-                return fma ? push_device_frames_f64<uint8_t, true>(s, dev_frames, n, stride)
-                           : push_device_frames_f64<uint8_t, false>(s, dev_frames, n, stride);
-            case MI_U16:
-                return fma ? push_device_frames_f64<uint16_t, true>(s, dev_frames, n, stride)
-                           : push_device_frames_f64<uint16_t, false>(s, dev_frames, n, stride);
-            case MI_F32:
-                return fma ? push_device_frames_f64<float, true>(s, dev_frames, n, stride)
-                           : push_device_frames_f64<float, false>(s, dev_frames, n, stride);
-        }
-        return fail(MI_ERR_INVALID, "bad in_dtype %d", s->p.in_dtype);
-    }
-    switch (s->p.in_dtype) {
-        case MI_U8:
-            return fma ? push_device_frames<uint8_t, true>(s, dev_frames, n, stride)
-                       : push_device_frames<uint8_t, false>(s, dev_frames, n, stride);
-        case MI_U16:
-            return fma ? push_device_frames<uint16_t, true>(s, dev_frames, n, stride)
-                       : push_device_frames<uint16_t, false>(s, dev_frames, n, stride);
-        case MI_F32:
-            return fma ? push_device_frames<float, true>(s, dev_frames, n, stride)
-                       : push_device_frames<float, false>(s, dev_frames, n, stride);
-    }
-    return fail(MI_ERR_INVALID, "bad in_dtype %d", s->p.in_dtype);
+    if (s->f64)
+        return dispatch_input(s, [&](auto tin, auto fma) {
+            return push_device_frames_f64<decltype(tin), decltype(fma)::value>(s, dev_frames, n, stride);
+        });
+    return dispatch_input(s, [&](auto tin, auto fma) {
+        return push_device_frames<decltype(tin), decltype(fma)::value>(s, dev_frames, n, stride);
+    });
 }
 namespace {
 
@@ -1348,7 +1340,7 @@ int mi_stack_create(mi_stack_t** out, const mi_stack_params_t* params) {
 
     mi_stack* s = new mi_stack();
     s->p = p;
-    if (s->p.impl == MI_IMPL_AUTO) s->p.impl = tiled_available() ? MI_IMPL_TILED : MI_IMPL_SIMPLE;
+    if (s->p.impl == MI_IMPL_AUTO) s->p.impl = MI_IMPL_TILED;
     // levels = int(log2(min(h,w)/min_size)), pyramid.py:165; stop when a side < 4, :129-130
     {
         double r = (double)(p.height < p.width ? p.height : p.width) / (double)p.min_size;

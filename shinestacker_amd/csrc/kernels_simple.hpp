@@ -406,25 +406,6 @@ __global__ void collapse_simple(const float* __restrict__ up, int hs, int ws,
     out[p + 2] = e2 + lap[p + 2];
 }
 
-// the finest collapse step fused with clip(abs()) and the cast (pyramid.py:62-64, :179): the collapsed float image
-// never goes to HBM (mi_stack_get_level(MI_TAP_COLLAPSED) rebuilds it on request)
-template <bool FMA, typename TOut>
-__global__ void collapse_final(const float* __restrict__ up, int hs, int ws, const float* __restrict__ lap, int h,
-                               int w, float maxv, TOut* __restrict__ out, K25 K) {
-    int x = blockIdx.x * blockDim.x + threadIdx.x;
-    int y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (y >= h || x >= w) return;
-    float e[3];
-    expand_at<FMA>(up, hs, ws, K, y, x, e[0], e[1], e[2]);
-    const size_t p = ((size_t)y * w + x) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float v = fabsf(e[c] + lap[p + c]);
-        v = v > maxv ? maxv : v;
-        out[p + c] = (TOut)v;
-    }
-}
-
 // clip(abs(img), 0, max) then .astype(dtype) (truncation), pyramid.py:64, :179
 template <typename TOut>
 __global__ void finalize_cast(const float* __restrict__ img, size_t n, float maxv,

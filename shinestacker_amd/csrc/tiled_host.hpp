@@ -10,7 +10,9 @@
 // MI_ARITH_EXACT: batches of 32 frames; level 0 of batch k+1 runs while st2 still works on batch k, so the
 // latency-bound small levels hide behind the level-0 kernel.  MI_ARITH_SEPARABLE: a resident push is ONE batch
 // (up to 256 frames), processed level after level -- many-tile levels as consecutive launches of 16 frames,
-// few-tile levels as parallel frame chunks + merge (launch_level_sep), the payload pass of a level behind it on st1.
+// few-tile levels as parallel frame chunks whose partial maxima the level's payload pass folds, the payload pass of a
+// level behind it on st1.  Both level launchers (launch_level: exact, launch_level_sep: separable) walk the batch's
+// frames through level_walk + launch_walk; they differ in their tile grids, kernels and per-frame fields only.
 // The per-batch Gaussian images Gb[set][l] are double-buffered (set = k & 1) and allocated on demand; events
 // order producers and consumers.  Selection state is only ever touched by one stream per level (level 0: st0/st1
 // on disjoint pixels; levels >= 1 and base: st2; payload passes: events per level), so stream order keeps the first-max semantics.
@@ -26,7 +28,7 @@ struct TiledState {
     int dev_cap = 0;                // MI_ARITH_SEPARABLE, frames resident in HBM: largest batch (0 = not decided yet)
     int gcap[2] = {0, 0};           // frames the per-batch buffers of a set hold at the moment
     std::vector<float*> Gb[2];      // Gb[set][l], l = 1..L : gcap[set] images of level l
-    std::vector<float*> partE;      // [l] frame-chunk partial maxima / arg-maxima of level l (launch_level_sep)
+    std::vector<float*> partE;      // [l] frame-chunk partial maxima / arg-maxima of level l (level_walk)
     std::vector<int32_t*> partI;
     std::vector<size_t> part_cap;   // elements allocated in partE[l] / partI[l]
     std::vector<uint16_t*> sbOrder; // [l] super-block order of the level's interior launch (LevelArgs::sb_order), device
@@ -80,8 +82,6 @@ struct TiledState {
 
 inline TiledState*& tstate(mi_stack* s) { return *reinterpret_cast<TiledState**>(&s->tiled); }
 inline TiledState* tstate(const mi_stack* s) { return reinterpret_cast<TiledState*>(s->tiled); }
-
-bool tiled_available() { return true; }
 
 void dev_release(mi_stack* s, void* p) {
     if (!p) return;
@@ -258,9 +258,6 @@ constexpr int ilcm(int a, int b) {
     return a / x * b;
 }
 
-// MI_ARITH_SEPARABLE: interior and border tiles of level l on the separable kernel (kernels_sep.hpp); one tile
-// grid (28 x 56, origin at the image corner) for both, the interior rectangle = the whole tiles whose 6-pixel
-// halo stays inside the image.
 // How a level with `tiles` workgroups walks the `nb` frames of a batch.  A workgroup visits its frames one after the
 // other, so (a) a level with few tiles is latency-bound unless the batch is cut into chunks that run side by side
 // (blockIdx.y; about four rounds of workgroups for the GPU's 768 slots, chunks of 16 to 32 frames, partial maxima merged
@@ -316,16 +313,10 @@ inline int build_sb_order(mi_stack* s, int l, int nty, int ntx, int sbw = SB, in
     return MI_OK;
 }
 
-// Launch the interior and border kernels of level l for `nb` frames.
-//   interior kernel: tile config A (TH, TW, NT, padded LDS), stream st_in
-//   border kernel  : tile config B (BH, BW, BNT, unpadded LDS: small enough to co-reside
-//                    with two level-0 interior workgroups on one CU), stream st_bd
-template <typename TIn, bool FMA, int TH, int TW, int NT, bool PADA, int BH, int BW, int BNT, bool COARSE_NAME = false>
-int launch_level(mi_stack* s, int l, int set, const void* src, size_t src_stride, int nb,
-                 hipStream_t st_in, hipStream_t st_bd, hipEvent_t ev_bd) {
-    using GA = TileGeom<TH, TW, NT, PADA>;
-    using GB = TileGeom<BH, BW, BNT, false>;
-    TiledState* t = tstate(s);
+// The LevelArgs fields both level launchers fill alike: level l's shapes and running state, the batch's frames `src` and
+// images Gb[set][l + 1], the frame numbers.  The launcher adds its interior rectangle and the fields of its own kernels.
+inline LevelArgs level_args(const mi_stack* s, int l, int set, const void* src, size_t src_stride, int nb) {
+    const TiledState* t = tstate(s);
     LevelArgs a{};
     a.src = src;
     a.src_stride = src_stride;
@@ -336,54 +327,45 @@ int launch_level(mi_stack* s, int l, int set, const void* src, size_t src_stride
     a.w = s->lw[l];
     a.hn = s->lh[l + 1];
     a.wn = s->lw[l + 1];
-    // interior rectangle: whole 6-pixel-haloed patches inside the image, aligned to both tilings
-    constexpr int AY = ilcm(TH, BH), AX = ilcm(TW, BW);
-    if (TH % BH == 0 && TW % BW == 0) {
-        // origin on the border tiling, whole interior tiles from there
-        a.iy0 = cdiv(6, BH) * BH;
-        a.ix0 = cdiv(6, BW) * BW;
-        a.iy1 = a.iy0 + (a.h - 6 - a.iy0 > 0 ? (a.h - 6 - a.iy0) / TH * TH : 0);
-        a.ix1 = a.ix0 + (a.w - 6 - a.ix0 > 0 ? (a.w - 6 - a.ix0) / TW * TW : 0);
-    } else {
-        a.iy0 = cdiv(6, AY) * AY;
-        a.ix0 = cdiv(6, AX) * AX;
-        a.iy1 = (a.h - 6) / AY * AY;
-        a.ix1 = (a.w - 6) / AX * AX;
-    }
-    if (a.iy1 <= a.iy0 || a.ix1 <= a.ix0) a.iy0 = a.iy1 = a.ix0 = a.ix1 = 0;
-    const int nyi = (a.iy1 - a.iy0) / TH, nxi = (a.ix1 - a.ix0) / TW;
     a.best_e = s->bestE[l];
     a.best_lap = s->bestLap[l];
     a.best_idx = s->bestIdx[l];
     a.first = s->n_pushed == 0;
     a.frame_idx0 = s->first_index + s->n_pushed;
+    return a;
+}
+
+// algorithmic bytes of a level pass over `nb` frames, SURVEY.md 8(d) attribution: read G_l once, write G_{l+1} once, read
+// G_{l+1} once as the expand source
+inline double level_bytes(const mi_stack* s, int l, int nb) {
+    return ((double)(l == 0 ? dtype_size(s->p.in_dtype) : 4) * 3.0 * s->lh[l] * s->lw[l] + 24.0 * s->lh[l + 1] * s->lw[l + 1]) * nb;
+}
+
+// the six distinct taps of the 5 x 5 kernel (K6, kernels_tiled.hpp)
+inline K6 k6_of(const mi_stack* s) {
+    K6 K{};
     for (int i = 0; i < 3; ++i)
-        for (int j = i; j < 3; ++j) a.K.c[i == 0 ? j : (i == 1 ? 2 + j : 5)] = s->K.k[i * 5 + j];
-    const size_t ldsA = (size_t)GA::LDS_FLOATS * sizeof(float), ldsB = (size_t)GB::LDS_FLOATS * sizeof(float);
-    auto kin = COARSE_NAME ? level_fused_coarse<TIn, FMA, true, TH, TW, NT, PADA> : level_fused<TIn, FMA, true, TH, TW, NT, PADA>;
-    auto kbd = level_fused<TIn, FMA, false, BH, BW, BNT, false>;
-    static thread_local bool attr_set = false;
-    if (!attr_set) {
-        int rc;
-        if ((rc = set_lds_once(kin, ldsA)) || (rc = set_lds_once(kbd, ldsB))) return rc;
-        attr_set = true;
-    }
-    // algorithmic bytes of this level pass, SURVEY.md 8(d) attribution: read G_l once,
-    // write G_{l+1} once, read G_{l+1} once as the expand source.
-    const double bytes = ((double)(l == 0 ? dtype_size(s->p.in_dtype) : 4) * 3.0 * a.h * a.w +
-                          24.0 * a.hn * a.wn) * nb;
-    const double frac_in = (double)(a.iy1 - a.iy0) * (a.ix1 - a.ix0) / ((double)a.h * a.w);
-    // Frames per launch / per chunk exactly as for the separable kernel (level_chunk_frames): levels with many tiles as
-    // consecutive launches of 16 frames, levels with few tiles as frame chunks side by side + merge_chunks.
-    const int tbx = cdiv(a.w, BW), tby = cdiv(a.h, BH);
-    const int nborder = tbx * tby - ((a.iy1 - a.iy0) / BH) * ((a.ix1 - a.ix0) / BW);
-    const int ntiles = nyi * nxi + nborder;
-    const size_t npx = (size_t)a.h * a.w;
+        for (int j = i; j < 3; ++j) K.c[i == 0 ? j : (i == 1 ? 2 + j : 5)] = s->K.k[i * 5 + j];
+    return K;
+}
+
+// How a level pass walks the `nb` frames of a batch (level_chunk_frames): `nchunks` chunks of `fc` frames side by side in one
+// launch (blockIdx.y) when `parallel`, else consecutive launches of `fc` frames.
+struct LevelWalk {
+    int nb, fc, nchunks;
+    bool parallel;
+};
+
+// The walk of a level whose launches have `ntiles` workgroups per frame chunk (`one_launch`: one launch over the whole batch,
+// the workgroups pick their frames themselves).  Chunks after the first leave their partial maxima / arg-maxima in
+// partE[l] / partI[l] (grown here) for the merge or the payload pass to fold.
+inline int level_walk(mi_stack* s, int l, int nb, int ntiles, bool one_launch, LevelArgs& a, LevelWalk* w) {
+    TiledState* t = tstate(s);
     bool parallel = false;
-    const int fc = level_chunk_frames(nb, ntiles, &parallel);
-    const int nchunks = parallel ? cdiv(nb, fc) : 1;
-    if (nchunks > 1) {
-        const size_t need = npx * (size_t)(nchunks - 1);
+    const int fc = one_launch ? nb : level_chunk_frames(nb, ntiles, &parallel);
+    *w = {nb, fc, parallel ? cdiv(nb, fc) : 1, parallel};
+    if (w->nchunks > 1) {
+        const size_t npx = (size_t)a.h * a.w, need = npx * (size_t)(w->nchunks - 1);
         if (t->part_cap[l] < need) {   // grows only; the buffers may still be in use by the previous batch
             int rc;
             if ((rc = tiled_sync_all(s))) return rc;
@@ -400,48 +382,114 @@ int launch_level(mi_stack* s, int l, int set, const void* src, size_t src_stride
         a.part_idx = t->partI[l];
         a.part_stride = npx;
     }
+    return MI_OK;
+}
+
+// One of a level pass's two launch sequences: kernel, workgroups per frame chunk (0: none), threads, dynamic LDS, stream, and
+// the kind and bytes its ProfScope records.
+struct TileLaunch {
+    void (*kern)(LevelArgs);
+    int groups;
+    int threads;
+    size_t lds;
+    hipStream_t st;
+    int kind;
+    double bytes;
+};
+
+// Launch a level pass along its walk: the border tiles first (their few, latency-bound workgroups should claim their slots
+// early), then the interior tiles.  The two touch disjoint pixels, so each sequence only keeps its own order; one timing-event
+// pair goes around each (an event record between two kernels of a stream costs a few microseconds of idle GPU: 30 launches
+// per level pass).  Every launch gets its frames' src / nframes / chunk_frames / first / frame_idx0, and `frame(f0, nf)` sets
+// the launcher's own per-frame fields.
+template <typename Frame>
+void launch_walk(mi_stack* s, LevelArgs& a, const LevelWalk& w, const TileLaunch& border, const TileLaunch& interior,
+                 Frame&& frame) {
+    const void* src = a.src;
     const int first = a.first, idx0 = a.frame_idx0;
-    const int step = parallel ? nb : fc, nlaunch = cdiv(nb, step);
-    auto frames_of = [&](int f0) {
-        const int nf = parallel ? nb : std::min(fc, nb - f0);
-        a.src = (const char*)src + (size_t)f0 * src_stride;
-        a.gnext = t->Gb[set][l + 1] + (size_t)f0 * a.gnext_stride;
-        a.nframes = nf;
-        a.chunk_frames = parallel ? fc : nf;
-        a.first = first && f0 == 0;
-        a.frame_idx0 = idx0 + f0;
-    };
-    if (nborder > 0) {   // border first: its few, latency-bound workgroups should claim their slots early
-        ProfScope ps(s, MI_PROF_LEVEL, bytes * (1.0 - frac_in), st_bd);
-        ps.r.launches = nlaunch;
-        for (int f0 = 0; f0 < nb; f0 += step) {
-            frames_of(f0);
-            hipLaunchKernelGGL(kbd, dim3(nborder, nchunks), dim3(BNT), ldsB, st_bd, a);
+    const int step = w.parallel ? w.nb : w.fc;
+    for (const TileLaunch* x : {&border, &interior}) {
+        if (x->groups <= 0) continue;
+        ProfScope ps(s, x->kind, x->bytes, x->st);
+        ps.r.launches = cdiv(w.nb, step);
+        for (int f0 = 0; f0 < w.nb; f0 += step) {
+            const int nf = w.parallel ? w.nb : std::min(w.fc, w.nb - f0);
+            a.src = (const char*)src + (size_t)f0 * a.src_stride;
+            a.nframes = nf;
+            a.chunk_frames = w.parallel ? w.fc : nf;
+            a.first = first && f0 == 0;
+            a.frame_idx0 = idx0 + f0;
+            frame(f0, nf);
+            hipLaunchKernelGGL(x->kern, dim3(x->groups, w.nchunks), dim3(x->threads), x->lds, x->st, a);
         }
     }
-    if (nyi > 0) {
-        const int nsb = cdiv(nxi, SB) * cdiv(nyi, SB);
-        ProfScope ps(s, l == 0 ? MI_PROF_LEVEL0 : MI_PROF_LEVEL, bytes * frac_in, st_in);
-        ps.r.launches = nlaunch;
-        for (int f0 = 0; f0 < nb; f0 += step) {
-            frames_of(f0);
-            hipLaunchKernelGGL(kin, dim3(cdiv(nsb, 8) * 8 * SB * SB, nchunks), dim3(NT), ldsA, st_in, a);
-        }
+}
+
+// MI_ARITH_EXACT: launch the interior and border kernels of level l for `nb` frames.
+//   interior kernel: tile config A (TH, TW, NT, padded LDS), stream st_in
+//   border kernel  : tile config B (BH, BW, BNT, unpadded LDS: small enough to co-reside
+//                    with two level-0 interior workgroups on one CU), stream st_bd
+// A level in frame chunks ends with merge_chunks on st_in, behind `ev_bd` (recorded on st_bd).
+template <typename TIn, bool FMA, int TH, int TW, int NT, bool PADA, int BH, int BW, int BNT, bool COARSE_NAME = false>
+int launch_level(mi_stack* s, int l, int set, const void* src, size_t src_stride, int nb,
+                 hipStream_t st_in, hipStream_t st_bd, hipEvent_t ev_bd) {
+    using GA = TileGeom<TH, TW, NT, PADA>;
+    using GB = TileGeom<BH, BW, BNT, false>;
+    TiledState* t = tstate(s);
+    LevelArgs a = level_args(s, l, set, src, src_stride, nb);
+    // interior rectangle: whole 6-pixel-haloed patches inside the image, aligned to both tilings
+    constexpr int AY = ilcm(TH, BH), AX = ilcm(TW, BW);
+    if (TH % BH == 0 && TW % BW == 0) {
+        // origin on the border tiling, whole interior tiles from there
+        a.iy0 = cdiv(6, BH) * BH;
+        a.ix0 = cdiv(6, BW) * BW;
+        a.iy1 = a.iy0 + (a.h - 6 - a.iy0 > 0 ? (a.h - 6 - a.iy0) / TH * TH : 0);
+        a.ix1 = a.ix0 + (a.w - 6 - a.ix0 > 0 ? (a.w - 6 - a.ix0) / TW * TW : 0);
+    } else {
+        a.iy0 = cdiv(6, AY) * AY;
+        a.ix0 = cdiv(6, AX) * AX;
+        a.iy1 = (a.h - 6) / AY * AY;
+        a.ix1 = (a.w - 6) / AX * AX;
     }
-    if (nchunks > 1) {
+    if (a.iy1 <= a.iy0 || a.ix1 <= a.ix0) a.iy0 = a.iy1 = a.ix0 = a.ix1 = 0;
+    const int nyi = (a.iy1 - a.iy0) / TH, nxi = (a.ix1 - a.ix0) / TW;
+    a.K = k6_of(s);
+    const size_t ldsA = (size_t)GA::LDS_FLOATS * sizeof(float), ldsB = (size_t)GB::LDS_FLOATS * sizeof(float);
+    auto kin = COARSE_NAME ? level_fused_coarse<TIn, FMA, true, TH, TW, NT, PADA> : level_fused<TIn, FMA, true, TH, TW, NT, PADA>;
+    auto kbd = level_fused<TIn, FMA, false, BH, BW, BNT, false>;
+    static thread_local bool attr_set = false;
+    if (!attr_set) {
+        int rc;
+        if ((rc = set_lds_once(kin, ldsA)) || (rc = set_lds_once(kbd, ldsB))) return rc;
+        attr_set = true;
+    }
+    const double bytes = level_bytes(s, l, nb);
+    const double frac_in = (double)(a.iy1 - a.iy0) * (a.ix1 - a.ix0) / ((double)a.h * a.w);
+    // frames per launch / per chunk exactly as for the separable kernel (level_walk)
+    const int nborder = cdiv(a.w, BW) * cdiv(a.h, BH) - ((a.iy1 - a.iy0) / BH) * ((a.ix1 - a.ix0) / BW);
+    LevelWalk w;
+    int rc = level_walk(s, l, nb, nyi * nxi + nborder, false, a, &w);
+    if (rc) return rc;
+    const int nsb = cdiv(nxi, SB) * cdiv(nyi, SB);
+    launch_walk(s, a, w, {kbd, nborder, BNT, ldsB, st_bd, MI_PROF_LEVEL, bytes * (1.0 - frac_in)},
+                {kin, cdiv(nsb, 8) * 8 * SB * SB, NT, ldsA, st_in, l == 0 ? MI_PROF_LEVEL0 : MI_PROF_LEVEL, bytes * frac_in},
+                [&](int f0, int) { a.gnext = t->Gb[set][l + 1] + (size_t)f0 * a.gnext_stride; });
+    if (w.nchunks > 1) {
         MI_HIP(hipEventRecord(ev_bd, st_bd));
         MI_HIP(hipStreamWaitEvent(st_in, ev_bd, 0));
         ProfScope ps(s, MI_PROF_LEVEL, 0.0, st_in);
+        const size_t npx = a.part_stride;
         hipLaunchKernelGGL(merge_chunks, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st_in, s->bestE[l], s->bestIdx[l],
-                           t->partE[l], t->partI[l], npx, nchunks - 1, npx);
+                           t->partE[l], t->partI[l], npx, w.nchunks - 1, npx);
     }
     return MI_OK;
 }
 
-// `ev_bd`: recorded on st_bd behind the border kernel when the level ran in chunks (the merge on st_in waits for it).
-// `info` (optional): what run_batch needs to finish the level -- how many chunk partials sep_payload has to fold (it then takes
-// merge_chunks' place) and whether border tiles were launched on st_bd (only then the streams have to join).  `ev_sync`
-// (optional): recorded on st_in and waited for on st_bd in front of a border launch (everything st_in has done so far).
+// MI_ARITH_SEPARABLE: interior and border tiles of level l on the separable kernel (kernels_sep.hpp); one tile grid (28 x 56,
+// origin at the image corner) for both.  `info`: what run_batch needs to finish the level -- how many chunk partials the payload
+// pass has to fold (the separable path has no merge_chunks) and whether border tiles were launched on st_bd (only then the
+// streams have to join).  `ev_sync` (optional): recorded on st_in and waited for on st_bd in front of the border launches
+// (everything st_in has done so far).
 // `PM` (level pairs, kernels_sep.hpp "PAIR"): 0 = a level on its own; 1 = the first level of a pair (level_sep_pair: writes
 // gray(G_{l+1}) into Gb[set][l+1] -- one float per pixel --, G_{l+2} into Gb[set][l+2] and the three-channel G_{l+1} of the
 // batch's last frame into Gkeep[set][l+1]); 2 = the second level of a pair (level_sep_e: `src` = that gray, reads G_{l+1});
@@ -450,22 +498,12 @@ int launch_level(mi_stack* s, int l, int set, const void* src, size_t src_stride
 struct SepLevelInfo { int nparts = 0; bool border = false; };
 template <typename TIn, bool L0_NAME, int PM = 0>
 int launch_level_sep(mi_stack* s, int l, int set, const void* src, size_t src_stride, int nb, hipStream_t st_in,
-                     hipStream_t st_bd, hipEvent_t ev_bd, SepLevelInfo* info = nullptr,
-                     hipEvent_t ev_sync = nullptr) {
+                     hipStream_t st_bd, SepLevelInfo& info, hipEvent_t ev_sync = nullptr) {
     constexpr int TH = MI_SEP_TH, NT = sep_nt<TIn>();
     using SG = SepGeom<TH, NT>;
     constexpr int TW = SG::TW;
     TiledState* t = tstate(s);
-    LevelArgs a{};
-    a.src = src;
-    a.src_stride = src_stride;
-    a.gnext = t->Gb[set][l + 1];
-    a.gnext_stride = t->gstride[l + 1];
-    a.nframes = nb;
-    a.h = s->lh[l];
-    a.w = s->lw[l];
-    a.hn = s->lh[l + 1];
-    a.wn = s->lw[l + 1];
+    LevelArgs a = level_args(s, l, set, src, src_stride, nb);
     a.g1_keep = -1;
     const size_t gray_stride = (size_t)a.hn * a.wn;
     if constexpr (PM == 1 || PM == 3) {
@@ -502,11 +540,6 @@ int launch_level_sep(mi_stack* s, int l, int set, const void* src, size_t src_st
     }
     if (a.iy1 <= a.iy0 || a.ix1 <= a.ix0) a.iy0 = a.iy1 = a.ix0 = a.ix1 = 0;
     const int nyi = (a.iy1 - a.iy0) / TH, nxi = (a.ix1 - a.ix0) / TW;
-    a.best_e = s->bestE[l];
-    a.best_lap = s->bestLap[l];
-    a.best_idx = s->bestIdx[l];
-    a.first = s->n_pushed == 0;
-    a.frame_idx0 = s->first_index + s->n_pushed;
     for (int i = 0; i < 3; ++i) a.k1d[i] = s->k1d[i];
     for (int i = 0; i < 4; ++i) a.rk[i] = s->rk[i];
     const size_t lds = (size_t)(PM == 3 ? sep_pl_lds_floats<TIn, TH, NT>(false) : PM == 2 ? sep_e_lds_floats<TH, NT>()
@@ -528,100 +561,48 @@ int launch_level_sep(mi_stack* s, int l, int set, const void* src, size_t src_st
         if ((rc = set_lds_once(kin, lds_in)) || (rc = set_lds_once(kbd, lds))) return rc;
         attr_set = true;
     }
-    const double bytes = PM == 3 ? 0.0 : ((double)(l == 0 ? dtype_size(s->p.in_dtype) : 4) * 3.0 * a.h * a.w + 24.0 * a.hn * a.wn) * nb;
+    const double bytes = PM == 3 ? 0.0 : level_bytes(s, l, nb);
     const double frac_in = (double)(std::min(a.iy1, a.h) - a.iy0) * (std::min(a.ix1, a.w) - a.ix0) / ((double)a.h * a.w);
     const int ntiles = cdiv(a.w, TW) * cdiv(a.h, TH);
-    const size_t npx = (size_t)a.h * a.w;
-    bool parallel = false;
-    int fc = level_chunk_frames(nb, ntiles, &parallel);
-    if (PM == 3) { parallel = false; fc = nb; }   // the payload pass: one launch, the workgroup picks its frames itself
-    const int nchunks = parallel ? cdiv(nb, fc) : 1;
-    if (nchunks > 1) {
-        const size_t need = npx * (size_t)(nchunks - 1);
-        if (t->part_cap[l] < need) {   // grows only; the buffers may still be in use by the previous batch
-            int rc;
-            if ((rc = tiled_sync_all(s))) return rc;
-            MI_HIP(hipStreamSynchronize(s->stream));
-            dev_release(s, t->partE[l]);
-            dev_release(s, t->partI[l]);
-            t->partE[l] = nullptr;
-            t->partI[l] = nullptr;
-            t->part_cap[l] = 0;
-            if ((rc = dev_alloc_t(s, &t->partE[l], need)) || (rc = dev_alloc_t(s, &t->partI[l], need))) return rc;
-            t->part_cap[l] = need;
-        }
-        a.part_e = t->partE[l];
-        a.part_idx = t->partI[l];
-        a.part_stride = npx;
-    }
-    // parallel chunks: one launch over all the frames; otherwise consecutive launches of `fc` frames (the interior and the
-    // border launches of a level touch disjoint pixels, so each sequence only has to keep its own order)
+    LevelWalk w;
+    int rc = level_walk(s, l, nb, ntiles, PM == 3, a, &w);
+    if (rc) return rc;
     const int nborder = ntiles - nyi * nxi;
     const int nsb = cdiv(nxi, SEP_SBW) * cdiv(nyi, SEP_SBH);
     int ngroups = cdiv(nsb, 8) * 8;   // super-block-sized groups of workgroups of the interior launch
     if (nyi > 0) {
-        int rc = build_sb_order(s, l, nyi, nxi, SEP_SBW, SEP_SBH);
-        if (rc) return rc;
+        if ((rc = build_sb_order(s, l, nyi, nxi, SEP_SBW, SEP_SBH))) return rc;
         if (t->sbOrder[l]) { a.sb_order = t->sbOrder[l]; ngroups = t->sbGroups[l]; }
     }
-    const int first = a.first, idx0 = a.frame_idx0;
-    const int step = parallel ? nb : fc, nlaunch = cdiv(nb, step);
-    auto frames_of = [&](int f0) {
-        const int nf = parallel ? nb : std::min(fc, nb - f0);
-        a.src = (const char*)src + (size_t)f0 * src_stride;
-        if constexpr (PM == 3) {
-        } else if constexpr (PM == 1) {
-            a.gray1 = t->Gb[set][l + 1] + (size_t)f0 * gray_stride;
-            a.g2 = t->Gb[set][l + 2] + (size_t)f0 * a.g2_stride;
-            a.g1_keep = nb - 1 >= f0 && nb - 1 < f0 + nf ? nb - 1 - f0 : -1;   // the batch's last frame, if this launch holds it
-        } else a.gnext = t->Gb[set][l + 1] + (size_t)f0 * a.gnext_stride;
-        a.nframes = nf;
-        a.chunk_frames = parallel ? fc : nf;
-        a.first = first && f0 == 0;
-        a.frame_idx0 = idx0 + f0;
-    };
-    // one timing-event pair around each stream's sequence of launches (an event record between two kernels of a stream
-    // costs a few microseconds of idle GPU: 30 launches per level pass)
-    if (info) { info->nparts = nchunks - 1; info->border = nborder > 0; }
-    if (nborder > 0) {
-        if (ev_sync) {
-            MI_HIP(hipEventRecord(ev_sync, st_in));
-            MI_HIP(hipStreamWaitEvent(st_bd, ev_sync, 0));
-        }
-        ProfScope ps(s, MI_PROF_LEVEL, bytes * (1.0 - frac_in), st_bd);
-        ps.r.launches = nlaunch;
-        for (int f0 = 0; f0 < nb; f0 += step) {
-            frames_of(f0);
-            hipLaunchKernelGGL(kbd, dim3(nborder, nchunks), dim3(NT), lds, st_bd, a);
-        }
+    info.nparts = w.nchunks - 1;
+    info.border = nborder > 0;
+    if (nborder > 0 && ev_sync) {
+        MI_HIP(hipEventRecord(ev_sync, st_in));
+        MI_HIP(hipStreamWaitEvent(st_bd, ev_sync, 0));
     }
-    if (nyi > 0) {
-        ProfScope ps(s, l == 0 && PM != 3 ? MI_PROF_LEVEL0 : MI_PROF_LEVEL, bytes * frac_in, st_in);
-        ps.r.launches = nlaunch;
-        for (int f0 = 0; f0 < nb; f0 += step) {
-            frames_of(f0);
-            hipLaunchKernelGGL(kin, dim3(ngroups * SEP_SBW * SEP_SBH, nchunks), dim3(NT), lds_in, st_in, a);
-        }
-    }
-    if (nchunks > 1 && !info) {   // (callers that pass `info` fold the partials in their payload pass)
-        MI_HIP(hipEventRecord(ev_bd, st_bd));
-        MI_HIP(hipStreamWaitEvent(st_in, ev_bd, 0));
-        ProfScope ps(s, MI_PROF_LEVEL, 0.0, st_in);
-        hipLaunchKernelGGL(merge_chunks, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st_in, s->bestE[l], s->bestIdx[l],
-                           t->partE[l], t->partI[l], npx, nchunks - 1, npx);
-    }
+    launch_walk(s, a, w, {kbd, nborder, NT, lds, st_bd, MI_PROF_LEVEL, bytes * (1.0 - frac_in)},
+                {kin, ngroups * SEP_SBW * SEP_SBH, NT, lds_in, st_in, l == 0 && PM != 3 ? MI_PROF_LEVEL0 : MI_PROF_LEVEL, bytes * frac_in},
+                [&](int f0, int nf) {
+                    if constexpr (PM == 1) {
+                        a.gray1 = t->Gb[set][l + 1] + (size_t)f0 * gray_stride;
+                        a.g2 = t->Gb[set][l + 2] + (size_t)f0 * a.g2_stride;
+                        a.g1_keep = nb - 1 >= f0 && nb - 1 < f0 + nf ? nb - 1 - f0 : -1;   // the batch's last frame, if this launch holds it
+                    } else if constexpr (PM != 3) a.gnext = t->Gb[set][l + 1] + (size_t)f0 * a.gnext_stride;
+                });
     return MI_OK;
 }
+
+// The per-quad payload kernels: one thread per 2 x 2 quad of an h x w level, workgroups of QUAD_WG threads
+const dim3 QUAD_WG(32, 8);
+inline dim3 quad_grid(int h, int w) { return dim3(cdiv(cdiv(w, 2), QUAD_WG.x), cdiv(cdiv(h, 2), QUAD_WG.y)); }
 
 // MI_ARITH_SEPARABLE: the winners' Laplacians of level l for the frames of this batch (the level kernel keeps only
 // the running maximum and its frame index); reads the batch's G_l (level 0: the frames) and G_{l+1}.
 template <typename TIn>
 int launch_payload_sep(mi_stack* s, int l, int set, const void* src, size_t src_stride, int nb, hipStream_t st, int nparts = 0) {
     TiledState* t = tstate(s);
-    const dim3 blk(32, 8);
-    const dim3 grd(cdiv(cdiv(s->lw[l], 2), blk.x), cdiv(cdiv(s->lh[l], 2), blk.y));
     ProfScope ps(s, MI_PROF_LEVEL, 0.0, st);
-    hipLaunchKernelGGL((sep_payload<TIn>), grd, blk, 0, st, src, src_stride, (const float*)t->Gb[set][l + 1], t->gstride[l + 1],
+    hipLaunchKernelGGL((sep_payload<TIn>), quad_grid(s->lh[l], s->lw[l]), QUAD_WG, 0, st, src, src_stride, (const float*)t->Gb[set][l + 1], t->gstride[l + 1],
                        nb, s->lh[l], s->lw[l], s->lh[l + 1], s->lw[l + 1], s->bestIdx[l],
                        s->first_index + s->n_pushed, s->bestLap[l], s->k1d[0], s->k1d[1], s->k1d[2], s->bestE[l],
                        (const float*)(nparts > 0 ? t->partE[l] : nullptr), (const int32_t*)(nparts > 0 ? t->partI[l] : nullptr),
@@ -635,10 +616,8 @@ template <typename TIn>
 int launch_payload_pair0(mi_stack* s, int l, int set, const void* src, size_t src_stride, int nb, hipStream_t st, int nparts,
                          const uint8_t* tile_flag = nullptr) {
     TiledState* t = tstate(s);
-    const dim3 blk(32, 8);
-    const dim3 grd(cdiv(cdiv(s->lw[l], 2), blk.x), cdiv(cdiv(s->lh[l], 2), blk.y));
     ProfScope ps(s, MI_PROF_LEVEL, 0.0, st);
-    hipLaunchKernelGGL((sep_payload_pair0<TIn>), grd, blk, 0, st, src, src_stride, nb, s->lh[l], s->lw[l], s->lh[l + 1], s->lw[l + 1],
+    hipLaunchKernelGGL((sep_payload_pair0<TIn>), quad_grid(s->lh[l], s->lw[l]), QUAD_WG, 0, st, src, src_stride, nb, s->lh[l], s->lw[l], s->lh[l + 1], s->lw[l + 1],
                        s->bestIdx[l], s->first_index + s->n_pushed, s->bestLap[l], s->k1d[0], s->k1d[1], s->k1d[2], s->rk[0],
                        s->rk[1], s->rk[2], s->rk[3], s->bestE[l], (const float*)(nparts > 0 ? t->partE[l] : nullptr),
                        (const int32_t*)(nparts > 0 ? t->partI[l] : nullptr), (size_t)s->lh[l] * s->lw[l], nparts, tile_flag,
@@ -649,10 +628,8 @@ template <typename TIn>
 int launch_payload_pair1(mi_stack* s, int l, int set, const void* src, size_t src_stride, int nb, hipStream_t st, int nparts,
                          const uint8_t* tile_flag = nullptr) {
     TiledState* t = tstate(s);
-    const dim3 blk(32, 8);
-    const dim3 grd(cdiv(cdiv(s->lw[l + 1], 2), blk.x), cdiv(cdiv(s->lh[l + 1], 2), blk.y));
     ProfScope ps(s, MI_PROF_LEVEL, 0.0, st);
-    hipLaunchKernelGGL((sep_payload_pair1<TIn>), grd, blk, 0, st, src, src_stride, (const float*)t->Gb[set][l + 2], t->gstride[l + 2], nb,
+    hipLaunchKernelGGL((sep_payload_pair1<TIn>), quad_grid(s->lh[l + 1], s->lw[l + 1]), QUAD_WG, 0, st, src, src_stride, (const float*)t->Gb[set][l + 2], t->gstride[l + 2], nb,
                        s->lh[l], s->lw[l], s->lh[l + 1], s->lw[l + 1], s->lh[l + 2], s->lw[l + 2], s->bestIdx[l + 1],
                        s->first_index + s->n_pushed, s->bestLap[l + 1], s->k1d[0], s->k1d[1], s->k1d[2], s->rk[0], s->rk[1], s->rk[2],
                        s->rk[3], s->bestE[l + 1], (const float*)(nparts > 0 ? t->partE[l + 1] : nullptr),
@@ -670,7 +647,8 @@ int launch_payload_pair_tiles(mi_stack* s, int l, int set, const void* src, size
     int rc;
     if (!t->tileFlag[l] && (rc = dev_alloc_t(s, &t->tileFlag[l], ntiles))) return rc;
     MI_HIP(hipMemsetAsync(t->tileFlag[l], 0, ntiles, st));
-    if ((rc = launch_level_sep<TIn, false, 3>(s, l, set, src, src_stride, nb, st, st, nullptr))) return rc;
+    SepLevelInfo info;   // (one launch: no chunk partials)
+    if ((rc = launch_level_sep<TIn, false, 3>(s, l, set, src, src_stride, nb, st, st, info))) return rc;
     if ((rc = launch_payload_pair0<TIn>(s, l, set, src, src_stride, nb, st, 0, t->tileFlag[l]))) return rc;
     return launch_payload_pair1<TIn>(s, l, set, src, src_stride, nb, st, 0, t->tileFlag[l]);
 }
@@ -705,15 +683,10 @@ inline void sep_pair_plan(const mi_stack* s, int nb, std::vector<int>& pm) {
 template <typename TIn, bool FMA>
 int launch_payload_exact(mi_stack* s, int l, int set, const void* src, size_t src_stride, int nb, hipStream_t st) {
     TiledState* t = tstate(s);
-    const dim3 blk(32, 8);
-    const dim3 grd(cdiv(cdiv(s->lw[l], 2), blk.x), cdiv(cdiv(s->lh[l], 2), blk.y));
-    K6 K{};
-    for (int i = 0; i < 3; ++i)
-        for (int j = i; j < 3; ++j) K.c[i == 0 ? j : (i == 1 ? 2 + j : 5)] = s->K.k[i * 5 + j];
     ProfScope ps(s, MI_PROF_LEVEL, 0.0, st);
-    hipLaunchKernelGGL((exact_payload<TIn, FMA>), grd, blk, 0, st, src, src_stride, (const float*)t->Gb[set][l + 1],
+    hipLaunchKernelGGL((exact_payload<TIn, FMA>), quad_grid(s->lh[l], s->lw[l]), QUAD_WG, 0, st, src, src_stride, (const float*)t->Gb[set][l + 1],
                        t->gstride[l + 1], nb, s->lh[l], s->lw[l], s->lh[l + 1], s->lw[l + 1], (const int32_t*)s->bestIdx[l],
-                       s->first_index + s->n_pushed, s->bestLap[l], K);
+                       s->first_index + s->n_pushed, s->bestLap[l], k6_of(s));
     return MI_OK;
 }
 
@@ -752,8 +725,8 @@ int run_batch(mi_stack* s, const void* frames, size_t stride, int nb) {
     std::vector<int> pm;   // the batch's pair plan (sep_pair_plan): 1 = first level of a pair, 2 = second
     sep_pair_plan(s, nb, pm);
     const bool pair = pm[0] == 1;
-    if (pair) rc = launch_level_sep<TIn, true, 1>(s, 0, set, frames, stride, nb, st0, st1, t->evL0b[set], &li0);
-    else if (s->sep) rc = launch_level_sep<TIn, true>(s, 0, set, frames, stride, nb, st0, st1, t->evL0b[set], &li0);
+    if (pair) rc = launch_level_sep<TIn, true, 1>(s, 0, set, frames, stride, nb, st0, st1, li0);
+    else if (s->sep) rc = launch_level_sep<TIn, true>(s, 0, set, frames, stride, nb, st0, st1, li0);
     else
         rc = launch_level<TIn, FMA, MI_TILE0_H, MI_TILE0_W, MI_TILE0_NT, MI_TILE_PAD != 0, MI_TILE_H, MI_TILE_W, MI_TILE_NT>(
             s, 0, set, frames, stride, nb, st0, st1, t->evL0b[set]);
@@ -790,72 +763,51 @@ int run_batch(mi_stack* s, const void* frames, size_t stride, int nb) {
     // coarser levels: interior tiles on st2, border tiles on st1 (disjoint tiles of one level run
     // side by side); both streams join after every level because level l+1 reads all of G_{l+1}
     for (int l = 1; l < L; ++l) {
+        hipEvent_t ei = t->evLvl[(set * (L + 1) + l) * 2], eb = t->evLvl[(set * (L + 1) + l) * 2 + 1];
+        if (s->sep) {
+            // interior tiles on st2; border tiles, if the level has any, on st1 behind everything st2 has done so far (`ei`);
+            // the streams join again (`eb`) in front of the payload pass, which also folds the frame chunks' partial maxima.
+            //   pm[l] == 2, the second level of a pair: energy only, from gray(G_l) -- one float per pixel -- and G_{l+1} (both
+            //     written by level l - 1's kernel); the pair's payload pass recomputes the winners' G_l from level l - 1's images
+            //   pm[l] == 1, the first level of a pair beyond level 0: level_sep_pair on the float images of level l (gray(G_{l+1})
+            //     and G_{l+2} out); its payload waits for level l + 1
+            auto level = pm[l] == 2 ? launch_level_sep<float, false, 2> : pm[l] == 1 ? launch_level_sep<float, false, 1>
+                                                                                     : launch_level_sep<float, false>;
+            const size_t src_stride = (pm[l] == 2 ? (size_t)s->lh[l] * s->lw[l] : t->gstride[l]) * sizeof(float);
+            SepLevelInfo li;
+            if ((rc = level(s, l, set, t->Gb[set][l], src_stride, nb, st2, st1, li, ei))) return rc;
+            if (li.border) {
+                MI_HIP(hipEventRecord(eb, st1));
+                MI_HIP(hipStreamWaitEvent(st2, eb, 0));
+            }
+            if (pm[l] == 1) {
+                nparts_first = li.nparts;
+                continue;
+            }
+            if ((rc = payload_after(l))) return rc;
+            if (pm[l] == 2)
+                rc = l == 1 ? pair_payload(l, li.nparts, TIn{}, frames, stride)
+                            : pair_payload(l, li.nparts, float{}, t->Gb[set][l - 1], t->gstride[l - 1] * sizeof(float));
+            else rc = launch_payload_sep<float>(s, l, set, t->Gb[set][l], src_stride, nb, st3, li.nparts);
+            if (rc) return rc;
+            continue;
+        }
         // coarser levels that still have thousands of tiles (4 MP and more: level 1 of a 24 MP frame) run on
         // level 0's tile configuration -- less halo per tile: +2 % on the 256 x 24 MP job
         const bool wide = (size_t)s->lh[l] * s->lw[l] >= ((size_t)4 << 20);
-        hipEvent_t ei = t->evLvl[(set * (L + 1) + l) * 2], eb = t->evLvl[(set * (L + 1) + l) * 2 + 1];
-        if (pm[l] == 2) {
-            // the second level of a pair: energy only, from gray(G_l) and G_{l+1} (both written by level l - 1's kernel);
-            // the pair's payload pass recomputes the winners' G_l from level l - 1's images
-            SepLevelInfo li;
-            if ((rc = launch_level_sep<float, false, 2>(s, l, set, t->Gb[set][l], (size_t)s->lh[l] * s->lw[l] * sizeof(float), nb,
-                                                        st2, st1, eb, &li, ei)))
-                return rc;
-            if (li.border) {
-                MI_HIP(hipEventRecord(eb, st1));
-                MI_HIP(hipStreamWaitEvent(st2, eb, 0));
-            }
-            if ((rc = payload_after(l))) return rc;
-            if ((rc = l == 1 ? pair_payload(l, li.nparts, TIn{}, frames, stride)
-                             : pair_payload(l, li.nparts, float{}, t->Gb[set][l - 1], t->gstride[l - 1] * sizeof(float))))
-                return rc;
-            continue;
-        }
-        if (pm[l] == 1) {
-            // the first level of a pair beyond level 0: level_sep_pair on the float images of level l (gray(G_{l+1}) and G_{l+2}
-            // out); its payload waits for level l + 1
-            SepLevelInfo li;
-            if ((rc = launch_level_sep<float, false, 1>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, eb,
-                                                        &li, ei)))
-                return rc;
-            if (li.border) {
-                MI_HIP(hipEventRecord(eb, st1));
-                MI_HIP(hipStreamWaitEvent(st2, eb, 0));
-            }
-            nparts_first = li.nparts;
-            continue;
-        }
-        if (s->sep) {
-            // interior tiles on st2; border tiles, if the level has any, on st1 behind everything st2 has done so far (`ei`);
-            // the streams join again (`eb`) in front of the payload pass, which also folds the frame chunks' partial maxima
-            SepLevelInfo li;
-            if ((rc = launch_level_sep<float, false>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, eb, &li,
-                                                     ei)))
-                return rc;
-            if (li.border) {
-                MI_HIP(hipEventRecord(eb, st1));
-                MI_HIP(hipStreamWaitEvent(st2, eb, 0));
-            }
-            if ((rc = payload_after(l))) return rc;
-            if ((rc = launch_payload_sep<float>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st3, li.nparts))) return rc;
-            continue;
-        }
         if (wide)
             rc = launch_level<float, FMA, MI_TILE0_H, MI_TILE0_W, MI_TILE0_NT, MI_TILE_PAD != 0, MI_TILE_H, MI_TILE_W, MI_TILE_NT, true>(
-                s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, t->evLvl[(set * (L + 1) + l) * 2 + 1]);
+                s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, eb);
         else
             rc = launch_level<float, FMA, MI_TILE_H, MI_TILE_W, MI_TILE_NT, false, MI_TILE_H, MI_TILE_W, MI_TILE_NT>(
-                s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, t->evLvl[(set * (L + 1) + l) * 2 + 1]);
-        if (rc)
-            return rc;
+                s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st2, st1, eb);
+        if (rc) return rc;
         MI_HIP(hipEventRecord(ei, st2));
         MI_HIP(hipEventRecord(eb, st1));
         MI_HIP(hipStreamWaitEvent(st2, eb, 0));
         MI_HIP(hipStreamWaitEvent(st1, ei, 0));
         if ((rc = payload_after(l))) return rc;
-        if ((rc = s->sep ? launch_payload_sep<float>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st3)
-                         : launch_payload_exact<float, FMA>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st3)))
-            return rc;
+        if ((rc = launch_payload_exact<float, FMA>(s, l, set, t->Gb[set][l], t->gstride[l] * sizeof(float), nb, st3))) return rc;
     }
     MI_HIP(hipGetLastError());
     {   // base level of the whole batch
@@ -924,7 +876,6 @@ int tiled_push(mi_stack* s, const void* dev_frames, int n, size_t stride) {
     if (s->L == 0) return fail(MI_ERR_UNSUPPORTED, "frames smaller than 2*min_size have no pyramid levels");
     int rc = tiled_flush(s);  // keep global frame order: staged host frames come first
     if (rc) return rc;
-    const bool fma = s->p.use_fma != 0;
     // MI_ARITH_SEPARABLE: the whole push is one batch when its per-batch buffers fit (level after level over all the
     // frames: every kernel has the GPU to itself, a pixel's winning Laplacian is filled in once, and the small levels run
     // in frame chunks); longer pushes are cut into equal batches.  MI_ARITH_EXACT runs on the same schedule since round 3.
@@ -952,12 +903,7 @@ int tiled_push(mi_stack* s, const void* dev_frames, int n, size_t stride) {
         if (left <= t->bcap && left >= 16 && n > t->bcap) nb = (left / 2 + 3) & ~3;
         if (sep_nb) nb = std::min(left, sep_nb);
         const void* fr = (const char*)dev_frames + (size_t)f0 * stride;
-        switch (s->p.in_dtype) {
-            case MI_U8: rc = fma ? run_batch<uint8_t, true>(s, fr, stride, nb) : run_batch<uint8_t, false>(s, fr, stride, nb); break;
-            case MI_U16: rc = fma ? run_batch<uint16_t, true>(s, fr, stride, nb) : run_batch<uint16_t, false>(s, fr, stride, nb); break;
-            case MI_F32: rc = fma ? run_batch<float, true>(s, fr, stride, nb) : run_batch<float, false>(s, fr, stride, nb); break;
-            default: rc = fail(MI_ERR_INVALID, "bad in_dtype");
-        }
+        rc = dispatch_input(s, [&](auto tin, auto fma) { return run_batch<decltype(tin), decltype(fma)::value>(s, fr, stride, nb); });
         if (rc) return rc;
         f0 += nb;
     }

@@ -57,8 +57,8 @@ def chunk_frames(nb, tiles):
 
 
 def level_launches(h, w, nb, payload_tiles=False):
-    """(border launches, interior launches, chunked) of one launch_level_sep call over a batch of `nb` frames of an h x w
-    level.  The interior launch takes the edge tiles too (levels of 16 x 16 and more) except the rows / columns at an odd
+    """(border launches, interior launches, chunked) of one launch_level_sep call -- its level_walk / launch_walk -- over a
+    batch of `nb` frames of an h x w level.  The interior launch takes the edge tiles too (levels of 16 x 16 and more) except the rows / columns at an odd
     far edge; chunked levels are one launch (blockIdx.y = chunk), the others consecutive launches of 16 frames;
     `payload_tiles` (PM = 3, level_sep_pl): one launch over the whole batch."""
     if h >= 16 and w >= 16:
@@ -77,7 +77,7 @@ def level_launches(h, w, nb, payload_tiles=False):
 
 def expected_launches(shapes, batches):
     """The profiler's launch counts after `batches` = [(frames, paired), ...], derived from run_batch / launch_level_sep
-    (csrc/tiled_host.hpp).  Per batch:
+    and the frame walk it shares with launch_level (level_walk / launch_walk, csrc/tiled_host.hpp).  Per batch:
       level 0 (level_sep, or level_sep_pair when paired): border launches -> PROF_LEVEL, interior launches -> PROF_LEVEL0;
         unpaired, its payload pass (sep_payload, which also folds the chunk partials: no merge_chunks) -> PROF_LEVEL;
       level l >= 1 (level_sep, or level_sep_e for the second level of a pair): border + interior launches -> PROF_LEVEL, then
