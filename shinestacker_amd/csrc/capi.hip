@@ -840,7 +840,8 @@ int aligner_reserve(mi_aligner* al, int n) {
     al->partial = (double*)dalloc((size_t)n * ECC_MAX_BLOCKS * (ECC_NSUM_H > ECC_NSUM ? ECC_NSUM_H : ECC_NSUM) * sizeof(double));
     al->ticket = (unsigned int*)dalloc(sizeof(unsigned int) * n);
     ok = ok && al->partial && al->ticket;
-    if (ok) ok = hipMemset(al->ticket, 0, sizeof(unsigned int) * n) == hipSuccess;
+    // (null stream: complete before any kernel on the aligner's non-blocking streams reads the tickets)
+    if (ok) ok = hipMemset(al->ticket, 0, sizeof(unsigned int) * n) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
     al->dstate = (EccState*)dalloc(sizeof(EccState) * n);
     ok = ok && al->dstate;
     al->pc_out = (double*)dalloc(sizeof(double) * 3 * n);
@@ -1413,9 +1414,12 @@ int mi_stack_create(mi_stack_t** out, const mi_stack_params_t* params) {
         TRY(dev_alloc_t(s, &s->slabE, off));
         TRY(dev_alloc_t(s, &s->slabI, off));
         TRY(dev_alloc_t(s, &s->slabL, off * 3));
-        MI_HIP(hipMemset(s->slabE, 0, off * 4));
-        MI_HIP(hipMemset(s->slabI, 0, off * 4));
-        MI_HIP(hipMemset(s->slabL, 0, off * 12));
+        // on the handle's stream, and waited for: a plain hipMemset runs on the null stream, which the handle's non-blocking
+        // streams do not wait for -- it could land after the first pushed frame's kernels and zero part of their state
+        MI_HIP(hipMemsetAsync(s->slabE, 0, off * 4, s->stream));
+        MI_HIP(hipMemsetAsync(s->slabI, 0, off * 4, s->stream));
+        MI_HIP(hipMemsetAsync(s->slabL, 0, off * 12, s->stream));
+        MI_HIP(hipStreamSynchronize(s->stream));
     }
     for (int l = 0; l < L; ++l) {
         size_t np = (size_t)s->lh[l] * s->lw[l];

@@ -1,11 +1,14 @@
 """Frame-sharded multi-GPU stacking: the cross-GPU combine of the per-level selection state.
 
-Frames of one stack are split into contiguous blocks, one block per rank (one process per
-GPU, `torch.distributed`, backend "nccl" = RCCL over xGMI).  Every rank runs the ordinary
-single-GPU path on its block (`Stack.set_first_index(first global frame)`); what remains is an
-arg-max-with-payload reduction of the running state `(E, idx, lap)` of every level and of the
-two base-level features -- the multi-GPU form of `np.argmax(energies, axis=0)` with first-max
-tie-breaking (reference algorithms/pyramid.py:48-55, :103-110).
+Frames of one stack are dealt to the ranks (one process per GPU, `torch.distributed`, backend "nccl" = RCCL over xGMI)
+either in contiguous blocks (`Stack.set_first_index(first global frame)`) or interleaved -- rank r holds frames
+r, r + W, ... (`Stack.set_first_index(r, W)`, the default shard layout of bench.py).  Every rank runs the ordinary
+single-GPU path on its shard; what remains is an arg-max-with-payload reduction of the running state `(E, idx, lap)` of
+every level and of the two base-level features -- the multi-GPU form of `np.argmax(energies, axis=0)` with first-max
+tie-breaking (reference algorithms/pyramid.py:48-55, :103-110).  With contiguous blocks the rank order is the frame
+order and a tie goes to the lower rank; with interleaved shards it is not, and a tie goes to the lower GLOBAL frame index
+(`tiebreak_index`: the candidates' indices travel with their energies).  A rank that pushed no frames (more ranks than
+frames) offers no candidate at all (`withdraw_candidates`).
 
 No stock collective has that operator, and a ring all-reduce of the ~640 MB of state would be
 per-link bound on xGMI.  The exchange is therefore a pixel-domain reduce-scatter over the full
@@ -13,16 +16,17 @@ point-to-point mesh:
 
   1. all_to_all_single  -- rank r receives, from every rank, the r-th pixel chunk of (E, idx, lap)
                            (7 of 8 chunks travel, each over its own xGMI link, in parallel);
-  2. local first-max    -- candidates are ordered by rank = by global frame index, strict '>'
-                           keeps the first maximum (HIP kernel `mi_combine_select`);
-  3. send/recv          -- the winners' chunks go to rank 0, which owns the collapse.
+  2. local first-max    -- strict '>' keeps the first maximum: in rank order (HIP kernel `mi_combine_select`), or by
+                           global frame index (`mi_combine_winner_idx` + a gather);
+  3. gather to rank 0   -- the winners' chunks go to rank 0, which owns the collapse.
 
 The state of all levels (and of the two base features) is exchanged as ONE flat pixel vector per
 array -- 3 all-to-all + 3 gather-to-root collectives per stack in total (`combine_all`), a handful of
 large transfers instead of some 190 small ones (per level: 3 all-to-all + 21 point-to-point at 8 GPUs).
+`combine_winners` reaches the same state with less traffic (only the energies travel twice).
 
-Everything here is host-side plumbing on torch tensors; the same function runs on CPU tensors
-under the "gloo" backend in tests/ (with a torch implementation of step 2 injected there).
+Everything here is host-side plumbing on torch tensors; the same functions run on CPU tensors
+under the "gloo" backend in tests/ (with the torch statements of step 2: `torch_select`, `TorchWinnerOps`).
 """
 import ctypes as C
 
@@ -38,49 +42,16 @@ def chunk_bounds(n, world):
     return [(min(r * per, n), min((r + 1) * per, n)) for r in range(world)]
 
 
-def combine_state(energy, lap, index, group, select_fn, width=3):
+def combine_state(energy, lap, index, group, select_fn, width=3, comm=None, tiebreak_index=False):
     """In-place combine of one level's state across `group`; rank 0 ends up with the result.
 
-    energy: (n,) f32, lap: (n*width,) f32, index: (n,) i32 -- this rank's running state.
-    select_fn(cand_e [W,m], cand_lap [W,m*width], cand_idx [W,m]) -> (e [m], lap [m*width], idx [m])
+    energy: (n,) f32, lap: (n*width,) f32, index: (n,) i32 -- this rank's running state (global frame indices).
+    `combine_all` of this one level: see there for `select_fn`, `comm` and `tiebreak_index`.
     """
-    world = dist.get_world_size(group)
-    rank = dist.get_rank(group)
-    n = energy.numel()
-    bounds = chunk_bounds(n, world)
-    sizes = [b - a for a, b in bounds]
-    mine = sizes[rank]
-
-    def exchange(t, w):
-        out = torch.empty(world * mine * w, dtype=t.dtype, device=t.device)
-        dist.all_to_all_single(out, t, output_split_sizes=[mine * w] * world,
-                               input_split_sizes=[s * w for s in sizes], group=group)
-        return out.view(world, mine * w)
-
-    cand_e = exchange(energy, 1)
-    cand_l = exchange(lap, width)
-    cand_i = exchange(index, 1)
-    win_e, win_l, win_i = select_fn(cand_e, cand_l, cand_i)
-    # winners to rank 0
-    if rank == 0:
-        a, b = bounds[0]
-        energy[a:b] = win_e
-        lap[a * width:b * width] = win_l
-        index[a:b] = win_i
-        for r in range(1, world):
-            a, b = bounds[r]
-            if b > a:
-                dist.recv(energy[a:b], src=dist.get_global_rank(group, r), group=group)
-                dist.recv(lap[a * width:b * width], src=dist.get_global_rank(group, r), group=group)
-                dist.recv(index[a:b], src=dist.get_global_rank(group, r), group=group)
-    elif mine > 0:
-        root = dist.get_global_rank(group, 0)
-        dist.send(win_e.contiguous(), dst=root, group=group)
-        dist.send(win_l.contiguous(), dst=root, group=group)
-        dist.send(win_i.contiguous(), dst=root, group=group)
+    combine_all([(energy, lap, index)], group, select_fn, width, comm=comm, tiebreak_index=tiebreak_index)
 
 
-def combine_all(states, group, select_fn, width=3, with_index=True, root_energy=True):
+def combine_all(states, group, select_fn, width=3, with_index=True, root_energy=True, comm=None, tiebreak_index=False):
     """Combine the state of all levels at once.  `states`: list of (energy (n_l,), lap (n_l*width,),
     index (n_l,)) tensors of this rank; on return rank 0's tensors hold the combined state.
     Same arithmetic as `combine_state` level by level (the pixel chunks just run across level
@@ -88,17 +59,26 @@ def combine_all(states, group, select_fn, width=3, with_index=True, root_energy=
     indices of rank 0 stale (they only feed the debug taps; the fused image needs E and lap alone)
     and moves 16 instead of 20 bytes per pixel.  `root_energy=False` also keeps the winners' energies on the
     chunk owners (3 collectives, 12 instead of 20 bytes per pixel to rank 0): the collapse reads the fused Laplacians
-    and base pixels only, so the fused image is the same; rank 0's energy taps are then stale too."""
+    and base pixels only, so the fused image is the same; rank 0's energy taps are then stale too.
+
+    `select_fn(cand_e [W,m], cand_lap [W,m*width], cand_idx [W,m] or None) -> (e [m], lap [m*width], idx [m] or None)`:
+    the first maximum over the W candidates of every pixel, ties to the lower rank (`torch_select`, `Combiner._select_hip`).
+    `tiebreak_index` (interleaved shards: the rank order is not the frame order): the candidates' global frame indices are
+    exchanged even with `with_index=False` (they still do not go to rank 0 then) and `select_fn` is called with
+    `tiebreak_index=True`: a tie goes to the lower index.
+    `comm`: how the collectives move the tensors (default `DirectComm(group)`; `HostStagedComm` for device tensors over gloo)."""
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
+    comm = comm or DirectComm(group)
+    need_index = with_index or tiebreak_index
     single = len(states) == 1   # the library's contiguous slabs: exchanged in place, no packing copies
     if single:
         e_all, l_all = states[0][0].reshape(-1), states[0][1].reshape(-1)
-        i_all = states[0][2].reshape(-1) if with_index else None
+        i_all = states[0][2].reshape(-1) if need_index else None
     else:
         e_all = torch.cat([e.reshape(-1) for e, _, _ in states])
         l_all = torch.cat([lp.reshape(-1) for _, lp, _ in states])
-        i_all = torch.cat([ix.reshape(-1) for _, _, ix in states]) if with_index else None
+        i_all = torch.cat([ix.reshape(-1) for _, _, ix in states]) if need_index else None
     n = e_all.numel()
     bounds = chunk_bounds(n, world)
     sizes = [b - a for a, b in bounds]
@@ -106,19 +86,17 @@ def combine_all(states, group, select_fn, width=3, with_index=True, root_energy=
 
     def exchange(t, w):
         out = torch.empty(world * mine * w, dtype=t.dtype, device=t.device)
-        dist.all_to_all_single(out, t, output_split_sizes=[mine * w] * world,
-                               input_split_sizes=[s_ * w for s_ in sizes], group=group)
+        comm.all_to_all(out, t, [mine * w] * world, [s_ * w for s_ in sizes])
         return out.view(world, mine * w)
 
-    win_e, win_l, win_i = select_fn(exchange(e_all, 1), exchange(l_all, width),
-                                    exchange(i_all, 1) if with_index else None)
+    cand = (exchange(e_all, 1), exchange(l_all, width), exchange(i_all, 1) if need_index else None)
+    win_e, win_l, win_i = select_fn(*cand, tiebreak_index=True) if tiebreak_index else select_fn(*cand)
 
     def to_root(win, full, w):
         # every rank's winners to rank 0: an all-to-all in which only rank 0 receives
         out = full if rank == 0 else torch.empty(0, dtype=win.dtype, device=win.device)
-        dist.all_to_all_single(out, win.contiguous(),
-                               output_split_sizes=[s_ * w for s_ in sizes] if rank == 0 else [0] * world,
-                               input_split_sizes=[mine * w] + [0] * (world - 1), group=group)
+        comm.all_to_all(out, win.contiguous(), [s_ * w for s_ in sizes] if rank == 0 else [0] * world,
+                        [mine * w] + [0] * (world - 1))
 
     if root_energy:
         to_root(win_e, e_all, 1)
@@ -135,6 +113,33 @@ def combine_all(states, group, select_fn, width=3, with_index=True, root_energy=
             if with_index:
                 ix.reshape(-1).copy_(i_all[off:off + m])
             off += m
+
+
+def withdraw_candidates(energy, index):
+    """Make this rank's state lose every pixel of the exchange.  A rank that pushed no frames (more ranks than frames)
+    holds no candidate, yet its slabs hold whatever they held -- the previous stack's state on a reset handle (the first
+    pushed frame initialises the state, a reset does not clear it), zeros on a fresh one -- which beat negative energies.
+    Energy -inf loses to every real energy, index INT32_MAX every tie by index, whichever rank holds the real candidate;
+    as long as any rank pushed a frame, every pixel keeps a real winner."""
+    energy.fill_(float("-inf"))
+    index.fill_(torch.iinfo(torch.int32).max)
+
+
+def gather_winners(win, cand_e, cand_l, cand_i):
+    """The select step's output from a map of winning ranks `win` [m]: the winners' energies, payload rows and indices."""
+    world, m = cand_e.shape
+    if m == 0:
+        return cand_e[0], cand_l[0], cand_i[0] if cand_i is not None else None
+    best = win.long().view(1, m)
+    width = cand_l.shape[1] // m
+    lap = cand_l.view(world, m, width).gather(0, best.view(1, m, 1).expand(1, m, width)).reshape(-1)
+    return cand_e.gather(0, best).view(m), lap, cand_i.gather(0, best).view(m) if cand_i is not None else None
+
+
+def torch_select(cand_e, cand_l, cand_i=None, tiebreak_index=False):
+    """torch form of the select step of `combine_all` (mi_combine_select; with `tiebreak_index` mi_combine_winner_idx and
+    a gather): the CPU tests' select_fn"""
+    return gather_winners(first_max_rank(cand_e, cand_i if tiebreak_index else None), cand_e, cand_l, cand_i)
 
 
 def first_max_rank(cand_e, cand_i=None):
@@ -326,7 +331,9 @@ class Combiner:
         self._keep = []         # receive buffers / pointer tables the enqueued unpack kernels still read
         self.timings = {}       # host milliseconds of the last combine_winners(): see there
 
-    def _select_hip(self, cand_e, cand_l, cand_i):
+    def _select_hip(self, cand_e, cand_l, cand_i, tiebreak_index=False):
+        if tiebreak_index:      # ties by global frame index: the winner map (mi_combine_winner_idx), then a gather
+            return gather_winners(self.winner(cand_e, cand_i), cand_e, cand_l, cand_i)
         world, m = cand_e.shape
         out_e = torch.empty(m, dtype=torch.float32, device=cand_e.device)
         out_l = torch.empty(cand_l.shape[1], dtype=torch.float32, device=cand_e.device)
@@ -337,6 +344,17 @@ class Combiner:
             cand_i.data_ptr() if cand_i is not None else None, m, out_e.data_ptr(), out_l.data_ptr(),
             out_i.data_ptr() if out_i is not None else None))
         return out_e, out_l, out_i
+
+    def _state(self):
+        """this handle's state as device tensors (all levels, then base entropy twin, base deviation twin: one contiguous
+        slab per array, padding pixels included) and n0, the level-0 part of it"""
+        if self._slabs is None:
+            st = self.stack
+            e_ptr, l_ptr, i_ptr, n = st.state_ptrs(-1)     # (synchronises; once per handle: the slabs do not move)
+            n0 = -(-(st.shapes[0][0] * st.shapes[0][1]) // 64) * 64 if st.levels > 0 else 0
+            self._slabs = (wrap_device(e_ptr, n, torch.float32, self.device), wrap_device(l_ptr, n * 3, torch.float32, self.device),
+                           wrap_device(i_ptr, n, torch.int32, self.device), n0)
+        return self._slabs
 
     # ---- the library's kernels behind the TorchWinnerOps protocol
     def winner(self, cand_e, cand_i=None):
@@ -383,27 +401,28 @@ class Combiner:
         the last batch's level-0 kernels are through -- is exchanged while that batch's coarser levels still run on
         the stacker's side streams; the rest follows after the full synchronisation."""
         st = self.stack
-        if self._slabs is None:
-            e_ptr, l_ptr, i_ptr, n = st.state_ptrs(-1)     # (synchronises; once per handle: the slabs do not move)
-            n0 = -(-(st.shapes[0][0] * st.shapes[0][1]) // 64) * 64 if st.levels > 0 else 0
-            self._slabs = (wrap_device(e_ptr, n, torch.float32, self.device), wrap_device(l_ptr, n * 3, torch.float32, self.device),
-                           wrap_device(i_ptr, n, torch.int32, self.device), n0)
-        e, l, i, n0 = self._slabs
+        e, l, i, n0 = self._state()
         import time
         ts = torch.cuda.current_stream(torch.device("cuda", self.device))
         interleaved = getattr(st, "index_stride", 1) > 1    # the indices break ties, in their global form (export_indices)
+        empty = st.frames_pushed == 0
         kw = dict(with_index=with_index, root_energy=root_energy, comm=self.comm, force=self.force, tiebreak_index=interleaved)
         t0 = time.perf_counter()
-        st.sync_level(0)
-        if interleaved and n0:
-            st.export_indices(0)
+        if empty:       # no candidates here: whatever the slabs hold must not compete (torch's stream, before the exchange)
+            st.sync()
+            withdraw_candidates(e, i)
+        else:
+            st.sync_level(0)
+            if interleaved and n0:
+                st.export_indices(0)
         t1 = time.perf_counter()
         if n0:
             combine_winners(e[:n0], l[:3 * n0], i[:n0], self.group, self, **kw)
         t2 = time.perf_counter()
-        st.sync()       # the coarser levels + base of this rank: they ran on the stacker's streams beside the exchange above
-        if interleaved:
-            st.export_indices(-1)
+        if not empty:
+            st.sync()   # the coarser levels + base of this rank: they ran on the stacker's streams beside the exchange above
+            if interleaved:
+                st.export_indices(-1)
         t3 = time.perf_counter()
         combine_winners(e[n0:], l[3 * n0:], i[n0:], self.group, self, **kw)
         ts.synchronize()
@@ -420,11 +439,13 @@ class Combiner:
         `with_index=False`: do not exchange the winner indices (debug taps only); `root_energy=False`: do not send the
         winners' energies to rank 0 either (the fused image needs the winners' Laplacians / base pixels alone)."""
         st = self.stack
-        st.sync()  # the library's streams are not torch's
-        # all levels, then base entropy twin, base deviation twin: one contiguous slab per array
-        e_ptr, l_ptr, i_ptr, n = st.state_ptrs(-1)
-        states = [(wrap_device(e_ptr, n, torch.float32, self.device),
-                   wrap_device(l_ptr, n * 3, torch.float32, self.device),
-                   wrap_device(i_ptr, n, torch.int32, self.device))]
-        combine_all(states, self.group, self._select_hip, with_index=with_index, root_energy=root_energy)
+        st.state_ptrs(-1)  # runs the pending batch, synchronises: the library's streams are not torch's
+        e, l, i, _ = self._state()
+        interleaved = getattr(st, "index_stride", 1) > 1
+        if st.frames_pushed == 0:
+            withdraw_candidates(e, i)
+        elif interleaved:
+            st.export_indices(-1)
+        combine_all([(e, l, i)], self.group, self._select_hip, with_index=with_index, root_energy=root_energy, comm=self.comm,
+                    tiebreak_index=interleaved)
         torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()

@@ -235,3 +235,213 @@ def test_bench_flow_with_two_ranks_on_one_gpu(scaling):
     d = json.loads(lines[-1])
     assert d["n_gpus"] == 2 and d["scaling"] == scaling and d["verified"] is True, d
     assert d["combine_ms"] > 0 and "SHARING ONE GPU" in d["config"]["parallelism"]
+
+
+MANY_RANKS = r'''
+import os, sys
+import numpy as np
+import torch, torch.distributed as dist
+torch.cuda.init()
+sys.path.insert(0, os.getcwd())
+from shinestacker_amd import _lib as L
+from shinestacker_amd.multigpu import Combiner, HostStagedComm
+from oracle import oracle as orc
+rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+dist.init_process_group("gloo", rank=rank, world_size=world)      # every rank on device 0: RCCL refuses that
+comm = HostStagedComm(dist.group.WORLD)
+H, W = 264, 360                   # 3 levels + a 33 x 45 base
+FULL, PAYLOAD = dict(with_index=True, root_energy=True), dict(with_index=False, root_energy=False)
+fails = []
+
+
+def make_frames(n, seed, hi=256, lo=0, band=True):
+    rng = np.random.default_rng(seed)
+    fr = [rng.integers(lo, hi, (H, W, 3)).astype(np.uint16 if hi > 256 else np.uint8) for _ in range(n)]
+    if band:
+        for f in fr:
+            f[96:160] = (lo + hi) // 3    # flat in every frame: energy exactly 0 there, the frame index alone decides
+    return fr
+
+
+def shard(n, layout):
+    """(global frame indices of this rank, first index, index stride)"""
+    if layout == "interleaved":
+        return list(range(rank, n, world)), rank, world
+    sizes = [n // world + (r >= world - n % world) for r in range(world)]     # ragged contiguous blocks
+    a = sum(sizes[:rank])
+    return list(range(a, a + sizes[rank])), a, 1
+
+
+def push(st, frames, idx, dtype, how):
+    data = [frames[k].astype(dtype) for k in idx]
+    if not data:
+        return
+    if how == "host":
+        for f in data:
+            st.push_frame(f)
+        return
+    fb = data[0].nbytes
+    stride = fb + 4096            # frames apart in device memory: push_frames_device with a frame stride
+    buf = L.DeviceBuffer(stride * len(data))
+    for k, f in enumerate(data):
+        buf.upload(f, k * stride)
+    st.push_frames_device(buf.ptr, len(data), stride)
+    st.sync()
+    buf.free()
+
+
+def check(name, st, frames, kw, dtype, arith, gen, pl):
+    """rank 0 after the combine == one handle that pushed every frame == the oracle of every frame, bit for bit"""
+    whole = L.Stack(H, W, in_dtype=dtype, arith=arith, gen_kernel=gen, pair_levels=pl)
+    for f in frames:
+        whole.push_frame(f.astype(dtype))
+    so = orc.StreamingOracle(H, W, frames[0].dtype, arith=arith, gen_kernel=gen, keep_gauss=False)
+    for f in frames:
+        so.push_frame(f)
+    taps = [(L.TAP_FUSED_LAP, lv, so.best_lap[lv]) for lv in range(st.levels)]
+    if kw["root_energy"]:
+        taps += [(L.TAP_ENERGY, lv, so.best_e[lv]) for lv in range(st.levels)]
+    if kw["with_index"]:
+        taps += [(L.TAP_INDEX, lv, so.best_idx[lv]) for lv in range(st.levels)]
+        taps += [(L.TAP_BASE_IDX_E, st.levels, so.idx_e), (L.TAP_BASE_IDX_D, st.levels, so.idx_d)]
+    for tap, lv, want in taps:
+        got, ref = st.tap(tap, lv), whole.tap(tap, lv)
+        if not np.array_equal(got, ref):
+            fails.append(f"{name}: tap {tap} level {lv} differs from the whole stack at {int((got != ref).sum())} values")
+        if not np.array_equal(got, want):
+            fails.append(f"{name}: tap {tap} level {lv} differs from the oracle at {int((got != want).sum())} values")
+    got, ref, want = st.finish(), whole.finish(), so.finish()
+    if not np.array_equal(got, ref):
+        fails.append(f"{name}: finish() differs from the whole stack at {int((got != ref).sum())} values")
+    if not np.array_equal(got, want):
+        fails.append(f"{name}: finish() differs from the oracle at {int((got != want).sum())} values")
+    fb = st.tap(L.TAP_FUSED_BASE)
+    if not (np.array_equal(fb, whole.tap(L.TAP_FUSED_BASE)) and np.array_equal(fb, so.fused_base())):
+        fails.append(f"{name}: fused base differs")
+    whole.close()
+
+
+def local(name, frames, layout, dtype, arith, how):
+    """every rank's OWN state right after its push == the oracle of its shard (global indices): the per-GPU half of the
+    protocol, with every rank's process on the one GPU at once and every handle fresh (its slabs zeroed at creation: that
+    zeroing must be complete before the first frame's kernels write them)"""
+    idx, first, stride = shard(len(frames), layout)
+    bad = []
+    if idx:
+        st = L.Stack(H, W, in_dtype=dtype, arith=arith)
+        st.set_first_index(first, stride)
+        push(st, frames, idx, dtype, how)
+        so = orc.StreamingOracle(H, W, frames[0].dtype, arith=arith, keep_gauss=False)
+        for k in idx:
+            so.push_frame(frames[k])
+        g = lambda a: first + a * stride
+        taps = [(t, lv, want) for lv in range(st.levels)
+                for t, want in ((L.TAP_ENERGY, so.best_e[lv]), (L.TAP_INDEX, g(so.best_idx[lv])), (L.TAP_FUSED_LAP, so.best_lap[lv]))]
+        taps += [(L.TAP_BASE_IDX_E, st.levels, g(so.idx_e)), (L.TAP_BASE_IDX_D, st.levels, g(so.idx_d))]
+        for tap, lv, want in taps:
+            got = st.tap(tap, lv)
+            if not np.array_equal(got, want):
+                bad.append(f"{name}: rank {rank} ({len(idx)} frames) tap {tap} level {lv} differs at {int((got != want).sum())} values")
+        st.close()
+    every = [None] * world
+    dist.all_gather_object(every, bad)
+    if rank == 0:
+        fails.extend(sum(every, []))
+        print("CASE", name, flush=True)
+
+
+def run(name, frames, layout, proto, kw, dtype=np.uint8, arith="exact", how="host", gen=0.4, pl=0, handle=None):
+    """one stack sharded over the ranks; `handle`: (Stack, Combiner) of an earlier stack, reset and reused"""
+    idx, first, stride = shard(len(frames), layout)
+    if handle is None:
+        st = L.Stack(H, W, in_dtype=dtype, arith=arith, gen_kernel=gen, pair_levels=pl)
+        handle = (st, Combiner(st, comm=comm))     # the library's HIP kernels, not TorchWinnerOps
+    st, cb = handle
+    st.reset()
+    st.set_first_index(first, stride)
+    push(st, frames, idx, dtype, how)
+    if proto == "combine":
+        cb.combine(**kw)
+    else:
+        cb.combine_winners(**kw)
+    if rank == 0:
+        check(name, st, frames, kw, dtype, arith, gen, pl)
+        print("CASE", name, flush=True)
+    return handle
+
+
+N = 13                            # ragged at both worlds: blocks of 1 / 2 at world 8, 4 / 5 at world 3
+dup = make_frames(N, 1)
+dup[2] = dup[1].copy()            # contiguous: inside rank 0 at world 3, across ranks at world 8 ...
+dup[N - 1] = dup[1].copy()        # ... and from the last rank
+ilv = make_frames(N, 2)
+ilv[world] = ilv[world - 1].copy()    # interleaved: frame W - 1 on rank W - 1, its copy W on rank 0 -- the lower index must win
+ilv[1 + world] = ilv[1].copy()        # the same rank (1) twice
+ilv16 = make_frames(N, 3, hi=65536)
+ilv16[world] = ilv16[world - 1].copy()
+fewg = make_frames(min(5, world - 1), 6)     # fewer frames than ranks, on FRESH handles: their zeroed slabs would beat the
+                                             # negative winning energies of gen_kernel=0.7 unless the empty ranks withdraw
+# (name, frames, layout, protocol, variant, dtype, arith, push, gen_kernel, pair_levels): input types and pushes rotate
+cases = [
+    ("combine/full/exact/u8/host/contiguous", dup, "contiguous", "combine", FULL, np.uint8, "exact", "host", 0.4, 0),
+    ("combine/payload/separable/u16/host/interleaved", ilv16, "interleaved", "combine", PAYLOAD, np.uint16, "separable", "host", 0.4, 0),
+    ("combine/full/separable/f32/host/interleaved", ilv, "interleaved", "combine", FULL, np.float32, "separable", "host", 0.4, 0),
+    ("combine/full/exact/u16/device/interleaved/gen0.7", ilv16, "interleaved", "combine", FULL, np.uint16, "exact", "device", 0.7, 0),
+    ("combine/payload/exact/u8/host/interleaved/gen0.7/few", fewg, "interleaved", "combine", PAYLOAD, np.uint8, "exact", "host", 0.7, 0),
+    ("winners/full/separable/f32/device/interleaved/pair_levels=1", ilv, "interleaved", "winners", FULL, np.float32, "separable", "device", 0.4, 1),
+    ("winners/payload/exact/u8/host/contiguous", dup, "contiguous", "winners", PAYLOAD, np.uint8, "exact", "host", 0.4, 0),
+    ("winners/full/exact/u16/host/interleaved", ilv16, "interleaved", "winners", FULL, np.uint16, "exact", "host", 0.4, 0),
+    ("winners/payload/separable/u8/device/interleaved/gen0.7", ilv, "interleaved", "winners", PAYLOAD, np.uint8, "separable", "device", 0.7, 0),
+    ("winners/full/exact/u8/host/interleaved/gen0.7/few", fewg, "interleaved", "winners", FULL, np.uint8, "exact", "host", 0.7, 0),
+]
+# each rank's own stack first: one host frame per rank on three ranks at world 8 (dup, contiguous), one or two elsewhere
+for name, frames, layout, dtype, arith, how in (("local/exact/u8/host/contiguous", dup, "contiguous", np.uint8, "exact", "host"),
+                                                 ("local/exact/u16/host/interleaved", ilv16, "interleaved", np.uint16, "exact", "host"),
+                                                 ("local/separable/u8/host/contiguous", dup, "contiguous", np.uint8, "separable", "host")):
+    local(name, frames, layout, dtype, arith, how)
+for name, frames, layout, proto, kw, dtype, arith, how, gen, pl in cases:
+    st, _ = run(name, frames, layout, proto, kw, dtype, arith, how, gen, pl)
+    st.close()
+# handle reuse: one Stack and one Combiner per rank run three stacks back to back, reset in between, each in another layout.
+# The first two are full-range noise (high energies); the last holds low-contrast frames only, fewer frames than ranks, so the
+# ranks past its frames push nothing and their slabs still hold the previous stack's state -- which must not win anything.
+loud = make_frames(N, 4, band=False)
+few = make_frames(min(5, world - 1), 5, lo=100, hi=132)
+for proto, dtype, arith, how, kws in (("winners", np.uint8, "exact", "host", (FULL, FULL, FULL)),
+                                      ("combine", np.float32, "separable", "device", (PAYLOAD, FULL, FULL))):
+    h = None
+    for k, (frames, layout) in enumerate(((loud, "contiguous"), (ilv, "interleaved"), (few, "interleaved"))):
+        h = run(f"reuse/{proto}/{arith}/stack{k}/{layout}/{len(frames)} frames", frames, layout, proto, kws[k], dtype, arith, how,
+                handle=h)
+    assert h[0].frames_pushed == (1 if rank < len(few) else 0)
+    h[0].close()
+dist.barrier()
+if rank == 0:
+    for f in fails:
+        print("FAIL", f)
+    print(f"MANY_RANKS_OK {world}" if not fails else f"MANY_RANKS_FAILED {len(fails)}")
+dist.destroy_process_group()
+'''
+
+
+@pytest.mark.timeout(1200)
+@pytest.mark.parametrize("world", [3, 8])
+def test_whole_protocol_with_many_ranks_on_one_gpu(tmp_path, world):
+    """`Combiner.combine()` and `Combiner.combine_winners()` with 3 and 8 ranks, every rank a process on the one GPU (gloo +
+    `HostStagedComm`): rank 0's every tap and its image == one handle that pushed all frames == the oracle, bit for bit.
+    Both protocols in the full and the payload-only variant, both arithmetics, 8- / 16-bit and float-32 frames, host and
+    strided device pushes, ragged contiguous and interleaved shards, ties across and inside ranks, a flat band, negative
+    taps, the forced level pair, fresh handles on ranks without frames; then handles reused across stacks, the last with
+    fewer frames than ranks.  First every rank's own state right after its push, against the oracle of its shard."""
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    script = tmp_path / "many_ranks.py"
+    script.write_text(MANY_RANKS)
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
+                        "--master-addr", "127.0.0.1", "--master-port", str(port), str(script)],
+                       env=env, capture_output=True, text=True, timeout=1100,
+                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    print(r.stdout[-6000:])
+    assert f"MANY_RANKS_OK {world}" in r.stdout, r.stdout[-6000:] + r.stderr[-4000:]
