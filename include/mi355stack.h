@@ -494,6 +494,18 @@ MI_API int mi_dmap_push_frame_device(mi_dmap_t* d, const void* dev_bgr);
 MI_API int mi_dmap_finish(mi_dmap_t* d, void* host_out, size_t row_stride_bytes);
 MI_API int mi_dmap_finish_device(mi_dmap_t* d, void* dev_out);
 
+/* Read-only taps (tests): a copy of a plane the handle already holds, height x width, to host memory.  F = float_type;
+ * W = float32 when smooth_size > 0 or float_type is float-32, else float64.  Each plane exists in one phase only; a tap
+ * outside it returns MI_ERR_STATE before anything is read. */
+enum {
+    MI_DM_TAP_ENERGY_RAW = 0, /* F: energy of frame `frame` as pushed; between push and finish                        */
+    MI_DM_TAP_ENERGY_IN = 1,  /* W: what the focus map divides for frame `frame` (normalised, smoothed, or the MAX
+                                 map's relative exp((e - max) / T)); after finish                                     */
+    MI_DM_TAP_TOTAL = 2,      /* W: sum over the frames of the planes above (`frame` ignored); after finish           */
+    MI_DM_TAP_MAX = 3         /* W: MAX map only, maximum over the frames of the (smoothed) energies; after finish    */
+};
+MI_API int mi_dmap_tap(mi_dmap_t* d, int what, int frame, void* host_out);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

@@ -166,9 +166,18 @@ def bilateral_tables(d, sigma_color, sigma_space):
     return radius, offs, np.array(sw, F32), -0.5 / (sigma_color * sigma_color)
 
 
-def bilateral_lut(vmin, vmax, color_coeff, nbins=4096):
+def nudge(v, ulps):
+    """v moved `ulps` representable values up (down if negative) in its own type: the probe behind exp_ulp"""
+    v = np.asarray(v)
+    for _ in range(abs(int(ulps))):
+        v = np.nextafter(v, v.dtype.type(np.inf if ulps > 0 else -np.inf))
+    return v
+
+
+def bilateral_lut(vmin, vmax, color_coeff, nbins=4096, exp_ulp=0):
     """expLUT of the float32 bilateral filter: nbins + 2 entries, entry i = exp((i/scale)^2 * coeff)
-    until it underflows to 0; scale_index = nbins / (max - min) in float32."""
+    until it underflows to 0; scale_index = nbins / (max - min) in float32.
+    exp_ulp: every exp result moved that many float32 values (a probe of how far one last bit of exp carries)."""
     length = F32(F32(float(vmax) - float(vmin)))
     scale_index = F32(F32(nbins) / length)
     lut = np.zeros(nbins + 2, F32)
@@ -176,12 +185,12 @@ def bilateral_lut(vmin, vmax, color_coeff, nbins=4096):
     for i in range(nbins + 2):
         if last > 0:
             val = float(F32(F32(i) / scale_index))
-            lut[i] = F32(math.exp(val * val * color_coeff))
+            lut[i] = nudge(F32(math.exp(val * val * color_coeff)), exp_ulp)
             last = lut[i]
     return lut, scale_index
 
 
-def bilateral_f32(img, d, sigma_color=25.0, sigma_space=25.0):
+def bilateral_f32(img, d, sigma_color=25.0, sigma_space=25.0, exp_ulp=0):
     """cv2.bilateralFilter on a 1-channel float32 image: disc of radius d/2 in raster order,
     range weight from the 4096-bin interpolated exp table, float32 accumulation
     sum += val*w, wsum += w, result sum / wsum.  A constant image is returned unchanged."""
@@ -190,7 +199,7 @@ def bilateral_f32(img, d, sigma_color=25.0, sigma_space=25.0):
     if abs(vmin - vmax) < np.finfo(F32).eps:
         return img.copy()
     radius, offs, sw, cc = bilateral_tables(d, sigma_color, sigma_space)
-    lut, scale_index = bilateral_lut(vmin, vmax, cc)
+    lut, scale_index = bilateral_lut(vmin, vmax, cc, exp_ulp=exp_ulp)
     h, w = img.shape
     p = _pad101(img, radius)
     s = np.zeros((h, w), F32)
@@ -264,12 +273,39 @@ def pyr_up(img, dstsize):
 
 
 # --------------------------------------------------------------------------- the stacker
+def focus_map(en, map_type="average", temperature=0.1, exp_ulp=0):
+    """get_focus_map (depth_map.py:54-62) on a list of planes of one type.  Returns (weights, the planes the division
+    works on -- `en` itself or the MAX map's relatives --, their sum, the per-pixel maximum or None)."""
+    WT = en[0].dtype.type
+    if map_type == "average":                                                     # :55-57
+        tot = np.zeros_like(en[0])
+        for e in en:
+            tot = tot + e
+        # where the sum is 0 the reference leaves np.divide's output uninitialised; 0 here
+        return [np.divide(e, tot, out=np.zeros_like(e), where=tot != 0) for e in en], en, tot, None
+    if map_type == "max":                                                         # :58-61
+        m = en[0]
+        for e in en[1:]:
+            m = np.maximum(m, e)
+        rel = [nudge(exp_rounded((e - m) / WT(temperature)), exp_ulp) for e in en]
+        tot = np.zeros_like(rel[0])
+        for r in rel:
+            tot = tot + r
+        return [r / tot for r in rel], rel, tot, m
+    raise ValueError("map_type")
+
+
 def depth_map_stack(frames, map_type="average", energy="laplacian", kernel_size=5, blur_size=5,
-                    smooth_size=15, temperature=0.1, levels=3, float_type="float-32", gray_fn=None):
+                    smooth_size=15, temperature=0.1, levels=3, float_type="float-32", gray_fn=None, stages=False, exp_ulp=0):
     """DepthMapStack.focus_stack (depth_map.py:64-123), frame at a time, for float_type 'float-32' / 'float-64'.
     `frames`: list of H x W x 3 uint8 / uint16 BGR arrays.  Returns the fused frame.
     float-64: gray / energy planes and the image pyramids are float64; the bilateral filter still runs on
-    float32 copies and its output array is float32 (depth_map.py:46-51), so with smoothing the weights are float32."""
+    float32 copies and its output array is float32 (depth_map.py:46-51), so with smoothing the weights are float32.
+    stages: True returns a dict instead -- 'energy_raw' (per frame, before the division by the global maximum),
+    'energy_in' (per frame, what the focus map divides: normalised, smoothed, or the MAX map's relatives), 'mx' (MAX map:
+    the per-pixel maximum), 'tot', 'weights' and 'out' (the fused frame); 'maps' stops before the blend (no 'out').
+    exp_ulp: every exp of the algorithm (range table, softmax) moved that many values of its type -- tests derive
+    their bounds for the stages behind an exp from the spread between -1, 0 and +1."""
     from . import oracle as orc
     gray_fn = gray_fn or orc.bgr2gray_int
     FT = {"float-32": np.float32, "float-64": np.float64}[float_type]
@@ -281,29 +317,18 @@ def depth_map_stack(frames, map_type="average", energy="laplacian", kernel_size=
         en = [laplacian_energy(g, blur_size, kernel_size, FT) for g in grays]     # :36-41
     else:
         raise ValueError("energy")
+    st = {"energy_raw": en}
     mx = max(e.max() for e in en)                                                 # :88
     if mx > 0:
         en = [e / mx for e in en]                                                 # :90
     if smooth_size > 0:
-        en = [bilateral_f32(e.astype(F32), smooth_size, 25, 25) for e in en]      # :43-52 (float32 result array)
-    WT = en[0].dtype.type
-    if map_type == "average":                                                     # :55-57
-        tot = np.zeros_like(en[0])
-        for e in en:
-            tot = tot + e
-        # where the sum is 0 the reference leaves np.divide's output uninitialised; 0 here
-        weights = [np.divide(e, tot, out=np.zeros_like(e), where=tot != 0) for e in en]
-    elif map_type == "max":                                                       # :58-61
-        m = en[0]
-        for e in en[1:]:
-            m = np.maximum(m, e)
-        rel = [exp_rounded((e - m) / WT(temperature)) for e in en]
-        tot = np.zeros_like(rel[0])
-        for r in rel:
-            tot = tot + r
-        weights = [r / tot for r in rel]
-    else:
-        raise ValueError("map_type")
+        en = [bilateral_f32(e.astype(F32), smooth_size, 25, 25, exp_ulp) for e in en]      # :43-52 (float32 result array)
+    weights, en, tot, m = focus_map(en, map_type, temperature, exp_ulp)
+    if m is not None:
+        st["mx"] = m
+    st.update(energy_in=en, tot=tot, weights=weights)
+    if stages == "maps":
+        return st
     blended = None
     for f, wgt in zip(frames, weights):                                           # :94-112
         gp_img, gp_w = [f.astype(FT)], [wgt]
@@ -321,7 +346,11 @@ def depth_map_stack(frames, map_type="average", energy="laplacian", kernel_size=
         size = (blended[j].shape[1], blended[j].shape[0])
         result = pyr_up(result, size) + blended[j]
     n_values = 255 if dtype == np.uint8 else 65535
-    return np.clip(np.absolute(result), 0, n_values).astype(dtype)               # :122-123
+    out = np.clip(np.absolute(result), 0, n_values).astype(dtype)                # :122-123
+    if stages:
+        st["out"] = out
+        return st
+    return out
 
 
 def exp_rounded(x):

@@ -63,6 +63,7 @@ class DepthMapParams(C.Structure):
 
 DM_MAP_AVERAGE, DM_MAP_MAX = 0, 1
 DM_ENERGY_LAPLACIAN, DM_ENERGY_SOBEL = 0, 1
+DM_TAP_ENERGY_RAW, DM_TAP_ENERGY_IN, DM_TAP_TOTAL, DM_TAP_MAX = range(4)
 
 # name -> (restype, argtypes); also the list the symbol-export test walks
 SIGNATURES = {
@@ -186,6 +187,7 @@ SIGNATURES = {
     "mi_dmap_push_frame_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mi_dmap_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi_dmap_finish_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_dmap_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }
@@ -592,6 +594,7 @@ class DepthMap:
         p.kernel_size, p.blur_size, p.smooth_size = int(kernel_size), int(blur_size), int(smooth_size)
         p.levels, p.temperature, p.float_type = int(levels), float(temperature), int(float_type)
         self.height, self.width, self.device = p.height, p.width, p.device
+        self._f64, self._smooth = p.float_type == MI_F64, p.smooth_size > 0
         h = C.c_void_p()
         check(lib.mi_dmap_create(C.byref(h), C.byref(p)))
         self._h = h
@@ -652,6 +655,15 @@ class DepthMap:
 
     def finish_device(self, dev_ptr=None):
         check(load().mi_dmap_finish_device(self._h, dev_ptr))
+
+    def tap(self, what, frame=0):
+        """mi_dmap_tap: a plane the handle holds, H x W.  DM_TAP_ENERGY_RAW (float_type, between push and finish);
+        DM_TAP_ENERGY_IN / DM_TAP_TOTAL / DM_TAP_MAX (the weights' type, after finish)"""
+        ft = np.float64 if self._f64 else np.float32
+        wt = np.float32 if self._smooth or not self._f64 else np.float64
+        out = np.empty((self.height, self.width), ft if what == DM_TAP_ENERGY_RAW else wt)
+        check(load().mi_dmap_tap(self._h, int(what), int(frame), out.ctypes.data))
+        return out
 
 
 def synth_frames_device(dev_ptr, dtype, height, width, first_frame, n_frames, stack_size,

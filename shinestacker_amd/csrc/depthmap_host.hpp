@@ -82,7 +82,7 @@ void dmap_gauss_taps(int ksize, DmTapsT<F>& t) {
     double sum = 0.0;
     for (int i = 0; i < ksize; ++i) {
         const double x = i - (ksize - 1) * 0.5;
-        t.k[i] = (F)std::exp(scale * x * x);
+        t.k[i] = (F)std::exp(scale * (x * x));   // the oracle's grouping: (scale * x) * x differs in the last bit of float-64 taps (9, 15, 21, 31)
         sum += (double)t.k[i];
     }
     sum = 1.0 / sum;
@@ -628,6 +628,44 @@ int mi_dmap_finish_device(mi_dmap_t* d, void* dev_out) {
     if (dev_out)
         MI_HIP(hipMemcpyAsync(dev_out, d->out_dev, (size_t)d->p.height * d->p.width * 3 * d->esz, hipMemcpyDeviceToDevice,
                               d->stream));
+    MI_HIP(hipStreamSynchronize(d->stream));
+    return MI_OK;
+}
+
+// Read-only copy of a plane the stacker already holds: no kernel, no change of state.  Which planes are valid depends on
+// the phase -- en[i] is the raw energy until finish turns it into the focus map's input in place -- so a tap outside its
+// phase is refused on the host instead of returning whatever the buffer holds.
+int mi_dmap_tap(mi_dmap_t* d, int what, int frame, void* host_out) {
+    if (!d || !host_out) return fail(MI_ERR_INVALID, "null argument");
+    const size_t np = (size_t)d->p.height * d->p.width;
+    const size_t wsz = (d->p.smooth_size > 0 || !d->f64) ? 4 : 8;   // W (dmap_finish_t)
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (what) {
+        case MI_DM_TAP_ENERGY_RAW:
+            if (d->finished) return fail(MI_ERR_STATE, "raw energies are gone after finish (normalised in place)");
+            if (frame < 0 || frame >= d->n) return fail(MI_ERR_INVALID, "frame %d of %d pushed", frame, d->n);
+            src = d->en[frame];
+            bytes = np * d->fsz;
+            break;
+        case MI_DM_TAP_ENERGY_IN:
+            if (!d->finished) return fail(MI_ERR_STATE, "the focus map's input exists after finish");
+            if (frame < 0 || frame >= d->n) return fail(MI_ERR_INVALID, "frame %d of %d pushed", frame, d->n);
+            src = d->en[frame];
+            bytes = np * wsz;
+            break;
+        case MI_DM_TAP_TOTAL:
+        case MI_DM_TAP_MAX:
+            if (!d->finished) return fail(MI_ERR_STATE, "the total / maximum plane exists after finish");
+            if (what == MI_DM_TAP_MAX && d->p.map_type != MI_DM_MAP_MAX) return fail(MI_ERR_INVALID, "the AVERAGE map keeps no maximum plane");
+            src = what == MI_DM_TAP_TOTAL ? d->tot : d->mx;
+            bytes = np * wsz;
+            break;
+        default:
+            return fail(MI_ERR_INVALID, "unknown tap %d", what);
+    }
+    MI_HIP(hipSetDevice(d->p.device));
+    MI_HIP(hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, d->stream));
     MI_HIP(hipStreamSynchronize(d->stream));
     return MI_OK;
 }

@@ -85,6 +85,15 @@ def test_argument_validation_without_gpu(hiplib):
     assert lib.mi_stack_create(None, None) == hiplib.MI_ERR_INVALID
     assert b"null" in lib.mi_last_error()
     assert lib.mi_stack_levels(None, None) == hiplib.MI_ERR_INVALID
+    assert lib.mi_dmap_tap(None, hiplib.DM_TAP_TOTAL, 0, None) == hiplib.MI_ERR_INVALID
+
+
+def test_depth_map_tap_is_declared_exported_and_bound(hiplib):
+    assert "mi_dmap_tap" in header_symbols() and "mi_dmap_tap" in hiplib.SIGNATURES
+    assert hasattr(ctypes.CDLL(hiplib.LIB_PATH), "mi_dmap_tap")
+    text = open(HEADER).read()
+    for i, name in enumerate(("ENERGY_RAW", "ENERGY_IN", "TOTAL", "MAX")):
+        assert re.search(rf"MI_DM_TAP_{name} = {i}\b", text) and getattr(hiplib, "DM_TAP_" + name) == i
 
 
 @pytest.mark.skipif(os.environ.get("MI_EXPECT_GPU") == "1", reason="GPU box")
