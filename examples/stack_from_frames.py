@@ -3,18 +3,20 @@
 script on the MI355X path.  Same action graph, same parameter names as shinestacker's
 StackJob / CombinedActions / AlignFrames / BalanceFrames / FocusStack; only the imports differ.
 
-    python examples/stack_from_frames.py <working_dir> <input_subdir> [--no-align]
+    python examples/stack_from_frames.py <working_dir> <input_subdir> [--no-align] [--vignetting] [--noise-map FOLDER]
 
-Without OpenCV the transform is estimated by the GPU ECC estimator (shinestacker_amd.align.ecc_estimator);
-with OpenCV installed, drop the `estimator=` argument to use the reference's SIFT + RANSAC recipe."""
+`--noise-map FOLDER` and `--vignetting` build the reference's full graph: NoiseDetection over the frames of FOLDER (dark frames,
+under the working directory) writes noise-map/hot_pixels.png, then MaskNoise and Vignetting run in front of AlignFrames -- the
+reference's sub-action order MaskNoise, Vignetting, AlignFrames, BalanceFrames.
+"""
 import argparse
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from shinestacker_amd import (AlignFrames, BalanceFrames, CombinedActions, FocusStack, PyramidStack,  # noqa: E402
-                              StackJob)
+from shinestacker_amd import (AlignFrames, BalanceFrames, CombinedActions, FocusStack, MaskNoise, NoiseDetection,  # noqa: E402
+                              PyramidStack, StackJob, Vignetting)
 from shinestacker_amd.align import ecc_estimator  # noqa: E402
 
 
@@ -23,14 +25,20 @@ def main():
     ap.add_argument("working_dir")
     ap.add_argument("input_subdir")
     ap.add_argument("--no-align", action="store_true")
+    ap.add_argument("--vignetting", action="store_true", help="correct the vignetting of every frame before it is aligned")
+    ap.add_argument("--noise-map", metavar="FOLDER", help="map the hot pixels of the frames in FOLDER (relative to the working "
+                    "directory) first, and mask them in every frame")
     args = ap.parse_args()
     job = StackJob("focus-stack", args.working_dir, input_path=args.input_subdir)
     stack_input = args.input_subdir
+    if args.noise_map:
+        job.add_action(NoiseDetection("noise-map", input_path=args.noise_map))
     if not args.no_align:
+        pre = ([MaskNoise()] if args.noise_map else []) + ([Vignetting()] if args.vignetting else [])
         job.add_action(CombinedActions("align-and-balance",
-                                       [AlignFrames(estimator=ecc_estimator()),
-                                        BalanceFrames(channel="RGB", corr_map="MATCH_HIST")],
-                                       output_path="align"))
+                                       pre + [AlignFrames(estimator=ecc_estimator()),
+                                              BalanceFrames(channel="RGB", corr_map="MATCH_HIST")],
+                                       input_path=args.input_subdir, output_path="align"))
         stack_input = "align"
     job.add_action(FocusStack("stack", PyramidStack(), input_path=stack_input, output_path="stack",
                               prefix="stack_"))

@@ -446,6 +446,50 @@ MI_API int mi_cvt_color(int device, const void* host_src, void* host_dst, int he
 MI_API int mi_cvt_color_device(int device, void* stream, const void* dev_src, void* dev_dst, size_t npixels, int dtype,
                         int code);
 
+/* ---- Vignetting and MaskNoise: the corrections a frame gets before it is aligned (reference algorithms/vignetting.py,
+ * algorithms/noise_detection.py:145-198; kernels in csrc/kernels_prestack.hpp).
+ * mi_subsampled_size: the size of an image sub-sampled by `subsample` as utils.py:79-86 does it (fast: img[::s, ::s] ->
+ * ceil(dim / s); otherwise cv2.resize(INTER_AREA) -> round-half-even(dim / s)).
+ * mi_radial_ring_sums_device: vignetting.py:23-39 (radial_mean_intensity) over the sub-sampled 8-bit gray image of a device
+ * BGR frame (vignetting.py:52-55: img >> 8 for 16-bit, integer BGR2GRAY, then the sub-sampling), as integers: sums[i] and
+ * counts[i] of the pixels with radii[i] <= d < radii[i + 1], d = sqrt((x - ws/2)^2 + (y - hs/2)^2) in float64 on the
+ * sub-sampled grid.  radii: host array of r_steps + 1 doubles (np.linspace(0, r_max, r_steps + 1)); sums / counts: host
+ * arrays of r_steps.  The ring mean is sums[i] / counts[i] (NaN where counts[i] == 0).  dev_scratch:
+ * mi_radial_ring_scratch_bytes(r_steps) bytes.  r_steps <= 2048.  Synchronises `stream`. */
+MI_API int mi_subsampled_size(int height, int width, int subsample, int fast, int* hs, int* ws);
+MI_API size_t mi_radial_ring_scratch_bytes(int r_steps);
+MI_API int mi_radial_ring_sums_device(int device, void* stream, const void* dev_img, void* dev_scratch, int height, int width,
+                               int dtype, int subsample, int fast, int r_steps, const double* radii, uint64_t* sums,
+                               uint32_t* counts);
+/* mi_vignette_apply_device: vignetting.py:84-97 (correct_vignetting) with the model's parameters given: per pixel
+ * gain = clip(sigmoid_model(r, i0, k, r0) / v0, 1e-6, 1), blended (1 - max_correction) + gain * max_correction when
+ * max_correction < 1, 1 where min(B, G, R) < threshold; dst = trunc(clip(src / gain, 0, max)), float64.  uint8 / uint16 BGR,
+ * 16-byte aligned, in place allowed (dev_dst == dev_src).  Enqueued on `stream`, no synchronisation. */
+MI_API int mi_vignette_apply_device(int device, void* stream, const void* dev_src, void* dev_dst, int height, int width,
+                             int dtype, double i0, double k, double r0, double v0, double max_correction, double threshold);
+/* mi_mask_noise_device: noise_detection.py:171-198 for n hot pixels: dev_coords = n (y, x) int32 pairs; every channel of
+ * each of them becomes the truncated mean (method 0) or median (method 1) of the non-zero values of the UNCORRECTED channel
+ * in the kernel_size x kernel_size window clipped to the image (unchanged when there is none).  dev_stage: n * 3 uint32.
+ * dev_dst may be dev_src (in place) or a distinct image, which first receives a copy of the source.  Coordinates outside
+ * the image are ignored.  Enqueued on `stream`, no synchronisation. */
+enum { MI_MASK_NOISE_MEAN = 0, MI_MASK_NOISE_MEDIAN = 1 };
+MI_API int mi_mask_noise_device(int device, void* stream, const void* dev_src, void* dev_dst, int height, int width,
+                         int dtype, const int32_t* dev_coords, int n, int kernel_size, int method, void* dev_stage);
+
+/* ---- NoiseDetection (noise_detection.py:21-143).
+ * mi_frame_accumulate_device: dev_sum[i] += sum over the n contiguous uint8 frames of frame[i]; dev_sum: uint32, 16-byte
+ * aligned, zeroed by the caller before the first batch; exact below 2^24 frames.  Enqueued, no synchronisation.
+ * mi_hot_pixel_map_device: mean = sum / n_frames (truncated, uint8) -> cv2.GaussianBlur(mean, (blur_size, blur_size), 0) for
+ * blur_size 3, 5, 7 (OpenCV's fixed small kernels in its 8.8 fixed-point path, BORDER_REFLECT101; MI_ERR_UNSUPPORTED
+ * otherwise) -> |mean - blur| > thresholds[c] per channel -> dev_map (H x W uint8, 255 where any channel is hot); dev_mean:
+ * NULL or H x W x 3 uint8 that receives the mean image; counts[4] (host): hot pixels in the map and in channels 0, 1, 2;
+ * dev_counts: 16 bytes of device scratch.  Synchronises `stream`. */
+MI_API int mi_frame_accumulate_device(int device, void* stream, const void* dev_frames, int n, size_t elements_per_frame,
+                               void* dev_sum);
+MI_API int mi_hot_pixel_map_device(int device, void* stream, const void* dev_sum, int n_frames, int height, int width,
+                            int blur_size, const int* thresholds, void* dev_mean, void* dev_map, void* dev_counts,
+                            uint32_t* counts);
+
 /* ---- DepthMapStack: the second stacker behind the same plug-in boundary ----
  * Replaces the arithmetic of DepthMapStack.focus_stack (reference algorithms/depth_map.py:64-123) for
  * both float types: push = the first file loop (:67-75: read, img_bw, then per frame get_sobel_map :28-34

@@ -10,6 +10,8 @@ from .actions import (StackJob, FocusStack, FocusStackBunch, CombinedActions, Su
 
 from .align import AlignFrames, align_images  # noqa: F401,E402
 from .balance import BalanceFrames  # noqa: F401,E402
+from .vignetting import Vignetting  # noqa: F401,E402
+from .noise_detection import MaskNoise, NoiseDetection  # noqa: F401,E402
 
-__all__ = ["AlignFrames", "BalanceFrames", "align_images", "PyramidStack", "DepthMapStack", "BaseStackAlgo", "StackJob", "FocusStack", "FocusStackBunch",
+__all__ = ["AlignFrames", "BalanceFrames", "Vignetting", "MaskNoise", "NoiseDetection", "align_images", "PyramidStack", "DepthMapStack", "BaseStackAlgo", "StackJob", "FocusStack", "FocusStackBunch",
            "CombinedActions", "SubAction", "get_bunches", "constants"]

@@ -22,6 +22,7 @@
 #include "kernels_ecc.hpp"
 #include "kernels_phase.hpp"
 #include "kernels_balance.hpp"
+#include "kernels_prestack.hpp"
 #include "kernels_f64.hpp"
 #include "kernels_steps.hpp"
 
@@ -2633,6 +2634,144 @@ int mi_apply_lut(int device, const void* host_src, void* host_dst, int height, i
     if (!rc && hipMemcpy(host_dst, dst, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
     cleanup();
     return rc;
+}
+
+// ---------------------------------------------------------------- Vignetting / MaskNoise (kernels_prestack.hpp)
+int mi_subsampled_size(int height, int width, int subsample, int fast, int* hs, int* ws) {
+    if (!hs || !ws || height < 1 || width < 1 || subsample < 1) return fail(MI_ERR_INVALID, "bad argument");
+    if (subsample == 1) { *hs = height; *ws = width; }
+    else if (fast) { *hs = cdiv(height, subsample); *ws = cdiv(width, subsample); }   // img[::s, ::s]
+    else {   // cv2.resize's output size: round half to even of dim / s
+        *hs = (int)std::nearbyint((double)height * (1.0 / subsample));
+        *ws = (int)std::nearbyint((double)width * (1.0 / subsample));
+    }
+    if (*hs < 1 || *ws < 1) return fail(MI_ERR_INVALID, "image smaller than the sub-sampling factor");
+    return MI_OK;
+}
+
+size_t mi_radial_ring_scratch_bytes(int r_steps) {
+    return r_steps < 1 ? 0 : sizeof(double) * ((size_t)r_steps + 1) + (sizeof(uint64_t) + sizeof(uint32_t)) * (size_t)r_steps;
+}
+
+int mi_radial_ring_sums_device(int device, void* stream, const void* dev_img, void* dev_scratch, int height, int width, int dtype,
+                               int subsample, int fast, int r_steps, const double* radii, uint64_t* sums, uint32_t* counts) {
+    if (!dev_img || !dev_scratch || !radii || !sums || !counts) return fail(MI_ERR_INVALID, "null argument");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
+    if (r_steps < 1 || r_steps > MI_MAX_RINGS) return fail(MI_ERR_INVALID, "r_steps must be in [1, %d]", MI_MAX_RINGS);
+    RingArgs a{};
+    int rc = mi_subsampled_size(height, width, subsample, fast, &a.hs, &a.ws);
+    if (rc) return rc;
+    if (!(radii[r_steps] > 0.0)) return fail(MI_ERR_INVALID, "radii[r_steps] must be positive");
+    const size_t total = (size_t)a.hs * a.ws;
+    if (total > ((size_t)1 << 31)) return fail(MI_ERR_INVALID, "image too large");
+    MI_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: radii [r_steps + 1] double | sums [r_steps] uint64 | counts [r_steps] uint32
+    double* d_radii = (double*)dev_scratch;
+    unsigned long long* d_sums = (unsigned long long*)(d_radii + r_steps + 1);
+    uint32_t* d_counts = (uint32_t*)(d_sums + r_steps);
+    MI_HIP(hipMemcpyAsync(d_radii, radii, sizeof(double) * (r_steps + 1), hipMemcpyHostToDevice, st));
+    MI_HIP(hipMemsetAsync(d_sums, 0, (sizeof(uint64_t) + sizeof(uint32_t)) * (size_t)r_steps, st));
+    a.img = dev_img; a.h = height; a.w = width; a.s = subsample; a.fast = fast ? 1 : 0; a.r_steps = r_steps;
+    a.radii = d_radii; a.cx = (double)a.ws / 2.0; a.cy = (double)a.hs / 2.0; a.per_r = (double)r_steps / radii[r_steps];
+    a.sums = d_sums; a.counts = d_counts;
+    const unsigned nblk = (unsigned)std::min<size_t>((total + 255) / 256, 2048);   // <= 2^20 + 256 pixels per workgroup
+    if (dtype == MI_U8) hipLaunchKernelGGL(radial_ring_sums<uint8_t>, dim3(nblk), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(radial_ring_sums<uint16_t>, dim3(nblk), dim3(256), 0, st, a);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipMemcpyAsync(sums, d_sums, sizeof(uint64_t) * r_steps, hipMemcpyDeviceToHost, st));
+    MI_HIP(hipMemcpyAsync(counts, d_counts, sizeof(uint32_t) * r_steps, hipMemcpyDeviceToHost, st));
+    MI_HIP(hipStreamSynchronize(st));
+    return MI_OK;
+}
+
+int mi_vignette_apply_device(int device, void* stream, const void* dev_src, void* dev_dst, int height, int width, int dtype,
+                             double i0, double k, double r0, double v0, double max_correction, double threshold) {
+    if (!dev_src || !dev_dst) return fail(MI_ERR_INVALID, "null argument");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
+    if (height < 1 || width < 1) return fail(MI_ERR_INVALID, "bad image size");
+    if (((uintptr_t)dev_src | (uintptr_t)dev_dst) & 15) return fail(MI_ERR_INVALID, "images must be 16-byte aligned");
+    MI_HIP(hipSetDevice(device));
+    VignArgs a{};
+    a.h = height; a.w = width; a.cx = (double)width / 2.0; a.cy = (double)height / 2.0;
+    a.i0 = i0; a.k = k; a.r0 = r0; a.v0 = v0; a.max_correction = max_correction; a.threshold = threshold;
+    const size_t nspan = (size_t)height * width * 3 * dtype_size(dtype) / 48;
+    const unsigned nblk = (unsigned)std::min<size_t>((nspan + 255) / 256 + 1, 256 * 16);
+    if (dtype == MI_U8)
+        hipLaunchKernelGGL(vignette_apply<uint8_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)dev_src,
+                           (uint8_t*)dev_dst, a);
+    else
+        hipLaunchKernelGGL(vignette_apply<uint16_t>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)dev_src,
+                           (uint16_t*)dev_dst, a);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_mask_noise_device(int device, void* stream, const void* dev_src, void* dev_dst, int height, int width, int dtype,
+                         const int32_t* dev_coords, int n, int kernel_size, int method, void* dev_stage) {
+    if (!dev_src || !dev_dst) return fail(MI_ERR_INVALID, "null argument");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
+    if (height < 1 || width < 1 || n < 0) return fail(MI_ERR_INVALID, "bad argument");
+    if (kernel_size < 1 || !(kernel_size & 1)) return fail(MI_ERR_INVALID, "kernel_size must be odd and >= 1");
+    if (method != MASK_NOISE_MEAN && method != MASK_NOISE_MEDIAN) return fail(MI_ERR_INVALID, "bad method %d", method);
+    if (n > 0 && (!dev_coords || !dev_stage)) return fail(MI_ERR_INVALID, "null argument");
+    MI_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    if (dev_dst != dev_src)
+        MI_HIP(hipMemcpyAsync(dev_dst, dev_src, (size_t)height * width * 3 * dtype_size(dtype), hipMemcpyDeviceToDevice, st));
+    if (n == 0) return MI_OK;
+    const dim3 grid((unsigned)cdiv(n * 3, 256)), blk(256);
+    if (dtype == MI_U8) {
+        hipLaunchKernelGGL(mask_noise_apply<uint8_t>, grid, blk, 0, st, (const uint8_t*)dev_src, height, width, dev_coords, n,
+                           kernel_size / 2, method, (uint32_t*)dev_stage);
+        hipLaunchKernelGGL(mask_noise_store<uint8_t>, grid, blk, 0, st, (uint8_t*)dev_dst, width, dev_coords, n,
+                           (const uint32_t*)dev_stage);
+    } else {
+        hipLaunchKernelGGL(mask_noise_apply<uint16_t>, grid, blk, 0, st, (const uint16_t*)dev_src, height, width, dev_coords, n,
+                           kernel_size / 2, method, (uint32_t*)dev_stage);
+        hipLaunchKernelGGL(mask_noise_store<uint16_t>, grid, blk, 0, st, (uint16_t*)dev_dst, width, dev_coords, n,
+                           (const uint32_t*)dev_stage);
+    }
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_frame_accumulate_device(int device, void* stream, const void* dev_frames, int n, size_t elements_per_frame, void* dev_sum) {
+    if (!dev_frames || !dev_sum || n < 0) return fail(MI_ERR_INVALID, "bad argument");
+    if (((uintptr_t)dev_sum & 15) || ((uintptr_t)dev_frames & 3) || (n > 1 && (elements_per_frame & 3)))
+        return fail(MI_ERR_INVALID, "sums must be 16-byte aligned, frames 4-byte aligned");
+    if (n == 0 || elements_per_frame == 0) return MI_OK;
+    MI_HIP(hipSetDevice(device));
+    const unsigned nblk = (unsigned)std::min<size_t>((elements_per_frame / 4 + 255) / 256 + 1, 256 * 16);
+    hipLaunchKernelGGL(frame_accumulate, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)dev_frames, n,
+                       elements_per_frame, (uint32_t*)dev_sum);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_hot_pixel_map_device(int device, void* stream, const void* dev_sum, int n_frames, int height, int width, int blur_size,
+                            const int* thresholds, void* dev_mean, void* dev_map, void* dev_counts, uint32_t* counts) {
+    if (!dev_sum || !thresholds || !dev_map || !dev_counts || !counts) return fail(MI_ERR_INVALID, "null argument");
+    if (height < 1 || width < 1 || n_frames < 1) return fail(MI_ERR_INVALID, "bad argument");
+    if (blur_size != 3 && blur_size != 5 && blur_size != 7)
+        return fail(MI_ERR_UNSUPPORTED, "blur_size must be 3, 5 or 7 (OpenCV's fixed small Gaussian kernels)");
+    static const int W3[3] = {1, 2, 1}, W5[5] = {1, 4, 6, 4, 1}, W7[7] = {2, 7, 14, 18, 14, 7, 2};
+    HotArgs a{};
+    a.sum = (const uint32_t*)dev_sum; a.h = height; a.w = width; a.n = n_frames; a.r = blur_size / 2;
+    const int* wt = blur_size == 3 ? W3 : (blur_size == 5 ? W5 : W7);
+    int total = 0;
+    for (int i = 0; i < blur_size; ++i) { a.wt[i] = wt[i]; total += wt[i]; }
+    a.f2 = (256 / total) * (256 / total);
+    for (int c = 0; c < 3; ++c) a.th[c] = thresholds[c];
+    a.mean = (uint8_t*)dev_mean; a.map = (uint8_t*)dev_map; a.counts = (uint32_t*)dev_counts;
+    MI_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    MI_HIP(hipMemsetAsync(dev_counts, 0, 4 * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(hot_pixel_map, dim3(cdiv(width, MI_HOT_TILE), cdiv(height, MI_HOT_TILE)), dim3(MI_HOT_TILE, MI_HOT_TILE), 0, st, a);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipMemcpyAsync(counts, dev_counts, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    MI_HIP(hipStreamSynchronize(st));
+    return MI_OK;
 }
 
 int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,

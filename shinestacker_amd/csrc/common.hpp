@@ -98,6 +98,16 @@ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// cv2.resize(INTER_AREA) by an integer factor s on 8/16-bit data, one output value from the integer sum of its block
+// [from memory -- parity unpinned]: a whole block (n == s * s) is (sum + 2) >> 2 for s == 2, else the float32 product
+// sum * (1 / s^2) rounded half to even; a block that hangs over the image edge (the output size is round-half-even(dim / s))
+// averages the n pixels it has, float32 sum / n rounded half to even.  The one statement of the rule for the balance
+// histogram, the ECC gray pyramid and the vignetting ring sums.
+__device__ __forceinline__ uint32_t area_mean_int(uint32_t sum, int n, int s) {
+    if (n == s * s) return s == 2 ? (sum + 2u) >> 2 : (uint32_t)__float2int_rn((float)sum * (1.0f / (float)(s * s)));
+    return (uint32_t)__float2int_rn((float)sum / (float)n);
+}
+
 // MI_ARITH_SEPARABLE, taps of the reduce (kernels_sep.hpp header, oracle/oracle.py::red_taps_f32 is the same rule): when 20 k is
 // integral for the generating kernel k = [1/4 - a/2, 1/4, a, 1/4, 1/4 - a/2] (a = 0.4, the reference's default: 1 5 8 5 1) the
 // taps are those integers and the result is scaled once by float32(1/400); else float32(k) and scale 1.

@@ -55,11 +55,7 @@ __device__ __forceinline__ void sub_pixel(const HistArgs& a, int sy, int sx, uin
             else { sum[0] += p[0]; sum[1] += p[1]; sum[2] += p[2]; }
         }
     }
-    const float scale = 1.0f / (float)(a.s * a.s);
-    for (int c = 0; c < nch; ++c) {
-        if (ny * nx == a.s * a.s) out[c] = a.s == 2 ? (sum[c] + 2u) >> 2 : (uint32_t)__float2int_rn((float)sum[c] * scale);
-        else out[c] = (uint32_t)__float2int_rn((float)sum[c] / (float)(ny * nx));
-    }
+    for (int c = 0; c < nch; ++c) out[c] = area_mean_int(sum[c], ny * nx, a.s);
 }
 
 // 8-bit: per-workgroup histogram in LDS, one flush per bin and workgroup

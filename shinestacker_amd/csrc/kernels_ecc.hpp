@@ -45,10 +45,7 @@ __global__ void ecc_gray(const T* __restrict__ img, int src_h, int src_w, int h,
         // of a last row / column float32 sum / count, rounded half to even
         const int n = ny * nx;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (n == s * s) c[k] = s == 2 ? (float)((sum[k] + 2u) >> 2) : (float)__float2int_rn((float)sum[k] * (1.0f / (float)(s * s)));
-            else c[k] = (float)__float2int_rn((float)sum[k] / (float)n);
-        }
+        for (int k = 0; k < 3; ++k) c[k] = (float)area_mean_int(sum[k], n, s);
     }
     out[(size_t)y * w + x] = 0.114f * c[0] + 0.587f * c[1] + 0.299f * c[2];
 }

@@ -1,5 +1,5 @@
 """Defaults of the hot path, as the reference's config/constants.py holds them
-(:11-14 pixel ranges, :100-110 alignment apply, :112-127 balance, :139-141 bunches, :144-157 depth map, :154-162 float types
+(:11-14 pixel ranges, :100-110 alignment apply, :112-127 balance, :53-62 noise mask, :129-133 vignetting, :139-141 bunches, :144-157 depth map, :154-162 float types
 and pyramid parameters).  Read-only."""
 from types import SimpleNamespace
 
@@ -40,6 +40,12 @@ constants = SimpleNamespace(
     VALID_DM_MAP=("average", "max"), VALID_DM_ENERGY=("laplacian", "sobel"),
     DEFAULT_DM_MAP="average", DEFAULT_DM_ENERGY="laplacian", DEFAULT_DM_KERNEL_SIZE=5,
     DEFAULT_DM_BLUR_SIZE=5, DEFAULT_DM_SMOOTH_SIZE=15, DEFAULT_DM_TEMPERATURE=0.1, DEFAULT_DM_LEVELS=3,
+    # noise mask (constants.py:53-62) and vignetting (constants.py:129-133)
+    DEFAULT_NOISE_MAP_FILENAME="noise-map/hot_pixels.png", DEFAULT_MN_KERNEL_SIZE=3, RGB_LABELS=('r', 'g', 'b'),
+    DEFAULT_CHANNEL_THRESHOLDS=(13, 13, 13), DEFAULT_BLUR_SIZE=5, DEFAULT_NOISE_PLOT_RANGE=(5, 30),
+    INTERPOLATE_MEAN="MEAN", INTERPOLATE_MEDIAN="MEDIAN", VALID_INTERPOLATE=frozenset(["MEAN", "MEDIAN"]),
+    DEFAULT_R_STEPS=100, DEFAULT_BLACK_THRESHOLD=1.0, DEFAULT_MAX_CORRECTION=1, DEFAULT_VIGN_SUBSAMPLE=8,
+    DEFAULT_VIGN_FAST_SUBSAMPLING=False,
 )
 
 

@@ -22,16 +22,62 @@ from .errors import AlignmentError, InvalidOptionError
 from .imageio import validate_image
 
 
+def _prestack_steps(mask_noise, vignetting, n_frames, device):
+    """The sub-actions that run on a frame before it is aligned, in the reference's order (constants.py:34 SUB_ACTION_TYPES:
+    MaskNoise, Vignetting, AlignFrames, BalanceFrames), from the `mask_noise=` / `vignetting=` option dicts.  `mask_noise`
+    takes MaskNoise's options; its `noise_mask` is the mask as an H x W array, or the path of the mask file (there is no
+    working directory here: the path is used as given)."""
+    steps = []
+    if mask_noise is not None:
+        from .noise_detection import MaskNoise
+        opts = dict(mask_noise)
+        mask = opts.pop("noise_mask", constants.DEFAULT_NOISE_MAP_FILENAME)
+        if isinstance(mask, str):
+            mn = MaskNoise(noise_mask=mask, device=device, **opts)
+            mn.load(mn.noise_mask)
+        else:
+            mn = MaskNoise(device=device, **opts)
+            mn.set_mask(mask)
+        steps.append(mn)
+    if vignetting is not None:
+        from .vignetting import Vignetting
+        vg = Vignetting(device=device, **dict(vignetting))
+        vg.begin(None, counts=n_frames)
+        steps.append(vg)
+    return steps
+
+
+def _prestack_info(steps, info):
+    for s in steps:
+        if info is not None and hasattr(s, "corrections"):
+            info["vignetting_corrections"] = s.corrections
+        s.end()
+
+
 def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, feature_config=None,
-                    matching_config=None, device=0, batch_frames=16, check_running=None,
-                    **stack_kwargs):
+                    matching_config=None, device=0, batch_frames=16, check_running=None, mask_noise=None, vignetting=None,
+                    info=None, **stack_kwargs):
     """Align every frame to frames[ref_idx] (fixed reference, `step_process=False` order,
     stack_framework.py:191-232) and fuse them.  `frames`: sequence of H x W x 3 uint8/uint16 BGR
-    arrays.  Returns (fused image, list of n_good_matches)."""
+    arrays.  Returns (fused image, list of n_good_matches).
+
+    `mask_noise` / `vignetting`: optional dicts of the MaskNoise / Vignetting sub-actions' options (`_prestack_steps`);
+    every frame, the reference frame included, then passes through them, in that order, before it is estimated or warped
+    -- the reference's sub-action order.  None (default): the frames are taken as they are.  `info`: an optional dict that
+    receives `info["vignetting_corrections"]` (the sub-action's percentile radii per frame)."""
     _lib.require_device()
     n = len(frames)
     if n == 0:
         raise ValueError("no frames")
+    pre = _prestack_steps(mask_noise, vignetting, n, device)
+    if pre:
+        fixed = []
+        for i, fr in enumerate(frames):
+            for step in pre:
+                fr = step.run_frame(i, ref_idx, fr)
+            fixed.append(fr)
+        frames = fixed
+        _prestack_info(pre, info)
     feature_config = {**_DEFAULT_FEATURE_CONFIG, **(feature_config or {})}
     matching_config = {**_DEFAULT_MATCHING_CONFIG, **(matching_config or {})}
     cfg = {**_DEFAULT_ALIGNMENT_CONFIG, **(alignment_config or {})}
@@ -419,7 +465,8 @@ def auto_batch_frames(n_frames, height, width, dtype, device=0, share=0.25):
 def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-1, alignment_config=None,
                            min_correlation=0.5, max_iters=60, device=0, batch_frames=None, out_dev=None,
                            balance=None, ecc_batch=16, step_process=False, native_loop=True, handles=None,
-                           keep_handles=False, info=None, chain_refine=True, chain_serial=False, **stack_kwargs):
+                           keep_handles=False, info=None, chain_refine=True, chain_serial=False, mask_noise=None,
+                           vignetting=None, **stack_kwargs):
     """BASELINE config 4 with every frame resident in HBM: `dev_frames` is the device address of
     `n_frames` contiguous H x W x 3 frames.  Each frame is registered against frames[ref_idx] by
     the device ECC estimator (mi_aligner_*), warped with the blurred replicate border of
@@ -452,6 +499,16 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     `info`: an optional dict; with `balance` it receives `info["corrections"]` = the per-frame correction factors the
     reference's sub-action records (balance.py: `self.corrections`), for the frames that were processed.
 
+    `mask_noise` / `vignetting`: optional dicts of the MaskNoise / Vignetting sub-actions' options (`_prestack_steps`).
+    Every resident frame, the reference frame included, is then corrected IN PLACE in `dev_frames` -- hot pixels first, then
+    the vignetting, the reference's sub-action order -- before any frame is estimated or warped, and the Python frame loop
+    is used (as with a non-LINEAR `balance=`; the native loop does not know these steps).  Per frame the vignetting fit costs
+    one host round trip (the ring sums).  `info["vignetting_corrections"]` receives the sub-action's percentile radii.
+    None (default): nothing is touched.  With `vignetting=` the byte size of a frame must be a multiple of 16
+    (InvalidOptionError otherwise: the apply pass needs every frame of the contiguous stack 16-byte aligned).  Because the
+    corrections overwrite `dev_frames`, a second call on the same buffer
+    with the options set would correct the frames a second time: upload the frames again, or leave the options out.
+
     `step_process=True`: the reference's chained order (see `_align_chains_device`): every frame is registered against
     its already-aligned neighbour; the aligned frames are kept in one extra device buffer (n_frames frames) and fused in
     file order afterwards, so that the stack sees them exactly as the reference's FocusStack reads the aligned files.
@@ -464,6 +521,11 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     Returns (fused image as ndarray, or None when `out_dev` -- a device address for the result --
     is given; list of 2x3 transforms, None at ref_idx; list of correlation coefficients)."""
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
+    if vignetting is not None and (height * width * 3 * np.dtype(dtype).itemsize) % 16:
+        # mi_vignette_apply_device works on 16-byte accesses: every frame of the contiguous stack must start on one
+        raise InvalidOptionError("vignetting", f"{height} x {width} {np.dtype(dtype).name}",
+                                 "with vignetting= the byte size of a resident frame must be a multiple of 16 (the frames are "
+                                 "contiguous and the apply pass needs each 16-byte aligned); use Vignetting.run_frame on host frames")
     _lib.require_device()
     if n_frames < 1:
         raise ValueError("no frames")
@@ -479,6 +541,16 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     dt = np.dtype(dtype)
     fb = height * width * 3 * dt.itemsize
     lib = _lib.load()
+    pre = _prestack_steps(mask_noise, vignetting, n_frames, device)
+    if pre:
+        if handles is not None or keep_handles:
+            raise InvalidOptionError("handles", "reuse", ": handle reuse is not implemented with mask_noise= / vignetting=")
+        native_loop = False
+        for i in range(n_frames):
+            for step in pre:
+                step.run_frame_device(i, dev_frames + i * fb, height, width, dt)
+        _lib.check(lib.mi_device_synchronize(device))   # the corrections ran on the default stream
+        _prestack_info(pre, info)
     if step_process:
         reusing = handles is not None or keep_handles
         if reusing and (chain_serial or homography):

@@ -59,6 +59,7 @@ def main():
     ap.add_argument("--arith", default="exact", choices=["exact", "separable"], help="stacker arithmetic (resident mode)")
     ap.add_argument("--ecc-batch", type=int, default=0, help="frames per batched Gauss-Newton (0 = the pipeline's default)")
     ap.add_argument("--reuse-handles", action="store_true", help="time a second stack on the handles of a first one (no allocation in the timed region)")
+    ap.add_argument("--vignetting", action="store_true", help="resident mode: correct the vignetting of every frame first (Vignetting's defaults; uses the Python loop)")
     ap.add_argument("--python-loop", action="store_true", help="the call-by-call Python loop instead of mi_align_stack_device")
     args = ap.parse_args()
     from shinestacker_amd import _lib as L
@@ -99,7 +100,10 @@ def main():
         out = L.DeviceBuffer(fb)
         bal = {'channel': 'LUMI', 'corr_map': 'LINEAR', 'subsample': 8} if args.balance else None
         acfg = {'transform': 'ALIGN_HOMOGRAPHY'} if args.homography else None
-        align_and_stack_device(buf.ptr, min(N, 4), H, W, np.uint8, out_dev=out.ptr, balance=bal, arith=args.arith, step_process=args.step_process, chain_refine=not args.no_chain_refine, chain_serial=args.chain_serial, batch_frames=(args.batch or None), alignment_config=acfg, native_loop=not args.python_loop, **({'ecc_batch': args.ecc_batch} if args.ecc_batch else {}))   # warm-up
+        pre = {'vignetting': {}} if args.vignetting else {}
+        if pre and args.reuse_handles:
+            raise SystemExit("--vignetting cannot be combined with --reuse-handles")
+        align_and_stack_device(buf.ptr, min(N, 4), H, W, np.uint8, out_dev=out.ptr, balance=bal, arith=args.arith, step_process=args.step_process, chain_refine=not args.no_chain_refine, chain_serial=args.chain_serial, batch_frames=(args.batch or None), alignment_config=acfg, native_loop=not args.python_loop, **pre, **({'ecc_batch': args.ecc_batch} if args.ecc_batch else {}))   # warm-up
         if args.reuse_handles:   # what a job of many stacks pays per stack: the handles exist already
             if args.python_loop or (args.step_process and (args.chain_serial or args.homography)):
                 # (round 3 dropped these flags silently here and wrote a non-chained run into config4_resident_step.json)
@@ -119,12 +123,12 @@ def main():
             report(N, H, W, dt, recovered, truth, ref, cx, cy, ("resident, step_process (chained, neighbour pairs + composition" + (", plain" if args.no_chain_refine else ", refined against the global reference") + "), handles reused") if args.step_process else "resident, handles reused", list(out.download((H, W, 3), np.uint8).shape))
             return
         t0 = time.perf_counter()
-        _, tr, ccs = align_and_stack_device(buf.ptr, N, H, W, np.uint8, ref_idx=ref, out_dev=out.ptr, balance=bal, arith=args.arith, step_process=args.step_process, chain_refine=not args.no_chain_refine, chain_serial=args.chain_serial, batch_frames=(args.batch or None), alignment_config=acfg, native_loop=not args.python_loop, **({'ecc_batch': args.ecc_batch} if args.ecc_batch else {}))
+        _, tr, ccs = align_and_stack_device(buf.ptr, N, H, W, np.uint8, ref_idx=ref, out_dev=out.ptr, balance=bal, arith=args.arith, step_process=args.step_process, chain_refine=not args.no_chain_refine, chain_serial=args.chain_serial, batch_frames=(args.batch or None), alignment_config=acfg, native_loop=not args.python_loop, **pre, **({'ecc_batch': args.ecc_batch} if args.ecc_batch else {}))
         dt = time.perf_counter() - t0
         recovered = {k: m.copy() for k, m in enumerate(t for t in tr if t is not None)}
         for m in recovered.values():
             m[:, 2] /= 2    # compare at the sub-sampled scale like the host path below
-        report(N, H, W, dt, recovered, truth, ref, cx, cy, ("resident, step_process (chained" + (", serial" if args.chain_serial else ", neighbour pairs + composition") + (", plain" if args.no_chain_refine else ", refined against the global reference") + ")" if args.step_process else "resident") + (" + balance" if args.balance else ""), list(out.download((H, W, 3), np.uint8).shape))
+        report(N, H, W, dt, recovered, truth, ref, cx, cy, ("resident, step_process (chained" + (", serial" if args.chain_serial else ", neighbour pairs + composition") + (", plain" if args.no_chain_refine else ", refined against the global reference") + ")" if args.step_process else "resident") + (" + balance" if args.balance else "") + (" + vignetting" if args.vignetting else ""), list(out.download((H, W, 3), np.uint8).shape))
         return
     est = ecc_estimator()
     recovered = {}
