@@ -3,11 +3,12 @@
 script on the MI355X path.  Same action graph, same parameter names as shinestacker's
 StackJob / CombinedActions / AlignFrames / BalanceFrames / FocusStack; only the imports differ.
 
-    python examples/stack_from_frames.py <working_dir> <input_subdir> [--no-align] [--vignetting] [--noise-map FOLDER]
+    python examples/stack_from_frames.py <working_dir> <input_subdir> [--no-align] [--vignetting] [--noise-map FOLDER] [--denoise N]
 
 `--noise-map FOLDER` and `--vignetting` build the reference's full graph: NoiseDetection over the frames of FOLDER (dark frames,
 under the working directory) writes noise-map/hot_pixels.png, then MaskNoise and Vignetting run in front of AlignFrames -- the
-reference's sub-action order MaskNoise, Vignetting, AlignFrames, BalanceFrames.
+reference's sub-action order MaskNoise, Vignetting, AlignFrames, BalanceFrames.  `--denoise N` (1-10) is FocusStack's
+`denoise_amount`: the fused frame passes through the non-local-means filter before it is written.
 """
 import argparse
 import os
@@ -28,6 +29,8 @@ def main():
     ap.add_argument("--vignetting", action="store_true", help="correct the vignetting of every frame before it is aligned")
     ap.add_argument("--noise-map", metavar="FOLDER", help="map the hot pixels of the frames in FOLDER (relative to the working "
                     "directory) first, and mask them in every frame")
+    ap.add_argument("--denoise", type=int, default=0, metavar="N", help="FocusStack(denoise_amount=N): denoise the result, "
+                    "strength and template window N (1-10)")
     args = ap.parse_args()
     job = StackJob("focus-stack", args.working_dir, input_path=args.input_subdir)
     stack_input = args.input_subdir
@@ -41,7 +44,7 @@ def main():
                                        input_path=args.input_subdir, output_path="align"))
         stack_input = "align"
     job.add_action(FocusStack("stack", PyramidStack(), input_path=stack_input, output_path="stack",
-                              prefix="stack_"))
+                              prefix="stack_", denoise_amount=args.denoise))
     job.run()
     print("written:", sorted(os.listdir(os.path.join(args.working_dir, "stack"))))
 

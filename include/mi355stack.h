@@ -490,6 +490,25 @@ MI_API int mi_hot_pixel_map_device(int device, void* stream, const void* dev_sum
                             int blur_size, const int* thresholds, void* dev_mean, void* dev_map, void* dev_counts,
                             uint32_t* counts);
 
+/* ---- Post-stack denoise (reference algorithms/denoise.py -> cv2.fastNlMeansDenoising on a three-channel frame; kernel in
+ * csrc/kernels_denoise.hpp): non-local means, all three channels filtered jointly.  MI_U8: squared differences (NORM_L2), 32-bit
+ * sums; MI_U16: absolute differences (NORM_L1), 64-bit sums.  Window sizes are forced odd as OpenCV does (2 * (size / 2) + 1);
+ * borders are BORDER_REFLECT_101 over search / 2 + template / 2 pixels.  Per output pixel p and channel c
+ *     out[p, c] = (sum_q w(p, q) * in[q, c] + W / 2) / W,   w(p, q) = table[d(p, q) >> shift],   W = sum_q w(p, q)
+ * with q over the search window around p and d the patch distance summed over the template window and the channels.
+ * `table`: HOST array of table_len uint32 weights, the non-zero prefix of the weight table (entries at and past table_len are
+ * zero; table[0] > 0); `shift`: the smallest p with 2^p >= (2 * (template_size / 2) + 1)^2.  The library builds none of it:
+ * shinestacker_amd/denoise.py does.  template_size 1-11 and search_size 1-21, MI_ERR_UNSUPPORTED beyond.
+ * The weights are the caller's responsibility: for MI_U8 sum_q w * 255 must fit 32 bits (the builder's fixed-point multiplier
+ * INT_MAX / (search^2 * 255) guarantees it); larger weights wrap the sums -- wrong numbers, no fault.
+ * mi_nlm_denoise: host frames (host_dst may be host_src).  mi_nlm_denoise_device: a frame resident in device memory,
+ * dev_src != dev_dst; runs on `stream` and is synchronous by design: it allocates, uploads and frees its copy of the table and
+ * waits for `stream` before it returns, so it cannot be queued behind later work (a once-per-job filter of milliseconds). */
+MI_API int mi_nlm_denoise(int device, const void* host_src, void* host_dst, int height, int width, int dtype,
+                   const uint32_t* table, int table_len, int shift, int template_size, int search_size);
+MI_API int mi_nlm_denoise_device(int device, const void* dev_src, void* dev_dst, int height, int width, int dtype,
+                          const uint32_t* table, int table_len, int shift, int template_size, int search_size, void* stream);
+
 /* ---- DepthMapStack: the second stacker behind the same plug-in boundary ----
  * Replaces the arithmetic of DepthMapStack.focus_stack (reference algorithms/depth_map.py:64-123) for
  * both float types: push = the first file loop (:67-75: read, img_bw, then per frame get_sobel_map :28-34

@@ -12,6 +12,7 @@ from .align import AlignFrames, align_images  # noqa: F401,E402
 from .balance import BalanceFrames  # noqa: F401,E402
 from .vignetting import Vignetting  # noqa: F401,E402
 from .noise_detection import MaskNoise, NoiseDetection  # noqa: F401,E402
+from .denoise import denoise  # noqa: F401,E402
 
-__all__ = ["AlignFrames", "BalanceFrames", "Vignetting", "MaskNoise", "NoiseDetection", "align_images", "PyramidStack", "DepthMapStack", "BaseStackAlgo", "StackJob", "FocusStack", "FocusStackBunch",
+__all__ = ["AlignFrames", "BalanceFrames", "Vignetting", "MaskNoise", "NoiseDetection", "denoise", "align_images", "PyramidStack", "DepthMapStack", "BaseStackAlgo", "StackJob", "FocusStack", "FocusStackBunch",
            "CombinedActions", "SubAction", "get_bunches", "constants"]

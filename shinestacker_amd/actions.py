@@ -249,6 +249,12 @@ class _FocusStackCommon(FrameDirectory):
         self.exif_path = kwargs.pop('exif_path', '')
         self.prefix = kwargs.pop('prefix', constants.DEFAULT_STACK_PREFIX)
         self.denoise_amount = kwargs.pop('denoise_amount', 0)
+        if self.denoise_amount > 0:
+            # stack.py:35 passes the amount as the filter strength AND as the template window size
+            from .denoise import MAX_TEMPLATE_WINDOW
+            if self.denoise_amount != int(self.denoise_amount) or self.denoise_amount > MAX_TEMPLATE_WINDOW:
+                raise InvalidOptionError("denoise_amount", self.denoise_amount,
+                                         f"the amount is also the template window size: integral, at most {MAX_TEMPLATE_WINDOW}")
         self.plot_stack = kwargs.pop('plot_stack', constants.DEFAULT_PLOT_STACK)
         self.stack_algo.process = self
         self.frame_count = -1
@@ -261,8 +267,9 @@ class _FocusStackCommon(FrameDirectory):
         parts = filenames[0].split(".")
         out_filename = f"{self.output_dir}/{self.prefix}{parts[0]}." + '.'.join(parts[1:])
         if self.denoise_amount > 0:
-            raise InvalidOptionError("denoise_amount", self.denoise_amount,
-                                     "post-stack denoise is outside the MI355X hot path")
+            from .denoise import denoise
+            self.sub_message_r(': denoise image')
+            stacked = denoise(stacked, self.denoise_amount, int(self.denoise_amount))
         write_img(out_filename, stacked)
         if self.plot_stack:
             idx_str = f"{self.frame_count + 1:04d}" if self.frame_count >= 0 else ''

@@ -23,6 +23,7 @@
 #include "kernels_phase.hpp"
 #include "kernels_balance.hpp"
 #include "kernels_prestack.hpp"
+#include "kernels_denoise.hpp"
 #include "kernels_f64.hpp"
 #include "kernels_steps.hpp"
 
@@ -2772,6 +2773,70 @@ int mi_hot_pixel_map_device(int device, void* stream, const void* dev_sum, int n
     MI_HIP(hipMemcpyAsync(counts, dev_counts, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     MI_HIP(hipStreamSynchronize(st));
     return MI_OK;
+}
+
+// ---------------------------------------------------------------- post-stack denoise (kernels_denoise.hpp)
+static int nlm_check(const void* src, const void* dst, int height, int width, int dtype, const uint32_t* table, int table_len,
+                     int shift, int template_size, int search_size, bool may_alias) {
+    if (!src || !dst || !table) return fail(MI_ERR_INVALID, "null argument");
+    if (src == dst && !may_alias) return fail(MI_ERR_INVALID, "src and dst must differ (every output reads a neighbourhood of inputs)");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
+    if (height < 1 || width < 1) return fail(MI_ERR_INVALID, "bad image size");
+    if (template_size < 1 || search_size < 1) return fail(MI_ERR_INVALID, "window sizes must be positive");
+    if (template_size / 2 > MI_NLM_MAX_T || search_size / 2 > MI_NLM_MAX_S)
+        return fail(MI_ERR_UNSUPPORTED, "template window 1-%d and search window 1-%d are supported (got %d, %d)",
+                    2 * MI_NLM_MAX_T + 1, 2 * MI_NLM_MAX_S + 1, template_size, search_size);
+    const int n = (2 * (template_size / 2) + 1) * (2 * (template_size / 2) + 1);
+    int want = 0;
+    while ((1 << want) < n) ++want;
+    if (shift != want) return fail(MI_ERR_INVALID, "shift must be %d for template window %d", want, template_size);
+    if (table_len < 1 || table_len > (1 << 24)) return fail(MI_ERR_INVALID, "table_len must be in [1, 2^24]");
+    if (table[0] == 0) return fail(MI_ERR_INVALID, "table[0] (the weight of a pixel with itself) must be positive");
+    return MI_OK;
+}
+
+int mi_nlm_denoise_device(int device, const void* dev_src, void* dev_dst, int height, int width, int dtype, const uint32_t* table,
+                          int table_len, int shift, int template_size, int search_size, void* stream) {
+    int rc = nlm_check(dev_src, dev_dst, height, width, dtype, table, table_len, shift, template_size, search_size, false);
+    if (rc) return rc;
+    MI_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    void* dev_table = nullptr;
+    if (hipMalloc(&dev_table, sizeof(uint32_t) * (size_t)table_len) != hipSuccess) return fail(MI_ERR_NOMEM, "out of device memory");
+    hipError_t e = hipMemcpyAsync(dev_table, table, sizeof(uint32_t) * (size_t)table_len, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        nlm_launch(st, dev_src, dev_dst, height, width, dtype, (const uint32_t*)dev_table, (uint32_t)table_len, shift,
+                   template_size / 2, search_size / 2);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);     // the table is freed below
+    (void)hipFree(dev_table);
+    if (e != hipSuccess) return fail(MI_ERR_HIP, "denoise failed: %s", hipGetErrorString(e));
+    return MI_OK;
+}
+
+int mi_nlm_denoise(int device, const void* host_src, void* host_dst, int height, int width, int dtype, const uint32_t* table,
+                   int table_len, int shift, int template_size, int search_size) {
+    // host_src == host_dst is fine here: the frame passes through two device buffers
+    int rc = nlm_check(host_src, host_dst, height, width, dtype, table, table_len, shift, template_size, search_size, true);
+    if (rc) return rc;
+    int ndev = 0;
+    rc = mi_device_count(&ndev);
+    if (rc) return rc;
+    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
+    MI_HIP(hipSetDevice(device));
+    const size_t nb = (size_t)height * width * 3 * dtype_size(dtype);
+    void *src = nullptr, *dst = nullptr;
+    auto cleanup = [&]() { (void)hipFree(src); (void)hipFree(dst); };
+    if (hipMalloc(&src, nb) != hipSuccess || hipMalloc(&dst, nb) != hipSuccess) {
+        cleanup();
+        return fail(MI_ERR_NOMEM, "out of device memory");
+    }
+    if (hipMemcpy(src, host_src, nb, hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(MI_ERR_HIP, "upload failed"); }
+    rc = mi_nlm_denoise_device(device, src, dst, height, width, dtype, table, table_len, shift, template_size, search_size, nullptr);
+    if (!rc && hipMemcpy(host_dst, dst, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
+    cleanup();
+    return rc;
 }
 
 int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,

@@ -54,9 +54,45 @@ def _prestack_info(steps, info):
         s.end()
 
 
+def _check_denoise_amount(denoise_amount):
+    from .denoise import MAX_TEMPLATE_WINDOW
+    if denoise_amount < 0 or denoise_amount != int(denoise_amount) or denoise_amount > MAX_TEMPLATE_WINDOW:
+        raise InvalidOptionError("denoise_amount", denoise_amount, "the amount is also the template window size: a non-negative "
+                                 f"integral value, at most {MAX_TEMPLATE_WINDOW}")
+
+
+def _finish(stack, out_dev, denoise_amount, height, width, dtype, device):
+    """The stacker's result: downloaded (returned), or written to the device address `out_dev` (None returned).  With
+    `denoise_amount` > 0 the result first passes through the post-stack denoise on the device, with the reference's
+    arguments (stack.py:33-35: the amount is the filter strength and the template window size)."""
+    if not denoise_amount:
+        if out_dev is not None:
+            stack.finish_device(out_dev)
+            stack.sync()
+            return None
+        return stack.finish()
+    from .denoise import denoise_device
+    dt = np.dtype(dtype)
+    fb = height * width * 3 * dt.itemsize
+    raw = _lib.DeviceBuffer(fb, device)
+    res = None
+    try:
+        stack.finish_device(raw.ptr)
+        stack.sync()
+        if out_dev is None:
+            res = _lib.DeviceBuffer(fb, device)
+        denoise_device(raw.ptr, res.ptr if res is not None else out_dev, height, width, dt, denoise_amount, int(denoise_amount),
+                       device=device)
+        return res.download((height, width, 3), dt) if res is not None else None
+    finally:
+        raw.free()
+        if res is not None:
+            res.free()
+
+
 def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, feature_config=None,
                     matching_config=None, device=0, batch_frames=16, check_running=None, mask_noise=None, vignetting=None,
-                    info=None, **stack_kwargs):
+                    info=None, denoise_amount=0, **stack_kwargs):
     """Align every frame to frames[ref_idx] (fixed reference, `step_process=False` order,
     stack_framework.py:191-232) and fuse them.  `frames`: sequence of H x W x 3 uint8/uint16 BGR
     arrays.  Returns (fused image, list of n_good_matches).
@@ -64,7 +100,11 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     `mask_noise` / `vignetting`: optional dicts of the MaskNoise / Vignetting sub-actions' options (`_prestack_steps`);
     every frame, the reference frame included, then passes through them, in that order, before it is estimated or warped
     -- the reference's sub-action order.  None (default): the frames are taken as they are.  `info`: an optional dict that
-    receives `info["vignetting_corrections"]` (the sub-action's percentile radii per frame)."""
+    receives `info["vignetting_corrections"]` (the sub-action's percentile radii per frame).
+
+    `denoise_amount`: the stack actions' option (`_finish`): when positive the fused frame is denoised on the device before
+    it is downloaded.  0 (default): nothing is touched."""
+    _check_denoise_amount(denoise_amount)
     _lib.require_device()
     n = len(frames)
     if n == 0:
@@ -150,7 +190,7 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
             from .errors import RunStopException
             raise RunStopException("align_and_stack")
     flush()
-    out = stack.finish()
+    out = _finish(stack, None, denoise_amount, h, w, dt, device)
     stack.close()
     return out, matches
 
@@ -466,7 +506,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                            min_correlation=0.5, max_iters=60, device=0, batch_frames=None, out_dev=None,
                            balance=None, ecc_batch=16, step_process=False, native_loop=True, handles=None,
                            keep_handles=False, info=None, chain_refine=True, chain_serial=False, mask_noise=None,
-                           vignetting=None, **stack_kwargs):
+                           vignetting=None, denoise_amount=0, **stack_kwargs):
     """BASELINE config 4 with every frame resident in HBM: `dev_frames` is the device address of
     `n_frames` contiguous H x W x 3 frames.  Each frame is registered against frames[ref_idx] by
     the device ECC estimator (mi_aligner_*), warped with the blurred replicate border of
@@ -518,8 +558,12 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     device synchronisation per frame (`_align_chains_device`); the default factors the chain into independent
     neighbour estimates + composition (`_align_chains_pairs_device`).
 
+    `denoise_amount`: the stack actions' option (`_finish`): when positive the fused frame is denoised on the device before
+    it is downloaded or written to `out_dev`.  0 (default): nothing is touched.
+
     Returns (fused image as ndarray, or None when `out_dev` -- a device address for the result --
     is given; list of 2x3 transforms, None at ref_idx; list of correlation coefficients)."""
+    _check_denoise_amount(denoise_amount)
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
     if vignetting is not None and (height * width * 3 * np.dtype(dtype).itemsize) % 16:
         # mi_vignette_apply_device works on 16-byte accesses: every frame of the contiguous stack must start on one
@@ -596,12 +640,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                 stack = _lib.Stack(height, width, in_dtype=dt, out_dtype=dt, device=device, **stack_kwargs)
                 created.append(stack.close)
             stack.push_frames_device(aligned.ptr, n_frames, fb)
-            if out_dev is not None:
-                stack.finish_device(out_dev)
-                stack.sync()
-                out = None
-            else:
-                out = stack.finish()
+            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device)
             done = True
         finally:
             if not (keep_handles and done):
@@ -681,12 +720,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
             transforms = [None if i == ref_idx else (ms[i].reshape(3, 3).copy() if homography else ms[i, :6].reshape(2, 3).copy())
                           for i in range(n_frames)]
             ccs = [float(c) for c in cc]
-            if out_dev is not None:
-                stack.finish_device(out_dev)
-                stack.sync()
-                out = None
-            else:
-                out = stack.finish()
+            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device)
             done = True
         finally:
             if created is not None and not (keep_handles and done):
@@ -767,12 +801,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
             if filled == batch_frames:
                 flush()
         flush()
-        if out_dev is not None:
-            stack.finish_device(out_dev)
-            stack.sync()
-            out = None
-        else:
-            out = stack.finish()
+        out = _finish(stack, out_dev, denoise_amount, height, width, dt, device)
         if corr is not None and info is not None:
             info["corrections"] = corr.fetch_corrections()
     finally:
@@ -785,7 +814,8 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
 
 def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constants.DEFAULT_FRAMES,
                        overlap=constants.DEFAULT_OVERLAP, device=0, out_dev=None, on_bunch=None, on_final=None,
-                       check_running=None, stacks=None, results_buf=None, info=None, zero_copy=False, **stack_kwargs):
+                       check_running=None, stacks=None, results_buf=None, info=None, zero_copy=False, denoise_amount=0,
+                       **stack_kwargs):
     """BASELINE config 5's two-stage flow in memory (the reference's `FocusStackBunch` followed by `FocusStack`,
     stack.py:61-113, examples/stack-from-frames): the frames are fused in bunches of `frames` with `overlap` shared
     (`get_bunches`), every bunch result is the stacker's OUTPUT type -- truncated to the input dtype exactly as the file
@@ -804,9 +834,12 @@ def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constan
     short job; they are reset, not closed.  `results_buf`: an optional `_lib.DeviceBuffer` of at least n_bunches frames for the
     bunch results (`hipMalloc` / `hipFree` of the 38 GB a 1024-frame job needs cost ~2 s: a caller that runs job after job
     keeps it); it is not freed here.  `info`: an optional dict that receives `stage1_s` (first push to the last bunch result
-    on the device) and `stage2_s` (the stack over the bunch results, to its result).  Returns the fused image (or None when `out_dev` is given) and the list of
+    on the device) and `stage2_s` (the stack over the bunch results, to its result).  `denoise_amount`: when positive the final
+    result is denoised on the device before it is downloaded or written to `out_dev` (`_finish`; the reference's
+    FocusStack(denoise_amount=...) behind a FocusStackBunch without it); 0 (default) touches nothing.  Returns the fused image (or None when `out_dev` is given) and the list of
     bunches (frame indices)."""
     from .actions import get_bunches
+    _check_denoise_amount(denoise_amount)
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
     _lib.require_device()
     if overlap >= frames:
@@ -867,12 +900,7 @@ def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constan
         st2.push_frames_device(results.ptr, len(bunches), fb)
         if on_final is not None:
             on_final(st2, results)
-        if out_dev is not None:
-            st2.finish_device(out_dev)
-            st2.sync()
-            out = None
-        else:
-            out = st2.finish()
+        out = _finish(st2, out_dev, denoise_amount, height, width, dt, device)
     finally:
         if not stacks:
             st2.close()
