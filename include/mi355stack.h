@@ -509,6 +509,24 @@ MI_API int mi_nlm_denoise(int device, const void* host_src, void* host_dst, int 
 MI_API int mi_nlm_denoise_device(int device, const void* dev_src, void* dev_dst, int height, int width, int dtype,
                           const uint32_t* table, int table_len, int shift, int template_size, int search_size, void* stream);
 
+/* ---- Unsharp mask (reference algorithms/sharpen.py: cv2.GaussianBlur(image, (0, 0), radius), then cv2.addWeighted or the
+ * thresholded NumPy combine; kernel in csrc/kernels_unsharp.hpp): blur and combine in one pass, the blurred frame never leaves LDS.
+ * `taps`: HOST array of `ksize` uint32 fixed-point Gaussian taps, 8 fractional bits for MI_U8 and 16 for MI_U16, summing to
+ * exactly 256 / 65536 (OpenCV's getGaussianKernelBitExact + error diffusion; shinestacker_amd/sharpen.py builds them, the
+ * library evaluates no exp).  ksize odd, 1 (the identity blur) to 33.  Blur: exact integer row and column sums,
+ * (S + half) >> 16 / 32, saturated, BORDER_REFLECT_101 reflected as often as it takes.
+ * threshold == 0: out = saturate(round_half_even(f32(f32(1 + amount) * in) + f32(f32(-amount) * blurred))), float32, no fused
+ * multiply-add.  threshold != 0: where |in - blurred| > f32(threshold), out = trunc(clip(f32(in + f32(f32(amount) * (in -
+ * blurred))))), elsewhere out = in.  `threshold` is in sample units (the reference multiplies its argument by 256 for 16-bit
+ * frames before this point; so does the Python layer).
+ * MI_ERR_INVALID: null pointers, an even or oversized ksize, taps with another sum, a non-finite amount or threshold, and for
+ * the device form dev_src == dev_dst.  mi_unsharp_mask: host frames (host_dst may be host_src).  mi_unsharp_mask_device: a frame
+ * resident in device memory; the launch is queued on `stream` and not waited for (the taps travel in the kernel arguments). */
+MI_API int mi_unsharp_mask(int device, const void* host_src, void* host_dst, int height, int width, int dtype,
+                    const uint32_t* taps, int ksize, double amount, double threshold);
+MI_API int mi_unsharp_mask_device(int device, void* stream, const void* dev_src, void* dev_dst, int height, int width, int dtype,
+                           const uint32_t* taps, int ksize, double amount, double threshold);
+
 /* ---- DepthMapStack: the second stacker behind the same plug-in boundary ----
  * Replaces the arithmetic of DepthMapStack.focus_stack (reference algorithms/depth_map.py:64-123) for
  * both float types: push = the first file loop (:67-75: read, img_bw, then per frame get_sobel_map :28-34

@@ -24,6 +24,7 @@
 #include "kernels_balance.hpp"
 #include "kernels_prestack.hpp"
 #include "kernels_denoise.hpp"
+#include "kernels_unsharp.hpp"
 #include "kernels_f64.hpp"
 #include "kernels_steps.hpp"
 
@@ -2834,6 +2835,58 @@ int mi_nlm_denoise(int device, const void* host_src, void* host_dst, int height,
     }
     if (hipMemcpy(src, host_src, nb, hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(MI_ERR_HIP, "upload failed"); }
     rc = mi_nlm_denoise_device(device, src, dst, height, width, dtype, table, table_len, shift, template_size, search_size, nullptr);
+    if (!rc && hipMemcpy(host_dst, dst, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
+    cleanup();
+    return rc;
+}
+
+// ---------------------------------------------------------------- unsharp mask (kernels_unsharp.hpp)
+static int unsharp_check(const void* src, const void* dst, int height, int width, int dtype, const uint32_t* taps, int ksize,
+                         double amount, double threshold, bool may_alias) {
+    if (!src || !dst || !taps) return fail(MI_ERR_INVALID, "null argument");
+    if (src == dst && !may_alias) return fail(MI_ERR_INVALID, "src and dst must differ (every output reads a neighbourhood of inputs)");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
+    if (height < 1 || width < 1 || (size_t)width * 3 > (size_t)INT32_MAX) return fail(MI_ERR_INVALID, "bad image size");
+    if (ksize < 1 || !(ksize & 1) || ksize > MI_UNSHARP_MAX_KSIZE)
+        return fail(MI_ERR_INVALID, "ksize must be odd and in [1, %d] (got %d)", MI_UNSHARP_MAX_KSIZE, ksize);
+    uint64_t sum = 0;
+    for (int j = 0; j < ksize; ++j) sum += taps[j];
+    const uint64_t one = dtype == MI_U8 ? 256 : 65536;     // what keeps the row and column sums inside their words
+    if (sum != one) return fail(MI_ERR_INVALID, "the taps must sum to %llu (got %llu)", (unsigned long long)one, (unsigned long long)sum);
+    if (!std::isfinite(amount) || !std::isfinite(threshold)) return fail(MI_ERR_INVALID, "amount and threshold must be finite");
+    return MI_OK;
+}
+
+int mi_unsharp_mask_device(int device, void* stream, const void* dev_src, void* dev_dst, int height, int width, int dtype,
+                           const uint32_t* taps, int ksize, double amount, double threshold) {
+    int rc = unsharp_check(dev_src, dev_dst, height, width, dtype, taps, ksize, amount, threshold, false);
+    if (rc) return rc;
+    MI_HIP(hipSetDevice(device));
+    unsharp_launch((hipStream_t)stream, dev_src, dev_dst, height, width, dtype, taps, ksize, amount, threshold);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_unsharp_mask(int device, const void* host_src, void* host_dst, int height, int width, int dtype, const uint32_t* taps,
+                    int ksize, double amount, double threshold) {
+    // host_src == host_dst is fine here: the frame passes through two device buffers
+    int rc = unsharp_check(host_src, host_dst, height, width, dtype, taps, ksize, amount, threshold, true);
+    if (rc) return rc;
+    int ndev = 0;
+    rc = mi_device_count(&ndev);
+    if (rc) return rc;
+    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
+    MI_HIP(hipSetDevice(device));
+    const size_t nb = (size_t)height * width * 3 * dtype_size(dtype);
+    void *src = nullptr, *dst = nullptr;
+    auto cleanup = [&]() { (void)hipFree(src); (void)hipFree(dst); };
+    if (hipMalloc(&src, nb) != hipSuccess || hipMalloc(&dst, nb) != hipSuccess) {
+        cleanup();
+        return fail(MI_ERR_NOMEM, "out of device memory");
+    }
+    if (hipMemcpy(src, host_src, nb, hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(MI_ERR_HIP, "upload failed"); }
+    rc = mi_unsharp_mask_device(device, nullptr, src, dst, height, width, dtype, taps, ksize, amount, threshold);
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "unsharp kernel failed");
     if (!rc && hipMemcpy(host_dst, dst, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
     cleanup();
     return rc;

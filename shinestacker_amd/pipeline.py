@@ -61,38 +61,79 @@ def _check_denoise_amount(denoise_amount):
                                  f"integral value, at most {MAX_TEMPLATE_WINDOW}")
 
 
-def _finish(stack, out_dev, denoise_amount, height, width, dtype, device):
+def _check_retouch(white_balance, unsharp, dtype):
+    """The post-stack retouch options, refused before anything is stacked: `white_balance` an RGB triple, `unsharp` a
+    (radius, amount, threshold) triple.  None for both (the default) imports nothing."""
+    if white_balance is not None:
+        from .white_balance import white_balance_table
+        white_balance_table(dtype, white_balance)
+    if unsharp is not None:
+        from .sharpen import _prepare
+        try:
+            radius, amount, threshold = unsharp
+        except (TypeError, ValueError):
+            raise InvalidOptionError("unsharp", unsharp, "a (radius, amount, threshold) triple") from None
+        _prepare(dtype, radius, amount, threshold)
+
+
+def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_balance=None, unsharp=None):
     """The stacker's result: downloaded (returned), or written to the device address `out_dev` (None returned).  With
     `denoise_amount` > 0 the result first passes through the post-stack denoise on the device, with the reference's
-    arguments (stack.py:33-35: the amount is the filter strength and the template window size)."""
-    if not denoise_amount:
+    arguments (stack.py:33-35: the amount is the filter strength and the template window size); then through the white
+    balance (`white_balance`: the RGB triple) and the unsharp mask (`unsharp`: radius, amount, threshold) when given --
+    denoise -> white balance -> unsharp, all in HBM, one download."""
+    if not denoise_amount and white_balance is None and unsharp is None:
         if out_dev is not None:
             stack.finish_device(out_dev)
             stack.sync()
             return None
         return stack.finish()
-    from .denoise import denoise_device
     dt = np.dtype(dtype)
     fb = height * width * 3 * dt.itemsize
-    raw = _lib.DeviceBuffer(fb, device)
-    res = None
+    steps = []      # (run(src, dst), may src be dst)
+    if denoise_amount:
+        from .denoise import denoise_device
+        steps.append((lambda s, d: denoise_device(s, d, height, width, dt, denoise_amount, int(denoise_amount), device=device), False))
+    if white_balance is not None:
+        from .white_balance import white_balance_device
+        steps.append((lambda s, d: white_balance_device(s, d, height * width, dt, white_balance, device=device), True))
+    if unsharp is not None:
+        from .sharpen import unsharp_mask_device
+        steps.append((lambda s, d: unsharp_mask_device(s, d, height, width, dt, *unsharp, device=device), False))
+    bufs = []
     try:
-        stack.finish_device(raw.ptr)
+        bufs.append(_lib.DeviceBuffer(fb, device))
+        cur = bufs[0].ptr
+        stack.finish_device(cur)
         stack.sync()
+        res = None
         if out_dev is None:
             res = _lib.DeviceBuffer(fb, device)
-        denoise_device(raw.ptr, res.ptr if res is not None else out_dev, height, width, dt, denoise_amount, int(denoise_amount),
-                       device=device)
-        return res.download((height, width, 3), dt) if res is not None else None
-    finally:
-        raw.free()
+            bufs.append(res)
+        final = res.ptr if res is not None else out_dev
+        for i, (run, in_place) in enumerate(steps):
+            if i == len(steps) - 1:
+                dst = final
+            elif in_place:
+                dst = cur
+            else:
+                if len(bufs) < (3 if res is not None else 2):
+                    bufs.append(_lib.DeviceBuffer(fb, device))
+                dst = bufs[-1].ptr if cur == bufs[0].ptr else bufs[0].ptr
+            run(cur, dst)
+            cur = dst
         if res is not None:
-            res.free()
+            return res.download((height, width, 3), dt)
+        _lib.check(_lib.load().mi_device_synchronize(device))
+        return None
+    finally:
+        for b in bufs:
+            b.free()
 
 
 def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, feature_config=None,
                     matching_config=None, device=0, batch_frames=16, check_running=None, mask_noise=None, vignetting=None,
-                    info=None, denoise_amount=0, **stack_kwargs):
+                    info=None, denoise_amount=0, white_balance=None, unsharp=None, **stack_kwargs):
     """Align every frame to frames[ref_idx] (fixed reference, `step_process=False` order,
     stack_framework.py:191-232) and fuse them.  `frames`: sequence of H x W x 3 uint8/uint16 BGR
     arrays.  Returns (fused image, list of n_good_matches).
@@ -103,8 +144,12 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     receives `info["vignetting_corrections"]` (the sub-action's percentile radii per frame).
 
     `denoise_amount`: the stack actions' option (`_finish`): when positive the fused frame is denoised on the device before
-    it is downloaded.  0 (default): nothing is touched."""
+    it is downloaded.  0 (default): nothing is touched.  `white_balance` (an RGB triple) / `unsharp` ((radius, amount,
+    threshold)): the retouch filters (white_balance.py, sharpen.py), applied on the device after the denoise, in that order,
+    before the download.  None (default): nothing is built, loaded or called."""
     _check_denoise_amount(denoise_amount)
+    if white_balance is not None or unsharp is not None:
+        _check_retouch(white_balance, unsharp, np.asarray(frames[0]).dtype if len(frames) else np.uint8)
     _lib.require_device()
     n = len(frames)
     if n == 0:
@@ -190,7 +235,7 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
             from .errors import RunStopException
             raise RunStopException("align_and_stack")
     flush()
-    out = _finish(stack, None, denoise_amount, h, w, dt, device)
+    out = _finish(stack, None, denoise_amount, h, w, dt, device, white_balance, unsharp)
     stack.close()
     return out, matches
 
@@ -506,7 +551,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                            min_correlation=0.5, max_iters=60, device=0, batch_frames=None, out_dev=None,
                            balance=None, ecc_batch=16, step_process=False, native_loop=True, handles=None,
                            keep_handles=False, info=None, chain_refine=True, chain_serial=False, mask_noise=None,
-                           vignetting=None, denoise_amount=0, **stack_kwargs):
+                           vignetting=None, denoise_amount=0, white_balance=None, unsharp=None, **stack_kwargs):
     """BASELINE config 4 with every frame resident in HBM: `dev_frames` is the device address of
     `n_frames` contiguous H x W x 3 frames.  Each frame is registered against frames[ref_idx] by
     the device ECC estimator (mi_aligner_*), warped with the blurred replicate border of
@@ -559,11 +604,15 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     neighbour estimates + composition (`_align_chains_pairs_device`).
 
     `denoise_amount`: the stack actions' option (`_finish`): when positive the fused frame is denoised on the device before
-    it is downloaded or written to `out_dev`.  0 (default): nothing is touched.
+    it is downloaded or written to `out_dev`.  0 (default): nothing is touched.  `white_balance` (an RGB triple) / `unsharp`
+    ((radius, amount, threshold)): the retouch filters, applied on the device after the denoise, in that order; None
+    (default): nothing is built, loaded or called.
 
     Returns (fused image as ndarray, or None when `out_dev` -- a device address for the result --
     is given; list of 2x3 transforms, None at ref_idx; list of correlation coefficients)."""
     _check_denoise_amount(denoise_amount)
+    if white_balance is not None or unsharp is not None:
+        _check_retouch(white_balance, unsharp, dtype)
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
     if vignetting is not None and (height * width * 3 * np.dtype(dtype).itemsize) % 16:
         # mi_vignette_apply_device works on 16-byte accesses: every frame of the contiguous stack must start on one
@@ -640,7 +689,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                 stack = _lib.Stack(height, width, in_dtype=dt, out_dtype=dt, device=device, **stack_kwargs)
                 created.append(stack.close)
             stack.push_frames_device(aligned.ptr, n_frames, fb)
-            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device)
+            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp)
             done = True
         finally:
             if not (keep_handles and done):
@@ -720,7 +769,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
             transforms = [None if i == ref_idx else (ms[i].reshape(3, 3).copy() if homography else ms[i, :6].reshape(2, 3).copy())
                           for i in range(n_frames)]
             ccs = [float(c) for c in cc]
-            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device)
+            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp)
             done = True
         finally:
             if created is not None and not (keep_handles and done):
@@ -801,7 +850,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
             if filled == batch_frames:
                 flush()
         flush()
-        out = _finish(stack, out_dev, denoise_amount, height, width, dt, device)
+        out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp)
         if corr is not None and info is not None:
             info["corrections"] = corr.fetch_corrections()
     finally:
@@ -815,7 +864,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
 def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constants.DEFAULT_FRAMES,
                        overlap=constants.DEFAULT_OVERLAP, device=0, out_dev=None, on_bunch=None, on_final=None,
                        check_running=None, stacks=None, results_buf=None, info=None, zero_copy=False, denoise_amount=0,
-                       **stack_kwargs):
+                       white_balance=None, unsharp=None, **stack_kwargs):
     """BASELINE config 5's two-stage flow in memory (the reference's `FocusStackBunch` followed by `FocusStack`,
     stack.py:61-113, examples/stack-from-frames): the frames are fused in bunches of `frames` with `overlap` shared
     (`get_bunches`), every bunch result is the stacker's OUTPUT type -- truncated to the input dtype exactly as the file
@@ -836,10 +885,13 @@ def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constan
     keeps it); it is not freed here.  `info`: an optional dict that receives `stage1_s` (first push to the last bunch result
     on the device) and `stage2_s` (the stack over the bunch results, to its result).  `denoise_amount`: when positive the final
     result is denoised on the device before it is downloaded or written to `out_dev` (`_finish`; the reference's
-    FocusStack(denoise_amount=...) behind a FocusStackBunch without it); 0 (default) touches nothing.  Returns the fused image (or None when `out_dev` is given) and the list of
+    FocusStack(denoise_amount=...) behind a FocusStackBunch without it); 0 (default) touches nothing.  `white_balance` /
+    `unsharp`: the retouch filters on the final result, after the denoise (`_finish`); None (default) touches nothing.  Returns the fused image (or None when `out_dev` is given) and the list of
     bunches (frame indices)."""
     from .actions import get_bunches
     _check_denoise_amount(denoise_amount)
+    if white_balance is not None or unsharp is not None:
+        _check_retouch(white_balance, unsharp, dtype)
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
     _lib.require_device()
     if overlap >= frames:
@@ -900,7 +952,7 @@ def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constan
         st2.push_frames_device(results.ptr, len(bunches), fb)
         if on_final is not None:
             on_final(st2, results)
-        out = _finish(st2, out_dev, denoise_amount, height, width, dt, device)
+        out = _finish(st2, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp)
     finally:
         if not stacks:
             st2.close()
