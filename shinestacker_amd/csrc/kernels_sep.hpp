@@ -390,6 +390,21 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
     float* sHB = sV;         // (V is dead once P2 has read it)
     // PAIR: G_{l+1} patch, [3][NH][NW] (interior tiles: over the dead G_l patch; border tiles and PL: their own array)
     float* sN = (SN_ALIAS || (PL && INTERIOR)) ? smem : smem + (INTERIOR ? G::lds_floats((int)sizeof(TIn), true) : G::LDS_FLOATS);
+    // PL (round 7): nothing the payload phase consumes comes from a load issued behind the next winner's prefetch (memory
+    // returns loads in order: such a load drains the prefetch, and the step pays two trips to DRAM one after the other).
+    //  * PL_KEEP: the tile's pixels of the staged G_l patch stay alive through P2 and the winners' G_l is read from LDS.
+    //    Border tiles have the G_{l+1} patch in its own array anyway; fp32 interior tiles put its planes 0 and 1 over the
+    //    patch's six leading halo rows, which no quad of the tile owns, and plane 2 into X, which the payload pass never
+    //    fills.  (8 / 16-bit interior tiles: six raw rows are too short, the winners' G_l pixels come from memory as before.)
+    //  * sG2: the tile's window of G_{l+2} (PL_G2H x PL_G2W pixels, expand-source index maps applied, [row][column][3]) in
+    //    the rest of X: one pixel per lane of the last three waves, loaded AHEAD of the prefetch and stored beside P2.
+    constexpr bool PL_SPLIT = PL && INTERIOR && !RAW, PL_KEEP = PL && (!INTERIOR || !RAW);
+    constexpr int PL_G2H = TH / 4 + 2, PL_G2W = TW / 4 + 2, PL_G2N = PL_G2H * PL_G2W, PL_G2L0 = NT - 192;
+    static_assert(!PL || (TH % 4 == 0 && TW % 4 == 0 && PL_G2N <= 192 && PL_G2L0 >= 0), "PL: G_{l+2} window");
+    static_assert(!PL_SPLIT || 2 * NPL1 <= 6 * G::GS, "PL: two planes of the G_{l+1} patch fit the leading halo rows");
+    static_assert(!PL || NPL1 + 3 * PL_G2N <= G::NH * G::XS, "PL: a plane and the G_{l+2} window fit X");
+    [[maybe_unused]] auto sNp = [&](int c) -> float* { return PL_SPLIT ? (c < 2 ? smem + c * NPL1 : sX) : sN + c * NPL1; };
+    [[maybe_unused]] float* sG2 = sX + NPL1;
     // PL: [0..7] winner bit map, [8] count, [16..] frame list -- behind everything else (interior tiles: the patch is over G_l's)
     uint32_t* sFL = reinterpret_cast<uint32_t*>(smem + (INTERIOR ? G::lds_floats((int)sizeof(TIn), true) : G::LDS_FLOATS + 3 * G::NH * G::NW));
     float* sV2 = sV + G::HBH * G::HBS;                   // PAIR: column sums of the G_{l+2} reduce, [3][N2H][NW] (V's tail)
@@ -562,6 +577,15 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
             }
         }
     };
+    // PL: the lane's pixel of the G_{l+2} window (last three waves), as a float offset inside a frame's G_{l+2}
+    [[maybe_unused]] const int g2i = tid - PL_G2L0;
+    [[maybe_unused]] uint32_t g2off = 0;
+    if constexpr (PL) {
+        if (g2i >= 0 && g2i < PL_G2N) {
+            const int r = SmallDiv<PL_G2W, 256>::div(g2i), q = g2i - r * PL_G2W;
+            g2off = (uint32_t)(map_expand_src(y0 / 4 - 1 + r, a.hn2) * a.wn2 + map_expand_src(x0 / 4 - 1 + q, a.wn2)) * 3u;
+        }
+    }
     prefetch(0);
     v2f gq_e = {0.f, 0.f}, gq_o = {0.f, 0.f};   // GQ1: gray of the lane's quad (rows 2qy+4, +5 of the patch), taken in P1
 
@@ -603,6 +627,11 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
             }
         }
         __syncthreads();
+        // PL: this frame's G_{l+2} window first -- its consumer then waits for it alone, not for the prefetch behind it
+        Px3 g2v = {};
+        if constexpr (PL) {
+            if (g2i >= 0 && g2i < PL_G2N) g2v = *(const Px3*)(a.g2 + (size_t)fid(b) * a.g2_stride + g2off);
+        }
         // the next frame's loads, all of them here
         if (b + 1 < nfr) prefetch(b + 1);
         const BufRsrc gn_rs = make_rsrc(PAIR ? gnext0 : gnext0 + (size_t)b * a.gnext_stride, (uint32_t)hn * (uint32_t)wn * 12u);
@@ -733,8 +762,7 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
                 for (int c = 0; c < 3; ++c) n[c] = s5r(t5[0][c], t5[1][c], t5[2][c], t5[3][c], t5[4][c], w0, w1, w2) * rs;
             }
             if constexpr (PL) {   // the patch is all the payload phase wants
-                float* np = sN + it;
-                np[0] = n[0]; np[NPL1] = n[1]; np[2 * NPL1] = n[2];
+                sNp(0)[it] = n[0]; sNp(1)[it] = n[1]; sNp(2)[it] = n[2];
                 continue;
             }
             // gray of the pixel, its neighbours along the row by DPP, expanded columns 2j' (even) and 2j'+1 (odd)
@@ -764,6 +792,12 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
             const float gl = dpp_wave_prev(g), gr = dpp_wave_next(g);
             lds_store2(sX + mul24(r, G::XS) + 2 * jp, ex_even(gl, g, gr, ce, cc), ex_odd(g, gr, co));
         }
+        if constexpr (PL) {
+            if (g2i >= 0 && g2i < PL_G2N) {
+                float* q = sG2 + 3 * g2i;
+                q[0] = g2v.v[0]; q[1] = g2v.v[1]; q[2] = g2v.v[2];
+            }
+        }
         __syncthreads();
 
         if constexpr (PL) {
@@ -775,7 +809,7 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
                 float e[4][3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const float* np = sN + c * NPL1 + mul24(qy3, G::NW) + ql3 - 1;   // G_{l+1} rows i-1 .. i+1, columns j-1 .. j+1
+                    const float* np = sNp(c) + mul24(qy3, G::NW) + ql3 - 1;   // G_{l+1} rows i-1 .. i+1, columns j-1 .. j+1
                     float xe[3], xo[3];
 #pragma unroll
                     for (int r = 0; r < 3; ++r) {
@@ -793,7 +827,12 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
                     if (bI[p] != f) continue;
                     const size_t px = (size_t)(oy + (p >> 1)) * w + ox + (p & 1);
                     float gv[3];
-                    load_px3(gfr + px * 3, gv);
+                    if constexpr (PL_KEEP) {   // the staged patch: row 2 qy + 4 + (p >> 1), column 2 ql + 2 + (p & 1)
+                        const float* gp = sG + mul24(2 * qy3 + 4 + (p >> 1), G::GS) + 6 * ql3 + 6 + 3 * (p & 1);
+                        gv[0] = gp[0]; gv[1] = gp[1]; gv[2] = gp[2];
+                    } else {
+                        load_px3(gfr + px * 3, gv);
+                    }
                     Px3 o;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) o.v[c] = (gv[c] - e[p][c]) + 0.0f;   // -0 -> +0 (pyramid.py:52-54)
@@ -803,18 +842,26 @@ __device__ __forceinline__ void level_sep_body(const LevelArgs& a) {
             if (f1 == f) {   // (lanes below (TH / 2) * (TW / 2) only)
                 const int r1 = SmallDiv<TW / 2, NT>::div(lt), c1 = lt - r1 * (TW / 2);
                 const int i1 = y0 / 2 + r1, j1 = x0 / 2 + c1;
-                const float* g2f = a.g2 + (size_t)f * a.g2_stride;
-                const int hn2 = a.hn2, wn2 = a.wn2;
+                // expand_sep_of on the window: y0 / 2 and x0 / 2 are even, so pixel (i1, j1) has the parities of (r1, c1) and
+                // its source rows / columns i1 / 2 - 1 .. + 1 are the window's r1 / 2 .. + 2 (same operations, same order)
+                const float* wp = sG2 + 3 * ((r1 >> 1) * PL_G2W + (c1 >> 1));
+                const bool yo = r1 & 1, xo = c1 & 1;
                 Px3 o;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const float g1v = sN[c * NPL1 + mul24(r1 + 2, G::NW) + c1 + 2];
-                    const float ev = expand_sep_of([&](int r, int k) { return g2f[((size_t)r * wn2 + k) * 3 + c]; }, hn2, wn2, i1, j1, ce, cc, co);
+                    const float g1v = sNp(c)[mul24(r1 + 2, G::NW) + c1 + 2];
+                    float X[3];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) {
+                        const float m0 = wp[3 * (r * PL_G2W) + c], m1 = wp[3 * (r * PL_G2W + 1) + c], m2 = wp[3 * (r * PL_G2W + 2) + c];
+                        X[r] = xo ? ex_odd(m1, m2, co) : ex_even(m0, m1, m2, ce, cc);
+                    }
+                    const float ev = yo ? ex_odd(X[1], X[2], co) : ex_even(X[0], X[1], X[2], ce, cc);
                     o.v[c] = (g1v - ev) + 0.0f;
                 }
                 *(Px3*)(a.lap1 + ((size_t)i1 * wn + j1) * 3) = o;
             }
-            if constexpr (INTERIOR) __syncthreads();   // the patch lies over G_l's: the next step's staging must not overtake these reads
+            __syncthreads();   // the next step's staging (the G_l patch, the G_{l+1} planes over it) and its window must not overtake these reads
             continue;
         }
 
