@@ -218,6 +218,23 @@ MI_API int mi_stack_state(mi_stack_t* s, int level, void** dev_energy, void** de
 /* the HIP stream the handle launches on (hipStream_t as void*) */
 MI_API int mi_stack_stream(mi_stack_t* s, void** stream);
 
+/* ---- depth map output (csrc/kernels_depth.hpp; no reference counterpart) ----
+ * The frame index in focus at each pixel, height x width float32, in global frame numbers (first + k * stride under
+ * mi_stack_set_first_index / _set_index_stride, whether or not the indices were exported).  Computed from the level-0 state
+ * of the frames pushed so far: v = the winner index, w = the running energy.  sigma == 0: the index itself.  0 < sigma <= 16:
+ * confidence-weighted smoothing, out = B(v * w) / B(w) where B(w) > 0, else v, with B the separable Gaussian of radius
+ * ceil(3 sigma) < min(height, width) and BORDER_REFLECT_101, in a fixed evaluation order in the stack's float_type (the header
+ * of kernels_depth.hpp states it; tests/depth_restatement.py is held to it bit for bit).  Reads the state only: it may be
+ * called before or after finish, any number of times.  MI_ERR_STATE with no frame pushed, MI_ERR_UNSUPPORTED for a stack
+ * without a Laplacian level, MI_ERR_INVALID for a sigma outside [0, 16] or a radius that does not fit the frame.
+ * mi_stack_depth_map_device: `dev_out` in device memory; synchronises the handle, as mi_stack_state does. */
+MI_API int mi_stack_depth_map(mi_stack_t* s, double sigma, void* host_out);
+MI_API int mi_stack_depth_map_device(mi_stack_t* s, double sigma, void* dev_out);
+/* The smoothing above on caller-made host planes (tests, other callers): `host_value` is int32 (value_is_int32 != 0) or of
+ * `float_type` (MI_F32 / MI_F64), `host_weight` (>= 0) of `float_type`, `host_out` float32, all height x width. */
+MI_API int mi_weighted_smooth(int device, const void* host_value, const void* host_weight, int height, int width, int value_is_int32,
+                       int float_type, double sigma, void* host_out);
+
 /* ---- per-kernel timing (hipEvent pairs on the handle's stream) ---- */
 enum {
     MI_PROF_LEVEL = 0,    /* fused level launches of levels >= 1 (simple impl: whole frames) */
@@ -586,6 +603,13 @@ enum {
     MI_DM_TAP_MAX = 3         /* W: MAX map only, maximum over the frames of the (smoothed) energies; after finish    */
 };
 MI_API int mi_dmap_tap(mi_dmap_t* d, int what, int frame, void* host_out);
+
+/* The depth map of a finished stack, height x width float32: D = (sum_i in_i * i) / total over the MI_DM_TAP_ENERGY_IN planes,
+ * i ascending, multiply and add rounded separately, in their type W; 0 where total == 0.  sigma > 0 smooths it as
+ * mi_stack_depth_map does, in W, with w = total for the AVERAGE map and w = 1 for the MAX map.  Reads the state only.
+ * MI_ERR_STATE before finish.  mi_dmap_depth_map_device: `dev_out` in device memory; waits for the handle's stream. */
+MI_API int mi_dmap_depth_map(mi_dmap_t* d, double sigma, void* host_out);
+MI_API int mi_dmap_depth_map_device(mi_dmap_t* d, double sigma, void* dev_out);
 
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,

@@ -109,6 +109,9 @@ SIGNATURES = {
                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_size_t)]),
     "mi_stack_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mi_stack_depth_map": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "mi_stack_depth_map_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "mi_weighted_smooth": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "mi_stack_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "mi_stack_profile_get": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -207,6 +210,8 @@ SIGNATURES = {
     "mi_dmap_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi_dmap_finish_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mi_dmap_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "mi_dmap_depth_map": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "mi_dmap_depth_map_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }
@@ -587,6 +592,16 @@ class Stack:
         check(load().mi_stack_stream(self._h, C.byref(s)))
         return s.value
 
+    def depth_map(self, sigma=0.0, dev_ptr=None):
+        """mi_stack_depth_map: the level-0 winner index, smoothed with the running energy as the weight (sigma > 0), as an
+        H x W float32 array -- or written to `dev_ptr` (H x W float32 of device memory), in which case nothing is returned"""
+        if dev_ptr is not None:
+            check(load().mi_stack_depth_map_device(self._h, float(sigma), dev_ptr))
+            return None
+        out = np.empty((self.height, self.width), np.float32)
+        check(load().mi_stack_depth_map(self._h, float(sigma), out.ctypes.data))
+        return out
+
     # -- timing
     def profile(self, enable=True):
         check(load().mi_stack_profile(self._h, int(enable)))
@@ -682,6 +697,15 @@ class DepthMap:
         wt = np.float32 if self._smooth or not self._f64 else np.float64
         out = np.empty((self.height, self.width), ft if what == DM_TAP_ENERGY_RAW else wt)
         check(load().mi_dmap_tap(self._h, int(what), int(frame), out.ctypes.data))
+        return out
+
+    def depth_map(self, sigma=0.0, dev_ptr=None):
+        """mi_dmap_depth_map: the weighted mean frame index of a finished stack, H x W float32 (or written to `dev_ptr`)"""
+        if dev_ptr is not None:
+            check(load().mi_dmap_depth_map_device(self._h, float(sigma), dev_ptr))
+            return None
+        out = np.empty((self.height, self.width), np.float32)
+        check(load().mi_dmap_depth_map(self._h, float(sigma), out.ctypes.data))
         return out
 
 

@@ -256,6 +256,16 @@ class _FocusStackCommon(FrameDirectory):
                 raise InvalidOptionError("denoise_amount", self.denoise_amount,
                                          f"the amount is also the template window size: integral, at most {MAX_TEMPLATE_WINDOW}")
         self.plot_stack = kwargs.pop('plot_stack', constants.DEFAULT_PLOT_STACK)
+        # depth_map_path (extension; None: off): every output also gets {working_path}/{depth_map_path}/{prefix}{name}.png, the
+        # stacker's depth_map() as 16-bit grey (depth_out.quantize); depth_map_sigma None: the stacker's own default
+        self.depth_map_path = kwargs.pop('depth_map_path', None)
+        self.depth_map_sigma = kwargs.pop('depth_map_sigma', None)
+        if self.depth_map_path is not None:
+            if not callable(getattr(stack_algo, "depth_map", None)):
+                raise InvalidOptionError("depth_map_path", self.depth_map_path, f"the stacker {stack_algo.name()} reports no depth map")
+            if self.depth_map_sigma is not None:
+                from .depth_out import check_sigma
+                check_sigma(self.depth_map_sigma)
         self.stack_algo.process = self
         self.frame_count = -1
 
@@ -271,6 +281,11 @@ class _FocusStackCommon(FrameDirectory):
             self.sub_message_r(': denoise image')
             stacked = denoise(stacked, self.denoise_amount, int(self.denoise_amount))
         write_img(out_filename, stacked)
+        if self.depth_map_path is not None:
+            from . import depth_out
+            self.sub_message_r(': depth map')
+            depth = self.stack_algo.depth_map() if self.depth_map_sigma is None else self.stack_algo.depth_map(self.depth_map_sigma)
+            depth_out.save(_join(self.working_path, self.depth_map_path), f"{self.prefix}{parts[0]}", depth, len(filenames))
         if self.plot_stack:
             idx_str = f"{self.frame_count + 1:04d}" if self.frame_count >= 0 else ''
             title = f"{self.name}: {self.stack_algo.name()}"

@@ -25,6 +25,7 @@
 #include "kernels_prestack.hpp"
 #include "kernels_denoise.hpp"
 #include "kernels_unsharp.hpp"
+#include "kernels_depth.hpp"
 #include "kernels_f64.hpp"
 #include "kernels_steps.hpp"
 
@@ -2888,6 +2889,138 @@ int mi_unsharp_mask(int device, const void* host_src, void* host_dst, int height
     rc = mi_unsharp_mask_device(device, nullptr, src, dst, height, width, dtype, taps, ksize, amount, threshold);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "unsharp kernel failed");
     if (!rc && hipMemcpy(host_dst, dst, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
+    cleanup();
+    return rc;
+}
+
+// ---------------------------------------------------------------- depth map output (kernels_depth.hpp)
+enum { WS_I32 = 0, WS_F32 = 1, WS_F64 = 2 };   // element types of the value and weight planes
+
+// out = B(v w) / B(w) (sigma > 0) or v (sigma == 0) as float32, for device planes, on `st`; waits for it (the scratch planes
+// are freed here).  vtype / wtype: the planes' element types; dev_w == nullptr: every weight is 1.  f64: the working type.
+// first / stride: the consecutive -> global numbering of an int32 index plane (0, 1: none).
+static int ws_run(hipStream_t st, int vtype, const void* dev_v, int wtype, const void* dev_w, bool f64, int h, int w, double sigma,
+                  int first, int stride, float* dev_out) {
+    if (!dev_v || !dev_out) return fail(MI_ERR_INVALID, "null argument");
+    if (h < 1 || w < 1) return fail(MI_ERR_INVALID, "bad plane size");
+    if (!(sigma >= 0.0) || sigma > MI_WS_MAX_SIGMA) return fail(MI_ERR_INVALID, "sigma must be in [0, %g] (got %g)", MI_WS_MAX_SIGMA, sigma);
+    const size_t np = (size_t)h * w;
+    const int combo = vtype * 100 + wtype * 10 + (f64 ? 1 : 0);
+    if (sigma == 0.0) {
+        switch (vtype * 10 + (f64 ? 1 : 0)) {
+            case WS_I32 * 10 + 0: ws_passthrough_launch<int32_t, float>(st, (const int32_t*)dev_v, np, first, stride, dev_out); break;
+            case WS_I32 * 10 + 1: ws_passthrough_launch<int32_t, double>(st, (const int32_t*)dev_v, np, first, stride, dev_out); break;
+            case WS_F32 * 10 + 0: ws_passthrough_launch<float, float>(st, (const float*)dev_v, np, first, stride, dev_out); break;
+            case WS_F64 * 10 + 1: ws_passthrough_launch<double, double>(st, (const double*)dev_v, np, first, stride, dev_out); break;
+            default: return fail(MI_ERR_INVALID, "unsupported plane types");
+        }
+        MI_HIP(hipGetLastError());
+        MI_HIP(hipStreamSynchronize(st));
+        return MI_OK;
+    }
+    double taps[MI_WS_MAX_TAPS];
+    const int radius = ws_gaussian_taps(sigma, taps);
+    if (radius >= std::min(h, w))
+        return fail(MI_ERR_INVALID, "sigma %g needs a radius of %d pixels: the plane must be larger in both directions", sigma, radius);
+    void *P = nullptr, *Q = nullptr;
+    const size_t fb = f64 ? 8 : 4;
+    if (hipMalloc(&P, np * fb) != hipSuccess || hipMalloc(&Q, np * fb) != hipSuccess) {
+        (void)hipFree(P);
+        (void)hipGetLastError();
+        return fail(MI_ERR_NOMEM, "out of device memory");
+    }
+    int rc = MI_OK;
+    switch (combo) {
+        case WS_I32 * 100 + WS_F32 * 10 + 0:
+            ws_smooth_launch<int32_t, float, float>(st, (const int32_t*)dev_v, (const float*)dev_w, h, w, radius, taps, first, stride,
+                                                    (float*)P, (float*)Q, dev_out);
+            break;
+        case WS_I32 * 100 + WS_F32 * 10 + 1:
+            ws_smooth_launch<int32_t, float, double>(st, (const int32_t*)dev_v, (const float*)dev_w, h, w, radius, taps, first, stride,
+                                                     (double*)P, (double*)Q, dev_out);
+            break;
+        case WS_I32 * 100 + WS_F64 * 10 + 1:
+            ws_smooth_launch<int32_t, double, double>(st, (const int32_t*)dev_v, (const double*)dev_w, h, w, radius, taps, first, stride,
+                                                      (double*)P, (double*)Q, dev_out);
+            break;
+        case WS_F32 * 100 + WS_F32 * 10 + 0:
+            ws_smooth_launch<float, float, float>(st, (const float*)dev_v, (const float*)dev_w, h, w, radius, taps, first, stride,
+                                                  (float*)P, (float*)Q, dev_out);
+            break;
+        case WS_F64 * 100 + WS_F64 * 10 + 1:
+            ws_smooth_launch<double, double, double>(st, (const double*)dev_v, (const double*)dev_w, h, w, radius, taps, first, stride,
+                                                     (double*)P, (double*)Q, dev_out);
+            break;
+        default: rc = fail(MI_ERR_INVALID, "unsupported plane types");
+    }
+    hipError_t e = rc ? hipSuccess : hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(P);
+    (void)hipFree(Q);
+    if (!rc && e != hipSuccess) rc = fail(MI_ERR_HIP, "weighted smoothing failed: %s", hipGetErrorString(e));
+    return rc;
+}
+
+int mi_stack_depth_map_device(mi_stack_t* s, double sigma, void* dev_out) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!dev_out) return fail(MI_ERR_INVALID, "null output");
+    MI_HIP(hipSetDevice(s->p.device));
+    rc = tiled_flush(s);
+    if (rc) return rc;
+    if (s->n_pushed == 0) return fail(MI_ERR_STATE, "depth map with no frames pushed");
+    if (s->L < 1) return fail(MI_ERR_UNSUPPORTED, "the stack has no Laplacian level: no per-pixel winner exists");
+    rc = tiled_sync_all(s);
+    if (rc) return rc;
+    MI_HIP(hipStreamSynchronize(s->stream));
+    if (s->aux) MI_HIP(hipStreamSynchronize(s->aux));   // an index export in flight
+    // the stored indices are consecutive from first_index until they are exported (export_level_indices)
+    const bool local = s->index_stride != 1 && !(s->idx_exported & 1ull);
+    return ws_run(s->stream, WS_I32, s->bestIdx[0], WS_F32, s->bestE[0], s->f64, s->lh[0], s->lw[0], sigma, local ? s->first_index : 0,
+                  local ? s->index_stride : 1, (float*)dev_out);
+}
+
+int mi_stack_depth_map(mi_stack_t* s, double sigma, void* host_out) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!host_out) return fail(MI_ERR_INVALID, "null output");
+    MI_HIP(hipSetDevice(s->p.device));
+    const size_t nb = (size_t)s->p.height * s->p.width * sizeof(float);
+    void* out = nullptr;
+    if (hipMalloc(&out, nb) != hipSuccess) { (void)hipGetLastError(); return fail(MI_ERR_NOMEM, "out of device memory"); }
+    rc = mi_stack_depth_map_device(s, sigma, out);
+    if (!rc && hipMemcpy(host_out, out, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
+    (void)hipFree(out);
+    return rc;
+}
+
+int mi_weighted_smooth(int device, const void* host_value, const void* host_weight, int height, int width, int value_is_int32,
+                       int float_type, double sigma, void* host_out) {
+    if (!host_value || !host_weight || !host_out) return fail(MI_ERR_INVALID, "null argument");
+    if (height < 1 || width < 1) return fail(MI_ERR_INVALID, "bad plane size");
+    if (float_type != MI_F32 && float_type != MI_F64) return fail(MI_ERR_INVALID, "float_type must be MI_F32 or MI_F64");
+    int ndev = 0;
+    int rc = mi_device_count(&ndev);
+    if (rc) return rc;
+    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
+    MI_HIP(hipSetDevice(device));
+    const bool f64 = float_type == MI_F64;
+    const size_t np = (size_t)height * width, fb = f64 ? 8 : 4, vb = value_is_int32 ? 4 : fb;
+    void *v = nullptr, *w = nullptr, *out = nullptr;
+    auto cleanup = [&]() { (void)hipFree(v); (void)hipFree(w); (void)hipFree(out); };
+    if (hipMalloc(&v, np * vb) != hipSuccess || hipMalloc(&w, np * fb) != hipSuccess || hipMalloc(&out, np * 4) != hipSuccess) {
+        cleanup();
+        (void)hipGetLastError();
+        return fail(MI_ERR_NOMEM, "out of device memory");
+    }
+    if (hipMemcpy(v, host_value, np * vb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(w, host_weight, np * fb, hipMemcpyHostToDevice) != hipSuccess) {
+        cleanup();
+        return fail(MI_ERR_HIP, "upload failed");
+    }
+    const int ft = f64 ? WS_F64 : WS_F32;
+    rc = ws_run(nullptr, value_is_int32 ? WS_I32 : ft, v, ft, w, f64, height, width, sigma, 0, 1, (float*)out);
+    if (!rc && hipMemcpy(host_out, out, np * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
     cleanup();
     return rc;
 }

@@ -432,6 +432,34 @@ int dmap_planes_t(mi_dmap* d, int stage, const void* host_in, int n, void* host_
     return cleanup(fail(MI_ERR_INVALID, "stage must be 0 .. 3"));
 }
 
+// The depth map (kernels_depth.hpp): one pass over the N planes finish left in en[i] (type W), then the weighted smoothing
+// in the same type with w = total (AVERAGE) or 1 (MAX).  Reads the state only.
+template <typename W>
+int dmap_depth_map_t(mi_dmap* d, double sigma, float* dev_out) {
+    const int h = d->p.height, w = d->p.width;
+    const size_t np = (size_t)h * w;
+    hipStream_t st = d->stream;
+    struct Scratch {
+        void *tab = nullptr, *D = nullptr;
+        ~Scratch() { (void)hipFree(tab); (void)hipFree(D); }
+    } tmp;
+    MI_HIP(hipMalloc(&tmp.tab, sizeof(void*) * (size_t)d->n));
+    MI_HIP(hipMemcpyAsync(tmp.tab, d->en.data(), sizeof(void*) * (size_t)d->n, hipMemcpyHostToDevice, st));
+    if (sigma == 0.0) {
+        hipLaunchKernelGGL((dm_depth_index<W, float>), dm_grid1(np), dim3(256), 0, st, (const W* const*)tmp.tab, d->n, (const W*)d->tot, np,
+                           dev_out);
+        MI_HIP(hipGetLastError());
+        MI_HIP(hipStreamSynchronize(st));
+        return MI_OK;
+    }
+    MI_HIP(hipMalloc(&tmp.D, np * sizeof(W)));
+    hipLaunchKernelGGL((dm_depth_index<W, W>), dm_grid1(np), dim3(256), 0, st, (const W* const*)tmp.tab, d->n, (const W*)d->tot, np,
+                       (W*)tmp.D);
+    MI_HIP(hipGetLastError());
+    const int wt = sizeof(W) == 8 ? WS_F64 : WS_F32;
+    return ws_run(st, wt, tmp.D, wt, d->p.map_type == MI_DM_MAP_AVERAGE ? d->tot : nullptr, sizeof(W) == 8, h, w, sigma, 0, 1, dev_out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -668,6 +696,29 @@ int mi_dmap_tap(mi_dmap_t* d, int what, int frame, void* host_out) {
     MI_HIP(hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, d->stream));
     MI_HIP(hipStreamSynchronize(d->stream));
     return MI_OK;
+}
+
+int mi_dmap_depth_map_device(mi_dmap_t* d, double sigma, void* dev_out) {
+    if (!d || !dev_out) return fail(MI_ERR_INVALID, "null argument");
+    if (!d->finished) return fail(MI_ERR_STATE, "the depth map exists after finish");
+    if (!(sigma >= 0.0) || sigma > MI_WS_MAX_SIGMA) return fail(MI_ERR_INVALID, "sigma must be in [0, %g] (got %g)", MI_WS_MAX_SIGMA, sigma);
+    MI_HIP(hipSetDevice(d->p.device));
+    MI_HIP(hipStreamSynchronize(d->stream));
+    const bool w64 = d->f64 && d->p.smooth_size <= 0;   // W (dmap_finish_t)
+    return w64 ? dmap_depth_map_t<double>(d, sigma, (float*)dev_out) : dmap_depth_map_t<float>(d, sigma, (float*)dev_out);
+}
+
+int mi_dmap_depth_map(mi_dmap_t* d, double sigma, void* host_out) {
+    if (!d || !host_out) return fail(MI_ERR_INVALID, "null argument");
+    if (!d->finished) return fail(MI_ERR_STATE, "the depth map exists after finish");
+    MI_HIP(hipSetDevice(d->p.device));
+    const size_t nb = (size_t)d->p.height * d->p.width * sizeof(float);
+    void* out = nullptr;
+    if (hipMalloc(&out, nb) != hipSuccess) { (void)hipGetLastError(); return fail(MI_ERR_NOMEM, "out of device memory"); }
+    int rc = mi_dmap_depth_map_device(d, sigma, out);
+    if (!rc && hipMemcpy(host_out, out, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
+    (void)hipFree(out);
+    return rc;
 }
 
 int mi_dmap_finish(mi_dmap_t* d, void* host_out, size_t row_stride_bytes) {

@@ -22,7 +22,7 @@ in the reference (np.divide(..., where=...) without out=, :57); it is 0 here.
 """
 import numpy as np
 
-from . import _lib
+from . import _lib, depth_out
 from .defaults import constants
 from .errors import InvalidOptionError, RunStopException
 from .pyramid import BaseStackAlgo
@@ -74,6 +74,16 @@ class DepthMapStack(BaseStackAlgo):
         if self._dmap is not None:
             self._dmap.close()
             self._dmap = None
+
+    def depth_map(self, sigma=depth_out.DEPTH_MAP_SIGMA, dev_ptr=None):
+        """The depth map this stacker is named after, of the last focus_stack / focus_stack_arrays: the mean frame index under
+        the focus map's weights, H x W float32 in frame numbers [0, N - 1]; sigma > 0 smooths it (weight: the total energy
+        for the AVERAGE map, 1 for the MAX map).  With `dev_ptr` (H x W float32 of device memory) the map is written there
+        and nothing is returned.  Reads the stack's state only; RuntimeError before any stack."""
+        if self._dmap is None:
+            raise RuntimeError("depth_map: no stack has been run yet")
+        sigma = depth_out.check_sigma(sigma, (self._dmap.height, self._dmap.width))
+        return self._dmap.depth_map(sigma, dev_ptr)
 
     def _step(self, i):
         self.process.callback('after_step', self.process.id, self.process.name, i)

@@ -76,6 +76,35 @@ def _check_retouch(white_balance, unsharp, dtype):
         _prepare(dtype, radius, amount, threshold)
 
 
+def _check_depth_map(depth_map, info, shape):
+    """`depth_map=`: None / False (off), True (the stacker's default sigma) or a sigma -> the sigma, or None when off.
+    Refused before anything is allocated: a sigma out of range or too wide for the frame, and no `info` dict to put the map in."""
+    if depth_map is None or depth_map is False:
+        return None
+    from . import depth_out
+    sigma = depth_out.check_sigma(depth_out.PYRAMID_SIGMA if depth_map is True else depth_map, shape)
+    if info is None:
+        raise InvalidOptionError("depth_map", depth_map, "the map is returned in the info dict: pass info={}")
+    return sigma
+
+
+def _depth_map_info(stack, sigma, info, on_device, height, width, device):
+    """info["depth_map"] = the stacker's depth map (Stack.depth_map): an H x W float32 array, or -- `on_device`, when the fused
+    image stays on the device too -- a DeviceBuffer of H x W float32 that the caller frees.  Reads the stack's state only."""
+    if sigma is None:
+        return
+    if not on_device:
+        info["depth_map"] = stack.depth_map(sigma)
+        return
+    buf = _lib.DeviceBuffer(height * width * 4, device)
+    try:
+        stack.depth_map(sigma, buf.ptr)
+    except BaseException:
+        buf.free()
+        raise
+    info["depth_map"] = buf
+
+
 def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_balance=None, unsharp=None):
     """The stacker's result: downloaded (returned), or written to the device address `out_dev` (None returned).  With
     `denoise_amount` > 0 the result first passes through the post-stack denoise on the device, with the reference's
@@ -133,7 +162,7 @@ def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_
 
 def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, feature_config=None,
                     matching_config=None, device=0, batch_frames=16, check_running=None, mask_noise=None, vignetting=None,
-                    info=None, denoise_amount=0, white_balance=None, unsharp=None, **stack_kwargs):
+                    info=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, **stack_kwargs):
     """Align every frame to frames[ref_idx] (fixed reference, `step_process=False` order,
     stack_framework.py:191-232) and fuse them.  `frames`: sequence of H x W x 3 uint8/uint16 BGR
     arrays.  Returns (fused image, list of n_good_matches).
@@ -146,8 +175,13 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     `denoise_amount`: the stack actions' option (`_finish`): when positive the fused frame is denoised on the device before
     it is downloaded.  0 (default): nothing is touched.  `white_balance` (an RGB triple) / `unsharp` ((radius, amount,
     threshold)): the retouch filters (white_balance.py, sharpen.py), applied on the device after the denoise, in that order,
-    before the download.  None (default): nothing is built, loaded or called."""
+    before the download.  None (default): nothing is built, loaded or called.
+
+    `depth_map`: a sigma, or True for the stacker's default -- `info["depth_map"]` then receives the frame index in focus at
+    each pixel (H x W float32, `Stack.depth_map`, depth_out.py).  None (default): nothing is computed; the return values are
+    the same either way."""
     _check_denoise_amount(denoise_amount)
+    dm_sigma = _check_depth_map(depth_map, info, np.asarray(frames[0]).shape if len(frames) else None)
     if white_balance is not None or unsharp is not None:
         _check_retouch(white_balance, unsharp, np.asarray(frames[0]).dtype if len(frames) else np.uint8)
     _lib.require_device()
@@ -236,6 +270,7 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
             raise RunStopException("align_and_stack")
     flush()
     out = _finish(stack, None, denoise_amount, h, w, dt, device, white_balance, unsharp)
+    _depth_map_info(stack, dm_sigma, info, False, h, w, device)
     stack.close()
     return out, matches
 
@@ -551,7 +586,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                            min_correlation=0.5, max_iters=60, device=0, batch_frames=None, out_dev=None,
                            balance=None, ecc_batch=16, step_process=False, native_loop=True, handles=None,
                            keep_handles=False, info=None, chain_refine=True, chain_serial=False, mask_noise=None,
-                           vignetting=None, denoise_amount=0, white_balance=None, unsharp=None, **stack_kwargs):
+                           vignetting=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, **stack_kwargs):
     """BASELINE config 4 with every frame resident in HBM: `dev_frames` is the device address of
     `n_frames` contiguous H x W x 3 frames.  Each frame is registered against frames[ref_idx] by
     the device ECC estimator (mi_aligner_*), warped with the blurred replicate border of
@@ -608,11 +643,16 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     ((radius, amount, threshold)): the retouch filters, applied on the device after the denoise, in that order; None
     (default): nothing is built, loaded or called.
 
+    `depth_map`: a sigma, or True for the stacker's default -- `info["depth_map"]` then receives the frame index in focus at
+    each pixel (H x W float32, `Stack.depth_map`, depth_out.py): an array, or with `out_dev` a `DeviceBuffer` the caller frees.
+    None (default): nothing is computed; the return values are the same either way.
+
     Returns (fused image as ndarray, or None when `out_dev` -- a device address for the result --
     is given; list of 2x3 transforms, None at ref_idx; list of correlation coefficients)."""
     _check_denoise_amount(denoise_amount)
     if white_balance is not None or unsharp is not None:
         _check_retouch(white_balance, unsharp, dtype)
+    dm_sigma = _check_depth_map(depth_map, info, (height, width))
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
     if vignetting is not None and (height * width * 3 * np.dtype(dtype).itemsize) % 16:
         # mi_vignette_apply_device works on 16-byte accesses: every frame of the contiguous stack must start on one
@@ -690,6 +730,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                 created.append(stack.close)
             stack.push_frames_device(aligned.ptr, n_frames, fb)
             out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp)
+            _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
             done = True
         finally:
             if not (keep_handles and done):
@@ -770,6 +811,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                           for i in range(n_frames)]
             ccs = [float(c) for c in cc]
             out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp)
+            _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
             done = True
         finally:
             if created is not None and not (keep_handles and done):
@@ -851,6 +893,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                 flush()
         flush()
         out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp)
+        _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
         if corr is not None and info is not None:
             info["corrections"] = corr.fetch_corrections()
     finally:

@@ -25,7 +25,7 @@ import logging
 
 import numpy as np
 
-from . import _lib
+from . import _lib, depth_out
 from .defaults import constants, resolve_arith
 from .errors import ImageLoadError, InvalidOptionError, RunStopException
 from .imageio import get_img_metadata, read_img, validate_image
@@ -169,6 +169,17 @@ class PyramidStack(BaseStackAlgo):
         if self._stack is not None:
             self._stack.close()
             self._stack = None
+
+    # ------------------------------------------------------------------ depth map (depth_out.py; no reference counterpart)
+    def depth_map(self, sigma=depth_out.PYRAMID_SIGMA, dev_ptr=None):
+        """The frame in focus at each pixel of the last focus_stack / focus_stack_arrays: the level-0 winner index, smoothed
+        with the winner's energy as the weight (sigma 0: the index itself), H x W float32 in frame numbers [0, N - 1].  With
+        `dev_ptr` (H x W float32 of device memory) the map is written there and nothing is returned.  Reads the stack's state
+        only; RuntimeError before any stack."""
+        if self._stack is None:
+            raise RuntimeError("depth_map: no stack has been run yet")
+        sigma = depth_out.check_sigma(sigma, (self._stack.height, self._stack.width))
+        return self._stack.depth_map(sigma, dev_ptr)
 
     # ------------------------------------------------------------------ the steps, one at a time (pyramid.py:24-148)
     # The reference's public methods of the same names, on NumPy arrays, run on the GPU.  They always use the reference's
