@@ -146,7 +146,8 @@ def test_seeded_random_vs_streaming_oracle(L, oracle, impl, shape, dtype, n, kw)
 
 @pytest.mark.parametrize("impl", [1, 2])
 def test_f32_input_equals_u8_input(L, impl):
-    """config 2 feeds fp32 frames holding integer values (img.astype(float32), pyramid.py:126)."""
+    """config 2 feeds fp32 frames holding integer values (img.astype(float32), pyramid.py:126).  Float-32 frames in general
+    -- full mantissas, values outside the output range, subnormal energies -- are tests/test_gpu_f32_values.py."""
     rng = np.random.default_rng(11)
     frames = [rng.integers(0, 256, (200, 300, 3), dtype=np.uint8) for _ in range(3)]
     a = run_stack(L, frames, impl)
