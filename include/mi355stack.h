@@ -544,6 +544,35 @@ MI_API int mi_unsharp_mask(int device, const void* host_src, void* host_dst, int
 MI_API int mi_unsharp_mask_device(int device, void* stream, const void* dev_src, void* dev_dst, int height, int width, int dtype,
                            const uint32_t* taps, int ksize, double amount, double threshold);
 
+/* ---- Stereo views from the depth map (csrc/kernels_stereo.hpp; no reference counterpart) ----
+ * The frame re-rendered from a viewpoint shifted sideways: every source pixel moves along its row by
+ * d = rint(f32(shift) * (t - f32(pivot))) pixels, t = clamp(depth / f32(n_frames - 1), 0, 1) (1 - t with near_first; 0 for a single
+ * frame), all float32 and separately rounded; where several land on one target the largest t wins; a target nothing landed on
+ * takes the nearer-to-the-background (smaller t, left on a tie) of the nearest filled targets to its left and right, the
+ * source pixel itself when the row has none.  Samples are copied, never computed.  The header of kernels_stereo.hpp is the
+ * specification; tests/stereo_restatement.py is held to it bit for bit.
+ * `img`, `out`: height x width x 3 of `dtype` (MI_U8 / MI_U16); `depth`: height x width float32 in frame numbers, as the
+ * depth map entry points write it.  MI_ERR_INVALID: null pointers, another dtype, n_frames < 1, a shift that is not finite,
+ * exceeds 64 in size or whose ceil(|shift|) does not stay below width, a pivot outside [0, 1], near_first other than 0 / 1,
+ * and for the device form dev_img == dev_out -- all before any device call.
+ * mi_stereo_view: host frames (host_out may be host_img).  mi_stereo_view_device: frames resident in device memory; the
+ * launch is queued on `stream` and not waited for. */
+MI_API int mi_stereo_view(int device, const void* host_img, const void* host_depth, void* host_out, int height, int width, int dtype,
+                   int n_frames, double shift, double pivot, int near_first);
+MI_API int mi_stereo_view_device(int device, void* stream, const void* dev_img, const void* dev_depth, void* dev_out, int height,
+                          int width, int dtype, int n_frames, double shift, double pivot, int near_first);
+/* Two views of height x width x 3 composed on the device, queued on `stream`: side by side into height x 2 width x 3 (left
+ * then right: MI_STEREO_PARALLEL, right then left: MI_STEREO_CROSS), or the red-cyan anaglyph, height x width x 3 with BGR
+ * channel 2 from the left view and channels 0 and 1 from the right one (MI_STEREO_ANAGLYPH; its three frames start on 4-byte
+ * boundaries).  A copy of samples; `dev_out` is a buffer of its own. */
+enum {
+    MI_STEREO_PARALLEL = 0,
+    MI_STEREO_CROSS = 1,
+    MI_STEREO_ANAGLYPH = 2
+};
+MI_API int mi_stereo_compose_device(int device, void* stream, const void* dev_left, const void* dev_right, void* dev_out, int height,
+                             int width, int dtype, int layout);
+
 /* ---- DepthMapStack: the second stacker behind the same plug-in boundary ----
  * Replaces the arithmetic of DepthMapStack.focus_stack (reference algorithms/depth_map.py:64-123) for
  * both float types: push = the first file loop (:67-75: read, img_bw, then per frame get_sobel_map :28-34

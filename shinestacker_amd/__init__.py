@@ -16,6 +16,7 @@ from .denoise import denoise  # noqa: F401,E402
 from .sharpen import unsharp_mask  # noqa: F401,E402
 from .white_balance import white_balance_from_rgb  # noqa: F401,E402
 from . import depth_out  # noqa: F401,E402
+from . import stereo  # noqa: F401,E402
 
-__all__ = ["AlignFrames", "BalanceFrames", "Vignetting", "MaskNoise", "NoiseDetection", "denoise", "unsharp_mask", "white_balance_from_rgb", "depth_out", "align_images", "PyramidStack", "DepthMapStack", "BaseStackAlgo", "StackJob", "FocusStack", "FocusStackBunch",
+__all__ = ["AlignFrames", "BalanceFrames", "Vignetting", "MaskNoise", "NoiseDetection", "denoise", "unsharp_mask", "white_balance_from_rgb", "depth_out", "stereo", "align_images", "PyramidStack", "DepthMapStack", "BaseStackAlgo", "StackJob", "FocusStack", "FocusStackBunch",
            "CombinedActions", "SubAction", "get_bunches", "constants"]

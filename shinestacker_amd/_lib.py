@@ -199,6 +199,11 @@ SIGNATURES = {
                                         C.POINTER(AlignStackOpts), C.POINTER(BalanceLinearOpts), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "mi_dmap_default_params": (None, [C.POINTER(DepthMapParams)]),
+    "mi_stereo_view": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                 C.c_int]),
+    "mi_stereo_view_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_double, C.c_double, C.c_int]),
+    "mi_stereo_compose_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_dmap_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(DepthMapParams)]),
     "mi_dmap_destroy": (None, [C.c_void_p]),
     "mi_dmap_reset": (C.c_int, [C.c_void_p]),

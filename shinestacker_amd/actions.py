@@ -266,6 +266,24 @@ class _FocusStackCommon(FrameDirectory):
             if self.depth_map_sigma is not None:
                 from .depth_out import check_sigma
                 check_sigma(self.depth_map_sigma)
+        # stereo_path (extension; None: off): every output also gets {working_path}/{stereo_path}/{prefix}{name}.{ext}, a stereo
+        # pair (stereo.pair) of the image as written, from the stacker's depth_map() (depth_map_sigma applies here too);
+        # stereo_separation None: stereo.DEFAULT_SEPARATION
+        self.stereo_path = kwargs.pop('stereo_path', None)
+        self.stereo_layout = kwargs.pop('stereo_layout', 'anaglyph')
+        self.stereo_separation = kwargs.pop('stereo_separation', None)
+        self.stereo_pivot = kwargs.pop('stereo_pivot', 0.5)
+        self.stereo_near = kwargs.pop('stereo_near', 'last')
+        if self.stereo_path is not None:
+            from . import stereo
+            if not callable(getattr(stack_algo, "depth_map", None)):
+                raise InvalidOptionError("stereo_path", self.stereo_path, f"the stacker {stack_algo.name()} reports no depth map")
+            if self.stereo_separation is None:
+                self.stereo_separation = stereo.DEFAULT_SEPARATION
+            stereo.check_options(self.stereo_layout, self.stereo_separation, self.stereo_pivot, self.stereo_near)
+            if self.depth_map_sigma is not None and self.depth_map_path is None:
+                from .depth_out import check_sigma
+                check_sigma(self.depth_map_sigma)
         self.stack_algo.process = self
         self.frame_count = -1
 
@@ -286,6 +304,15 @@ class _FocusStackCommon(FrameDirectory):
             self.sub_message_r(': depth map')
             depth = self.stack_algo.depth_map() if self.depth_map_sigma is None else self.stack_algo.depth_map(self.depth_map_sigma)
             depth_out.save(_join(self.working_path, self.depth_map_path), f"{self.prefix}{parts[0]}", depth, len(filenames))
+        if self.stereo_path is not None:
+            from . import stereo
+            self.sub_message_r(': stereo view')
+            depth = self.stack_algo.depth_map() if self.depth_map_sigma is None else self.stack_algo.depth_map(self.depth_map_sigma)
+            stereo_dir = _join(self.working_path, self.stereo_path)
+            os.makedirs(stereo_dir, exist_ok=True)
+            write_img(f"{stereo_dir}/{self.prefix}{parts[0]}." + '.'.join(parts[1:]),
+                      stereo.pair(stacked, depth, len(filenames), self.stereo_separation, self.stereo_pivot, self.stereo_near,
+                                  self.stereo_layout))
         if self.plot_stack:
             idx_str = f"{self.frame_count + 1:04d}" if self.frame_count >= 0 else ''
             title = f"{self.name}: {self.stack_algo.name()}"

@@ -26,6 +26,7 @@
 #include "kernels_denoise.hpp"
 #include "kernels_unsharp.hpp"
 #include "kernels_depth.hpp"
+#include "kernels_stereo.hpp"
 #include "kernels_f64.hpp"
 #include "kernels_steps.hpp"
 
@@ -3023,6 +3024,96 @@ int mi_weighted_smooth(int device, const void* host_value, const void* host_weig
     if (!rc && hipMemcpy(host_out, out, np * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
     cleanup();
     return rc;
+}
+
+// ---------------------------------------------------------------- stereo views (kernels_stereo.hpp)
+static int stereo_check(const void* img, const void* depth, const void* out, int height, int width, int dtype, int n_frames, double shift,
+                        double pivot, int near_first, bool may_alias) {
+    if (!img || !depth || !out) return fail(MI_ERR_INVALID, "null argument");
+    if (img == out && !may_alias) return fail(MI_ERR_INVALID, "the image and the view must differ (a view gathers from the whole row)");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
+    if (height < 1 || width < 1 || (size_t)width * 3 > (size_t)INT32_MAX ||
+        (size_t)height * (size_t)cdiv(width, MI_SV_SEG) > (size_t)INT32_MAX)
+        return fail(MI_ERR_INVALID, "bad image size");
+    if (n_frames < 1) return fail(MI_ERR_INVALID, "n_frames must be at least 1 (got %d)", n_frames);
+    if (!std::isfinite(shift) || std::fabs(shift) > (double)MI_SV_MAX_SHIFT)
+        return fail(MI_ERR_INVALID, "shift must be in [-%d, %d] (got %g)", MI_SV_MAX_SHIFT, MI_SV_MAX_SHIFT, shift);
+    if (std::ceil(std::fabs(shift)) >= (double)width)
+        return fail(MI_ERR_INVALID, "a shift of %g pixels does not fit a row of %d", shift, width);
+    if (!(pivot >= 0.0 && pivot <= 1.0)) return fail(MI_ERR_INVALID, "pivot must be in [0, 1] (got %g)", pivot);
+    if (near_first != 0 && near_first != 1) return fail(MI_ERR_INVALID, "near_first must be 0 or 1");
+    return MI_OK;
+}
+
+int mi_stereo_view_device(int device, void* stream, const void* dev_img, const void* dev_depth, void* dev_out, int height, int width,
+                          int dtype, int n_frames, double shift, double pivot, int near_first) {
+    int rc = stereo_check(dev_img, dev_depth, dev_out, height, width, dtype, n_frames, shift, pivot, near_first, false);
+    if (rc) return rc;
+    MI_HIP(hipSetDevice(device));
+    if (dtype == MI_U8)
+        stereo_view_launch<uint8_t>((hipStream_t)stream, dev_img, (const float*)dev_depth, dev_out, height, width, n_frames, (float)shift,
+                                    (float)pivot, near_first);
+    else
+        stereo_view_launch<uint16_t>((hipStream_t)stream, dev_img, (const float*)dev_depth, dev_out, height, width, n_frames, (float)shift,
+                                     (float)pivot, near_first);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_stereo_view(int device, const void* host_img, const void* host_depth, void* host_out, int height, int width, int dtype,
+                   int n_frames, double shift, double pivot, int near_first) {
+    // host_img == host_out is fine here: the frame passes through two device buffers
+    int rc = stereo_check(host_img, host_depth, host_out, height, width, dtype, n_frames, shift, pivot, near_first, true);
+    if (rc) return rc;
+    int ndev = 0;
+    rc = mi_device_count(&ndev);
+    if (rc) return rc;
+    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
+    MI_HIP(hipSetDevice(device));
+    const size_t np = (size_t)height * width, nb = np * 3 * dtype_size(dtype);
+    void *img = nullptr, *depth = nullptr, *out = nullptr;
+    auto cleanup = [&]() { (void)hipFree(img); (void)hipFree(depth); (void)hipFree(out); };
+    if (hipMalloc(&img, nb) != hipSuccess || hipMalloc(&depth, np * 4) != hipSuccess || hipMalloc(&out, nb) != hipSuccess) {
+        cleanup();
+        (void)hipGetLastError();
+        return fail(MI_ERR_NOMEM, "out of device memory");
+    }
+    if (hipMemcpy(img, host_img, nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(depth, host_depth, np * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        cleanup();
+        return fail(MI_ERR_HIP, "upload failed");
+    }
+    rc = mi_stereo_view_device(device, nullptr, img, depth, out, height, width, dtype, n_frames, shift, pivot, near_first);
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "stereo view kernel failed");
+    if (!rc && hipMemcpy(host_out, out, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
+    cleanup();
+    return rc;
+}
+
+int mi_stereo_compose_device(int device, void* stream, const void* dev_left, const void* dev_right, void* dev_out, int height, int width,
+                             int dtype, int layout) {
+    if (!dev_left || !dev_right || !dev_out) return fail(MI_ERR_INVALID, "null argument");
+    if (dev_out == dev_left || dev_out == dev_right) return fail(MI_ERR_INVALID, "the composition needs a buffer of its own");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
+    if (height < 1 || width < 1) return fail(MI_ERR_INVALID, "bad image size");
+    if (layout != MI_STEREO_PARALLEL && layout != MI_STEREO_CROSS && layout != MI_STEREO_ANAGLYPH)
+        return fail(MI_ERR_INVALID, "layout must be MI_STEREO_PARALLEL, MI_STEREO_CROSS or MI_STEREO_ANAGLYPH (got %d)", layout);
+    if (layout == MI_STEREO_ANAGLYPH && (((uintptr_t)dev_left | (uintptr_t)dev_right | (uintptr_t)dev_out) & 3u))
+        return fail(MI_ERR_INVALID, "the anaglyph's frames must start on 4-byte boundaries");
+    MI_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    if (layout == MI_STEREO_ANAGLYPH) {
+        if (dtype == MI_U8) anaglyph_launch<uint8_t>(st, dev_left, dev_right, dev_out, (size_t)height * width);
+        else anaglyph_launch<uint16_t>(st, dev_left, dev_right, dev_out, (size_t)height * width);
+        MI_HIP(hipGetLastError());
+        return MI_OK;
+    }
+    const size_t rb = (size_t)width * 3 * dtype_size(dtype);        // bytes of one view's row
+    const void* first = layout == MI_STEREO_PARALLEL ? dev_left : dev_right;
+    const void* second = layout == MI_STEREO_PARALLEL ? dev_right : dev_left;
+    MI_HIP(hipMemcpy2DAsync(dev_out, 2 * rb, first, rb, rb, (size_t)height, hipMemcpyDeviceToDevice, st));
+    MI_HIP(hipMemcpy2DAsync((char*)dev_out + rb, 2 * rb, second, rb, rb, (size_t)height, hipMemcpyDeviceToDevice, st));
+    return MI_OK;
 }
 
 int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,

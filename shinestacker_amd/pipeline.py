@@ -105,13 +105,63 @@ def _depth_map_info(stack, sigma, info, on_device, height, width, device):
     info["depth_map"] = buf
 
 
-def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_balance=None, unsharp=None):
+def _check_stereo(stereo, info, shape, dm_sigma):
+    """`stereo=`: None (off) or a dict of stereo.pair's options -- layout (default 'anaglyph'), separation, pivot, near -- and
+    `sigma`, the smoothing of the depth map the views are rendered from (default: the `depth_map=` sigma when that is given,
+    else the stacker's own).  Returns the options with every default filled in, or None when off.  Refused before anything
+    is allocated: an unknown key, an option out of range and no `info` dict to put the result in."""
+    if stereo is None:
+        return None
+    from . import depth_out
+    from . import stereo as sv
+    try:
+        opts = dict(stereo)
+    except (TypeError, ValueError):
+        raise InvalidOptionError("stereo", stereo, "a dict of layout, separation, pivot, near, sigma") from None
+    unknown = sorted(set(opts) - {"layout", "separation", "pivot", "near", "sigma"})
+    if unknown:
+        raise InvalidOptionError("stereo", unknown, "a dict of layout, separation, pivot, near, sigma")
+    opts = {"layout": "anaglyph", "separation": sv.DEFAULT_SEPARATION, "pivot": 0.5, "near": "last", "sigma": None, **opts}
+    sv.check_options(opts["layout"], opts["separation"], opts["pivot"], opts["near"], None if shape is None else shape[1])
+    if opts["sigma"] is None:
+        opts["sigma"] = depth_out.PYRAMID_SIGMA if dm_sigma is None else dm_sigma
+    opts["sigma"] = depth_out.check_sigma(opts["sigma"], shape)
+    if info is None:
+        raise InvalidOptionError("stereo", stereo, "the pair is returned in the info dict: pass info={}")
+    return opts
+
+
+def _stereo_render(stack, opts, info, n_frames, height, width, dtype, device):
+    """What `_finish` calls with the device address of the final frame when `stereo=` is set: info["stereo"] = stereo.pair of
+    that frame and of the stacker's depth map (written to a device plane, never downloaded), rendered and composed in HBM;
+    the pair is the one thing downloaded: an H x W x 3 ('anaglyph') or H x 2W x 3 array.  None when the option is off."""
+    if opts is None:
+        return None
+
+    def render(dev_frame):
+        from . import stereo as sv
+        depth = _lib.DeviceBuffer(height * width * 4, device)
+        try:
+            stack.depth_map(opts["sigma"], depth.ptr)
+            out = sv.pair_device(dev_frame, depth.ptr, height, width, dtype, n_frames, opts["separation"], opts["pivot"],
+                                 opts["near"], opts["layout"], device)
+            try:
+                info["stereo"] = out.download((height, width if opts["layout"] == "anaglyph" else 2 * width, 3), dtype)
+            finally:
+                out.free()
+        finally:
+            depth.free()
+    return render
+
+
+def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_balance=None, unsharp=None, on_device_frame=None):
     """The stacker's result: downloaded (returned), or written to the device address `out_dev` (None returned).  With
     `denoise_amount` > 0 the result first passes through the post-stack denoise on the device, with the reference's
     arguments (stack.py:33-35: the amount is the filter strength and the template window size); then through the white
     balance (`white_balance`: the RGB triple) and the unsharp mask (`unsharp`: radius, amount, threshold) when given --
-    denoise -> white balance -> unsharp, all in HBM, one download."""
-    if not denoise_amount and white_balance is None and unsharp is None:
+    denoise -> white balance -> unsharp, all in HBM, one download.  `on_device_frame` (`_stereo_render`): called with the
+    device address of the final frame, after the last filter and before the download."""
+    if not denoise_amount and white_balance is None and unsharp is None and on_device_frame is None:
         if out_dev is not None:
             stack.finish_device(out_dev)
             stack.sync()
@@ -129,6 +179,17 @@ def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_
     if unsharp is not None:
         from .sharpen import unsharp_mask_device
         steps.append((lambda s, d: unsharp_mask_device(s, d, height, width, dt, *unsharp, device=device), False))
+    if not steps:       # only on_device_frame asks for the frame in HBM
+        res = _lib.DeviceBuffer(fb, device) if out_dev is None else None
+        try:
+            final = out_dev if res is None else res.ptr
+            stack.finish_device(final)
+            stack.sync()
+            on_device_frame(final)
+            return None if res is None else res.download((height, width, 3), dt)
+        finally:
+            if res is not None:
+                res.free()
     bufs = []
     try:
         bufs.append(_lib.DeviceBuffer(fb, device))
@@ -151,6 +212,8 @@ def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_
                 dst = bufs[-1].ptr if cur == bufs[0].ptr else bufs[0].ptr
             run(cur, dst)
             cur = dst
+        if on_device_frame is not None:
+            on_device_frame(final)
         if res is not None:
             return res.download((height, width, 3), dt)
         _lib.check(_lib.load().mi_device_synchronize(device))
@@ -162,7 +225,7 @@ def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_
 
 def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, feature_config=None,
                     matching_config=None, device=0, batch_frames=16, check_running=None, mask_noise=None, vignetting=None,
-                    info=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, **stack_kwargs):
+                    info=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None, **stack_kwargs):
     """Align every frame to frames[ref_idx] (fixed reference, `step_process=False` order,
     stack_framework.py:191-232) and fuse them.  `frames`: sequence of H x W x 3 uint8/uint16 BGR
     arrays.  Returns (fused image, list of n_good_matches).
@@ -179,9 +242,16 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
 
     `depth_map`: a sigma, or True for the stacker's default -- `info["depth_map"]` then receives the frame index in focus at
     each pixel (H x W float32, `Stack.depth_map`, depth_out.py).  None (default): nothing is computed; the return values are
-    the same either way."""
+    the same either way.
+
+    `stereo`: a dict of `stereo.pair`'s options (layout -- default 'anaglyph' --, separation, pivot, near) and `sigma`, the
+    depth map's smoothing (default: the `depth_map=` sigma, else the stacker's own) -- `info["stereo"]` then receives the
+    stereo pair of the fused frame as an array, rendered on the device from the final frame and the depth plane before
+    anything is downloaded (stereo.py).  None (default): nothing is built, loaded or called; the return values are the same
+    either way."""
     _check_denoise_amount(denoise_amount)
     dm_sigma = _check_depth_map(depth_map, info, np.asarray(frames[0]).shape if len(frames) else None)
+    sv_opts = _check_stereo(stereo, info, np.asarray(frames[0]).shape if len(frames) else None, dm_sigma) if stereo is not None else None
     if white_balance is not None or unsharp is not None:
         _check_retouch(white_balance, unsharp, np.asarray(frames[0]).dtype if len(frames) else np.uint8)
     _lib.require_device()
@@ -269,7 +339,8 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
             from .errors import RunStopException
             raise RunStopException("align_and_stack")
     flush()
-    out = _finish(stack, None, denoise_amount, h, w, dt, device, white_balance, unsharp)
+    out = _finish(stack, None, denoise_amount, h, w, dt, device, white_balance, unsharp,
+                  _stereo_render(stack, sv_opts, info, n, h, w, dt, device))
     _depth_map_info(stack, dm_sigma, info, False, h, w, device)
     stack.close()
     return out, matches
@@ -586,7 +657,8 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                            min_correlation=0.5, max_iters=60, device=0, batch_frames=None, out_dev=None,
                            balance=None, ecc_batch=16, step_process=False, native_loop=True, handles=None,
                            keep_handles=False, info=None, chain_refine=True, chain_serial=False, mask_noise=None,
-                           vignetting=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, **stack_kwargs):
+                           vignetting=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None,
+                           **stack_kwargs):
     """BASELINE config 4 with every frame resident in HBM: `dev_frames` is the device address of
     `n_frames` contiguous H x W x 3 frames.  Each frame is registered against frames[ref_idx] by
     the device ECC estimator (mi_aligner_*), warped with the blurred replicate border of
@@ -647,12 +719,18 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     each pixel (H x W float32, `Stack.depth_map`, depth_out.py): an array, or with `out_dev` a `DeviceBuffer` the caller frees.
     None (default): nothing is computed; the return values are the same either way.
 
+    `stereo`: a dict of `stereo.pair`'s options (layout -- default 'anaglyph' --, separation, pivot, near) and `sigma`, the
+    depth map's smoothing (default: the `depth_map=` sigma, else the stacker's own) -- `info["stereo"]` then receives the
+    stereo pair of the fused frame, rendered on the device from the final frame and the depth plane before anything is
+    downloaded (stereo.py); it is an array, with `out_dev` too.  None (default): nothing is built, loaded or called.
+
     Returns (fused image as ndarray, or None when `out_dev` -- a device address for the result --
     is given; list of 2x3 transforms, None at ref_idx; list of correlation coefficients)."""
     _check_denoise_amount(denoise_amount)
     if white_balance is not None or unsharp is not None:
         _check_retouch(white_balance, unsharp, dtype)
     dm_sigma = _check_depth_map(depth_map, info, (height, width))
+    sv_opts = _check_stereo(stereo, info, (height, width), dm_sigma) if stereo is not None else None
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
     if vignetting is not None and (height * width * 3 * np.dtype(dtype).itemsize) % 16:
         # mi_vignette_apply_device works on 16-byte accesses: every frame of the contiguous stack must start on one
@@ -729,7 +807,8 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                 stack = _lib.Stack(height, width, in_dtype=dt, out_dtype=dt, device=device, **stack_kwargs)
                 created.append(stack.close)
             stack.push_frames_device(aligned.ptr, n_frames, fb)
-            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp)
+            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
+                          _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device))
             _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
             done = True
         finally:
@@ -810,7 +889,8 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
             transforms = [None if i == ref_idx else (ms[i].reshape(3, 3).copy() if homography else ms[i, :6].reshape(2, 3).copy())
                           for i in range(n_frames)]
             ccs = [float(c) for c in cc]
-            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp)
+            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
+                          _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device))
             _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
             done = True
         finally:
@@ -892,7 +972,8 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
             if filled == batch_frames:
                 flush()
         flush()
-        out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp)
+        out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
+                      _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device))
         _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
         if corr is not None and info is not None:
             info["corrections"] = corr.fetch_corrections()
