@@ -573,6 +573,36 @@ enum {
 MI_API int mi_stereo_compose_device(int device, void* stream, const void* dev_left, const void* dev_right, void* dev_out, int height,
                              int width, int dtype, int layout);
 
+/* ---- Brush retouching (reference retouch/brush_tool.py, brush_preview.py, image_editor_ui.py copy_brush_area_to_master; kernels
+ * in csrc/kernels_brush.hpp, whose header is the specification): a source frame painted into the master frame, a whole stroke
+ * in one launch.  Per pixel, over the stamps whose square |x - cx| <= radius, |y - cy| <= radius holds it, in stroke order:
+ * M = min(max(M + table[y - cy + radius][x - cx + radius], 0), 1) from M = 0, then once e = clip(M * opacity, 0, 1) and
+ * master = trunc(clip(master * (1 - e) + source * e, 0, max)), float64 throughout and without fused multiply-add.  Pixels no
+ * square holds are not written.
+ * `master` (written in place), `source`: height x width x 3 of `dtype` (MI_U8 / MI_U16), two distinct frames.  `table`:
+ * (2 radius + 1)^2 doubles, the reference's create_brush_mask(2 radius + 1, hardness, opacity) * flow / 100 (shinestacker_amd/
+ * retouch.py builds it; the library evaluates no cosine).  `stamps`: n_stamps (x, y) int32 centres, anywhere.  `opacity`:
+ * the brush's opacity / 100, which the reference applies a second time in the blend.  `mask`: optional height x width doubles
+ * that receive M (0 where nothing was painted).
+ * MI_ERR_INVALID, before any device call: null pointers, master == source, another dtype, a radius outside [2, 500], n_stamps
+ * outside [0, 65536], an opacity outside [0, 1], and for the device form a box that leaves the frame.
+ * mi_brush_stroke_device: everything resident in device memory; `box` (HOST, 4 int32: x_start, y_start, x_end, y_end) is the region
+ * the launch covers -- the union of the stamps' footprints clipped to the frame; an empty box launches nothing.  Queued on
+ * `stream`, not waited for.  mi_brush_stroke: host arrays; `area` (optional, 4 int32) receives that union, (0, 0, 0, 0) when
+ * every stamp misses the frame. */
+MI_API int mi_brush_stroke_device(int device, void* stream, void* dev_master, const void* dev_source, int height, int width, int dtype,
+                           const double* dev_table, int radius, const int32_t* dev_stamps, int n_stamps, const int32_t* box,
+                           double opacity, double* dev_mask);
+MI_API int mi_brush_stroke(int device, void* host_master, const void* host_source, int height, int width, int dtype,
+                    const double* host_table, int radius, const int32_t* host_stamps, int n_stamps, double opacity,
+                    double* host_mask, int32_t* area);
+/* The blend alone, over the whole frame, from a height x width float64 mask (the reference's apply_mask): e = clip(mask * opacity,
+ * 0, 1), master = trunc(clip(master * (1 - e) + source * e, 0, max)), in place.  The device form is queued on `stream`. */
+MI_API int mi_blend_mask_device(int device, void* stream, void* dev_master, const void* dev_source, const double* dev_mask, int height,
+                         int width, int dtype, double opacity);
+MI_API int mi_blend_mask(int device, void* host_master, const void* host_source, const double* host_mask, int height, int width,
+                  int dtype, double opacity);
+
 /* ---- DepthMapStack: the second stacker behind the same plug-in boundary ----
  * Replaces the arithmetic of DepthMapStack.focus_stack (reference algorithms/depth_map.py:64-123) for
  * both float types: push = the first file loop (:67-75: read, img_bw, then per frame get_sobel_map :28-34

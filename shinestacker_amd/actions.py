@@ -284,8 +284,38 @@ class _FocusStackCommon(FrameDirectory):
             if self.depth_map_sigma is not None and self.depth_map_path is None:
                 from .depth_out import check_sigma
                 check_sigma(self.depth_map_sigma)
+        # retouch (extension, FocusStack only; None: off): retouch.Stroke objects painted into the fused frame before the denoise;
+        # a stroke's source is an index into the sorted input list or one of its file names, and only those files are read again
+        self.retouch = kwargs.pop('retouch', None)
+        if self.retouch is not None:
+            from .retouch import check_strokes
+            self.retouch = check_strokes(self.retouch)
         self.stack_algo.process = self
         self.frame_count = -1
+
+    def _retouch_sources(self, filenames, img_files, stacked):
+        """the frames the strokes name, each read once: {stroke.source: frame}"""
+        sources = {}
+        for s in self.retouch:
+            if s.source in sources:
+                continue
+            if isinstance(s.source, str):
+                if s.source not in filenames:
+                    raise InvalidOptionError("source", s.source, "no such file among the inputs")
+                path = os.path.join(self.input_full_path, s.source)
+            else:
+                if not -len(img_files) <= s.source < len(img_files):
+                    raise InvalidOptionError("source", s.source, f"the stack has {len(img_files)} frames")
+                path = img_files[s.source]
+            img = read_img(path)
+            if img is None:
+                raise RuntimeError(f"Invalid file: {path}")
+            if img.dtype != stacked.dtype:
+                raise BitDepthError(stacked.dtype, img.dtype)
+            if img.shape != stacked.shape:
+                raise ShapeError(stacked.shape, img.shape)
+            sources[s.source] = img
+        return sources
 
     def focus_stack(self, filenames):
         """stack.py:26-52: fuse `filenames`, write the result, emit 'save_plot'."""
@@ -294,6 +324,11 @@ class _FocusStackCommon(FrameDirectory):
         stacked = self.stack_algo.focus_stack(img_files)
         parts = filenames[0].split(".")
         out_filename = f"{self.output_dir}/{self.prefix}{parts[0]}." + '.'.join(parts[1:])
+        if self.retouch:
+            from . import retouch
+            self.sub_message_r(': retouch image')
+            stacked = retouch.apply(stacked, self.retouch, self._retouch_sources(filenames, img_files, stacked),
+                                    device=getattr(self.stack_algo, "device", 0))
         if self.denoise_amount > 0:
             from .denoise import denoise
             self.sub_message_r(': denoise image')
@@ -411,6 +446,8 @@ class FocusStackBunch(StepList, _FocusStackCommon, _Sharded):
     file), so that no rank writes into a directory that is still being emptied."""
 
     def __init__(self, name, stack_algo, enabled=True, shard=None, **kwargs):
+        if kwargs.get('retouch') is not None:
+            raise InvalidOptionError("retouch", kwargs['retouch'], "strokes belong to one fused frame: FocusStack takes them, a bunch action does not")
         self._shard_setup(shard, kwargs, (stack_algo,))
         StepList.__init__(self, name, enabled)
         FrameDirectory.__init__(self, name, **kwargs)

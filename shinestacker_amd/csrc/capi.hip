@@ -27,6 +27,7 @@
 #include "kernels_unsharp.hpp"
 #include "kernels_depth.hpp"
 #include "kernels_stereo.hpp"
+#include "kernels_brush.hpp"
 #include "kernels_f64.hpp"
 #include "kernels_steps.hpp"
 
@@ -3114,6 +3115,152 @@ int mi_stereo_compose_device(int device, void* stream, const void* dev_left, con
     MI_HIP(hipMemcpy2DAsync(dev_out, 2 * rb, first, rb, rb, (size_t)height, hipMemcpyDeviceToDevice, st));
     MI_HIP(hipMemcpy2DAsync((char*)dev_out + rb, 2 * rb, second, rb, rb, (size_t)height, hipMemcpyDeviceToDevice, st));
     return MI_OK;
+}
+
+// ---------------------------------------------------------------- brush retouching (kernels_brush.hpp)
+static int brush_frame_check(const void* master, const void* source, int height, int width, int dtype, double opacity) {
+    if (!master || !source) return fail(MI_ERR_INVALID, "null argument");
+    if (master == source) return fail(MI_ERR_INVALID, "the master and the source must be two frames");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
+    if (height < 1 || width < 1 || (size_t)width * 3 > (size_t)INT32_MAX || (size_t)height > (size_t)65535 * MI_BR_TH ||
+        (size_t)height * (size_t)width > ((size_t)1 << 40))
+        return fail(MI_ERR_INVALID, "bad image size");
+    if (!(opacity >= 0.0 && opacity <= 1.0)) return fail(MI_ERR_INVALID, "opacity must be in [0, 1] (got %g)", opacity);
+    return MI_OK;
+}
+
+static int brush_stroke_check(const void* master, const void* source, int height, int width, int dtype, const double* table, int radius,
+                              const int32_t* stamps, int n_stamps, double opacity) {
+    int rc = brush_frame_check(master, source, height, width, dtype, opacity);
+    if (rc) return rc;
+    if (!table) return fail(MI_ERR_INVALID, "null argument");
+    if (radius < MI_BR_MIN_RADIUS || radius > MI_BR_MAX_RADIUS)
+        return fail(MI_ERR_INVALID, "radius must be in [%d, %d] (got %d)", MI_BR_MIN_RADIUS, MI_BR_MAX_RADIUS, radius);
+    if (n_stamps < 0 || n_stamps > MI_BR_MAX_STAMPS)
+        return fail(MI_ERR_INVALID, "a call takes 0 to %d stamps (got %d)", MI_BR_MAX_STAMPS, n_stamps);
+    if (n_stamps > 0 && !stamps) return fail(MI_ERR_INVALID, "null argument");
+    return MI_OK;
+}
+
+int mi_brush_stroke_device(int device, void* stream, void* dev_master, const void* dev_source, int height, int width, int dtype,
+                           const double* dev_table, int radius, const int32_t* dev_stamps, int n_stamps, const int32_t* box,
+                           double opacity, double* dev_mask) {
+    int rc = brush_stroke_check(dev_master, dev_source, height, width, dtype, dev_table, radius, dev_stamps, n_stamps, opacity);
+    if (rc) return rc;
+    if (!box) return fail(MI_ERR_INVALID, "null argument");
+    const bool empty = box[0] >= box[2] || box[1] >= box[3];
+    if (!empty && (box[0] < 0 || box[1] < 0 || box[2] > width || box[3] > height))
+        return fail(MI_ERR_INVALID, "the box (%d, %d, %d, %d) leaves the frame", box[0], box[1], box[2], box[3]);
+    MI_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    if (dev_mask) MI_HIP(hipMemsetAsync(dev_mask, 0, (size_t)height * (size_t)width * sizeof(double), st));
+    if (empty || n_stamps == 0) return MI_OK;
+    if (dtype == MI_U8)
+        brush_stroke_launch<uint8_t>(st, dev_master, dev_source, dev_table, dev_stamps, n_stamps, radius, width, box, opacity, dev_mask);
+    else
+        brush_stroke_launch<uint16_t>(st, dev_master, dev_source, dev_table, dev_stamps, n_stamps, radius, width, box, opacity, dev_mask);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+// the union of the stamps' footprints clipped to the frame, (x_start, y_start, x_end, y_end), or (0, 0, 0, 0)
+static void brush_area(const int32_t* stamps, int n_stamps, int radius, int height, int width, int32_t* area) {
+    int64_t x0 = INT64_MAX, y0 = INT64_MAX, x1 = 0, y1 = 0;
+    for (int i = 0; i < n_stamps; ++i) {
+        const int64_t cx = stamps[2 * i], cy = stamps[2 * i + 1];
+        const int64_t xs = std::max<int64_t>(0, cx - radius), xe = std::min<int64_t>(width, cx + radius + 1);
+        const int64_t ys = std::max<int64_t>(0, cy - radius), ye = std::min<int64_t>(height, cy + radius + 1);
+        if (xs >= xe || ys >= ye) continue;
+        x0 = std::min(x0, xs); y0 = std::min(y0, ys); x1 = std::max(x1, xe); y1 = std::max(y1, ye);
+    }
+    if (x1 == 0) x0 = y0 = y1 = 0;
+    area[0] = (int32_t)x0; area[1] = (int32_t)y0; area[2] = (int32_t)x1; area[3] = (int32_t)y1;
+}
+
+int mi_brush_stroke(int device, void* host_master, const void* host_source, int height, int width, int dtype, const double* host_table,
+                    int radius, const int32_t* host_stamps, int n_stamps, double opacity, double* host_mask, int32_t* area) {
+    int rc = brush_stroke_check(host_master, host_source, height, width, dtype, host_table, radius, host_stamps, n_stamps, opacity);
+    if (rc) return rc;
+    int ndev = 0;
+    rc = mi_device_count(&ndev);
+    if (rc) return rc;
+    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
+    int32_t box[4];
+    brush_area(host_stamps, n_stamps, radius, height, width, box);
+    if (area) memcpy(area, box, sizeof(box));
+    const size_t np = (size_t)height * width, nb = np * 3 * dtype_size(dtype);
+    if (box[0] >= box[2]) {           // nothing is painted: the master stays as it is
+        if (host_mask) memset(host_mask, 0, np * sizeof(double));
+        return MI_OK;
+    }
+    MI_HIP(hipSetDevice(device));
+    const size_t side = 2 * (size_t)radius + 1, tb = side * side * sizeof(double), sb = (size_t)n_stamps * 2 * sizeof(int32_t);
+    void *master = nullptr, *source = nullptr, *table = nullptr, *stamps = nullptr, *mask = nullptr;
+    auto cleanup = [&]() { (void)hipFree(master); (void)hipFree(source); (void)hipFree(table); (void)hipFree(stamps); (void)hipFree(mask); };
+    if (hipMalloc(&master, nb) != hipSuccess || hipMalloc(&source, nb) != hipSuccess || hipMalloc(&table, tb) != hipSuccess ||
+        hipMalloc(&stamps, sb) != hipSuccess || (host_mask && hipMalloc(&mask, np * sizeof(double)) != hipSuccess)) {
+        cleanup();
+        (void)hipGetLastError();
+        return fail(MI_ERR_NOMEM, "out of device memory");
+    }
+    if (hipMemcpy(master, host_master, nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(source, host_source, nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(table, host_table, tb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(stamps, host_stamps, sb, hipMemcpyHostToDevice) != hipSuccess) {
+        cleanup();
+        return fail(MI_ERR_HIP, "upload failed");
+    }
+    rc = mi_brush_stroke_device(device, nullptr, master, source, height, width, dtype, (const double*)table, radius, (const int32_t*)stamps,
+                                n_stamps, box, opacity, (double*)mask);
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "brush stroke kernel failed");
+    if (!rc && hipMemcpy(host_master, master, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
+    if (!rc && host_mask && hipMemcpy(host_mask, mask, np * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(MI_ERR_HIP, "download failed");
+    cleanup();
+    return rc;
+}
+
+int mi_blend_mask_device(int device, void* stream, void* dev_master, const void* dev_source, const double* dev_mask, int height,
+                         int width, int dtype, double opacity) {
+    int rc = brush_frame_check(dev_master, dev_source, height, width, dtype, opacity);
+    if (rc) return rc;
+    if (!dev_mask) return fail(MI_ERR_INVALID, "null argument");
+    MI_HIP(hipSetDevice(device));
+    if (dtype == MI_U8) blend_mask_launch<uint8_t>((hipStream_t)stream, dev_master, dev_source, dev_mask, (size_t)height * width, opacity);
+    else blend_mask_launch<uint16_t>((hipStream_t)stream, dev_master, dev_source, dev_mask, (size_t)height * width, opacity);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_blend_mask(int device, void* host_master, const void* host_source, const double* host_mask, int height, int width, int dtype,
+                  double opacity) {
+    int rc = brush_frame_check(host_master, host_source, height, width, dtype, opacity);
+    if (rc) return rc;
+    if (!host_mask) return fail(MI_ERR_INVALID, "null argument");
+    int ndev = 0;
+    rc = mi_device_count(&ndev);
+    if (rc) return rc;
+    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
+    MI_HIP(hipSetDevice(device));
+    const size_t np = (size_t)height * width, nb = np * 3 * dtype_size(dtype);
+    void *master = nullptr, *source = nullptr, *mask = nullptr;
+    auto cleanup = [&]() { (void)hipFree(master); (void)hipFree(source); (void)hipFree(mask); };
+    if (hipMalloc(&master, nb) != hipSuccess || hipMalloc(&source, nb) != hipSuccess || hipMalloc(&mask, np * sizeof(double)) != hipSuccess) {
+        cleanup();
+        (void)hipGetLastError();
+        return fail(MI_ERR_NOMEM, "out of device memory");
+    }
+    if (hipMemcpy(master, host_master, nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(source, host_source, nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(mask, host_mask, np * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        cleanup();
+        return fail(MI_ERR_HIP, "upload failed");
+    }
+    rc = mi_blend_mask_device(device, nullptr, master, source, (const double*)mask, height, width, dtype, opacity);
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "blend kernel failed");
+    if (!rc && hipMemcpy(host_master, master, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
+    cleanup();
+    return rc;
 }
 
 int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,

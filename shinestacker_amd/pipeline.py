@@ -154,14 +154,41 @@ def _stereo_render(stack, opts, info, n_frames, height, width, dtype, device):
     return render
 
 
-def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_balance=None, unsharp=None, on_device_frame=None):
+def _check_brush(retouch, n_frames):
+    """`retouch=`: None (off) or a sequence of retouch.Stroke whose `source` is a frame index in [0, n_frames).  Returns the
+    strokes as a list, or None when off.  Refused before anything is allocated."""
+    if retouch is None:
+        return None
+    from .retouch import check_strokes
+    strokes = check_strokes(retouch)
+    for s in strokes:
+        if isinstance(s.source, str) or not 0 <= s.source < n_frames:
+            raise InvalidOptionError("source", s.source, f"a stroke names a frame by its index in [0, {n_frames})")
+    return strokes
+
+
+def _brush_paint(strokes, kept, height, width, dtype, device):
+    """What `_finish` calls with the device address of the fused frame when `retouch=` is set: the strokes painted into it in
+    place from `kept`, {frame index: DeviceBuffer of that frame as it was pushed to the stacker}.  None when the option is off."""
+    if not strokes:
+        return None
+
+    def paint(dev_frame):
+        from .retouch import apply_device
+        apply_device(dev_frame, height, width, dtype, strokes, {i: b.ptr for i, b in kept.items()}, device)
+    return paint
+
+
+def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_balance=None, unsharp=None, on_device_frame=None,
+            on_fused_frame=None):
     """The stacker's result: downloaded (returned), or written to the device address `out_dev` (None returned).  With
     `denoise_amount` > 0 the result first passes through the post-stack denoise on the device, with the reference's
     arguments (stack.py:33-35: the amount is the filter strength and the template window size); then through the white
     balance (`white_balance`: the RGB triple) and the unsharp mask (`unsharp`: radius, amount, threshold) when given --
     denoise -> white balance -> unsharp, all in HBM, one download.  `on_device_frame` (`_stereo_render`): called with the
-    device address of the final frame, after the last filter and before the download."""
-    if not denoise_amount and white_balance is None and unsharp is None and on_device_frame is None:
+    device address of the final frame, after the last filter and before the download.  `on_fused_frame` (`_brush_paint`): called
+    with the device address of the fused frame before the first filter; it may change the frame in place."""
+    if not denoise_amount and white_balance is None and unsharp is None and on_device_frame is None and on_fused_frame is None:
         if out_dev is not None:
             stack.finish_device(out_dev)
             stack.sync()
@@ -179,13 +206,16 @@ def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_
     if unsharp is not None:
         from .sharpen import unsharp_mask_device
         steps.append((lambda s, d: unsharp_mask_device(s, d, height, width, dt, *unsharp, device=device), False))
-    if not steps:       # only on_device_frame asks for the frame in HBM
+    if not steps:       # only the hooks ask for the frame in HBM
         res = _lib.DeviceBuffer(fb, device) if out_dev is None else None
         try:
             final = out_dev if res is None else res.ptr
             stack.finish_device(final)
             stack.sync()
-            on_device_frame(final)
+            if on_fused_frame is not None:
+                on_fused_frame(final)
+            if on_device_frame is not None:
+                on_device_frame(final)
             return None if res is None else res.download((height, width, 3), dt)
         finally:
             if res is not None:
@@ -196,6 +226,8 @@ def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_
         cur = bufs[0].ptr
         stack.finish_device(cur)
         stack.sync()
+        if on_fused_frame is not None:
+            on_fused_frame(cur)
         res = None
         if out_dev is None:
             res = _lib.DeviceBuffer(fb, device)
@@ -225,7 +257,8 @@ def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_
 
 def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, feature_config=None,
                     matching_config=None, device=0, batch_frames=16, check_running=None, mask_noise=None, vignetting=None,
-                    info=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None, **stack_kwargs):
+                    info=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None, retouch=None,
+                    **stack_kwargs):
     """Align every frame to frames[ref_idx] (fixed reference, `step_process=False` order,
     stack_framework.py:191-232) and fuse them.  `frames`: sequence of H x W x 3 uint8/uint16 BGR
     arrays.  Returns (fused image, list of n_good_matches).
@@ -248,8 +281,15 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     depth map's smoothing (default: the `depth_map=` sigma, else the stacker's own) -- `info["stereo"]` then receives the
     stereo pair of the fused frame as an array, rendered on the device from the final frame and the depth plane before
     anything is downloaded (stereo.py).  None (default): nothing is built, loaded or called; the return values are the same
-    either way."""
+    either way.
+
+    `retouch`: a sequence of `retouch.Stroke` (retouch.py) painted into the fused frame on the device, in order, right after the
+    fusion: before the denoise, the white balance, the unsharp mask, the stereo render and the one download.  A stroke's
+    `source` is a frame index and means that frame as it was pushed to the stacker -- after the pre-stack corrections and the
+    warp; the reference frame untouched -- of which a device copy is kept as it passes.  None (default): nothing is built,
+    loaded, copied or called."""
     _check_denoise_amount(denoise_amount)
+    strokes = _check_brush(retouch, len(frames))
     dm_sigma = _check_depth_map(depth_map, info, np.asarray(frames[0]).shape if len(frames) else None)
     sv_opts = _check_stereo(stereo, info, np.asarray(frames[0]).shape if len(frames) else None, dm_sigma) if stereo is not None else None
     if white_balance is not None or unsharp is not None:
@@ -294,6 +334,7 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     mode = _BORDER_CODE[cfg['border_mode']]
     bv = (C.c_double * 4)(*(list(cfg['border_value']) + [0, 0, 0, 0])[:4])
     matches, filled = [], 0
+    kept = {s.source: None for s in strokes} if strokes else {}      # frame index -> device copy of the frame as pushed
 
     def flush():
         nonlocal filled
@@ -332,6 +373,9 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
             warp = lib.mi_warp_perspective_device if homography else lib.mi_warp_affine_device
             _lib.check(warp(device, None, src.ptr, dst, tmp.ptr, mask.ptr, h, w, _lib.DTYPE_CODE[dt], mm, mode, bv, 21,
                             float(cfg['border_blur'])))
+        if i in kept:
+            kept[i] = _lib.DeviceBuffer(fb, device)
+            _lib.check(lib.mi_memcpy_d2d(device, kept[i].ptr, dst, fb))     # on the stream the warp ran on: after it
         filled += 1
         if filled == batch_frames:
             flush()
@@ -339,8 +383,13 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
             from .errors import RunStopException
             raise RunStopException("align_and_stack")
     flush()
-    out = _finish(stack, None, denoise_amount, h, w, dt, device, white_balance, unsharp,
-                  _stereo_render(stack, sv_opts, info, n, h, w, dt, device))
+    try:
+        out = _finish(stack, None, denoise_amount, h, w, dt, device, white_balance, unsharp,
+                      _stereo_render(stack, sv_opts, info, n, h, w, dt, device), _brush_paint(strokes, kept, h, w, dt, device))
+    finally:
+        for b in kept.values():
+            if b is not None:
+                b.free()
     _depth_map_info(stack, dm_sigma, info, False, h, w, device)
     stack.close()
     return out, matches
@@ -723,6 +772,9 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     depth map's smoothing (default: the `depth_map=` sigma, else the stacker's own) -- `info["stereo"]` then receives the
     stereo pair of the fused frame, rendered on the device from the final frame and the depth plane before anything is
     downloaded (stereo.py); it is an array, with `out_dev` too.  None (default): nothing is built, loaded or called.
+
+    Brush retouching (`align_and_stack`'s `retouch=`) is not offered here: the frames live in the caller's buffer and the handles
+    are reused between calls, so the caller paints the result itself with `retouch.apply_device`.
 
     Returns (fused image as ndarray, or None when `out_dev` -- a device address for the result --
     is given; list of 2x3 transforms, None at ref_idx; list of correlation coefficients)."""
