@@ -603,6 +603,32 @@ MI_API int mi_blend_mask_device(int device, void* stream, void* dev_master, cons
 MI_API int mi_blend_mask(int device, void* host_master, const void* host_source, const double* host_mask, int height, int width,
                   int dtype, double opacity);
 
+/* ---- Depth-selected composite (csrc/kernels_composite.hpp, whose header is the specification; no reference counterpart) ----
+ * Every pixel taken from the frame the depth plane names.  Per pixel, float32, every operation rounded on its own:
+ * d = depth (NaN -> 0) clamped to [0, n_frames - 1]; MI_COMPOSITE_NEAREST copies the three samples of frame rint(d) (ties to
+ * even); MI_COMPOSITE_LINEAR takes k0 = floor(d), f = d - k0, k1 = min(k0 + 1, n_frames - 1) and stores a + f * (b - a) per
+ * sample (a, b the samples of frames k0, k1; rint and a clamp for the integer types; a itself when f == 0).
+ * A call holds `count` consecutive frames of the stack, global indices first .. first + count - 1, and writes the pixels with
+ * first <= k0 < first + count - 1, or k0 == n_frames - 1 == first + count - 1; every other pixel of `out` keeps what it holds and
+ * is not read in the frames.  Calls whose chunks overlap by one frame and cover [0, n_frames) give the one-call result.
+ * `frame_ptrs`: HOST array of `count` frame addresses, height x width x 3 of `dtype` (MI_U8 / MI_U16 / MI_F32) each; `depth`:
+ * height x width float32; `out`: height x width x 3 of `dtype`.  The frames and the depth plane are only read.
+ * MI_ERR_INVALID, before any device call: null pointers (a null table entry too), another dtype or interp, count < 1, a chunk
+ * outside [0, n_frames), count == 1 with n_frames > 1, n_frames > 2^24, an output that overlaps a frame or is the depth plane,
+ * and for the device form a frame that is not aligned to its sample type, a depth plane off a 16-byte or an output off a 4-byte
+ * boundary.
+ * mi_depth_composite_device: the addresses are device addresses; they travel in the kernel arguments, 64 per launch (more frames:
+ * several launches over overlapping sub-chunks), so the call allocates nothing, is queued on `stream` and waits for nothing.  mi_depth_composite: host frames; `host_out` is uploaded first, so that the
+ * pixels of other chunks survive. */
+enum {
+    MI_COMPOSITE_LINEAR = 0,
+    MI_COMPOSITE_NEAREST = 1
+};
+MI_API int mi_depth_composite_device(int device, void* stream, const void* const* frame_ptrs, int first, int count, int n_frames,
+                              const void* dev_depth, void* dev_out, int height, int width, int dtype, int interp);
+MI_API int mi_depth_composite(int device, const void* const* frame_ptrs, int first, int count, int n_frames, const void* host_depth,
+                       void* host_out, int height, int width, int dtype, int interp);
+
 /* ---- DepthMapStack: the second stacker behind the same plug-in boundary ----
  * Replaces the arithmetic of DepthMapStack.focus_stack (reference algorithms/depth_map.py:64-123) for
  * both float types: push = the first file loop (:67-75: read, img_bw, then per frame get_sobel_map :28-34

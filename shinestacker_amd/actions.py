@@ -284,20 +284,53 @@ class _FocusStackCommon(FrameDirectory):
             if self.depth_map_sigma is not None and self.depth_map_path is None:
                 from .depth_out import check_sigma
                 check_sigma(self.depth_map_sigma)
+        # depth_composite_path (extension; None: off): every output also gets {working_path}/{depth_composite_path}/{prefix}{name}.{ext},
+        # the depth-selected composite (depth_render.composite) of the input files by the stacker's depth_map() (depth_map_sigma
+        # applies here too): every pixel taken from the frame the depth map names
+        self.depth_composite_path = kwargs.pop('depth_composite_path', None)
+        self.depth_composite_interp = kwargs.pop('depth_composite_interp', 'linear')
+        if self.depth_composite_path is not None:
+            from . import depth_render
+            if not callable(getattr(stack_algo, "depth_map", None)):
+                raise InvalidOptionError("depth_composite_path", self.depth_composite_path,
+                                         f"the stacker {stack_algo.name()} reports no depth map")
+            depth_render.check_options(self.depth_composite_interp)
+            if self.depth_map_sigma is not None and self.depth_map_path is None and self.stereo_path is None:
+                from .depth_out import check_sigma
+                check_sigma(self.depth_map_sigma)
         # retouch (extension, FocusStack only; None: off): retouch.Stroke objects painted into the fused frame before the denoise;
-        # a stroke's source is an index into the sorted input list or one of its file names, and only those files are read again
+        # a stroke's source is an index into the sorted input list or one of its file names, and only those files are read again;
+        # the source "depth_composite" is the composite above (depth_composite_path must be set), not a file of that name
         self.retouch = kwargs.pop('retouch', None)
         if self.retouch is not None:
             from .retouch import check_strokes
             self.retouch = check_strokes(self.retouch)
+            if self.depth_composite_path is None and any(s.source == "depth_composite" for s in self.retouch):
+                raise InvalidOptionError("source", "depth_composite", "a stroke paints from the composite only with depth_composite_path set")
         self.stack_algo.process = self
         self.frame_count = -1
 
-    def _retouch_sources(self, filenames, img_files, stacked):
-        """the frames the strokes name, each read once: {stroke.source: frame}"""
+    def _depth_composite(self, img_files):
+        """the composite of the input files by the stacker's depth map; the files are read one chunk frame at a time"""
+        from . import depth_render
+
+        def frames():
+            for path in img_files:
+                img = read_img(path)
+                if img is None:
+                    raise RuntimeError(f"Invalid file: {path}")
+                yield img
+        depth = self.stack_algo.depth_map() if self.depth_map_sigma is None else self.stack_algo.depth_map(self.depth_map_sigma)
+        return depth_render.composite(frames(), depth, self.depth_composite_interp, device=getattr(self.stack_algo, "device", 0))
+
+    def _retouch_sources(self, filenames, img_files, stacked, composite=None):
+        """the frames the strokes name, each read once: {stroke.source: frame}; `composite`: the frame "depth_composite" names"""
         sources = {}
         for s in self.retouch:
             if s.source in sources:
+                continue
+            if composite is not None and s.source == "depth_composite":
+                sources[s.source] = composite
                 continue
             if isinstance(s.source, str):
                 if s.source not in filenames:
@@ -324,10 +357,14 @@ class _FocusStackCommon(FrameDirectory):
         stacked = self.stack_algo.focus_stack(img_files)
         parts = filenames[0].split(".")
         out_filename = f"{self.output_dir}/{self.prefix}{parts[0]}." + '.'.join(parts[1:])
+        composite = None
+        if self.depth_composite_path is not None:
+            self.sub_message_r(': depth composite')
+            composite = self._depth_composite(img_files)
         if self.retouch:
             from . import retouch
             self.sub_message_r(': retouch image')
-            stacked = retouch.apply(stacked, self.retouch, self._retouch_sources(filenames, img_files, stacked),
+            stacked = retouch.apply(stacked, self.retouch, self._retouch_sources(filenames, img_files, stacked, composite),
                                     device=getattr(self.stack_algo, "device", 0))
         if self.denoise_amount > 0:
             from .denoise import denoise
@@ -339,6 +376,10 @@ class _FocusStackCommon(FrameDirectory):
             self.sub_message_r(': depth map')
             depth = self.stack_algo.depth_map() if self.depth_map_sigma is None else self.stack_algo.depth_map(self.depth_map_sigma)
             depth_out.save(_join(self.working_path, self.depth_map_path), f"{self.prefix}{parts[0]}", depth, len(filenames))
+        if composite is not None:
+            composite_dir = _join(self.working_path, self.depth_composite_path)
+            os.makedirs(composite_dir, exist_ok=True)
+            write_img(f"{composite_dir}/{self.prefix}{parts[0]}." + '.'.join(parts[1:]), composite)
         if self.stereo_path is not None:
             from . import stereo
             self.sub_message_r(': stereo view')

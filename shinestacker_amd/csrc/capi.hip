@@ -28,6 +28,7 @@
 #include "kernels_depth.hpp"
 #include "kernels_stereo.hpp"
 #include "kernels_brush.hpp"
+#include "kernels_composite.hpp"
 #include "kernels_f64.hpp"
 #include "kernels_steps.hpp"
 
@@ -3259,6 +3260,83 @@ int mi_blend_mask(int device, void* host_master, const void* host_source, const 
     rc = mi_blend_mask_device(device, nullptr, master, source, (const double*)mask, height, width, dtype, opacity);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "blend kernel failed");
     if (!rc && hipMemcpy(host_master, master, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
+    cleanup();
+    return rc;
+}
+
+// ---------------------------------------------------------------- depth-selected composite (kernels_composite.hpp)
+static int composite_check(const void* const* frame_ptrs, int first, int count, int n_frames, const void* depth, const void* out,
+                           int height, int width, int dtype, int interp, bool on_device) {
+    if (!frame_ptrs || !depth || !out) return fail(MI_ERR_INVALID, "null argument");
+    if (dtype != MI_U8 && dtype != MI_U16 && dtype != MI_F32) return fail(MI_ERR_INVALID, "dtype must be MI_U8, MI_U16 or MI_F32");
+    if (interp != MI_COMPOSITE_LINEAR && interp != MI_COMPOSITE_NEAREST)
+        return fail(MI_ERR_INVALID, "interp must be MI_COMPOSITE_LINEAR or MI_COMPOSITE_NEAREST (got %d)", interp);
+    if (height < 1 || width < 1 || (size_t)height * (size_t)width > ((size_t)1 << 40)) return fail(MI_ERR_INVALID, "bad image size");
+    if (n_frames < 1 || n_frames > (1 << 24)) return fail(MI_ERR_INVALID, "n_frames must be in [1, 2^24] (got %d)", n_frames);
+    if (count < 1) return fail(MI_ERR_INVALID, "count must be at least 1 (got %d)", count);
+    if (first < 0 || first > n_frames - count)
+        return fail(MI_ERR_INVALID, "the chunk [%d, %d + %d) leaves the stack's [0, %d)", first, first, count, n_frames);
+    if (count == 1 && n_frames > 1) return fail(MI_ERR_INVALID, "a chunk of a stack of %d frames holds at least 2 of them", n_frames);
+    const size_t fb = (size_t)height * width * 3 * dtype_size(dtype);
+    for (int i = 0; i < count; ++i) {
+        const char* p = (const char*)frame_ptrs[i];
+        if (!p) return fail(MI_ERR_INVALID, "null frame (chunk entry %d)", i);
+        if (p < (const char*)out + fb && (const char*)out < p + fb)
+            return fail(MI_ERR_INVALID, "the output must not alias a frame (chunk entry %d): frames are only read", i);
+        if (on_device && ((uintptr_t)p & (dtype_size(dtype) - 1))) return fail(MI_ERR_INVALID, "frame %d is not aligned to its sample type", i);
+    }
+    if (depth == out) return fail(MI_ERR_INVALID, "the output must not alias the depth plane");
+    if (on_device && (((uintptr_t)depth & 15u) || ((uintptr_t)out & 3u)))
+        return fail(MI_ERR_INVALID, "the depth plane starts on a 16-byte boundary and the output on a 4-byte boundary");
+    return MI_OK;
+}
+
+int mi_depth_composite_device(int device, void* stream, const void* const* frame_ptrs, int first, int count, int n_frames,
+                              const void* dev_depth, void* dev_out, int height, int width, int dtype, int interp) {
+    int rc = composite_check(frame_ptrs, first, count, n_frames, dev_depth, dev_out, height, width, dtype, interp, true);
+    if (rc) return rc;
+    MI_HIP(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t npx = (size_t)height * width;
+    const int nearest = interp == MI_COMPOSITE_NEAREST;
+    // the addresses travel in the kernel arguments (64 per launch): nothing is allocated or copied, the call never waits
+    if (dtype == MI_U8) depth_composite_launch<uint8_t>(st, frame_ptrs, (const float*)dev_depth, dev_out, npx, first, count, n_frames, nearest);
+    else if (dtype == MI_U16) depth_composite_launch<uint16_t>(st, frame_ptrs, (const float*)dev_depth, dev_out, npx, first, count, n_frames, nearest);
+    else depth_composite_launch<float>(st, frame_ptrs, (const float*)dev_depth, dev_out, npx, first, count, n_frames, nearest);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_depth_composite(int device, const void* const* frame_ptrs, int first, int count, int n_frames, const void* host_depth,
+                       void* host_out, int height, int width, int dtype, int interp) {
+    int rc = composite_check(frame_ptrs, first, count, n_frames, host_depth, host_out, height, width, dtype, interp, false);
+    if (rc) return rc;
+    int ndev = 0;
+    rc = mi_device_count(&ndev);
+    if (rc) return rc;
+    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
+    MI_HIP(hipSetDevice(device));
+    const size_t np = (size_t)height * width, nb = np * 3 * dtype_size(dtype);
+    std::vector<void*> bufs((size_t)count + 2, nullptr);       // the chunk's frames, the depth plane, the output
+    auto cleanup = [&]() { for (void* b : bufs) (void)hipFree(b); };
+    for (size_t i = 0; i < bufs.size(); ++i)
+        if (hipMalloc(&bufs[i], i == (size_t)count ? np * 4 : nb) != hipSuccess) {
+            cleanup();
+            (void)hipGetLastError();
+            return fail(MI_ERR_NOMEM, "out of device memory");
+        }
+    void *depth = bufs[(size_t)count], *out = bufs[(size_t)count + 1];
+    bool ok = hipMemcpy(depth, host_depth, np * 4, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(out, host_out, nb, hipMemcpyHostToDevice) == hipSuccess;     // pixels of other chunks keep what they hold
+    for (int i = 0; ok && i < count; ++i) ok = hipMemcpy(bufs[(size_t)i], frame_ptrs[i], nb, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        cleanup();
+        return fail(MI_ERR_HIP, "upload failed");
+    }
+    rc = mi_depth_composite_device(device, nullptr, (const void* const*)bufs.data(), first, count, n_frames, depth, out, height, width,
+                                   dtype, interp);
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "depth composite kernel failed");
+    if (!rc && hipMemcpy(host_out, out, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
     cleanup();
     return rc;
 }

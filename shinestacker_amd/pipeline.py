@@ -154,28 +154,106 @@ def _stereo_render(stack, opts, info, n_frames, height, width, dtype, device):
     return render
 
 
-def _check_brush(retouch, n_frames):
-    """`retouch=`: None (off) or a sequence of retouch.Stroke whose `source` is a frame index in [0, n_frames).  Returns the
-    strokes as a list, or None when off.  Refused before anything is allocated."""
+def _check_depth_composite(depth_composite, info, shape, dm_sigma):
+    """`depth_composite=`: None (off) or a dict of `interp` (default 'linear') and `sigma`, the smoothing of the depth map the
+    composite is gathered by (default: the `depth_map=` sigma when that is given, else the stacker's own).  Returns the options
+    with every default filled in, or None when off.  Refused before anything is allocated: an unknown key, an option out of range
+    and no `info` dict to put the result in."""
+    if depth_composite is None:
+        return None
+    from . import depth_out, depth_render
+    try:
+        opts = dict(depth_composite)
+    except (TypeError, ValueError):
+        raise InvalidOptionError("depth_composite", depth_composite, "a dict of interp, sigma") from None
+    unknown = sorted(set(opts) - {"interp", "sigma"}, key=repr)
+    if unknown:
+        raise InvalidOptionError("depth_composite", unknown, "a dict of interp, sigma")
+    opts = {"interp": "linear", "sigma": None, **opts}
+    depth_render.check_options(opts["interp"])
+    if opts["sigma"] is None:
+        opts["sigma"] = depth_out.PYRAMID_SIGMA if dm_sigma is None else dm_sigma
+    opts["sigma"] = depth_out.check_sigma(opts["sigma"], shape)
+    if info is None:
+        raise InvalidOptionError("depth_composite", depth_composite, "the composite is returned in the info dict: pass info={}")
+    return opts
+
+
+def _check_brush(retouch, n_frames, depth_composite=None):
+    """`retouch=`: None (off) or a sequence of retouch.Stroke whose `source` is a frame index in [0, n_frames), or the string
+    "depth_composite" when that option (`depth_composite`: its checked options) is on.  Returns the strokes as a list, or None
+    when off.  Refused before anything is allocated."""
     if retouch is None:
         return None
     from .retouch import check_strokes
     strokes = check_strokes(retouch)
     for s in strokes:
+        if s.source == "depth_composite":
+            if depth_composite is None:
+                raise InvalidOptionError("source", s.source, "a stroke paints from the composite only with depth_composite= set")
+            continue
         if isinstance(s.source, str) or not 0 <= s.source < n_frames:
             raise InvalidOptionError("source", s.source, f"a stroke names a frame by its index in [0, {n_frames})")
     return strokes
 
 
-def _brush_paint(strokes, kept, height, width, dtype, device):
-    """What `_finish` calls with the device address of the fused frame when `retouch=` is set: the strokes painted into it in
-    place from `kept`, {frame index: DeviceBuffer of that frame as it was pushed to the stacker}.  None when the option is off."""
-    if not strokes:
+def _composite_render(stack, opts, info, frame_ptrs, height, width, dtype, device, on_device):
+    """The render of `depth_composite=`, a callable for `_brush_paint`: the stacker's depth map written to a device plane (never
+    downloaded) and the frames at the device addresses `frame_ptrs` -- all of the stack, as they were pushed -- gathered by it
+    into a new DeviceBuffer, which is returned.  None when the option is off."""
+    if opts is None:
+        return None
+
+    def render():
+        from . import depth_render
+        ptrs = list(frame_ptrs())
+        fb = height * width * 3 * np.dtype(dtype).itemsize
+        depth = _lib.DeviceBuffer(height * width * 4, device)
+        out = None
+        try:
+            stack.depth_map(opts["sigma"], depth.ptr)
+            stack.sync()
+            out = _lib.DeviceBuffer(fb, device)
+            depth_render.composite_device(ptrs, 0, len(ptrs), len(ptrs), depth.ptr, out.ptr, height, width, dtype, opts["interp"], device)
+            _lib.check(_lib.load().mi_device_synchronize(device))      # the depth plane is freed below
+        except BaseException:
+            if out is not None:
+                out.free()
+            raise
+        finally:
+            depth.free()
+        return out
+    render.on_device = on_device
+    render.info = info
+    return render
+
+
+def _brush_paint(strokes, kept, height, width, dtype, device, composite=None):
+    """What `_finish` calls with the device address of the fused frame when `retouch=` or `depth_composite=` is set: the
+    composite rendered (`composite`: `_composite_render`'s callable), then the strokes painted into the fused frame in place from
+    `kept`, {frame index: DeviceBuffer of that frame as it was pushed to the stacker}, and from the composite under the name
+    "depth_composite"; info["depth_composite"] then receives the composite, downloaded or as the DeviceBuffer.  None when both
+    options are off."""
+    if not strokes and composite is None:
         return None
 
     def paint(dev_frame):
-        from .retouch import apply_device
-        apply_device(dev_frame, height, width, dtype, strokes, {i: b.ptr for i, b in kept.items()}, device)
+        sources = {i: b.ptr for i, b in kept.items() if b is not None}
+        comp = composite() if composite is not None else None
+        try:
+            if comp is not None:
+                sources["depth_composite"] = comp.ptr
+            if strokes:
+                from .retouch import apply_device
+                apply_device(dev_frame, height, width, dtype, strokes, sources, device)
+            if comp is not None:
+                if composite.on_device:
+                    composite.info["depth_composite"], comp = comp, None
+                else:
+                    composite.info["depth_composite"] = comp.download((height, width, 3), dtype)
+        finally:
+            if comp is not None:
+                comp.free()
     return paint
 
 
@@ -258,7 +336,7 @@ def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_
 def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, feature_config=None,
                     matching_config=None, device=0, batch_frames=16, check_running=None, mask_noise=None, vignetting=None,
                     info=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None, retouch=None,
-                    **stack_kwargs):
+                    depth_composite=None, **stack_kwargs):
     """Align every frame to frames[ref_idx] (fixed reference, `step_process=False` order,
     stack_framework.py:191-232) and fuse them.  `frames`: sequence of H x W x 3 uint8/uint16 BGR
     arrays.  Returns (fused image, list of n_good_matches).
@@ -287,10 +365,20 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     fusion: before the denoise, the white balance, the unsharp mask, the stereo render and the one download.  A stroke's
     `source` is a frame index and means that frame as it was pushed to the stacker -- after the pre-stack corrections and the
     warp; the reference frame untouched -- of which a device copy is kept as it passes.  None (default): nothing is built,
-    loaded, copied or called."""
+    loaded, copied or called.
+
+    `depth_composite`: a dict of `interp` ('linear', the default, or 'nearest') and `sigma`, the depth map's smoothing (default:
+    the `depth_map=` sigma, else the stacker's own) -- `info["depth_composite"]` then receives the depth-selected composite
+    (depth_render.py) as an array: every pixel taken from the frame the depth map names, the frames being those pushed to the
+    stacker.  A device copy of EVERY frame is kept as it passes (InvalidOptionError, before anything is allocated, when the free
+    device memory does not hold them), and the composite is rendered in HBM from the depth plane, which is not downloaded.  A
+    stroke of `retouch=` whose `source` is the string "depth_composite" paints from it.  None (default): nothing is built, loaded,
+    copied or called; the return values are the same either way."""
     _check_denoise_amount(denoise_amount)
-    strokes = _check_brush(retouch, len(frames))
     dm_sigma = _check_depth_map(depth_map, info, np.asarray(frames[0]).shape if len(frames) else None)
+    dc_opts = _check_depth_composite(depth_composite, info, np.asarray(frames[0]).shape if len(frames) else None, dm_sigma) \
+        if depth_composite is not None else None
+    strokes = _check_brush(retouch, len(frames), dc_opts)
     sv_opts = _check_stereo(stereo, info, np.asarray(frames[0]).shape if len(frames) else None, dm_sigma) if stereo is not None else None
     if white_balance is not None or unsharp is not None:
         _check_retouch(white_balance, unsharp, np.asarray(frames[0]).dtype if len(frames) else np.uint8)
@@ -324,6 +412,12 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     dt = ref.dtype
     fb = h * w * 3 * dt.itemsize
     lib = _lib.load()
+    if dc_opts is not None:     # n kept frames, the composite and the depth plane, beside what the stack itself takes
+        need = (n + 1) * fb + h * w * 4
+        free, _total = _lib.mem_info(device)
+        if need > free:
+            raise InvalidOptionError("depth_composite", depth_composite, f"keeping the {n} frames resident needs {need} bytes of device "
+                                     f"memory and {free} bytes are free")
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
     stack = _lib.Stack(h, w, in_dtype=dt, out_dtype=dt, device=device, batch_frames=batch_frames,
                        **stack_kwargs)
@@ -334,7 +428,8 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     mode = _BORDER_CODE[cfg['border_mode']]
     bv = (C.c_double * 4)(*(list(cfg['border_value']) + [0, 0, 0, 0])[:4])
     matches, filled = [], 0
-    kept = {s.source: None for s in strokes} if strokes else {}      # frame index -> device copy of the frame as pushed
+    # frame index -> device copy of the frame as pushed: the frames the strokes name, or every frame for the composite
+    kept = dict.fromkeys(range(n)) if dc_opts is not None else {s.source: None for s in strokes} if strokes else {}
 
     def flush():
         nonlocal filled
@@ -385,7 +480,9 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     flush()
     try:
         out = _finish(stack, None, denoise_amount, h, w, dt, device, white_balance, unsharp,
-                      _stereo_render(stack, sv_opts, info, n, h, w, dt, device), _brush_paint(strokes, kept, h, w, dt, device))
+                      _stereo_render(stack, sv_opts, info, n, h, w, dt, device),
+                      _brush_paint(strokes, kept, h, w, dt, device,
+                                   _composite_render(stack, dc_opts, info, lambda: [kept[i].ptr for i in range(n)], h, w, dt, device, False)))
     finally:
         for b in kept.values():
             if b is not None:
@@ -707,7 +804,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                            balance=None, ecc_batch=16, step_process=False, native_loop=True, handles=None,
                            keep_handles=False, info=None, chain_refine=True, chain_serial=False, mask_noise=None,
                            vignetting=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None,
-                           **stack_kwargs):
+                           depth_composite=None, **stack_kwargs):
     """BASELINE config 4 with every frame resident in HBM: `dev_frames` is the device address of
     `n_frames` contiguous H x W x 3 frames.  Each frame is registered against frames[ref_idx] by
     the device ECC estimator (mi_aligner_*), warped with the blurred replicate border of
@@ -773,6 +870,13 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     stereo pair of the fused frame, rendered on the device from the final frame and the depth plane before anything is
     downloaded (stereo.py); it is an array, with `out_dev` too.  None (default): nothing is built, loaded or called.
 
+    `depth_composite`: a dict of `interp` ('linear' or 'nearest') and `sigma` (default: the `depth_map=` sigma, else the
+    stacker's own) -- `info["depth_composite"]` then receives the depth-selected composite (depth_render.py) of the aligned
+    (and balanced) frames as the stacker saw them, as a `DeviceBuffer` the caller frees.  The aligned frames are gathered where
+    they lie -- the `step_process` buffer, or the stacker's input batch -- so no copy is made; without `step_process` that needs
+    the whole job in one push (`batch_frames` >= `n_frames`, InvalidOptionError otherwise).  None (default): nothing is built,
+    loaded or called.
+
     Brush retouching (`align_and_stack`'s `retouch=`) is not offered here: the frames live in the caller's buffer and the handles
     are reused between calls, so the caller paints the result itself with `retouch.apply_device`.
 
@@ -783,6 +887,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
         _check_retouch(white_balance, unsharp, dtype)
     dm_sigma = _check_depth_map(depth_map, info, (height, width))
     sv_opts = _check_stereo(stereo, info, (height, width), dm_sigma) if stereo is not None else None
+    dc_opts = _check_depth_composite(depth_composite, info, (height, width), dm_sigma) if depth_composite is not None else None
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
     if vignetting is not None and (height * width * 3 * np.dtype(dtype).itemsize) % 16:
         # mi_vignette_apply_device works on 16-byte accesses: every frame of the contiguous stack must start on one
@@ -860,7 +965,10 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                 created.append(stack.close)
             stack.push_frames_device(aligned.ptr, n_frames, fb)
             out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
-                          _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device))
+                          _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device),
+                          _brush_paint(None, {}, height, width, dt, device,
+                                       _composite_render(stack, dc_opts, info, lambda: [aligned.ptr + i * fb for i in range(n_frames)],
+                                                         height, width, dt, device, True)))
             _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
             done = True
         finally:
@@ -878,6 +986,9 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                     subsample=max(1, int(cfg['subsample'])), fast=bool(cfg['fast_subsampling']), device=int(device),
                     stack_kwargs=tuple(sorted((k, repr(v)) for k, v in stack_kwargs.items())))   # the stacker's own options
     # everything that can be refused is refused BEFORE anything is allocated
+    if dc_opts is not None and n_frames > batch_frames:
+        raise InvalidOptionError("depth_composite", depth_composite, f"the composite gathers the aligned frames where they lie: the {n_frames} "
+                                 f"frames must pass in one push (batch_frames = {batch_frames}), or use step_process=True")
     corr = bal_opts = None
     if balance is not None:
         corr = _make_correction(balance, device)
@@ -942,7 +1053,10 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                           for i in range(n_frames)]
             ccs = [float(c) for c in cc]
             out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
-                          _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device))
+                          _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device),
+                          _brush_paint(None, {}, height, width, dt, device,
+                                       _composite_render(stack, dc_opts, info, lambda: [batches.ptr + i * fb for i in range(n_frames)],
+                                                         height, width, dt, device, True)))
             _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
             done = True
         finally:
@@ -1025,7 +1139,10 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                 flush()
         flush()
         out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
-                      _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device))
+                      _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device),
+                      _brush_paint(None, {}, height, width, dt, device,
+                                   _composite_render(stack, dc_opts, info, lambda: [batches[0].ptr + i * fb for i in range(n_frames)],
+                                                     height, width, dt, device, True)))
         _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
         if corr is not None and info is not None:
             info["corrections"] = corr.fetch_corrections()
