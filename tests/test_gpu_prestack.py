@@ -45,8 +45,8 @@ def test_radial_ring_sums_equal_the_reference_means(gold):
 
 
 def test_radial_ring_sums_full_size_against_the_rule_in_numpy(hiplib):
-    """One 4000 x 6000 frame, no sub-sampling, against the same rule stated here: integer BGR2GRAY, d in float64,
-    radii[i] <= d < radii[i + 1] by binary search in the table; every pixel with d < r_max is counted once."""
+    """One 4000 x 6000 frame, no sub-sampling, against the rule as tests/prestack_restatement.py states it: integer BGR2GRAY,
+    d in float64, radii[i] <= d < radii[i + 1] by binary search in the table; every pixel with d < r_max is counted once."""
     from shinestacker_amd import vignetting as vg
     h, w, r_steps = 4000, 6000, 100
     idx = np.arange(h * w * 3, dtype=np.uint32)
@@ -59,18 +59,12 @@ def test_radial_ring_sums_full_size_against_the_rule_in_numpy(hiplib):
     buf.upload(img)
     _, means, sums, counts = vg.radial_ring_sums_device(buf.ptr, h, w, np.uint8, r_steps, subsample=1)
     buf.free()
-    b, g, r = (img[..., k].astype(np.uint32) for k in range(3))
-    gray = ((b * 1868 + g * 9617 + r * 4899 + (1 << 13)) >> 14).astype(np.int64)
-    y, x = np.ogrid[:h, :w]
-    d = np.sqrt((x - w / 2)**2 + (y - h / 2)**2)
-    table = vg.ring_table(h, w, r_steps)
-    ring = np.searchsorted(table, d.reshape(-1), side="right") - 1
-    inside = ring < r_steps
-    want_counts = np.bincount(ring[inside], minlength=r_steps)
-    want_sums = np.bincount(ring[inside], weights=gray.reshape(-1)[inside], minlength=r_steps)   # < 2^53: exact in float64
-    assert int(counts.sum()) == int((d < table[-1]).sum()) == h * w - 1       # the corner pixel (0, 0) has d == r_max
+    import prestack_restatement as pr
+    assert np.array_equal(pr.ring_table(h, w, r_steps), vg.ring_table(h, w, r_steps))
+    want_sums, want_counts = pr.ring_sums(img, r_steps)     # asserts itself that the counted pixels are those with d < r_max
+    assert int(counts.sum()) == int(want_counts.sum()) == h * w - 1       # the corner pixel (0, 0) has d == r_max
     assert np.array_equal(counts.astype(np.int64), want_counts)
-    assert np.array_equal(sums.astype(np.int64), want_sums.astype(np.int64))
+    assert np.array_equal(sums.astype(np.int64), want_sums)
     assert np.array_equal(means, want_sums / want_counts)
 
 
