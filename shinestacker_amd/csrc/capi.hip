@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "host_scratch.hpp"
 #include "kernels_simple.hpp"
 #include "kernels_tiled.hpp"
 #include "kernels_sep.hpp"
@@ -1263,30 +1264,18 @@ int mi_pyr_step(int device, int op, int use_fma, double gen_kernel, const void* 
         if (!host_in2 || h2 < 1 || w2 < 1 || 2 * h2 < h || 2 * w2 < w) return fail(MI_ERR_INVALID, "bad coarse level");
         in2_elems = (size_t)h2 * w2 * c;
     }
-    struct Scratch {
-        std::vector<void*> v;
-        ~Scratch() {
-            (void)hipDeviceSynchronize();
-            for (void* q : v) (void)hipFree(q);
-        }
-        float* get(size_t elems) {
-            void* q = nullptr;
-            if (hipMalloc(&q, (elems ? elems : 1) * sizeof(float)) != hipSuccess) return nullptr;
-            v.push_back(q);
-            return (float*)q;
-        }
-    } tmp;
-    float *din = tmp.get(in_elems), *dout = tmp.get(out_elems), *din2 = in2_elems ? tmp.get(in2_elems) : nullptr;
-    if (!din || !dout || (in2_elems && !din2)) return fail(MI_ERR_NOMEM, "out of device memory");
     hipStream_t st = nullptr;
-    MI_HIP(hipMemcpyAsync(din, host_in, in_elems * sizeof(float), hipMemcpyHostToDevice, st));
+    DevScratch tmp(st);
+    float *din = nullptr, *dout = nullptr;
+    int rc;
+    if ((rc = tmp.upload(&din, host_in, in_elems * sizeof(float))) || (rc = tmp.alloc(&dout, out_elems * sizeof(float)))) return rc;
     const bool fma = use_fma != 0;
     if (op <= MI_PYR_EXPAND) {
         if (c == 3) fma ? pyr_step_launch<3, true>(op, st, din, h, w, dout, K) : pyr_step_launch<3, false>(op, st, din, h, w, dout, K);
         else fma ? pyr_step_launch<1, true>(op, st, din, h, w, dout, K) : pyr_step_launch<1, false>(op, st, din, h, w, dout, K);
     } else if (op == MI_PYR_FUSE_LAPLACIAN) {
-        float *q = tmp.get(npx * n), *e = tmp.get(npx * n);
-        if (!q || !e) return fail(MI_ERR_NOMEM, "out of device memory");
+        float *q = nullptr, *e = nullptr;
+        if ((rc = tmp.alloc(&q, npx * n * sizeof(float))) || (rc = tmp.alloc(&e, npx * n * sizeof(float)))) return rc;
         const unsigned g1 = (unsigned)((npx * n + 255) / 256);
         if (fma) hipLaunchKernelGGL((step_gray_sq<true>), dim3(g1), dim3(256), 0, st, (const float*)din, npx * n, q);
         else hipLaunchKernelGGL((step_gray_sq<false>), dim3(g1), dim3(256), 0, st, (const float*)din, npx * n, q);
@@ -1295,19 +1284,16 @@ int mi_pyr_step(int device, int op, int use_fma, double gen_kernel, const void* 
                 : pyr_step_launch<1, false>(MI_PYR_CONVOLVE, st, q + (size_t)i * npx, h, w, e + (size_t)i * npx, K);
         hipLaunchKernelGGL(step_fuse, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, (const float*)e, (const float*)din, n, npx, dout);
     } else if (op == MI_PYR_COLLAPSE_STEP) {
-        MI_HIP(hipMemcpyAsync(din2, host_in2, in2_elems * sizeof(float), hipMemcpyHostToDevice, st));
-        float* up = tmp.get((size_t)h2 * w2 * 4 * c);
-        if (!up) return fail(MI_ERR_NOMEM, "out of device memory");
+        float *din2 = nullptr, *up = nullptr;
+        if ((rc = tmp.upload(&din2, host_in2, in2_elems * sizeof(float))) || (rc = tmp.alloc(&up, (size_t)h2 * w2 * 4 * c * sizeof(float))))
+            return rc;
         if (c == 3) fma ? pyr_step_launch<3, true>(MI_PYR_EXPAND, st, din2, h2, w2, up, K) : pyr_step_launch<3, false>(MI_PYR_EXPAND, st, din2, h2, w2, up, K);
         else fma ? pyr_step_launch<1, true>(MI_PYR_EXPAND, st, din2, h2, w2, up, K) : pyr_step_launch<1, false>(MI_PYR_EXPAND, st, din2, h2, w2, up, K);
         hipLaunchKernelGGL(step_add_crop, dim3(cdiv(w, 64), cdiv(h, 4)), dim3(64, 4), 0, st, (const float*)up, 2 * w2, (const float*)din, h, w, c, dout);
     } else {   // MI_PYR_CLIP_ABS
         hipLaunchKernelGGL(step_clip_abs, dim3((unsigned)((out_elems + 255) / 256)), dim3(256), 0, st, (const float*)din, out_elems, (float)maxv, dout);
     }
-    MI_HIP(hipGetLastError());
-    MI_HIP(hipMemcpyAsync(host_out, dout, out_elems * sizeof(float), hipMemcpyDeviceToHost, st));
-    MI_HIP(hipStreamSynchronize(st));
-    return MI_OK;
+    return tmp.download(host_out, dout, out_elems * sizeof(float));
 }
 
 int mi_device_mem_info(int device, size_t* free_bytes, size_t* total_bytes) {
@@ -1340,9 +1326,8 @@ int mi_stack_create(mi_stack_t** out, const mi_stack_params_t* params) {
         return fail(MI_ERR_INVALID, "MI_ARITH_SEPARABLE needs float_type MI_F32");
     if (p.pair_levels < 0 || p.pair_levels > 3) return fail(MI_ERR_INVALID, "pair_levels must be 0 (automatic), 1 (pairs from level 0 on), 2 (none) or 3 (pairs from level 1 on)");
     int ndev = 0;
-    int rc = mi_device_count(&ndev);
+    int rc = visible_devices(&ndev);
     if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
     if (p.device < 0 || p.device >= ndev) return fail(MI_ERR_INVALID, "device %d out of range (have %d)", p.device, ndev);
     MI_HIP(hipSetDevice(p.device));
 
@@ -2035,31 +2020,19 @@ int warp_host_impl(int device, const void* host_src, void* host_dst, void* host_
     if (!host_src || !host_dst) return fail(MI_ERR_INVALID, "null image");
     if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
     if (height < 1 || width < 1) return fail(MI_ERR_INVALID, "bad image size");
-    int ndev = 0;
-    int rc = mi_device_count(&ndev);
+    int rc = open_device(device);
     if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
     const size_t nb = (size_t)height * width * 3 * dtype_size(dtype), np = (size_t)height * width;
+    DevScratch scratch(nullptr);
     void *src = nullptr, *dst = nullptr, *tmp = nullptr, *mask = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(src); (void)hipFree(dst); (void)hipFree(tmp); (void)hipFree(mask);
-    };
-#define TRYH(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(e_ == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
-    TRYH(hipMalloc(&src, nb));
-    TRYH(hipMalloc(&dst, nb));
-    TRYH(hipMalloc(&tmp, nb));
-    TRYH(hipMalloc(&mask, np));
-    TRYH(hipMemcpy(src, host_src, nb, hipMemcpyHostToDevice));
+    if ((rc = scratch.upload(&src, host_src, nb)) || (rc = scratch.alloc(&dst, nb)) || (rc = scratch.alloc(&tmp, nb)) ||
+        (rc = scratch.alloc(&mask, np)))
+        return rc;
     rc = warp_device_impl(device, nullptr, src, dst, tmp, mask, height, width, dtype, M, persp, border_mode, border_value,
                           blur_ksize, blur_sigma);
-    if (rc) { cleanup(); return rc; }
-    TRYH(hipDeviceSynchronize());
-    TRYH(hipMemcpy(host_dst, dst, nb, hipMemcpyDeviceToHost));
-    if (host_mask) TRYH(hipMemcpy(host_mask, mask, np, hipMemcpyDeviceToHost));
-#undef TRYH
-    cleanup();
-    return MI_OK;
+    if (!rc) rc = scratch.download(host_dst, dst, nb);
+    if (!rc && host_mask) rc = scratch.download(host_mask, mask, np);
+    return rc;
 }
 }  // namespace
 
@@ -2099,11 +2072,8 @@ int mi_aligner_create(mi_aligner_t* out, int device, int height, int width, int 
     if (subsample < 1) return fail(MI_ERR_INVALID, "subsample must be >= 1");
     const int h = (height + subsample - 1) / subsample, w = (width + subsample - 1) / subsample;
     if (h < 16 || w < 16) return fail(MI_ERR_INVALID, "image too small for ECC");
-    int ndev = 0;
-    int rc = mi_device_count(&ndev);
+    int rc = open_device(device);
     if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
     mi_aligner* al = new (std::nothrow) mi_aligner();
     if (!al) return fail(MI_ERR_NOMEM, "out of host memory");
     al->device = device; al->height = height; al->width = width; al->dtype = dtype; al->subsample = subsample;
@@ -2211,25 +2181,16 @@ int mi_phase_correlate_device(int device, void* stream, const void* dev_ref, con
     if (P > PC_MAX_N || Q > PC_MAX_N) return fail(MI_ERR_UNSUPPORTED, "phase correlation takes planes of at most %d pixels per side", PC_MAX_N);
     MI_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
+    DevScratch tmp(st);
     float2 *a = nullptr, *b = nullptr;
     double* o = nullptr;
-    MI_HIP(hipMalloc((void**)&a, sizeof(float2) * P * Q));
-    if (hipMalloc((void**)&b, sizeof(float2) * P * Q) != hipSuccess || hipMalloc((void**)&o, 3 * sizeof(double)) != hipSuccess) {
-        (void)hipFree(a);
-        if (b) (void)hipFree(b);
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
+    int rc;
+    if ((rc = tmp.alloc(&a, sizeof(float2) * P * Q)) || (rc = tmp.alloc(&b, sizeof(float2) * P * Q)) || (rc = tmp.alloc(&o, 3 * sizeof(double))))
+        return rc;
     pc_spectrum(st, (const float*)dev_ref, height, width, a, P, Q);
     pc_spectrum(st, (const float*)dev_mov, height, width, b, P, Q);
     pc_correlate(st, a, b, P, Q, o);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out3, o, 3 * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(a);
-    (void)hipFree(b);
-    (void)hipFree(o);
-    if (e != hipSuccess) return fail(MI_ERR_HIP, "phase correlation: %s", hipGetErrorString(e));
-    return MI_OK;
+    return tmp.download(out3, o, 3 * sizeof(double));
 }
 
 int mi_aligner_estimate_batch(mi_aligner_t al, void* stream, const void* const* dev_movs, int n, int max_iters,
@@ -2418,21 +2379,16 @@ int mi_ecc_similarity(int device, const void* host_ref, const void* host_mov, in
     int rc = mi_aligner_create(&al, device, height, width, dtype, 1, max_levels);
     if (rc) return rc;
     const size_t nb = (size_t)height * width * 3 * dtype_size(dtype);
-    void* raw = nullptr;
-    if (hipMalloc(&raw, nb) != hipSuccess) {
-        mi_aligner_destroy(al);
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
     auto run = [&]() -> int {
-        MI_HIP(hipMemcpy(raw, host_ref, nb, hipMemcpyHostToDevice));
-        int r = mi_aligner_set_reference(al, nullptr, raw);
-        if (r) return r;
+        DevScratch tmp(al->own);   // the aligner's stream: `raw` is freed behind its work, and before the handle goes
+        void* raw = nullptr;
+        int r = tmp.upload(&raw, host_ref, nb);
+        if (r || (r = mi_aligner_set_reference(al, nullptr, raw))) return r;
         MI_HIP(hipStreamSynchronize(al->own));   // the pyramid is built before `raw` is reused
         MI_HIP(hipMemcpy(raw, host_mov, nb, hipMemcpyHostToDevice));
         return mi_aligner_estimate(al, nullptr, raw, max_iters, eps, M_out, cc_out, iters_out);
     };
     rc = run();
-    (void)hipFree(raw);
     mi_aligner_destroy(al);
     return rc;
 }
@@ -2509,22 +2465,13 @@ int mi_histogram(int device, const void* host_img, int height, int width, int dt
     if (!host_img || !counts) return fail(MI_ERR_INVALID, "null argument");
     if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
     if (height < 1 || width < 1) return fail(MI_ERR_INVALID, "bad image size");
-    int ndev = 0;
-    int rc = mi_device_count(&ndev);
+    int rc = open_device(device);
     if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
     const size_t nb = (size_t)height * width * 3 * dtype_size(dtype);
+    DevScratch tmp(nullptr);
     void *img = nullptr, *scr = nullptr;
-    auto cleanup = [&]() { (void)hipFree(img); (void)hipFree(scr); };
-    if (hipMalloc(&img, nb) != hipSuccess || hipMalloc(&scr, sizeof(uint32_t) * 3 * 65536) != hipSuccess) {
-        cleanup();
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
-    if (hipMemcpy(img, host_img, nb, hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(MI_ERR_HIP, "upload failed"); }
-    rc = mi_histogram_device(device, nullptr, img, scr, height, width, dtype, mode, subsample, fast, mask_size, counts);
-    cleanup();
-    return rc;
+    if ((rc = tmp.upload(&img, host_img, nb)) || (rc = tmp.alloc(&scr, sizeof(uint32_t) * 3 * 65536))) return rc;
+    return mi_histogram_device(device, nullptr, img, scr, height, width, dtype, mode, subsample, fast, mask_size, counts);
 }
 
 int mi_apply_lut_device(int device, void* stream, const void* dev_src, void* dev_dst, size_t npixels,
@@ -2595,24 +2542,13 @@ int mi_cvt_color(int device, const void* host_src, void* host_dst, int height, i
     if (!host_src || !host_dst || height < 1 || width < 1) return fail(MI_ERR_INVALID, "bad argument");
     if (dtype != MI_U8)
         return fail(MI_ERR_UNSUPPORTED, "BGR <-> HSV / HLS is defined for 8-bit images only (as cv2.cvtColor: CV_8U / CV_32F)");
-    int ndev = 0;
-    int rc = mi_device_count(&ndev);
+    int rc = open_device(device);
     if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
     const size_t np = (size_t)height * width, nb = np * 3;
-    void* buf = nullptr;
-    MI_HIP(hipMalloc(&buf, nb));
-    hipError_t e = hipMemcpy(buf, host_src, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = mi_cvt_color_device(device, nullptr, buf, buf, np, dtype, code);
-        if (rc) { (void)hipFree(buf); return rc; }
-        e = hipDeviceSynchronize();
-    }
-    if (e == hipSuccess) e = hipMemcpy(host_dst, buf, nb, hipMemcpyDeviceToHost);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(MI_ERR_HIP, "mi_cvt_color: %s", hipGetErrorString(e));
-    return MI_OK;
+    DevScratch tmp(nullptr);
+    void* buf = nullptr;     // converted in place
+    if ((rc = tmp.upload(&buf, host_src, nb)) || (rc = mi_cvt_color_device(device, nullptr, buf, buf, np, dtype, code))) return rc;
+    return tmp.download(host_dst, buf, nb);
 }
 
 int mi_apply_lut(int device, const void* host_src, void* host_dst, int height, int width, int dtype,
@@ -2620,26 +2556,16 @@ int mi_apply_lut(int device, const void* host_src, void* host_dst, int height, i
     if (!host_src || !host_dst || !host_lut) return fail(MI_ERR_INVALID, "null argument");
     if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16");
     if (height < 1 || width < 1 || (nlut != 1 && nlut != 3)) return fail(MI_ERR_INVALID, "bad argument");
-    int ndev = 0;
-    int rc = mi_device_count(&ndev);
+    int rc = open_device(device);
     if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
     const size_t np = (size_t)height * width, nb = np * 3 * dtype_size(dtype);
     const size_t lb = (size_t)nlut * (dtype == MI_U8 ? 256 : 65536) * dtype_size(dtype);
+    DevScratch tmp(nullptr);
     void *src = nullptr, *dst = nullptr, *lut = nullptr;
-    auto cleanup = [&]() { (void)hipFree(src); (void)hipFree(dst); (void)hipFree(lut); };
-    if (hipMalloc(&src, nb) != hipSuccess || hipMalloc(&dst, nb) != hipSuccess || hipMalloc(&lut, lb) != hipSuccess) {
-        cleanup();
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
-    if (hipMemcpy(src, host_src, nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(lut, host_lut, lb, hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(MI_ERR_HIP, "upload failed"); }
-    rc = mi_apply_lut_device(device, nullptr, src, dst, np, dtype, lut, nlut);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "LUT kernel failed");
-    if (!rc && hipMemcpy(host_dst, dst, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
-    cleanup();
-    return rc;
+    if ((rc = tmp.upload(&src, host_src, nb)) || (rc = tmp.alloc(&dst, nb)) || (rc = tmp.upload(&lut, host_lut, lb)) ||
+        (rc = mi_apply_lut_device(device, nullptr, src, dst, np, dtype, lut, nlut)))
+        return rc;
+    return tmp.download(host_dst, dst, nb);
 }
 
 // ---------------------------------------------------------------- Vignetting / MaskNoise (kernels_prestack.hpp)
@@ -2806,17 +2732,12 @@ int mi_nlm_denoise_device(int device, const void* dev_src, void* dev_dst, int he
     if (rc) return rc;
     MI_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
-    void* dev_table = nullptr;
-    if (hipMalloc(&dev_table, sizeof(uint32_t) * (size_t)table_len) != hipSuccess) return fail(MI_ERR_NOMEM, "out of device memory");
-    hipError_t e = hipMemcpyAsync(dev_table, table, sizeof(uint32_t) * (size_t)table_len, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        nlm_launch(st, dev_src, dev_dst, height, width, dtype, (const uint32_t*)dev_table, (uint32_t)table_len, shift,
-                   template_size / 2, search_size / 2);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);     // the table is freed below
-    (void)hipFree(dev_table);
-    if (e != hipSuccess) return fail(MI_ERR_HIP, "denoise failed: %s", hipGetErrorString(e));
+    DevScratch tmp(st);
+    uint32_t* dev_table = nullptr;
+    if ((rc = tmp.upload(&dev_table, table, sizeof(uint32_t) * (size_t)table_len))) return rc;
+    nlm_launch(st, dev_src, dev_dst, height, width, dtype, dev_table, (uint32_t)table_len, shift, template_size / 2, search_size / 2);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipStreamSynchronize(st));     // synchronous by design: a failed run is reported here, the table goes with `tmp`
     return MI_OK;
 }
 
@@ -2825,23 +2746,14 @@ int mi_nlm_denoise(int device, const void* host_src, void* host_dst, int height,
     // host_src == host_dst is fine here: the frame passes through two device buffers
     int rc = nlm_check(host_src, host_dst, height, width, dtype, table, table_len, shift, template_size, search_size, true);
     if (rc) return rc;
-    int ndev = 0;
-    rc = mi_device_count(&ndev);
-    if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
+    if ((rc = open_device(device))) return rc;
     const size_t nb = (size_t)height * width * 3 * dtype_size(dtype);
+    DevScratch tmp(nullptr);
     void *src = nullptr, *dst = nullptr;
-    auto cleanup = [&]() { (void)hipFree(src); (void)hipFree(dst); };
-    if (hipMalloc(&src, nb) != hipSuccess || hipMalloc(&dst, nb) != hipSuccess) {
-        cleanup();
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
-    if (hipMemcpy(src, host_src, nb, hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(MI_ERR_HIP, "upload failed"); }
-    rc = mi_nlm_denoise_device(device, src, dst, height, width, dtype, table, table_len, shift, template_size, search_size, nullptr);
-    if (!rc && hipMemcpy(host_dst, dst, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
-    cleanup();
-    return rc;
+    if ((rc = tmp.upload(&src, host_src, nb)) || (rc = tmp.alloc(&dst, nb)) ||
+        (rc = mi_nlm_denoise_device(device, src, dst, height, width, dtype, table, table_len, shift, template_size, search_size, nullptr)))
+        return rc;
+    return tmp.download(host_dst, dst, nb);
 }
 
 // ---------------------------------------------------------------- unsharp mask (kernels_unsharp.hpp)
@@ -2876,31 +2788,21 @@ int mi_unsharp_mask(int device, const void* host_src, void* host_dst, int height
     // host_src == host_dst is fine here: the frame passes through two device buffers
     int rc = unsharp_check(host_src, host_dst, height, width, dtype, taps, ksize, amount, threshold, true);
     if (rc) return rc;
-    int ndev = 0;
-    rc = mi_device_count(&ndev);
-    if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
+    if ((rc = open_device(device))) return rc;
     const size_t nb = (size_t)height * width * 3 * dtype_size(dtype);
+    DevScratch tmp(nullptr);
     void *src = nullptr, *dst = nullptr;
-    auto cleanup = [&]() { (void)hipFree(src); (void)hipFree(dst); };
-    if (hipMalloc(&src, nb) != hipSuccess || hipMalloc(&dst, nb) != hipSuccess) {
-        cleanup();
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
-    if (hipMemcpy(src, host_src, nb, hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(MI_ERR_HIP, "upload failed"); }
-    rc = mi_unsharp_mask_device(device, nullptr, src, dst, height, width, dtype, taps, ksize, amount, threshold);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "unsharp kernel failed");
-    if (!rc && hipMemcpy(host_dst, dst, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
-    cleanup();
-    return rc;
+    if ((rc = tmp.upload(&src, host_src, nb)) || (rc = tmp.alloc(&dst, nb)) ||
+        (rc = mi_unsharp_mask_device(device, nullptr, src, dst, height, width, dtype, taps, ksize, amount, threshold)))
+        return rc;
+    return tmp.download(host_dst, dst, nb);
 }
 
 // ---------------------------------------------------------------- depth map output (kernels_depth.hpp)
 enum { WS_I32 = 0, WS_F32 = 1, WS_F64 = 2 };   // element types of the value and weight planes
 
 // out = B(v w) / B(w) (sigma > 0) or v (sigma == 0) as float32, for device planes, on `st`; waits for it (the scratch planes
-// are freed here).  vtype / wtype: the planes' element types; dev_w == nullptr: every weight is 1.  f64: the working type.
+// go with the call).  vtype / wtype: the planes' element types; dev_w == nullptr: every weight is 1.  f64: the working type.
 // first / stride: the consecutive -> global numbering of an int32 index plane (0, 1: none).
 static int ws_run(hipStream_t st, int vtype, const void* dev_v, int wtype, const void* dev_w, bool f64, int h, int w, double sigma,
                   int first, int stride, float* dev_out) {
@@ -2925,14 +2827,11 @@ static int ws_run(hipStream_t st, int vtype, const void* dev_v, int wtype, const
     const int radius = ws_gaussian_taps(sigma, taps);
     if (radius >= std::min(h, w))
         return fail(MI_ERR_INVALID, "sigma %g needs a radius of %d pixels: the plane must be larger in both directions", sigma, radius);
+    DevScratch tmp(st);
     void *P = nullptr, *Q = nullptr;
     const size_t fb = f64 ? 8 : 4;
-    if (hipMalloc(&P, np * fb) != hipSuccess || hipMalloc(&Q, np * fb) != hipSuccess) {
-        (void)hipFree(P);
-        (void)hipGetLastError();
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
-    int rc = MI_OK;
+    int rc;
+    if ((rc = tmp.alloc(&P, np * fb)) || (rc = tmp.alloc(&Q, np * fb))) return rc;
     switch (combo) {
         case WS_I32 * 100 + WS_F32 * 10 + 0:
             ws_smooth_launch<int32_t, float, float>(st, (const int32_t*)dev_v, (const float*)dev_w, h, w, radius, taps, first, stride,
@@ -2954,14 +2853,11 @@ static int ws_run(hipStream_t st, int vtype, const void* dev_v, int wtype, const
             ws_smooth_launch<double, double, double>(st, (const double*)dev_v, (const double*)dev_w, h, w, radius, taps, first, stride,
                                                      (double*)P, (double*)Q, dev_out);
             break;
-        default: rc = fail(MI_ERR_INVALID, "unsupported plane types");
+        default: return fail(MI_ERR_INVALID, "unsupported plane types");
     }
-    hipError_t e = rc ? hipSuccess : hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(P);
-    (void)hipFree(Q);
-    if (!rc && e != hipSuccess) rc = fail(MI_ERR_HIP, "weighted smoothing failed: %s", hipGetErrorString(e));
-    return rc;
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipStreamSynchronize(st));
+    return MI_OK;
 }
 
 int mi_stack_depth_map_device(mi_stack_t* s, double sigma, void* dev_out) {
@@ -2989,12 +2885,10 @@ int mi_stack_depth_map(mi_stack_t* s, double sigma, void* host_out) {
     if (!host_out) return fail(MI_ERR_INVALID, "null output");
     MI_HIP(hipSetDevice(s->p.device));
     const size_t nb = (size_t)s->p.height * s->p.width * sizeof(float);
+    DevScratch tmp(s->stream);
     void* out = nullptr;
-    if (hipMalloc(&out, nb) != hipSuccess) { (void)hipGetLastError(); return fail(MI_ERR_NOMEM, "out of device memory"); }
-    rc = mi_stack_depth_map_device(s, sigma, out);
-    if (!rc && hipMemcpy(host_out, out, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
-    (void)hipFree(out);
-    return rc;
+    if ((rc = tmp.alloc(&out, nb)) || (rc = mi_stack_depth_map_device(s, sigma, out))) return rc;
+    return tmp.download(host_out, out, nb);
 }
 
 int mi_weighted_smooth(int device, const void* host_value, const void* host_weight, int height, int width, int value_is_int32,
@@ -3002,30 +2896,18 @@ int mi_weighted_smooth(int device, const void* host_value, const void* host_weig
     if (!host_value || !host_weight || !host_out) return fail(MI_ERR_INVALID, "null argument");
     if (height < 1 || width < 1) return fail(MI_ERR_INVALID, "bad plane size");
     if (float_type != MI_F32 && float_type != MI_F64) return fail(MI_ERR_INVALID, "float_type must be MI_F32 or MI_F64");
-    int ndev = 0;
-    int rc = mi_device_count(&ndev);
+    int rc = open_device(device);
     if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
     const bool f64 = float_type == MI_F64;
     const size_t np = (size_t)height * width, fb = f64 ? 8 : 4, vb = value_is_int32 ? 4 : fb;
-    void *v = nullptr, *w = nullptr, *out = nullptr;
-    auto cleanup = [&]() { (void)hipFree(v); (void)hipFree(w); (void)hipFree(out); };
-    if (hipMalloc(&v, np * vb) != hipSuccess || hipMalloc(&w, np * fb) != hipSuccess || hipMalloc(&out, np * 4) != hipSuccess) {
-        cleanup();
-        (void)hipGetLastError();
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
-    if (hipMemcpy(v, host_value, np * vb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(w, host_weight, np * fb, hipMemcpyHostToDevice) != hipSuccess) {
-        cleanup();
-        return fail(MI_ERR_HIP, "upload failed");
-    }
+    DevScratch tmp(nullptr);
+    void *v = nullptr, *w = nullptr;
+    float* out = nullptr;
     const int ft = f64 ? WS_F64 : WS_F32;
-    rc = ws_run(nullptr, value_is_int32 ? WS_I32 : ft, v, ft, w, f64, height, width, sigma, 0, 1, (float*)out);
-    if (!rc && hipMemcpy(host_out, out, np * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
-    cleanup();
-    return rc;
+    if ((rc = tmp.upload(&v, host_value, np * vb)) || (rc = tmp.upload(&w, host_weight, np * fb)) || (rc = tmp.alloc(&out, np * 4)) ||
+        (rc = ws_run(nullptr, value_is_int32 ? WS_I32 : ft, v, ft, w, f64, height, width, sigma, 0, 1, out)))
+        return rc;
+    return tmp.download(host_out, out, np * 4);
 }
 
 // ---------------------------------------------------------------- stereo views (kernels_stereo.hpp)
@@ -3067,29 +2949,14 @@ int mi_stereo_view(int device, const void* host_img, const void* host_depth, voi
     // host_img == host_out is fine here: the frame passes through two device buffers
     int rc = stereo_check(host_img, host_depth, host_out, height, width, dtype, n_frames, shift, pivot, near_first, true);
     if (rc) return rc;
-    int ndev = 0;
-    rc = mi_device_count(&ndev);
-    if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
+    if ((rc = open_device(device))) return rc;
     const size_t np = (size_t)height * width, nb = np * 3 * dtype_size(dtype);
+    DevScratch tmp(nullptr);
     void *img = nullptr, *depth = nullptr, *out = nullptr;
-    auto cleanup = [&]() { (void)hipFree(img); (void)hipFree(depth); (void)hipFree(out); };
-    if (hipMalloc(&img, nb) != hipSuccess || hipMalloc(&depth, np * 4) != hipSuccess || hipMalloc(&out, nb) != hipSuccess) {
-        cleanup();
-        (void)hipGetLastError();
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
-    if (hipMemcpy(img, host_img, nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(depth, host_depth, np * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        cleanup();
-        return fail(MI_ERR_HIP, "upload failed");
-    }
-    rc = mi_stereo_view_device(device, nullptr, img, depth, out, height, width, dtype, n_frames, shift, pivot, near_first);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "stereo view kernel failed");
-    if (!rc && hipMemcpy(host_out, out, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
-    cleanup();
-    return rc;
+    if ((rc = tmp.upload(&img, host_img, nb)) || (rc = tmp.upload(&depth, host_depth, np * 4)) || (rc = tmp.alloc(&out, nb)) ||
+        (rc = mi_stereo_view_device(device, nullptr, img, depth, out, height, width, dtype, n_frames, shift, pivot, near_first)))
+        return rc;
+    return tmp.download(host_out, out, nb);
 }
 
 int mi_stereo_compose_device(int device, void* stream, const void* dev_left, const void* dev_right, void* dev_out, int height, int width,
@@ -3183,9 +3050,7 @@ int mi_brush_stroke(int device, void* host_master, const void* host_source, int 
     int rc = brush_stroke_check(host_master, host_source, height, width, dtype, host_table, radius, host_stamps, n_stamps, opacity);
     if (rc) return rc;
     int ndev = 0;
-    rc = mi_device_count(&ndev);
-    if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
+    if ((rc = visible_devices(&ndev))) return rc;
     int32_t box[4];
     brush_area(host_stamps, n_stamps, radius, height, width, box);
     if (area) memcpy(area, box, sizeof(box));
@@ -3196,28 +3061,17 @@ int mi_brush_stroke(int device, void* host_master, const void* host_source, int 
     }
     MI_HIP(hipSetDevice(device));
     const size_t side = 2 * (size_t)radius + 1, tb = side * side * sizeof(double), sb = (size_t)n_stamps * 2 * sizeof(int32_t);
-    void *master = nullptr, *source = nullptr, *table = nullptr, *stamps = nullptr, *mask = nullptr;
-    auto cleanup = [&]() { (void)hipFree(master); (void)hipFree(source); (void)hipFree(table); (void)hipFree(stamps); (void)hipFree(mask); };
-    if (hipMalloc(&master, nb) != hipSuccess || hipMalloc(&source, nb) != hipSuccess || hipMalloc(&table, tb) != hipSuccess ||
-        hipMalloc(&stamps, sb) != hipSuccess || (host_mask && hipMalloc(&mask, np * sizeof(double)) != hipSuccess)) {
-        cleanup();
-        (void)hipGetLastError();
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
-    if (hipMemcpy(master, host_master, nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(source, host_source, nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(table, host_table, tb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(stamps, host_stamps, sb, hipMemcpyHostToDevice) != hipSuccess) {
-        cleanup();
-        return fail(MI_ERR_HIP, "upload failed");
-    }
-    rc = mi_brush_stroke_device(device, nullptr, master, source, height, width, dtype, (const double*)table, radius, (const int32_t*)stamps,
-                                n_stamps, box, opacity, (double*)mask);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "brush stroke kernel failed");
-    if (!rc && hipMemcpy(host_master, master, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
-    if (!rc && host_mask && hipMemcpy(host_mask, mask, np * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(MI_ERR_HIP, "download failed");
-    cleanup();
+    DevScratch tmp(nullptr);
+    void *master = nullptr, *source = nullptr;
+    double *table = nullptr, *mask = nullptr;
+    int32_t* stamps = nullptr;
+    if ((rc = tmp.upload(&master, host_master, nb)) || (rc = tmp.upload(&source, host_source, nb)) ||
+        (rc = tmp.upload(&table, host_table, tb)) || (rc = tmp.upload(&stamps, host_stamps, sb)) ||
+        (host_mask && (rc = tmp.alloc(&mask, np * sizeof(double)))) ||
+        (rc = mi_brush_stroke_device(device, nullptr, master, source, height, width, dtype, table, radius, stamps, n_stamps, box, opacity, mask)))
+        return rc;
+    rc = tmp.download(host_master, master, nb);
+    if (!rc && host_mask) rc = tmp.download(host_mask, mask, np * sizeof(double));
     return rc;
 }
 
@@ -3238,30 +3092,16 @@ int mi_blend_mask(int device, void* host_master, const void* host_source, const 
     int rc = brush_frame_check(host_master, host_source, height, width, dtype, opacity);
     if (rc) return rc;
     if (!host_mask) return fail(MI_ERR_INVALID, "null argument");
-    int ndev = 0;
-    rc = mi_device_count(&ndev);
-    if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
+    if ((rc = open_device(device))) return rc;
     const size_t np = (size_t)height * width, nb = np * 3 * dtype_size(dtype);
-    void *master = nullptr, *source = nullptr, *mask = nullptr;
-    auto cleanup = [&]() { (void)hipFree(master); (void)hipFree(source); (void)hipFree(mask); };
-    if (hipMalloc(&master, nb) != hipSuccess || hipMalloc(&source, nb) != hipSuccess || hipMalloc(&mask, np * sizeof(double)) != hipSuccess) {
-        cleanup();
-        (void)hipGetLastError();
-        return fail(MI_ERR_NOMEM, "out of device memory");
-    }
-    if (hipMemcpy(master, host_master, nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(source, host_source, nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(mask, host_mask, np * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        cleanup();
-        return fail(MI_ERR_HIP, "upload failed");
-    }
-    rc = mi_blend_mask_device(device, nullptr, master, source, (const double*)mask, height, width, dtype, opacity);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "blend kernel failed");
-    if (!rc && hipMemcpy(host_master, master, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
-    cleanup();
-    return rc;
+    DevScratch tmp(nullptr);
+    void *master = nullptr, *source = nullptr;
+    double* mask = nullptr;
+    if ((rc = tmp.upload(&master, host_master, nb)) || (rc = tmp.upload(&source, host_source, nb)) ||
+        (rc = tmp.upload(&mask, host_mask, np * sizeof(double))) ||
+        (rc = mi_blend_mask_device(device, nullptr, master, source, mask, height, width, dtype, opacity)))
+        return rc;
+    return tmp.download(host_master, master, nb);
 }
 
 // ---------------------------------------------------------------- depth-selected composite (kernels_composite.hpp)
@@ -3311,34 +3151,17 @@ int mi_depth_composite(int device, const void* const* frame_ptrs, int first, int
                        void* host_out, int height, int width, int dtype, int interp) {
     int rc = composite_check(frame_ptrs, first, count, n_frames, host_depth, host_out, height, width, dtype, interp, false);
     if (rc) return rc;
-    int ndev = 0;
-    rc = mi_device_count(&ndev);
-    if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
-    MI_HIP(hipSetDevice(device));
+    if ((rc = open_device(device))) return rc;
     const size_t np = (size_t)height * width, nb = np * 3 * dtype_size(dtype);
-    std::vector<void*> bufs((size_t)count + 2, nullptr);       // the chunk's frames, the depth plane, the output
-    auto cleanup = [&]() { for (void* b : bufs) (void)hipFree(b); };
-    for (size_t i = 0; i < bufs.size(); ++i)
-        if (hipMalloc(&bufs[i], i == (size_t)count ? np * 4 : nb) != hipSuccess) {
-            cleanup();
-            (void)hipGetLastError();
-            return fail(MI_ERR_NOMEM, "out of device memory");
-        }
-    void *depth = bufs[(size_t)count], *out = bufs[(size_t)count + 1];
-    bool ok = hipMemcpy(depth, host_depth, np * 4, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(out, host_out, nb, hipMemcpyHostToDevice) == hipSuccess;     // pixels of other chunks keep what they hold
-    for (int i = 0; ok && i < count; ++i) ok = hipMemcpy(bufs[(size_t)i], frame_ptrs[i], nb, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        cleanup();
-        return fail(MI_ERR_HIP, "upload failed");
-    }
-    rc = mi_depth_composite_device(device, nullptr, (const void* const*)bufs.data(), first, count, n_frames, depth, out, height, width,
-                                   dtype, interp);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(MI_ERR_HIP, "depth composite kernel failed");
-    if (!rc && hipMemcpy(host_out, out, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
-    cleanup();
-    return rc;
+    DevScratch tmp(nullptr);
+    void *depth = nullptr, *out = nullptr;
+    std::vector<void*> frames((size_t)count, nullptr);
+    if ((rc = tmp.upload(&depth, host_depth, np * 4)) || (rc = tmp.upload(&out, host_out, nb))) return rc;   // `out`: pixels of other chunks keep what they hold
+    for (int i = 0; i < count; ++i)
+        if ((rc = tmp.upload(&frames[(size_t)i], frame_ptrs[i], nb))) return rc;
+    if ((rc = mi_depth_composite_device(device, nullptr, frames.data(), first, count, n_frames, depth, out, height, width, dtype, interp)))
+        return rc;
+    return tmp.download(host_out, out, nb);
 }
 
 int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,

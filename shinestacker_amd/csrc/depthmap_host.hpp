@@ -326,35 +326,23 @@ int dmap_finish_t(mi_dmap* d) {
 }
 
 // The stacker's steps one at a time on host planes (the reference's public methods, depth_map.py:28-62): same kernels as the
-// fused path, scratch planes allocated per call.
+// fused path, scratch planes allocated per call (a DevScratch on the handle's stream).
 template <typename F>
 int dmap_planes_t(mi_dmap* d, int stage, const void* host_in, int n, void* host_out) {
     const int h = d->p.height, w = d->p.width;
     const size_t np = (size_t)h * w;
     hipStream_t st = d->stream;
     const bool smoothed_w = d->p.smooth_size > 0 || sizeof(F) == 4;   // type of the planes the focus map works on (W)
-    struct Scratch {   // freed on every way out, the early returns of MI_HIP included
-        hipStream_t st;
-        std::vector<void*> v;
-        ~Scratch() {
-            (void)hipStreamSynchronize(st);
-            for (void* q : v) (void)hipFree(q);
-        }
-    } tmp{st, {}};
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* q = nullptr;
-        if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) return nullptr;
-        tmp.v.push_back(q);
-        return q;
-    };
-    auto cleanup = [&](int rc) { return rc; };
+    DevScratch tmp(st);
+    int rc;
     const DmTapsT<F>& taps = [&]() -> const DmTapsT<F>& {
         if constexpr (sizeof(F) == 4) return d->taps; else return d->tapsd;
     }();
     if (stage == 0 || stage == 1) {            // get_sobel_map / get_laplacian_map: gray planes (F) -> energies (F)
-        F* in = (F*)dalloc(np * sizeof(F));
-        F *tB = (F*)dalloc(np * sizeof(F)), *tC = (F*)dalloc(np * sizeof(F)), *en = (F*)dalloc(np * sizeof(F)), *gmax = (F*)dalloc(sizeof(F));
-        if (!in || !tB || !tC || !en || !gmax) return cleanup(fail(MI_ERR_NOMEM, "out of device memory"));
+        F *in = nullptr, *tB = nullptr, *tC = nullptr, *en = nullptr, *gmax = nullptr;
+        if ((rc = tmp.alloc(&in, np * sizeof(F))) || (rc = tmp.alloc(&tB, np * sizeof(F))) || (rc = tmp.alloc(&tC, np * sizeof(F))) ||
+            (rc = tmp.alloc(&en, np * sizeof(F))) || (rc = tmp.alloc(&gmax, sizeof(F))))
+            return rc;
         for (int i = 0; i < n; ++i) {
             MI_HIP(hipMemcpyAsync(in, (const F*)host_in + (size_t)i * np, np * sizeof(F), hipMemcpyHostToDevice, st));
             MI_HIP(hipMemsetAsync(gmax, 0, sizeof(F), st));
@@ -370,19 +358,19 @@ int dmap_planes_t(mi_dmap* d, int stage, const void* host_in, int n, void* host_
                 else
                     hipLaunchKernelGGL((dm_laplacian<0, F>), dm_grid2(h, w), dim3(256), 0, st, (const F*)tC, h, w, en, gmax, d->k2);
             }
-            MI_HIP(hipGetLastError());
-            MI_HIP(hipMemcpyAsync((F*)host_out + (size_t)i * np, en, np * sizeof(F), hipMemcpyDeviceToHost, st));
-            MI_HIP(hipStreamSynchronize(st));
+            if ((rc = tmp.download((F*)host_out + (size_t)i * np, en, np * sizeof(F)))) return rc;
         }
-        return cleanup(MI_OK);
+        return MI_OK;
     }
     if (stage == 2) {                          // smooth_energy: planes (F) -> float32 planes (cv2.bilateralFilter on float32)
-        if (d->p.smooth_size <= 0) return cleanup(fail(MI_ERR_STATE, "smooth_size <= 0: nothing to smooth"));
+        if (d->p.smooth_size <= 0) return fail(MI_ERR_STATE, "smooth_size <= 0: nothing to smooth");
         static const uint32_t mm_init[2] = {0x7f800000u, 0u};
         const dim3 gnorm((unsigned)std::min<size_t>((np + 255) / 256, 4096));
-        F* in = (F*)dalloc(np * sizeof(F));
-        float *f32 = (float*)dalloc(np * 4), *out = (float*)dalloc(np * 4), *acc = (float*)dalloc(np * 4), *sc = (float*)dalloc(8 * 4);
-        if (!in || !f32 || !out || !acc || !sc) return cleanup(fail(MI_ERR_NOMEM, "out of device memory"));
+        F* in = nullptr;
+        float *f32 = nullptr, *out = nullptr, *acc = nullptr, *sc = nullptr;
+        if ((rc = tmp.alloc(&in, np * sizeof(F))) || (rc = tmp.alloc(&f32, np * 4)) || (rc = tmp.alloc(&out, np * 4)) ||
+            (rc = tmp.alloc(&acc, np * 4)) || (rc = tmp.alloc(&sc, 8 * 4)))
+            return rc;
         MI_HIP(hipMemsetAsync(sc, 0, 8 * 4, st));
         for (int i = 0; i < n; ++i) {
             MI_HIP(hipMemcpyAsync(in, (const F*)host_in + (size_t)i * np, np * sizeof(F), hipMemcpyHostToDevice, st));
@@ -397,19 +385,18 @@ int dmap_planes_t(mi_dmap* d, int stage, const void* host_in, int n, void* host_
             hipLaunchKernelGGL(dm_bilateral_lut, dim3(1), dim3(1024), 0, st, (const float*)sc, d->color_coeff, d->lut, sc + 2);
             DmBilateral a{src, out, h, w, d->radius, d->ntaps, d->disc, d->lut, sc + 2, acc, 0, 1, nullptr};
             dm_bilateral_launch(st, a);
-            MI_HIP(hipGetLastError());
-            MI_HIP(hipMemcpyAsync((float*)host_out + (size_t)i * np, out, np * 4, hipMemcpyDeviceToHost, st));
-            MI_HIP(hipStreamSynchronize(st));
+            if ((rc = tmp.download((float*)host_out + (size_t)i * np, out, np * 4))) return rc;
         }
-        return cleanup(MI_OK);
+        return MI_OK;
     }
     if (stage == 3) {                          // get_focus_map: n energy planes -> n weight planes, same type (W)
         auto run = [&](auto zero) -> int {
             using W = decltype(zero);
-            W* e = (W*)dalloc(np * sizeof(W) * (size_t)n);
-            W *tot = (W*)dalloc(np * sizeof(W)), *mx = (W*)dalloc(np * sizeof(W)), *wgt = (W*)dalloc(np * sizeof(W));
-            if (!e || !tot || !mx || !wgt) return fail(MI_ERR_NOMEM, "out of device memory");
-            MI_HIP(hipMemcpyAsync(e, host_in, np * sizeof(W) * (size_t)n, hipMemcpyHostToDevice, st));
+            W *e = nullptr, *tot = nullptr, *mx = nullptr, *wgt = nullptr;
+            int r;
+            if ((r = tmp.upload(&e, host_in, np * sizeof(W) * (size_t)n)) || (r = tmp.alloc(&tot, np * sizeof(W))) ||
+                (r = tmp.alloc(&mx, np * sizeof(W))) || (r = tmp.alloc(&wgt, np * sizeof(W))))
+                return r;
             const bool avg = d->p.map_type == MI_DM_MAP_AVERAGE;
             for (int i = 0; i < n; ++i)
                 hipLaunchKernelGGL((dm_accumulate<W>), dm_grid1(np), dim3(256), 0, st, (const W*)(e + (size_t)i * np), np, avg ? tot : mx,
@@ -421,15 +408,13 @@ int dmap_planes_t(mi_dmap* d, int stage, const void* host_in, int n, void* host_
             for (int i = 0; i < n; ++i) {
                 hipLaunchKernelGGL((dm_weight<W>), dm_grid1(np), dim3(256), 0, st, (const W*)(e + (size_t)i * np), (const W*)tot, np,
                                    avg ? 1 : 0, wgt);
-                MI_HIP(hipGetLastError());
-                MI_HIP(hipMemcpyAsync((W*)host_out + (size_t)i * np, wgt, np * sizeof(W), hipMemcpyDeviceToHost, st));
-                MI_HIP(hipStreamSynchronize(st));
+                if ((r = tmp.download((W*)host_out + (size_t)i * np, wgt, np * sizeof(W)))) return r;
             }
             return MI_OK;
         };
-        return cleanup(smoothed_w ? run(0.0f) : run(F(0)));
+        return smoothed_w ? run(0.0f) : run(F(0));
     }
-    return cleanup(fail(MI_ERR_INVALID, "stage must be 0 .. 3"));
+    return fail(MI_ERR_INVALID, "stage must be 0 .. 3");
 }
 
 // The depth map (kernels_depth.hpp): one pass over the N planes finish left in en[i] (type W), then the weighted smoothing
@@ -439,25 +424,22 @@ int dmap_depth_map_t(mi_dmap* d, double sigma, float* dev_out) {
     const int h = d->p.height, w = d->p.width;
     const size_t np = (size_t)h * w;
     hipStream_t st = d->stream;
-    struct Scratch {
-        void *tab = nullptr, *D = nullptr;
-        ~Scratch() { (void)hipFree(tab); (void)hipFree(D); }
-    } tmp;
-    MI_HIP(hipMalloc(&tmp.tab, sizeof(void*) * (size_t)d->n));
-    MI_HIP(hipMemcpyAsync(tmp.tab, d->en.data(), sizeof(void*) * (size_t)d->n, hipMemcpyHostToDevice, st));
+    DevScratch tmp(st);
+    const W** tab = nullptr;
+    W* D = nullptr;
+    int rc;
+    if ((rc = tmp.upload(&tab, d->en.data(), sizeof(void*) * (size_t)d->n))) return rc;
     if (sigma == 0.0) {
-        hipLaunchKernelGGL((dm_depth_index<W, float>), dm_grid1(np), dim3(256), 0, st, (const W* const*)tmp.tab, d->n, (const W*)d->tot, np,
-                           dev_out);
+        hipLaunchKernelGGL((dm_depth_index<W, float>), dm_grid1(np), dim3(256), 0, st, tab, d->n, (const W*)d->tot, np, dev_out);
         MI_HIP(hipGetLastError());
         MI_HIP(hipStreamSynchronize(st));
         return MI_OK;
     }
-    MI_HIP(hipMalloc(&tmp.D, np * sizeof(W)));
-    hipLaunchKernelGGL((dm_depth_index<W, W>), dm_grid1(np), dim3(256), 0, st, (const W* const*)tmp.tab, d->n, (const W*)d->tot, np,
-                       (W*)tmp.D);
+    if ((rc = tmp.alloc(&D, np * sizeof(W)))) return rc;
+    hipLaunchKernelGGL((dm_depth_index<W, W>), dm_grid1(np), dim3(256), 0, st, tab, d->n, (const W*)d->tot, np, D);
     MI_HIP(hipGetLastError());
     const int wt = sizeof(W) == 8 ? WS_F64 : WS_F32;
-    return ws_run(st, wt, tmp.D, wt, d->p.map_type == MI_DM_MAP_AVERAGE ? d->tot : nullptr, sizeof(W) == 8, h, w, sigma, 0, 1, dev_out);
+    return ws_run(st, wt, D, wt, d->p.map_type == MI_DM_MAP_AVERAGE ? d->tot : nullptr, sizeof(W) == 8, h, w, sigma, 0, 1, dev_out);
 }
 
 }  // namespace
@@ -511,9 +493,8 @@ int mi_dmap_create(mi_dmap_t** out, const mi_dmap_params_t* params) {
     if (p.levels < 1 || p.levels > 16) return fail(MI_ERR_INVALID, "levels must be in [1, 16]");
     if (p.map_type == MI_DM_MAP_MAX && !(p.temperature != 0.f)) return fail(MI_ERR_INVALID, "temperature must not be 0");
     int ndev = 0;
-    int rc = mi_device_count(&ndev);
+    int rc = visible_devices(&ndev);
     if (rc) return rc;
-    if (ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible");
     if (p.device < 0 || p.device >= ndev) return fail(MI_ERR_INVALID, "bad device %d", p.device);
     MI_HIP(hipSetDevice(p.device));
     mi_dmap* d = new (std::nothrow) mi_dmap();
@@ -713,12 +694,11 @@ int mi_dmap_depth_map(mi_dmap_t* d, double sigma, void* host_out) {
     if (!d->finished) return fail(MI_ERR_STATE, "the depth map exists after finish");
     MI_HIP(hipSetDevice(d->p.device));
     const size_t nb = (size_t)d->p.height * d->p.width * sizeof(float);
+    DevScratch tmp(d->stream);
     void* out = nullptr;
-    if (hipMalloc(&out, nb) != hipSuccess) { (void)hipGetLastError(); return fail(MI_ERR_NOMEM, "out of device memory"); }
-    int rc = mi_dmap_depth_map_device(d, sigma, out);
-    if (!rc && hipMemcpy(host_out, out, nb, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(MI_ERR_HIP, "download failed");
-    (void)hipFree(out);
-    return rc;
+    int rc;
+    if ((rc = tmp.alloc(&out, nb)) || (rc = mi_dmap_depth_map_device(d, sigma, out))) return rc;
+    return tmp.download(host_out, out, nb);
 }
 
 int mi_dmap_finish(mi_dmap_t* d, void* host_out, size_t row_stride_bytes) {
