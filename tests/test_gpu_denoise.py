@@ -24,7 +24,11 @@ def gold(hiplib):
 def test_denoise_equals_every_recorded_case(gold):
     """both dtypes; odd and even frame sizes; frames smaller than the 32 x 32 tile (20 x 24, 3 x 2) and narrower than the
     search window (40 x 7: reflect-101 applied more than once); template 1 / 3 / 5 / 7 / 11 and the even 4 / 10; search
-    5 / 21 and the even 6 / 20; h 1 / 3 / 10 and a non-integral one"""
+    5 / 21 and the even 6 / 20; h 1 / 3 / 10 and a non-integral one.  What the fixtures reach of the kernel: template half
+    sizes 0, 1, 2, 3 and 5 (not 4; on uint16, 2 only on the 20 x 24 partial tile), search half sizes 2, 3 and 10, the table in LDS for every
+    uint8 case and read from global memory only for uint16 at h 10.  test_gpu_poststack_edges.py runs the rest: every template
+    half size, search half sizes 0, 1, 5 and 10, both table placements for both dtypes, one-row / one-column / one-pixel
+    frames, frames on the tile grid, saturated frames."""
     from shinestacker_amd import denoise
     z, meta = gold
     seen = set()
