@@ -632,6 +632,12 @@ template <typename T>
 int warp_launch(int device, hipStream_t st, const void* src, void* side, void* out, uint8_t* valid, int h, int w,
                 const AffineArgs& a, bool blur, const GaussArgs& g, const PerspArgs* persp) {
     bool tiles_marked = false;
+    if (sizeof(T) == 1 && (size_t)h * w == 1) {   // three bytes: no 4-byte tap load fits (warp_one_pixel_u8); its blur is itself
+        hipLaunchKernelGGL(warp_one_pixel_u8, dim3(1), dim3(1), 0, st, (const uint8_t*)src, (uint8_t*)out, valid, a,
+                           persp ? *persp : PerspArgs{}, persp != nullptr);
+        MI_HIP(hipGetLastError());
+        return MI_OK;
+    }
     if (persp) {
         const dim3 blk(64, 4), grid(cdiv(w, 64), cdiv(h, 4));
         hipLaunchKernelGGL((warp_perspective_kernel<T>), grid, blk, 0, st, (const T*)src, (T*)out, valid, a, *persp);

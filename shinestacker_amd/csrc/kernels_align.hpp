@@ -51,7 +51,8 @@ __global__ __launch_bounds__(256) void warp_coord_tables(AffineArgs a, int* __re
 
 // one destination pixel: the 3 channel values and the mask bit
 // (X, Y): the source position in 1/32 pixel
-template <typename T>
+// BYTES: 8-bit taps come in byte by byte (warp_one_pixel_u8 below: an image of three bytes holds no 4-byte load)
+template <typename T, bool BYTES = false>
 __device__ __forceinline__ void warp_pixel_xy(const T* __restrict__ src, const AffineArgs& a, int X, int Y,
                                               int out[3], int& ok) {
     const int h = a.h, w = a.w;
@@ -76,7 +77,9 @@ __device__ __forceinline__ void warp_pixel_xy(const T* __restrict__ src, const A
     const size_t last = (size_t)h * w - 1;
     auto tap = [&](int yy, int xx, int t[3]) {
         const size_t pi = (size_t)yy * w + xx;
-        if constexpr (sizeof(T) == 1) {
+        if constexpr (sizeof(T) == 1 && BYTES) {
+            t[0] = src[pi * 3]; t[1] = src[pi * 3 + 1]; t[2] = src[pi * 3 + 2];
+        } else if constexpr (sizeof(T) == 1) {
             uint32_t u;
             if (pi != last) {
                 __builtin_memcpy(&u, src + pi * 3, 4);
@@ -185,11 +188,8 @@ struct PerspArgs {
     int bw0;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void warp_perspective_kernel(const T* __restrict__ src, T* __restrict__ dst,
-                                                               uint8_t* __restrict__ valid, AffineArgs a, PerspArgs pa) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= a.w || y >= a.h) return;
+// the source position of destination pixel (x, y) in 1/32 pixel
+__device__ __forceinline__ void persp_xy(const PerspArgs& pa, int x, int y, int& X, int& Y) {
     const int bx = (x / pa.bw0) * pa.bw0, x1 = x - bx;
     const double* M = pa.iM;
     const double X0 = M[0] * bx + M[1] * y + M[2], Y0 = M[3] * bx + M[4] * y + M[5], W0 = M[6] * bx + M[7] * y + M[8];
@@ -197,11 +197,43 @@ __global__ __launch_bounds__(256) void warp_perspective_kernel(const T* __restri
     W = W != 0.0 ? 32.0 / W : 0.0;
     const double fX = fmax(-2147483648.0, fmin(2147483647.0, (X0 + M[0] * x1) * W));
     const double fY = fmax(-2147483648.0, fmin(2147483647.0, (Y0 + M[3] * x1) * W));
+    X = cv_round_d(fX);
+    Y = cv_round_d(fY);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void warp_perspective_kernel(const T* __restrict__ src, T* __restrict__ dst,
+                                                               uint8_t* __restrict__ valid, AffineArgs a, PerspArgs pa) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= a.w || y >= a.h) return;
+    int X, Y;
+    persp_xy(pa, x, y, X, Y);
     int v[3], ok;
-    warp_pixel_xy<T>(src, a, cv_round_d(fX), cv_round_d(fY), v, ok);
+    warp_pixel_xy<T>(src, a, X, Y, v, ok);
     const size_t px = (size_t)y * a.w + x;
     dst[px * 3 + 0] = (T)v[0]; dst[px * 3 + 1] = (T)v[1]; dst[px * 3 + 2] = (T)v[2];
     if (valid) valid[px] = (uint8_t)ok;
+}
+
+// ---- A one-pixel 8-bit image is three bytes.  The 8-bit taps of every kernel here are 4-byte loads, the image's last pixel
+// read one byte early so that the load ends with the buffer -- which for this image is one byte in FRONT of the buffer.  It gets
+// a kernel of its own (one thread, byte loads, the coordinate terms as warp_coord_tables / persp_xy state them for x = y = 0)
+// instead of a branch at every tap of the others.  There is no blur pass behind it: the taps sum to 1.0 and reflect-101 of a
+// single sample is that sample, so the blurred pixel is the pixel.
+__global__ void warp_one_pixel_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint8_t* __restrict__ valid,
+                                  AffineArgs a, PerspArgs pa, bool persp) {
+    int X, Y;
+    if (persp) {
+        persp_xy(pa, 0, 0, X, Y);
+    } else {
+        const int i = 0;
+        X = ((cv_round_d((a.iM[1] * i + a.iM[2]) * 1024.0) + 16) + cv_round_d(a.iM[0] * i * 1024.0)) >> 5;
+        Y = ((cv_round_d((a.iM[4] * i + a.iM[5]) * 1024.0) + 16) + cv_round_d(a.iM[3] * i * 1024.0)) >> 5;
+    }
+    int v[3], ok;
+    warp_pixel_xy<uint8_t, true>(src, a, X, Y, v, ok);
+    dst[0] = (uint8_t)v[0]; dst[1] = (uint8_t)v[1]; dst[2] = (uint8_t)v[2];
+    if (valid) valid[0] = (uint8_t)ok;
 }
 
 // ---- The warp kernel.  A per-pixel gather spends its time in the texture-address unit (four unaligned 4-byte
