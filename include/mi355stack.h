@@ -338,6 +338,18 @@ MI_API int mi_aligner_set_phase_init(mi_aligner_t al, int enable);
  * out3 = (dx, dy, response) with mov(x + dx, y + dy) ~ ref(x, y). */
 MI_API int mi_phase_correlate_device(int device, void* stream, const void* dev_ref, const void* dev_mov, int height, int width,
                               double* out3);
+/* Read-only tap (tests): the same launches as mi_phase_correlate_device up to one stage, and that stage's plane to host
+ * memory as P x Q complex float32 (re, im; P, Q = height, width rounded up to powers of two).  Same argument checks;
+ * `what` out of range is MI_ERR_INVALID. */
+enum {
+    MI_PC_TAP_WINDOWED_MOV = 0, /* mov times the Hann window, zero-padded to P x Q                                    */
+    MI_PC_TAP_SPECTRUM_REF = 1, /* forward DFT of the windowed ref                                                    */
+    MI_PC_TAP_SPECTRUM_MOV = 2, /* forward DFT of the windowed mov                                                    */
+    MI_PC_TAP_CROSS_POWER = 3,  /* R = Mov conj(Ref) / |Mov conj(Ref)|, 0 where the magnitude is not above 1e-20      */
+    MI_PC_TAP_SURFACE = 4       /* un-normalised inverse DFT of R: the correlation surface, imaginary part included   */
+};
+MI_API int mi_phase_correlate_tap_device(int device, void* stream, const void* dev_ref, const void* dev_mov, int height,
+                                  int width, int what, void* host_out);
 MI_API int mi_aligner_destroy(mi_aligner_t al);
 MI_API int mi_aligner_set_reference(mi_aligner_t al, void* stream, const void* dev_ref);
 MI_API int mi_aligner_estimate(mi_aligner_t al, void* stream, const void* dev_mov, int max_iters, double eps,

@@ -64,6 +64,7 @@ class DepthMapParams(C.Structure):
 DM_MAP_AVERAGE, DM_MAP_MAX = 0, 1
 DM_ENERGY_LAPLACIAN, DM_ENERGY_SOBEL = 0, 1
 DM_TAP_ENERGY_RAW, DM_TAP_ENERGY_IN, DM_TAP_TOTAL, DM_TAP_MAX = range(4)
+PC_TAP_WINDOWED_MOV, PC_TAP_SPECTRUM_REF, PC_TAP_SPECTRUM_MOV, PC_TAP_CROSS_POWER, PC_TAP_SURFACE = range(5)
 
 # name -> (restype, argtypes); also the list the symbol-export test walks
 SIGNATURES = {
@@ -149,6 +150,8 @@ SIGNATURES = {
                                                        C.POINTER(C.c_int)]),
     "mi_phase_correlate_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                             C.POINTER(C.c_double)]),
+    "mi_phase_correlate_tap_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p]),
     "mi_aligner_destroy": (C.c_int, [C.c_void_p]),
     "mi_aligner_set_reference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_aligner_estimate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
@@ -806,6 +809,25 @@ def phase_correlate(ref, mov, device=0):
     finally:
         buf.free()
     return out[0], out[1], out[2]
+
+
+def phase_tap(ref, mov, what, device=0):
+    """mi_phase_correlate_tap_device (tests): stage `what` (PC_TAP_*) of phase_correlate(ref, mov) as P x Q complex64"""
+    require_device()
+    a, b = np.ascontiguousarray(ref, np.float32), np.ascontiguousarray(mov, np.float32)
+    if a.ndim != 2 or a.shape != b.shape:
+        raise ValueError("phase_tap expects two H x W planes of the same shape")
+    P, Q = (1 << max(int(n) - 1, 0).bit_length() for n in a.shape)
+    out = np.empty((P, Q), np.complex64)
+    buf = DeviceBuffer(2 * a.nbytes, device)
+    try:
+        buf.upload(a)
+        buf.upload(b, a.nbytes)
+        check(load().mi_phase_correlate_tap_device(device, None, buf.ptr, buf.ptr + a.nbytes, a.shape[0], a.shape[1],
+                                                   int(what), out.ctypes.data))
+    finally:
+        buf.free()
+    return out
 
 
 class Aligner:

@@ -773,17 +773,24 @@ void pc_fft2(hipStream_t st, float2* d, int P, int Q) {
     hipLaunchKernelGGL((pc_fft_lines<INVERSE>), dim3(Q), dim3(std::max(P / 2, 1)), 0, st, d, P, pc_log2(P), (size_t)Q, (size_t)1);
 }
 
-// spectrum of one windowed, padded plane
-void pc_spectrum(hipStream_t st, const float* plane, int h, int w, float2* out, int P, int Q) {
+constexpr int PC_WHOLE = -1;   // `last` of the two functions below: no stage is the last one, run to the end
+
+// spectrum of one windowed, padded plane.  `last` (mi_phase_correlate_tap_device): MI_PC_TAP_WINDOWED_MOV stops in front of
+// the transform
+void pc_spectrum(hipStream_t st, const float* plane, int h, int w, float2* out, int P, int Q, int last = PC_WHOLE) {
     hipLaunchKernelGGL(pc_prepare, dim3(cdiv(Q, 64), cdiv(P, 4)), dim3(64, 4), 0, st, plane, h, w, out, P, Q);
+    if (last == MI_PC_TAP_WINDOWED_MOV) return;
     pc_fft2<false>(st, out, P, Q);
 }
 
-// mov's spectrum (in `fm`, destroyed) against the reference's `fr`: (dx, dy, response) -> dev_out3
-void pc_correlate(hipStream_t st, const float2* fr, float2* fm, int P, int Q, double* dev_out3) {
+// mov's spectrum (in `fm`, destroyed) against the reference's `fr`: (dx, dy, response) -> dev_out3.  `last`: the tap's
+// stage, left in `fm` (MI_PC_TAP_CROSS_POWER, MI_PC_TAP_SURFACE); dev_out3 is not written then
+void pc_correlate(hipStream_t st, const float2* fr, float2* fm, int P, int Q, double* dev_out3, int last = PC_WHOLE) {
     const size_t n = (size_t)P * Q;
     hipLaunchKernelGGL(pc_cross_power, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fm, fr, n);
+    if (last == MI_PC_TAP_CROSS_POWER) return;
     pc_fft2<true>(st, fm, P, Q);
+    if (last == MI_PC_TAP_SURFACE) return;
     hipLaunchKernelGGL(pc_peak, dim3(1), dim3(1024), 0, st, (const float2*)fm, P, Q, dev_out3);
 }
 
@@ -2179,24 +2186,47 @@ int mi_aligner_set_phase_init(mi_aligner_t al, int enable) {
     return MI_OK;
 }
 
-int mi_phase_correlate_device(int device, void* stream, const void* dev_ref, const void* dev_mov, int height, int width,
-                              double* out3) {
-    if (!dev_ref || !dev_mov || !out3) return fail(MI_ERR_INVALID, "null argument");
+namespace {
+
+// what mi_phase_correlate_device and its tap share: the argument checks, the scratch and the launches.  `last`: PC_WHOLE
+// -> (dx, dy, response) to `host_out`; a MI_PC_TAP_* stage -> the launches up to that stage, its P x Q float2 plane to `host_out`
+int pc_run(int device, void* stream, const void* dev_ref, const void* dev_mov, int height, int width, int last, void* host_out) {
+    if (!dev_ref || !dev_mov || !host_out) return fail(MI_ERR_INVALID, "null argument");
     if (height < 2 || width < 2) return fail(MI_ERR_INVALID, "plane too small");
     const int P = 1 << pc_log2(height), Q = 1 << pc_log2(width);
     if (P > PC_MAX_N || Q > PC_MAX_N) return fail(MI_ERR_UNSUPPORTED, "phase correlation takes planes of at most %d pixels per side", PC_MAX_N);
     MI_HIP(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     DevScratch tmp(st);
+    const size_t plane = sizeof(float2) * P * Q;
     float2 *a = nullptr, *b = nullptr;
     double* o = nullptr;
     int rc;
-    if ((rc = tmp.alloc(&a, sizeof(float2) * P * Q)) || (rc = tmp.alloc(&b, sizeof(float2) * P * Q)) || (rc = tmp.alloc(&o, 3 * sizeof(double))))
-        return rc;
+    if ((rc = tmp.alloc(&a, plane)) || (rc = tmp.alloc(&b, plane)) || (rc = tmp.alloc(&o, 3 * sizeof(double)))) return rc;
+    if (last == MI_PC_TAP_WINDOWED_MOV) {
+        pc_spectrum(st, (const float*)dev_mov, height, width, b, P, Q, last);
+        return tmp.download(host_out, b, plane);
+    }
     pc_spectrum(st, (const float*)dev_ref, height, width, a, P, Q);
+    if (last == MI_PC_TAP_SPECTRUM_REF) return tmp.download(host_out, a, plane);
     pc_spectrum(st, (const float*)dev_mov, height, width, b, P, Q);
-    pc_correlate(st, a, b, P, Q, o);
-    return tmp.download(out3, o, 3 * sizeof(double));
+    if (last == MI_PC_TAP_SPECTRUM_MOV) return tmp.download(host_out, b, plane);
+    pc_correlate(st, a, b, P, Q, o, last);
+    if (last != PC_WHOLE) return tmp.download(host_out, b, plane);
+    return tmp.download(host_out, o, 3 * sizeof(double));
+}
+
+}  // namespace
+
+int mi_phase_correlate_device(int device, void* stream, const void* dev_ref, const void* dev_mov, int height, int width,
+                              double* out3) {
+    return pc_run(device, stream, dev_ref, dev_mov, height, width, PC_WHOLE, out3);
+}
+
+int mi_phase_correlate_tap_device(int device, void* stream, const void* dev_ref, const void* dev_mov, int height, int width,
+                                  int what, void* host_out) {
+    if (what < MI_PC_TAP_WINDOWED_MOV || what > MI_PC_TAP_SURFACE) return fail(MI_ERR_INVALID, "unknown phase-correlation tap %d", what);
+    return pc_run(device, stream, dev_ref, dev_mov, height, width, what, host_out);
 }
 
 int mi_aligner_estimate_batch(mi_aligner_t al, void* stream, const void* const* dev_movs, int n, int max_iters,

@@ -96,6 +96,21 @@ def test_depth_map_tap_is_declared_exported_and_bound(hiplib):
         assert re.search(rf"MI_DM_TAP_{name} = {i}\b", text) and getattr(hiplib, "DM_TAP_" + name) == i
 
 
+def test_phase_correlation_tap_is_declared_exported_and_bound(hiplib):
+    name = "mi_phase_correlate_tap_device"
+    assert name in header_symbols() and name in hiplib.SIGNATURES and callable(hiplib.phase_tap)
+    assert hasattr(ctypes.CDLL(hiplib.LIB_PATH), name)
+    assert len(hiplib.SIGNATURES[name][1]) == len(hiplib.SIGNATURES["mi_phase_correlate_device"][1]) + 1
+    text = open(HEADER).read()
+    for i, stage in enumerate(("WINDOWED_MOV", "SPECTRUM_REF", "SPECTRUM_MOV", "CROSS_POWER", "SURFACE")):
+        assert re.search(rf"MI_PC_TAP_{stage} = {i}\b", text) and getattr(hiplib, "PC_TAP_" + stage) == i
+    lib = hiplib.load()   # the argument checks come before the first device call
+    assert lib.mi_phase_correlate_tap_device(0, None, None, None, 8, 8, 0, None) == hiplib.MI_ERR_INVALID
+    assert b"null" in lib.mi_last_error()
+    assert lib.mi_phase_correlate_tap_device(0, None, None, None, 8, 8, 5, None) == hiplib.MI_ERR_INVALID
+    assert b"unknown phase-correlation tap 5" in lib.mi_last_error()
+
+
 @pytest.mark.skipif(os.environ.get("MI_EXPECT_GPU") == "1", reason="GPU box")
 def test_no_gpu_means_loud_failure(hiplib):
     if hiplib.device_count() > 0:
