@@ -176,8 +176,10 @@ MI_API int mi_stack_push_frame(mi_stack_t* s, const void* host_bgr, size_t row_s
  * The buffer must stay untouched until mi_stack_wait_uploads reports the upload done.  MI_ERR_INVALID when the memory is
  * not pinned. */
 MI_API int mi_stack_push_frame_pinned(mi_stack_t* st, const void* host_bgr, size_t row_stride_bytes);
-/* blocks until at most `max_outstanding` of the frames pushed with mi_stack_push_frame_pinned are still being uploaded
- * (0: all of them are on the device; a decoder that cycles k pinned buffers calls it with k - 1 before it reuses one) */
+/* blocks until at most `max_outstanding` of the frames pushed with mi_stack_push_frame_pinned -- and of the pinned mosaics
+ * pushed with mi_stack_push_mosaic -- are still being uploaded (0: all of them are on the device; a decoder that cycles k
+ * pinned buffers calls it with k - 1 before it reuses one).  On a handle that received both kinds, only the most recent run
+ * of one kind is left in flight: it may wait for more uploads than asked, never for fewer. */
 MI_API int mi_stack_wait_uploads(mi_stack_t* st, int max_outstanding);
 /* pinned host memory: allocate / free, or pin / unpin memory the caller owns */
 MI_API int mi_host_alloc(void** ptr, size_t bytes);
@@ -707,6 +709,34 @@ MI_API int mi_dmap_tap(mi_dmap_t* d, int what, int frame, void* host_out);
  * MI_ERR_STATE before finish.  mi_dmap_depth_map_device: `dev_out` in device memory; waits for the handle's stream. */
 MI_API int mi_dmap_depth_map(mi_dmap_t* d, double sigma, void* host_out);
 MI_API int mi_dmap_depth_map_device(mi_dmap_t* d, double sigma, void* dev_out);
+
+/* ---- raw Bayer mosaics in (kernels_demosaic.hpp; no reference counterpart: the reference reads developed frames) ----
+ * A height x width mosaic of MI_U8 / MI_U16, one colour sample per site, becomes a height x width x 3 BGR frame of the same
+ * dtype.  Per site: v' = min(white, (max(v - black[pos], 0) * gain_q[pos] + 2048) >> 12) with pos = 2 (y & 1) + (x & 1), then
+ * the Malvar-He-Cutler 5 x 5 linear interpolation in integers over 16, clamp((sum + 8) >> 4, 0, white), BORDER_REFLECT_101 on
+ * the mosaic.  Exact: tests/demosaic_restatement.py states it in NumPy and the kernel is held to it bit for bit. */
+enum { MI_CFA_RGGB = 0, MI_CFA_BGGR = 1, MI_CFA_GRBG = 2, MI_CFA_GBRG = 3 };   /* the 2 x 2 cell at (y & 1, x & 1), row-major */
+typedef struct mi_cfa {
+    int32_t pattern;      /* MI_CFA_*                                                                            */
+    int32_t black[4];     /* black level per cell position, >= 0                                                 */
+    uint32_t gain_q[4];   /* round(gain * 4096) per cell position, <= 65535 (gain < 16): white balance, bit depth */
+    int32_t white;        /* output clamp, 1 .. the dtype's maximum                                              */
+} mi_cfa_t;
+/* height, width >= 2 (odd sizes are fine).  MI_ERR_INVALID names the argument; the checks come before the first device call.
+ * The device form enqueues on `stream`; the host form uploads, runs and downloads, and waits. */
+MI_API int mi_demosaic_device(int device, void* stream, const void* dev_mosaic, void* dev_bgr, int height, int width, int dtype,
+                              const mi_cfa_t* cfa);
+MI_API int mi_demosaic(int device, const void* host_mosaic, void* host_bgr, int height, int width, int dtype, const mi_cfa_t* cfa);
+/* One frame from host memory as its mosaic (the handle's height x width samples of in_dtype, MI_U8 / MI_U16; rows
+ * row_stride_bytes apart, 0 = packed): a third of the bytes of mi_stack_push_frame over the host link.  The mosaic is
+ * uploaded on a copy stream of the handle's mosaic stage and demosaiced behind the copy into a device buffer of batch_frames
+ * BGR frames; a full buffer is fused as one batch, a partly filled one by whatever flushes pending host frames (finish, a tap,
+ * mi_stack_sync_level, mi_stack_export_indices, a push of another kind).  Frames are fused in call order, mixed with
+ * mi_stack_push_frame and mi_stack_push_frames_device as the calls came.  pinned != 0: the mosaic lies in pinned host memory
+ * with contiguous rows and is read directly -- leave it alone until mi_stack_wait_uploads says so (MI_ERR_INVALID when it is
+ * not pinned); else it goes through a pinned bounce buffer and may be reused on return.  Float-64 and MI_IMPL_SIMPLE handles
+ * take the synchronous route: upload, demosaic, push, wait. */
+MI_API int mi_stack_push_mosaic(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa, int pinned);
 
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,

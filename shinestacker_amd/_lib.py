@@ -54,6 +54,11 @@ class BalanceLinearOpts(C.Structure):
                 ("dev_corr_out", C.c_void_p), ("ncorr", C.c_int)]
 
 
+class CfaStruct(C.Structure):
+    """mi_cfa_t: what the demosaic kernel sees of a Cfa (demosaic.Cfa.quantised)"""
+    _fields_ = [("pattern", C.c_int32), ("black", C.c_int32 * 4), ("gain_q", C.c_uint32 * 4), ("white", C.c_int32)]
+
+
 class DepthMapParams(C.Structure):
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32),
                 ("map_type", C.c_int32), ("energy", C.c_int32), ("kernel_size", C.c_int32),
@@ -230,6 +235,9 @@ SIGNATURES = {
     "mi_dmap_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mi_dmap_depth_map": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "mi_dmap_depth_map_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "mi_demosaic_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct)]),
+    "mi_demosaic": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct)]),
+    "mi_stack_push_mosaic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CfaStruct), C.c_int]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }
@@ -541,6 +549,33 @@ class Stack:
             if rc != MI_ERR_INVALID:     # MI_ERR_INVALID: the library does not see pinned memory there (stale record)
                 check(rc)
         check(load().mi_stack_push_frame(self._h, a.ctypes.data, 0))
+
+    def push_mosaic(self, mosaic, cfa, zero_copy=False):
+        """Push one host frame as its raw Bayer mosaic (H x W samples of the handle's input dtype, `cfa`: a demosaic.Cfa): a
+        third of push_frame's bytes cross the host link, and the frame is demosaiced on the device behind its upload.  Frames
+        are fused in call order, whichever of push_frame / push_mosaic / push_frames_device brought them.  `zero_copy` as in
+        push_frame."""
+        a = np.asarray(mosaic)
+        if a.shape != (self.height, self.width):
+            raise ValueError(f"mosaic shape {a.shape} != {(self.height, self.width)}")
+        if a.dtype != self.in_dtype:
+            raise ValueError(f"mosaic dtype {a.dtype} != {self.in_dtype}")
+        c = cfa.struct(self.in_dtype)
+        if not a.flags.c_contiguous:
+            if a.strides[1] == a.itemsize and a.strides[0] > 0:
+                check(load().mi_stack_push_mosaic(self._h, a.ctypes.data, a.strides[0], C.byref(c), 0))
+                return
+            a = np.ascontiguousarray(a)
+        if zero_copy and is_pinned(a):
+            rc = load().mi_stack_push_mosaic(self._h, a.ctypes.data, 0, C.byref(c), 1)
+            if rc == MI_OK:
+                self._inflight.append(a)
+                if len(self._inflight) > 64:
+                    self.wait_uploads(32)
+                return
+            if rc != MI_ERR_INVALID:     # MI_ERR_INVALID: the library does not see pinned memory there (stale record)
+                check(rc)
+        check(load().mi_stack_push_mosaic(self._h, a.ctypes.data, 0, C.byref(c), 0))
 
     def wait_uploads(self, max_outstanding=0):
         """block until at most `max_outstanding` of the pinned frames pushed so far are still being uploaded: a producer that

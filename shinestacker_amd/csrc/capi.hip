@@ -129,6 +129,7 @@ struct mi_stack {
 
     std::vector<void*> allocs;
     void* tiled = nullptr;  // TiledState (tiled_host.hpp)
+    void* mosaic = nullptr; // MosaicStage (mosaic_host.hpp): created by the first mi_stack_push_mosaic
 };
 
 namespace {
@@ -521,6 +522,17 @@ int check_handle(const mi_stack* s) {
 
 // tiled implementation hooks (kernels_tiled.hpp) need the handle layout
 #include "tiled_host.hpp"
+// raw-mosaic staging in front of it (kernels_demosaic.hpp)
+#include "mosaic_host.hpp"
+
+namespace {
+// every frame staged from host memory, of either kind, is handed to the kernels (at most one kind is pending at a time)
+int stack_flush(mi_stack* s) {
+    int rc = mosaic_flush(s);
+    return rc ? rc : tiled_flush(s);
+}
+int stack_pending(const mi_stack* s) { return tiled_pending(s) + mosaic_pending(s); }
+}  // namespace
 
 namespace {
 
@@ -1476,6 +1488,7 @@ void mi_stack_destroy(mi_stack_t* s) {
     (void)hipSetDevice(s->p.device);
     (void)tiled_sync_all(s);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
+    mosaic_destroy(s);
     tiled_destroy(s);
     for (auto& r : s->recs) {
         (void)hipEventDestroy(r.a);
@@ -1494,9 +1507,11 @@ int mi_stack_reset(mi_stack_t* s) {
     MI_HIP(hipSetDevice(s->p.device));
     rc = tiled_sync_all(s);
     if (rc) return rc;
+    if ((rc = mosaic_sync(s))) return rc;
     MI_HIP(hipStreamSynchronize(s->stream));
     rc = prof_drain(s);
     if (rc) return rc;
+    mosaic_reset(s);
     s->n_pushed = 0;
     s->finished = false;
     s->idx_exported = 0;
@@ -1524,14 +1539,14 @@ int mi_stack_frames_pushed(const mi_stack_t* s, int* n) {
     int rc = check_handle(s);
     if (rc) return rc;
     if (!n) return fail(MI_ERR_INVALID, "null n");
-    *n = s->n_pushed + tiled_pending(s);
+    *n = s->n_pushed + stack_pending(s);
     return MI_OK;
 }
 
 int mi_stack_set_first_index(mi_stack_t* s, int first_global_index) {
     int rc = check_handle(s);
     if (rc) return rc;
-    if (s->n_pushed + tiled_pending(s) != 0) return fail(MI_ERR_STATE, "set_first_index after frames were pushed");
+    if (s->n_pushed + stack_pending(s) != 0) return fail(MI_ERR_STATE, "set_first_index after frames were pushed");
     s->first_index = first_global_index;
     return MI_OK;
 }
@@ -1540,7 +1555,7 @@ int mi_stack_set_index_stride(mi_stack_t* s, int stride) {
     int rc = check_handle(s);
     if (rc) return rc;
     if (stride < 1) return fail(MI_ERR_INVALID, "index stride must be >= 1");
-    if (s->n_pushed + tiled_pending(s) != 0) return fail(MI_ERR_STATE, "set_index_stride after frames were pushed");
+    if (s->n_pushed + stack_pending(s) != 0) return fail(MI_ERR_STATE, "set_index_stride after frames were pushed");
     s->index_stride = stride;
     return MI_OK;
 }
@@ -1565,7 +1580,7 @@ int mi_stack_export_indices(mi_stack_t* s, int level) {
     if (rc) return rc;
     MI_HIP(hipSetDevice(s->p.device));
     if (level < -1 || level > s->L + 1) return fail(MI_ERR_INVALID, "bad level %d", level);
-    if ((rc = tiled_flush(s))) return rc;
+    if ((rc = stack_flush(s))) return rc;
     // the level's state must be final: level 0 is, once its last payload pass is through; everything else needs all of it
     if (level == 0) rc = tiled_sync_level0(s);
     else { rc = tiled_sync_all(s); if (!rc) MI_HIP(hipStreamSynchronize(s->stream)); }
@@ -1586,6 +1601,7 @@ int mi_stack_push_frames_device(mi_stack_t* s, const void* dev_frames, int n, si
     if (frame_stride_bytes == 0) frame_stride_bytes = fb;
     if (frame_stride_bytes < fb) return fail(MI_ERR_INVALID, "frame stride smaller than a frame");
     MI_HIP(hipSetDevice(s->p.device));
+    if ((rc = mosaic_flush(s))) return rc;   // call order: mosaics staged before these frames are fused first
     return dispatch_push(s, dev_frames, n, frame_stride_bytes);
 }
 
@@ -1596,6 +1612,7 @@ int mi_stack_push_frame(mi_stack_t* s, const void* host_bgr, size_t row_stride_b
     if (!host_bgr) return fail(MI_ERR_INVALID, "null frame");
     if (s->finished) return fail(MI_ERR_STATE, "push after finish; call mi_stack_reset first");
     MI_HIP(hipSetDevice(s->p.device));
+    if ((rc = mosaic_flush(s))) return rc;   // call order
     return tiled_push_host(s, host_bgr, row_stride_bytes);
 }
 
@@ -1612,6 +1629,7 @@ int mi_stack_push_frame_pinned(mi_stack_t* s, const void* host_bgr, size_t row_s
         (void)hipGetLastError();
         return fail(MI_ERR_INVALID, "mi_stack_push_frame_pinned: the frame is not in pinned host memory (mi_host_alloc / mi_host_register)");
     }
+    if ((rc = mosaic_flush(s))) return rc;   // call order
     return tiled_push_host(s, host_bgr, row_stride_bytes, true);
 }
 
@@ -1619,7 +1637,63 @@ int mi_stack_wait_uploads(mi_stack_t* s, int max_outstanding) {
     int rc = check_handle(s);
     if (rc) return rc;
     MI_HIP(hipSetDevice(s->p.device));
-    return tiled_wait_uploads(s, max_outstanding);
+    return mosaic_wait_uploads(s, max_outstanding);
+}
+
+// ---------------------------------------------------------------- raw mosaics (kernels_demosaic.hpp, mosaic_host.hpp)
+static int demosaic_check(const void* mosaic, const void* bgr, int height, int width, int dtype, const mi_cfa_t* cfa) {
+    if (!mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    if (!bgr) return fail(MI_ERR_INVALID, "null bgr output");
+    if (height < 2 || width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic (got %dx%d)", width, height);
+    if ((uint64_t)height * (uint64_t)width * 3ull >= (1ull << 32)) return fail(MI_ERR_INVALID, "height x width too large");
+    return cfa_check(cfa, dtype);
+}
+
+int mi_demosaic_device(int device, void* stream, const void* dev_mosaic, void* dev_bgr, int height, int width, int dtype,
+                       const mi_cfa_t* cfa) {
+    int rc = demosaic_check(dev_mosaic, dev_bgr, height, width, dtype, cfa);
+    if (rc) return rc;
+    MI_HIP(hipSetDevice(device));
+    demosaic_launch((hipStream_t)stream, dev_mosaic, dev_bgr, height, width, dtype, *cfa);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_demosaic(int device, const void* host_mosaic, void* host_bgr, int height, int width, int dtype, const mi_cfa_t* cfa) {
+    int rc = demosaic_check(host_mosaic, host_bgr, height, width, dtype, cfa);
+    if (rc) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t nb = (size_t)height * width * dtype_size(dtype);
+    DevScratch tmp(nullptr);
+    void *src = nullptr, *dst = nullptr;
+    if ((rc = tmp.upload(&src, host_mosaic, nb)) || (rc = tmp.alloc(&dst, nb * 3)) ||
+        (rc = mi_demosaic_device(device, nullptr, src, dst, height, width, dtype, cfa)))
+        return rc;
+    return tmp.download(host_bgr, dst, nb * 3);
+}
+
+int mi_stack_push_mosaic(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa, int pinned) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!host_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
+    if ((rc = cfa_check(cfa, s->p.in_dtype))) return rc;
+    const size_t rb = (size_t)s->p.width * dtype_size(s->p.in_dtype);
+    if (row_stride_bytes == 0) row_stride_bytes = rb;
+    if (row_stride_bytes < rb) return fail(MI_ERR_INVALID, "row stride smaller than a row");
+    if (s->idx_exported) return fail(MI_ERR_STATE, "the winner indices were exported (index stride > 1): reset the handle before pushing more frames");
+    if (s->finished) return fail(MI_ERR_STATE, "push after finish; call mi_stack_reset first");
+    MI_HIP(hipSetDevice(s->p.device));
+    const bool async = s->p.impl == MI_IMPL_TILED && !s->f64;
+    if (pinned && async) {
+        if (row_stride_bytes != rb) return fail(MI_ERR_INVALID, "a pinned mosaic must have contiguous rows");
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, host_mosaic) != hipSuccess || at.type != hipMemoryTypeHost) {
+            (void)hipGetLastError();
+            return fail(MI_ERR_INVALID, "mi_stack_push_mosaic: the mosaic is not in pinned host memory (mi_host_alloc / mi_host_register)");
+        }
+    }
+    return mosaic_push(s, host_mosaic, row_stride_bytes, *cfa, pinned && async);
 }
 
 int mi_host_alloc(void** ptr, size_t bytes) {
@@ -1650,6 +1724,7 @@ int mi_stack_sync(mi_stack_t* s) {
     MI_HIP(hipSetDevice(s->p.device));
     rc = tiled_sync_all(s);
     if (rc) return rc;
+    if ((rc = mosaic_sync(s))) return rc;
     MI_HIP(hipStreamSynchronize(s->stream));
     return MI_OK;
 }
@@ -1658,7 +1733,7 @@ int mi_stack_sync_level(mi_stack_t* s, int level) {
     int rc = check_handle(s);
     if (rc) return rc;
     MI_HIP(hipSetDevice(s->p.device));
-    rc = tiled_flush(s);
+    rc = stack_flush(s);
     if (rc) return rc;
     if (level != 0) return mi_stack_sync(s);
     return tiled_sync_level0(s);
@@ -1668,7 +1743,7 @@ int mi_stack_finish_device(mi_stack_t* s, void* dev_out) {
     int rc = check_handle(s);
     if (rc) return rc;
     MI_HIP(hipSetDevice(s->p.device));
-    rc = tiled_flush(s);
+    rc = stack_flush(s);
     if (rc) return rc;
     if (s->n_pushed == 0) return fail(MI_ERR_STATE, "finish with no frames pushed");
     if (s->f64) rc = s->p.use_fma ? finish_f64<true>(s) : finish_f64<false>(s);
@@ -1700,7 +1775,7 @@ int mi_stack_get_level(mi_stack_t* s, int level, int what, void* host_out, size_
     if (rc) return rc;
     if (!host_out) return fail(MI_ERR_INVALID, "null output");
     MI_HIP(hipSetDevice(s->p.device));
-    rc = tiled_flush(s);
+    rc = stack_flush(s);
     if (rc) return rc;
     const int L = s->L;
     const void* src = nullptr;
@@ -1772,7 +1847,7 @@ int mi_stack_state(mi_stack_t* s, int level, void** dev_energy, void** dev_lap, 
     int rc = check_handle(s);
     if (rc) return rc;
     MI_HIP(hipSetDevice(s->p.device));
-    rc = tiled_flush(s);
+    rc = stack_flush(s);
     if (rc) return rc;
     // hand-off point to foreign streams (RCCL, hipMemcpy on the null stream ...): everything this
     // handle enqueued on its own non-blocking streams must have finished
@@ -2901,7 +2976,7 @@ int mi_stack_depth_map_device(mi_stack_t* s, double sigma, void* dev_out) {
     if (rc) return rc;
     if (!dev_out) return fail(MI_ERR_INVALID, "null output");
     MI_HIP(hipSetDevice(s->p.device));
-    rc = tiled_flush(s);
+    rc = stack_flush(s);
     if (rc) return rc;
     if (s->n_pushed == 0) return fail(MI_ERR_STATE, "depth map with no frames pushed");
     if (s->L < 1) return fail(MI_ERR_UNSUPPORTED, "the stack has no Laplacian level: no per-pixel winner exists");

@@ -1,0 +1,216 @@
+// kernels_demosaic.hpp -- raw Bayer mosaics in: black level, gain and Malvar-He-Cutler demosaic in one pass, H x W samples of
+// uint8 / uint16 to H x W x 3 interleaved BGR of the same type (the layout every kernel here reads).  No reference
+// counterpart -- the reference never sees a mosaic; tests/demosaic_restatement.py is the definition, held bit for bit.
+//
+//   step A, per site:  v' = min(white, (max(v - black[pos], 0) * gain_q[pos] + 2048) >> 12), pos = 2 (y & 1) + (x & 1);
+//                      gain_q = round(gain * 4096) < 2^16 is quantised once by the caller, the product stays below 2^32
+//   step B:            Malvar, He, Cutler (ICASSP 2004): the 5 x 5 linear kernels, the paper's coefficients times 2 so that
+//                      every sum is an integer over 16 (|sum| < 2^22 at uint16):
+//                          G at an R/B site            8 c + 4 (l + r + u + d) - 2 (ll + rr + uu + dd)
+//                          C at a G site, C left/right 10 c + 8 (l + r) - 2 (4 diagonals) - 2 (ll + rr) + (uu + dd)
+//                          C at a G site, C above/below: its transpose
+//                          C at the opposite colour    12 c + 4 (4 diagonals) - 3 (ll + rr + uu + dd)
+//                      out = clamp((sum + 8) >> 4, 0, white), arithmetic shift; a site's own colour is v' itself
+//   borders:           BORDER_REFLECT_101 on the mosaic: the period 2 (n - 1) is even, so a reflected sample has the colour
+//                      the tap expects at every size >= 2
+//
+// One workgroup of 256 owns a TILE_H x TILE_W tile.  1. The tile and its halo of 2 sites, step A and the reflection applied, are
+// staged in LDS as uint16 (20 x 132 x 2 B = 5.3 KB): the 13 taps read LDS only.  A thread stages (even, odd) column pairs, which
+// share their black levels and gains and are one 32-bit LDS word, with all its loads issued before the first is used; a tile
+// whose halo lies inside the image takes a path without reflection.  2. A thread owns whole 2 x 2 CFA cells -- one
+// cell at uint16, two side by side at uint8, 12 bytes of BGR per output row either way -- so no lane branches on the colour of
+// its site (which cell positions hold G and whether the first row's colour is R are wave-uniform), its 6 x (4 + 2 CX) window is
+// read as aligned 32-bit LDS words with consecutive lanes on consecutive words (uint16) or word pairs (uint8), and a wave's
+// stores of one row are one contiguous run: 768 bytes.  A row whose address is 4-byte aligned is stored as one 12-byte store per
+// lane; other rows (odd widths at uint16, widths not a multiple of 4 at uint8) and the ragged last cell per sample.
+// Traffic: itemsize bytes read, 3 * itemsize written per pixel.  Bound by instruction issue rather than memory: 50 MP uint16 in
+// 0.113 ms, 1.5 x a device copy of the same bytes (docs/studies.md, raw mosaics).
+#pragma once
+#include "common.hpp"
+
+namespace mi {
+
+namespace demosaic {
+constexpr int TILE_H = 16;
+constexpr int TILE_W = 128;
+constexpr int NT = 256;
+constexpr int PITCH = TILE_W + 4;   // LDS row of the tile and its halo, in samples (even: 32-bit reads stay aligned)
+constexpr int ROWS = TILE_H + 4;
+}  // namespace demosaic
+
+struct DemosaicArgs {
+    const void* src;   // H x W
+    void* dst;         // H x W x 3
+    int h, w;
+    mi_cfa_t cfa;      // wave-uniform reads: scalar loads from the kernel arguments
+};
+
+struct alignas(4) DemosaicRow {
+    uint32_t w[3];
+};
+
+// One site of the window `v` (centre at row cy, column cx): CHROMA: (a, b, g) = (own, opposite colour, G); at a G site:
+// (the colour left and right, the colour above and below, own).  Sums over 16, not yet rounded.
+template <bool CHROMA, int NW>
+__device__ __forceinline__ void demosaic_site(const int (&v)[6][NW], int cy, int cx, int& a, int& b, int& g) {
+    const int c = v[cy][cx];
+    const int h2 = v[cy][cx - 1] + v[cy][cx + 1], v2 = v[cy - 1][cx] + v[cy + 1][cx];
+    const int d4 = v[cy - 1][cx - 1] + v[cy - 1][cx + 1] + v[cy + 1][cx - 1] + v[cy + 1][cx + 1];
+    const int fh = v[cy][cx - 2] + v[cy][cx + 2], fv = v[cy - 2][cx] + v[cy + 2][cx];
+    if constexpr (CHROMA) {
+        a = 16 * c;
+        b = 12 * c + 4 * d4 - 3 * (fh + fv);
+        g = 8 * c + 4 * (h2 + v2) - 2 * (fh + fv);
+    } else {
+        a = 10 * c + 8 * h2 - 2 * d4 - 2 * fh + fv;
+        b = 10 * c + 8 * v2 - 2 * d4 - 2 * fv + fh;
+        g = 16 * c;
+    }
+}
+
+__device__ __forceinline__ int demosaic_round(int sum, int white) {
+    const int r = (sum + 8) >> 4;
+    return r < 0 ? 0 : (r > white ? white : r);
+}
+
+// the cells of one thread: G0: the cell's first site is G (GRBG, GBRG); else its first site is R or B (RGGB, BGGR)
+template <typename T, bool G0, int CX>
+__device__ __forceinline__ void demosaic_unit(const uint16_t* tile, int ly, int lx, T* dst, int y, int x, int H, int W, bool r_first,
+                                              int white) {
+    using namespace demosaic;
+    constexpr int NW = 4 + 2 * CX;
+    int v[6][NW];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        const uint32_t* p = (const uint32_t*)(tile + (ly + r) * PITCH + lx);
+#pragma unroll
+        for (int k = 0; k < NW / 2; ++k) {
+            const uint32_t d = p[k];
+            v[r][2 * k] = (int)(d & 0xffffu);
+            v[r][2 * k + 1] = (int)(d >> 16);
+        }
+    }
+    constexpr int NPX = 2 * CX;
+#pragma unroll
+    for (int sy = 0; sy < 2; ++sy) {
+        if (y + sy >= H) break;
+        T e[NPX * 3];
+#pragma unroll
+        for (int px = 0; px < NPX; ++px) {
+            int a, b, g;
+            if (((px & 1) == sy) != G0) demosaic_site<true, NW>(v, 2 + sy, 2 + px, a, b, g);
+            else demosaic_site<false, NW>(v, 2 + sy, 2 + px, a, b, g);
+            // `a` belongs to this row's chroma: R in the cell's first row when r_first, in its second row otherwise
+            const bool a_is_r = (sy == 0) == r_first;
+            e[px * 3 + 0] = (T)demosaic_round(a_is_r ? b : a, white);
+            e[px * 3 + 1] = (T)demosaic_round(g, white);
+            e[px * 3 + 2] = (T)demosaic_round(a_is_r ? a : b, white);
+        }
+        T* row = dst + ((size_t)(y + sy) * W + x) * 3;
+        if (x + NPX <= W && ((uintptr_t)row & 3) == 0) {
+            constexpr int PER = 4 / (int)sizeof(T);
+            DemosaicRow o;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                uint32_t d = 0;
+#pragma unroll
+                for (int j = 0; j < PER; ++j) d |= (uint32_t)e[k * PER + j] << (8 * (int)sizeof(T) * j);
+                o.w[k] = d;
+            }
+            *(DemosaicRow*)row = o;
+        } else {
+#pragma unroll
+            for (int px = 0; px < NPX; ++px)
+                if (x + px < W) {
+                    row[px * 3 + 0] = e[px * 3 + 0];
+                    row[px * 3 + 1] = e[px * 3 + 1];
+                    row[px * 3 + 2] = e[px * 3 + 2];
+                }
+        }
+    }
+}
+
+// The loads of one thread's share of the tile and its halo: pair i = the sites (row i / PAIRS, columns 2 (i % PAIRS) and + 1) of
+// the staged tile.  INSIDE: the whole staged tile lies in the image -- no reflection, straight-line code.
+template <typename T, bool INSIDE, int STEPS>
+__device__ __forceinline__ void demosaic_load(const T* src, int H, int W, int ty0, int tx0, uint32_t (&raw)[STEPS][2]) {
+    using namespace demosaic;
+    constexpr int PAIRS = PITCH / 2, NPAIR = ROWS * PAIRS;
+#pragma unroll
+    for (int k = 0; k < STEPS; ++k) {
+        const int i = (int)threadIdx.x + k * NT;
+        raw[k][0] = raw[k][1] = 0;
+        if (k < NPAIR / NT || i < NPAIR) {      // (only the last step is ragged: the others are straight-line code)
+            const int r = i / PAIRS, c = 2 * (i - r * PAIRS);
+            int y = ty0 - 2 + r, x0 = tx0 - 2 + c, x1 = x0 + 1;
+            if constexpr (!INSIDE) {
+                // sites past n + 1 feed no output of this image (a ragged last tile): any in-bounds sample will do for them
+                y = r101_loop(y > H + 1 ? H + 1 : y, H);
+                x0 = r101_loop(x0 > W + 1 ? W + 1 : x0, W);
+                x1 = r101_loop(x1 > W + 1 ? W + 1 : x1, W);
+            }
+            const T* row = src + (size_t)y * W;
+            raw[k][0] = row[x0];
+            raw[k][1] = row[x1];
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void demosaic_mhc(DemosaicArgs A) {
+    using namespace demosaic;
+    constexpr int CX = sizeof(T) == 1 ? 2 : 1;
+    __shared__ __attribute__((aligned(16))) uint16_t tile[ROWS * PITCH];
+    const int H = A.h, W = A.w;
+    const int tx0 = blockIdx.x * TILE_W, ty0 = blockIdx.y * TILE_H;
+    const T* src = (const T*)A.src;
+    const bool inside = tx0 >= 2 && ty0 >= 2 && tx0 + TILE_W + 2 <= W && ty0 + TILE_H + 2 <= H;
+    const int white = A.cfa.white;
+    // Staging, two sites of a row per step: the tile's first column and row are even, so a pair is an (even, odd) column pair
+    // of one row parity and shares its black levels and gains.  All loads first, then step A: the loads of a thread are in
+    // flight together.
+    constexpr int PAIRS = PITCH / 2, NPAIR = ROWS * PAIRS, STEPS = (NPAIR + NT - 1) / NT;
+    uint32_t raw[STEPS][2];
+    if (inside) demosaic_load<T, true, STEPS>(src, H, W, ty0, tx0, raw);
+    else demosaic_load<T, false, STEPS>(src, H, W, ty0, tx0, raw);
+#pragma unroll
+    for (int k = 0; k < STEPS; ++k) {
+        const int i = (int)threadIdx.x + k * NT;
+        if (k < NPAIR / NT || i < NPAIR) {      // (only the last step is ragged: the others are straight-line code)
+            const bool odd_row = (i / PAIRS) & 1;      // the reflection keeps a coordinate's parity: its period is even
+            uint32_t q[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int black = odd_row ? A.cfa.black[2 + j] : A.cfa.black[j];
+                const uint32_t gain = odd_row ? A.cfa.gain_q[2 + j] : A.cfa.gain_q[j];
+                const int d = (int)raw[k][j] - black;
+                const uint32_t v = ((uint32_t)(d < 0 ? 0 : d) * gain + 2048u) >> 12;
+                q[j] = v > (uint32_t)white ? (uint32_t)white : v;
+            }
+            ((uint32_t*)tile)[i] = q[0] | (q[1] << 16);
+        }
+    }
+    __syncthreads();
+    constexpr int UX = TILE_W / (2 * CX);        // threads' units along a tile row
+    constexpr int UNITS = UX * (TILE_H / 2);
+    const bool r_first = !(A.cfa.pattern & 1);   // RGGB, GRBG: the cell's first row holds R
+    const bool g0 = (A.cfa.pattern & 2) != 0;    // GRBG, GBRG: the cell's first site is G
+    for (int u = threadIdx.x; u < UNITS; u += NT) {
+        const int uy = u / UX, ux = u - uy * UX;
+        const int ly = 2 * uy, lx = 2 * CX * ux;
+        const int y = ty0 + ly, x = tx0 + lx;
+        if (y >= H || x >= W) continue;
+        if (g0) demosaic_unit<T, true, CX>(tile, ly, lx, (T*)A.dst, y, x, H, W, r_first, white);
+        else demosaic_unit<T, false, CX>(tile, ly, lx, (T*)A.dst, y, x, H, W, r_first, white);
+    }
+}
+
+// the arguments were checked by the caller (capi.hip: demosaic_check)
+inline void demosaic_launch(hipStream_t st, const void* src, void* dst, int h, int w, int dtype, const mi_cfa_t& cfa) {
+    DemosaicArgs A{src, dst, h, w, cfa};
+    const dim3 grid(cdiv(w, demosaic::TILE_W), cdiv(h, demosaic::TILE_H));
+    if (dtype == MI_U8) hipLaunchKernelGGL(demosaic_mhc<uint8_t>, grid, dim3(demosaic::NT), 0, st, A);
+    else hipLaunchKernelGGL(demosaic_mhc<uint16_t>, grid, dim3(demosaic::NT), 0, st, A);
+}
+
+}  // namespace mi

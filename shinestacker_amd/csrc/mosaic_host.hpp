@@ -1,0 +1,206 @@
+// mosaic_host.hpp -- the mosaic stage of a stack handle: host frames arrive as raw Bayer mosaics (a third of the bytes of a BGR
+// frame over the host link) and become BGR frames on the device.  Included by capi.hip after tiled_host.hpp; nothing of it
+// exists until the first mi_stack_push_mosaic of a handle.
+//
+//   stc         the stage's copy stream (the low priority class, as the ring's copy stream and for its reason): the upload of
+//               mosaic k into device slot k % NSLOT, then evCopied[slot].  Uploads run ahead of the kernels by NSLOT mosaics.
+//   demosaic    on s->stream behind evCopied[slot], into frame `pending` of `bgr`, then evSlotFree[slot], which the copy stream
+//               waits for before it overwrites the slot.  The kernel is a twelfth of the copy's time; on the copy stream it
+//               would run in the low class behind another handle's level kernels and hold the next upload back (measured:
+//               docs/studies.md, "raw mosaics").  On s->stream it needs no stream of its own -- the handle stays inside its four
+//               hardware queues -- and is in order with the batch that reads its output.
+//   bgr         bcap BGR frames -- what the ring is for host BGR frames.  A full buffer, or a flush, hands it to dispatch_push
+//               as one batch: the level-0 interior kernel follows the demosaics on s->stream, run_batch's evInput carries them
+//               to the border stream, and tiled_push joins the side streams back into s->stream, so the next demosaic into
+//               `bgr` is ordered behind every reader of the batch -- the two-event handshake tiled_flush keeps with its ring,
+//               here evCopied / evSlotFree per slot and the stream's own order for `bgr`.
+//   order       frames are fused in call order: the first mosaic after host BGR frames flushes the ring (mosaic_push), and
+//               every call that takes frames of another kind or reads state flushes this stage first (stack_flush in capi.hip).
+#pragma once
+
+#include "kernels_demosaic.hpp"
+
+namespace mi {
+
+struct MosaicStage {
+    static constexpr int NSLOT = 4;
+    static constexpr int NPIN = 3;
+    static constexpr int NUP = MI_NUP;
+    hipStream_t stc = nullptr;                // copy stream
+    void* slot[NSLOT] = {};                   // H x W mosaics on the device
+    hipEvent_t evCopied[NSLOT] = {};          // the upload into slot[i] finished
+    hipEvent_t evSlotFree[NSLOT] = {};        // the demosaic out of slot[i] finished
+    void* bgr = nullptr;                      // bcap BGR frames
+    void* pin[NPIN] = {nullptr, nullptr, nullptr};
+    hipEvent_t evPin[NPIN] = {nullptr, nullptr, nullptr};   // the upload out of pin[i] finished
+    hipEvent_t evUp[NUP] = {};                // pinned mosaics: one event per upload, for mi_stack_wait_uploads
+    size_t mosaic_bytes = 0;
+    int pending = 0;                          // frames demosaiced (or being) into `bgr`, not yet handed over
+    long slot_no = 0, pin_no = 0, up_no = 0;
+    long frames_up_seen = 0;                  // TiledState::up_no at the most recent pinned mosaic
+    long run = 0;                             // pinned mosaics since the most recent pinned BGR frame
+};
+
+inline MosaicStage* mstage(const mi_stack* s) { return reinterpret_cast<MosaicStage*>(s->mosaic); }
+
+inline int mosaic_pending(const mi_stack* s) { return mstage(s) ? mstage(s)->pending : 0; }
+
+// argument checks shared by mi_demosaic, mi_demosaic_device and mi_stack_push_mosaic: no device call
+inline int cfa_check(const mi_cfa_t* cfa, int dtype) {
+    if (!cfa) return fail(MI_ERR_INVALID, "null cfa");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16 for a mosaic (got %d)", dtype);
+    if (cfa->pattern < MI_CFA_RGGB || cfa->pattern > MI_CFA_GBRG) return fail(MI_ERR_INVALID, "unknown cfa pattern %d", cfa->pattern);
+    const int maxv = dtype == MI_U8 ? 255 : 65535;
+    for (int k = 0; k < 4; ++k) {
+        if (cfa->black[k] < 0) return fail(MI_ERR_INVALID, "cfa black[%d] must be >= 0 (got %d)", k, cfa->black[k]);
+        if (cfa->gain_q[k] > 65535u) return fail(MI_ERR_INVALID, "cfa gain_q[%d] must be <= 65535 (got %u)", k, cfa->gain_q[k]);
+    }
+    if (cfa->white < 1 || cfa->white > maxv) return fail(MI_ERR_INVALID, "cfa white must be in [1, %d] (got %d)", maxv, cfa->white);
+    return MI_OK;
+}
+
+inline int mosaic_create(mi_stack* s) {
+    auto* m = new MosaicStage();
+    s->mosaic = m;
+    const TiledState* t = tstate(s);
+    m->mosaic_bytes = (size_t)s->p.height * s->p.width * dtype_size(s->p.in_dtype);
+    int rc;
+    if (s->p.impl != MI_IMPL_TILED) return dev_alloc(s, &m->slot[0], m->mosaic_bytes);   // the synchronous route: one slot
+    // the copy stream's priority class, for the reason tiled_push_host gives: the low one
+    int prio_lo = 0, prio_hi = 0;
+    MI_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+    MI_HIP(hipStreamCreateWithPriority(&m->stc, hipStreamNonBlocking, prio_lo));
+    for (int i = 0; i < MosaicStage::NSLOT; ++i) {
+        MI_HIP(hipEventCreateWithFlags(&m->evCopied[i], hipEventDisableTiming));
+        MI_HIP(hipEventCreateWithFlags(&m->evSlotFree[i], hipEventDisableTiming));
+        if ((rc = dev_alloc(s, &m->slot[i], m->mosaic_bytes))) return rc;
+    }
+    return dev_alloc(s, &m->bgr, t->frame_bytes * t->bcap);
+}
+
+inline int mosaic_sync(mi_stack* s) {
+    MosaicStage* m = mstage(s);
+    if (m && m->stc) MI_HIP(hipStreamSynchronize(m->stc));
+    return MI_OK;
+}
+
+inline void mosaic_destroy(mi_stack* s) {
+    MosaicStage* m = mstage(s);
+    if (!m) return;
+    if (m->stc) (void)hipStreamSynchronize(m->stc);
+    for (int i = 0; i < MosaicStage::NPIN; ++i) {
+        if (m->pin[i]) (void)hipHostFree(m->pin[i]);
+        if (m->evPin[i]) (void)hipEventDestroy(m->evPin[i]);
+    }
+    for (int i = 0; i < MosaicStage::NUP; ++i)
+        if (m->evUp[i]) (void)hipEventDestroy(m->evUp[i]);
+    for (int i = 0; i < MosaicStage::NSLOT; ++i) {
+        if (m->evCopied[i]) (void)hipEventDestroy(m->evCopied[i]);
+        if (m->evSlotFree[i]) (void)hipEventDestroy(m->evSlotFree[i]);
+    }
+    if (m->stc) (void)hipStreamDestroy(m->stc);
+    delete m;   // (the device buffers are in s->allocs)
+    s->mosaic = nullptr;
+}
+
+// mi_stack_reset: the stage is empty again and keeps its buffers (the caller has waited for its stream and the handle's)
+inline void mosaic_reset(mi_stack* s) {
+    if (mstage(s)) mstage(s)->pending = 0;
+}
+
+// hand the frames demosaiced so far to the stack as one batch
+inline int mosaic_flush(mi_stack* s) {
+    MosaicStage* m = mstage(s);
+    if (!m || m->pending == 0) return MI_OK;
+    const TiledState* t = tstate(s);
+    const int n = m->pending;
+    m->pending = 0;
+    // the frames are complete in s->stream order, which is what a device push asks for; behind it s->stream is ordered
+    // after every reader of `bgr` (tiled_push joins the side streams), and so is the next demosaic into it
+    return dispatch_push(s, m->bgr, n, t->frame_bytes);
+}
+
+// One host mosaic (arguments checked by mi_stack_push_mosaic): stage it, start upload and demosaic, return.
+inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t& cfa, bool pinned) {
+    TiledState* t = tstate(s);
+    int rc = tiled_flush(s);   // call order: host BGR frames staged before this mosaic are fused first
+    if (rc) return rc;
+    if (!mstage(s) && (rc = mosaic_create(s))) return rc;
+    MosaicStage* m = mstage(s);
+    const int H = s->p.height, W = s->p.width;
+    const size_t rb = (size_t)W * dtype_size(s->p.in_dtype);
+    if (s->p.impl != MI_IMPL_TILED) {
+        // float-64 and MI_IMPL_SIMPLE handles: upload, demosaic, push, wait -- one frame at a time on the handle's stream
+        MI_HIP(hipMemcpy2DAsync(m->slot[0], rb, host_mosaic, row_stride_bytes, rb, H, hipMemcpyHostToDevice, s->stream));
+        demosaic_launch(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa);
+        MI_HIP(hipGetLastError());
+        if ((rc = dispatch_push(s, s->frame_dev, 1, t->frame_bytes))) return rc;
+        MI_HIP(hipStreamSynchronize(s->stream));
+        return MI_OK;
+    }
+    const int si = (int)(m->slot_no % MosaicStage::NSLOT);
+    void* slot = m->slot[si];
+    if (m->slot_no >= MosaicStage::NSLOT) MI_HIP(hipStreamWaitEvent(m->stc, m->evSlotFree[si], 0));
+    m->slot_no++;
+    if (pinned) {
+        hipEvent_t& ev = m->evUp[m->up_no % MosaicStage::NUP];
+        if (!ev) MI_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        else MI_HIP(hipEventSynchronize(ev));   // (only when more than NUP uploads are in flight)
+        MI_HIP(hipMemcpyAsync(slot, host_mosaic, m->mosaic_bytes, hipMemcpyHostToDevice, m->stc));
+        MI_HIP(hipEventRecord(ev, m->stc));
+        if (m->frames_up_seen != t->up_no) { m->frames_up_seen = t->up_no; m->run = 0; }
+        m->run++;
+        m->up_no++;
+    } else {
+        if (!m->pin[0])
+            for (int i = 0; i < MosaicStage::NPIN; ++i) {
+                MI_HIP(hipHostMalloc(&m->pin[i], m->mosaic_bytes, hipHostMallocDefault));
+                MI_HIP(hipEventCreateWithFlags(&m->evPin[i], hipEventDisableTiming));
+            }
+        const int k = (int)(m->pin_no++ % MosaicStage::NPIN);
+        MI_HIP(hipEventSynchronize(m->evPin[k]));   // bounce buffer free again? (no-op when unused)
+        char* pb = (char*)m->pin[k];
+        // row bands on the copy pool for big mosaics, as tiled_push_host copies big frames
+        const int nthr = m->mosaic_bytes >= ((size_t)32 << 20) ? 4 : 1;
+        const std::function<void(int)> band = [&](int j) {
+            const int y0 = (int)((long)H * j / nthr), y1 = (int)((long)H * (j + 1) / nthr);
+            if (row_stride_bytes == rb) memcpy(pb + (size_t)y0 * rb, (const char*)host_mosaic + (size_t)y0 * rb, rb * (size_t)(y1 - y0));
+            else
+                for (int y = y0; y < y1; ++y) memcpy(pb + (size_t)y * rb, (const char*)host_mosaic + (size_t)y * row_stride_bytes, rb);
+        };
+        if (nthr == 1) band(0);
+        else CopyPool::get().run(nthr, band);
+        MI_HIP(hipMemcpyAsync(slot, pb, m->mosaic_bytes, hipMemcpyHostToDevice, m->stc));
+        MI_HIP(hipEventRecord(m->evPin[k], m->stc));
+    }
+    MI_HIP(hipEventRecord(m->evCopied[si], m->stc));
+    MI_HIP(hipStreamWaitEvent(s->stream, m->evCopied[si], 0));
+    demosaic_launch(s->stream, slot, (char*)m->bgr + (size_t)m->pending * t->frame_bytes, H, W, s->p.in_dtype, cfa);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipEventRecord(m->evSlotFree[si], s->stream));
+    m->pending++;
+    if (m->pending == t->bcap) return mosaic_flush(s);
+    return MI_OK;
+}
+
+// mi_stack_wait_uploads over both kinds of pinned upload.  Each kind keeps its own ring of events, and the two copy streams
+// are not ordered against each other, so of the `max_outstanding` most recent uploads only the run of the most recent kind is
+// left in flight; every upload of the other kind is waited for.  Never fewer waits than the contract asks for.
+inline int mosaic_wait_uploads(mi_stack* s, int max_outstanding) {
+    MosaicStage* m = mstage(s);
+    const TiledState* t = tstate(s);
+    if (!m || m->up_no == 0) return tiled_wait_uploads(s, max_outstanding);
+    if (max_outstanding < 0) max_outstanding = 0;
+    const long frames_since = (t ? t->up_no : 0) - m->frames_up_seen;   // pinned BGR frames after the last pinned mosaic
+    const long keep_m = frames_since > 0 ? 0 : std::min<long>(max_outstanding, m->run);
+    const long keep_f = frames_since > 0 ? std::min<long>(max_outstanding, frames_since) : 0;
+    int rc = tiled_wait_uploads(s, (int)keep_f);
+    if (rc) return rc;
+    const long upto = m->up_no - keep_m;
+    if (upto <= 0 || keep_m >= MosaicStage::NUP) return MI_OK;
+    hipEvent_t ev = m->evUp[(upto - 1) % MosaicStage::NUP];
+    if (ev) MI_HIP(hipEventSynchronize(ev));
+    return MI_OK;
+}
+
+}  // namespace mi

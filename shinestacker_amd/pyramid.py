@@ -310,9 +310,11 @@ class PyramidStack(BaseStackAlgo):
         self.print_message(': pyramids fusion completed')
         return stack.finish()
 
-    def focus_stack_arrays(self, frames):
+    def focus_stack_arrays(self, frames, mosaic=None):
         """In-memory variant (no file I/O): `frames` is a sequence of H x W x 3 uint8/uint16
-        BGR arrays.  Same callbacks as focus_stack, one step per frame per pass."""
+        BGR arrays.  Same callbacks as focus_stack, one step per frame per pass.  `mosaic`: a
+        `demosaic.Cfa` -- the frames are then raw H x W Bayer mosaics, uploaded as they are and
+        demosaiced on the device (demosaic.py)."""
         _lib.require_device()
         n = len(frames)
         if n == 0:
@@ -321,11 +323,17 @@ class PyramidStack(BaseStackAlgo):
         self._set_dtype(meta[1])
         for i, fr in enumerate(frames):
             validate_image(fr, *meta)
+            if mosaic is not None:
+                from .demosaic import check_mosaic
+                check_mosaic(fr)
             if self.process is not None:
                 self._step(i)
         stack = self._handle(meta[0], meta[1])
         for i, fr in enumerate(frames):
-            stack.push_frame(fr)
+            if mosaic is None:
+                stack.push_frame(fr)
+            else:
+                stack.push_mosaic(fr, mosaic)
             if self.process is not None:
                 self._step(i + n)
         return stack.finish()

@@ -26,7 +26,10 @@ def two_stage(args):
       wall_s     stage 1 as it runs: frames in host memory, upload + kernels overlapped.
     `--pinned` (default): the host frames lie in pinned memory (mi_host_alloc -- what a decoder writing into
     `_lib.host_alloc` arrays gives) and are uploaded without the bounce copy; `--pageable`: ordinary NumPy arrays through the
-    three pinned bounce buffers and the copy-thread pool."""
+    three pinned bounce buffers and the copy-thread pool.
+    `--mosaic`: stage 1 once more in the same process, from the RGGB mosaics of the same frames (`mi_stack_push_mosaic`: a third
+    of the bytes over the link, demosaiced on the device behind the upload); the result line carries both stage-1 times, both
+    byte counts and the stage-1 time of the resident BGR frames (`compute_s`) under "mosaic"."""
     from shinestacker_amd import _lib as L
     from shinestacker_amd.pipeline import bunches_then_stack
     N, H, W = args.frames, args.height, args.width
@@ -93,6 +96,31 @@ def two_stage(args):
     resident()
     compute_s = time.perf_counter() - t0
     upload_s = pushed * per / pinned_rate
+    extra = {}
+    if args.mosaic:
+        from shinestacker_amd.demosaic import Cfa, mosaic_of
+        cfa = Cfa("RGGB")
+        mos = []
+        for fr in host:
+            m = mosaic_of(fr, cfa.pattern)
+            if not args.pageable:
+                pin = L.host_alloc((H, W), np.uint16)
+                pin[...] = m
+                m = pin
+            mos.append(m)
+
+        def run_mosaic():
+            info = {}
+            bunches_then_stack(lambda i: mos[i % ndist], N, H, W, np.uint16, out_dev=out.ptr, stacks=stacks, results_buf=results,
+                               info=info, zero_copy=not args.pageable, mosaic=cfa)
+            return info["stage1_s"], info["stage2_s"]
+        run_mosaic()
+        m1, m2 = run_mosaic()
+        _, b1, _ = run()        # BGR stage 1 once more, after the mosaic runs: the two are compared inside one process
+        extra = {"mosaic": {"stage1_seconds": m1, "stage2_seconds": m2, "bgr_stage1_seconds": s1, "bgr_stage1_seconds_again": b1,
+                            "host_to_device_bytes": pushed * per // 3, "bgr_host_to_device_bytes": pushed * per,
+                            "host_to_device_GB_per_s": pushed * per / 3 / m1 / 1e9, "upload_s": upload_s / 3, "compute_s": compute_s,
+                            "stage1_Mpixels_per_s": pushed * H * W / m1 / 1e6, "speedup_over_bgr_stage1": s1 / m1}}
     print(json.dumps({"config": f"{N} x {W}x{H} u16 frames from {'pageable' if args.pageable else 'PINNED'} host memory -> "
                                 f"{len(bunches)} bunches of <= 10 (overlap 2) -> one stack over the {len(bunches)} bunch results "
                                 f"(resident, uint16), one GPU",
@@ -103,7 +131,7 @@ def two_stage(args):
                       "overlap_efficiency": max(upload_s, compute_s) / s1,
                       "results_buffer_GB": per * nbunch / 1e9, "results_alloc_s": results_alloc_s,
                       "stage1_handles": nst - 1, "upload_path": "bounce copy (3 pinned buffers, copy-thread pool)" if args.pageable else
-                                     "zero-copy from pinned frames (mi_stack_push_frame_pinned)"}))
+                                     "zero-copy from pinned frames (mi_stack_push_frame_pinned)", **extra}))
     for s_ in stacks:
         s_.close()
 
@@ -118,6 +146,7 @@ def main():
                          "the device, truncated to uint16 as the reference's intermediate files are -- fused once more "
                          "(pipeline.bunches_then_stack)")
     ap.add_argument("--one-handle", action="store_true", help="stage 1 on a single handle (no overlap across bunches)")
+    ap.add_argument("--mosaic", action="store_true", help="with --two-stage: stage 1 from the frames' raw mosaics as well")
     ap.add_argument("--pageable", action="store_true", help="host frames in ordinary (pageable) memory: the bounce-copy path")
     args = ap.parse_args()
     if args.two_stage:
