@@ -738,6 +738,44 @@ MI_API int mi_demosaic(int device, const void* host_mosaic, void* host_bgr, int 
  * take the synchronous route: upload, demosaic, push, wait. */
 MI_API int mi_stack_push_mosaic(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa, int pinned);
 
+/* ---- raw development around the demosaic: defect sites, colour matrix, tone curve (kernels_demosaic.hpp) ----
+ * Integer and exact like the demosaic, each step optional; tests/develop_restatement.py states it in NumPy.
+ *   step 0  defect sites, in place on the raw samples ahead of everything else: a listed site becomes (S + (k >> 1)) / k over
+ *           its k valid neighbours (y -+ 2, x) and (y, x -+ 2) -- the same colour, black level and gain; valid: inside the
+ *           image and not itself listed; k = 0 leaves the site.  Sites are linear indices y * width + x, int32, strictly
+ *           ascending, each < height * width.
+ *   step C  colour matrix on the demosaic's clamped output: matrix_q[3 i + j] = round(M[i][j] * 4096), i the output and j the
+ *           input channel, both in R, G, B order; out_i = clamp((sum_j matrix_q[3 i + j] * in_j + 2048) >> 12, 0, cfa.white),
+ *           arithmetic shift.  Per row sum_j |matrix_q[3 i + j]| <= 32767, so the sum fits int32.
+ *   step D  tone curve: out = tone[out], a table of 256 (MI_U8) or 65536 (MI_U16) entries of the frame's dtype. */
+enum { MI_DEVELOP_MATRIX = 1, MI_DEVELOP_TONE = 2 };
+typedef struct mi_develop {
+    int32_t flags;          /* MI_DEVELOP_* or-ed; 0: the plain demosaic                                    */
+    int32_t matrix_q[9];    /* step C, read when MI_DEVELOP_MATRIX is set                                   */
+    const void* dev_tone;   /* step D, device memory, read when MI_DEVELOP_TONE is set: it must stay valid  */
+                            /* until the kernels enqueued with it have run                                  */
+} mi_develop_t;
+/* MI_ERR_INVALID names the argument; every check comes before the first device call: null pointers, a flag without its
+ * table, the row-sum bound, height * width >= 2^31, n < 0 and, in the host form, a site >= height * width or a list that is
+ * not strictly ascending (the device forms take a valid list as their precondition; a kernel leaves a site outside the
+ * image alone).  mi_mosaic_defects_device: step 0 in place on `dev_mosaic`, enqueued on `stream`, not waited for; n == 0 (then
+ * dev_sites may be null) enqueues nothing.  mi_develop_device: steps A to D, `dev_mosaic` is only read; enqueued, not waited
+ * for.  mi_develop: the host form -- uploads, runs steps 0 to D, downloads and waits; matrix_q (9 ints) or NULL, host_tone
+ * (the table in host memory) or NULL, host_sites (n ints) or NULL with n == 0. */
+MI_API int mi_mosaic_defects_device(int device, void* stream, void* dev_mosaic, int height, int width, int dtype,
+                                    const int32_t* dev_sites, int n);
+MI_API int mi_develop_device(int device, void* stream, const void* dev_mosaic, void* dev_bgr, int height, int width, int dtype,
+                             const mi_cfa_t* cfa, const mi_develop_t* develop);
+MI_API int mi_develop(int device, const void* host_mosaic, void* host_bgr, int height, int width, int dtype, const mi_cfa_t* cfa,
+                      const int32_t* matrix_q, const void* host_tone, const int32_t* host_sites, int n);
+/* mi_stack_push_mosaic with development: step 0 runs on the handle's stream behind the mosaic's upload, in place on the
+ * stage's device slot, and the developed demosaic follows it.  `develop` is copied by the call; its dev_tone and `dev_sites`
+ * (device memory, n_sites ints, NULL with 0) are read by the queued kernels and must stay valid until the frame is fused
+ * (mi_stack_sync, mi_stack_finish, mi_stack_reset or the handle's destruction).  Plain and developed pushes may mix on one
+ * handle, frame by frame.  Everything else as mi_stack_push_mosaic. */
+MI_API int mi_stack_push_mosaic_developed(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa,
+                                          const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

@@ -59,6 +59,14 @@ class CfaStruct(C.Structure):
     _fields_ = [("pattern", C.c_int32), ("black", C.c_int32 * 4), ("gain_q", C.c_uint32 * 4), ("white", C.c_int32)]
 
 
+MI_DEVELOP_MATRIX, MI_DEVELOP_TONE = 1, 2
+
+
+class DevelopStruct(C.Structure):
+    """mi_develop_t: what the developed demosaic kernel sees of a demosaic.Develop"""
+    _fields_ = [("flags", C.c_int32), ("matrix_q", C.c_int32 * 9), ("dev_tone", C.c_void_p)]
+
+
 class DepthMapParams(C.Structure):
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32),
                 ("map_type", C.c_int32), ("energy", C.c_int32), ("kernel_size", C.c_int32),
@@ -238,6 +246,13 @@ SIGNATURES = {
     "mi_demosaic_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct)]),
     "mi_demosaic": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct)]),
     "mi_stack_push_mosaic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CfaStruct), C.c_int]),
+    "mi_mosaic_defects_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "mi_develop_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct),
+                                    C.POINTER(DevelopStruct)]),
+    "mi_develop": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct), C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_int]),
+    "mi_stack_push_mosaic_developed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CfaStruct), C.POINTER(DevelopStruct),
+                                                 C.c_void_p, C.c_int, C.c_int]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }
@@ -471,6 +486,7 @@ class Stack:
         check(lib.mi_stack_create(C.byref(h), C.byref(p)))
         self._h = h
         self._inflight = []     # pinned frames whose zero-copy upload may still be running (push_frame(zero_copy=True))
+        self._develops = []     # every demosaic.Develop a queued kernel may still read (push_mosaic(develop=))
         n = C.c_int()
         check(lib.mi_stack_levels(self._h, C.byref(n)))
         self.levels = n.value
@@ -482,6 +498,7 @@ class Stack:
             load().mi_stack_destroy(self._h)   # waits for the handle's streams: no upload reads a pinned frame any more
             self._h = None
         self._inflight = []
+        self._develops = []
 
     def __del__(self):
         try:
@@ -498,6 +515,7 @@ class Stack:
     def reset(self):
         check(load().mi_stack_reset(self._h))   # synchronises the handle: every upload has completed
         self._inflight = []
+        self._develops = []     # ... and every kernel that read a Develop's device tables
 
     # -- geometry
     def level_shape(self, level):
@@ -550,24 +568,38 @@ class Stack:
                 check(rc)
         check(load().mi_stack_push_frame(self._h, a.ctypes.data, 0))
 
-    def push_mosaic(self, mosaic, cfa, zero_copy=False):
+    def push_mosaic(self, mosaic, cfa, zero_copy=False, develop=None):
         """Push one host frame as its raw Bayer mosaic (H x W samples of the handle's input dtype, `cfa`: a demosaic.Cfa): a
         third of push_frame's bytes cross the host link, and the frame is demosaiced on the device behind its upload.  Frames
         are fused in call order, whichever of push_frame / push_mosaic / push_frames_device brought them.  `zero_copy` as in
-        push_frame."""
+        push_frame.  `develop`: a demosaic.Develop -- defect sites, colour matrix and tone curve around the demosaic; the
+        handle keeps the object (the queued kernels read its device tables) until finish, reset, sync or close.  None: the
+        plain push, exactly the calls it makes without this argument."""
         a = np.asarray(mosaic)
         if a.shape != (self.height, self.width):
             raise ValueError(f"mosaic shape {a.shape} != {(self.height, self.width)}")
         if a.dtype != self.in_dtype:
             raise ValueError(f"mosaic dtype {a.dtype} != {self.in_dtype}")
         c = cfa.struct(self.in_dtype)
+        if develop is None:
+            def push(ptr, stride, pinned):
+                return load().mi_stack_push_mosaic(self._h, ptr, stride, C.byref(c), pinned)
+        else:
+            from .demosaic import check_develop
+            d, sites, n_sites = check_develop(develop).prepared(a.shape, self.in_dtype, self.device)
+            self._develops = getattr(self, "_develops", [])
+            if not any(x is develop for x in self._develops):
+                self._develops.append(develop)
+
+            def push(ptr, stride, pinned):
+                return load().mi_stack_push_mosaic_developed(self._h, ptr, stride, C.byref(c), C.byref(d), sites, n_sites, pinned)
         if not a.flags.c_contiguous:
             if a.strides[1] == a.itemsize and a.strides[0] > 0:
-                check(load().mi_stack_push_mosaic(self._h, a.ctypes.data, a.strides[0], C.byref(c), 0))
+                check(push(a.ctypes.data, a.strides[0], 0))
                 return
             a = np.ascontiguousarray(a)
         if zero_copy and is_pinned(a):
-            rc = load().mi_stack_push_mosaic(self._h, a.ctypes.data, 0, C.byref(c), 1)
+            rc = push(a.ctypes.data, 0, 1)
             if rc == MI_OK:
                 self._inflight.append(a)
                 if len(self._inflight) > 64:
@@ -575,7 +607,7 @@ class Stack:
                 return
             if rc != MI_ERR_INVALID:     # MI_ERR_INVALID: the library does not see pinned memory there (stale record)
                 check(rc)
-        check(load().mi_stack_push_mosaic(self._h, a.ctypes.data, 0, C.byref(c), 0))
+        check(push(a.ctypes.data, 0, 0))
 
     def wait_uploads(self, max_outstanding=0):
         """block until at most `max_outstanding` of the pinned frames pushed so far are still being uploaded: a producer that
@@ -592,6 +624,7 @@ class Stack:
     def sync(self):
         check(load().mi_stack_sync(self._h))
         self._inflight = []
+        self._develops = []
 
     def sync_level(self, level):
         """wait until the state of `level` covers every pushed frame (level 0: before the coarser levels finish)"""
@@ -601,6 +634,7 @@ class Stack:
         out = np.empty((self.height, self.width, 3), self.out_dtype)
         check(load().mi_stack_finish(self._h, out.ctypes.data, 0))
         self._inflight = []      # the result is on the host: every upload it depends on has completed
+        self._develops = []
         return out
 
     def finish_device(self, dev_ptr=None):

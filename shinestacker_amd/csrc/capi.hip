@@ -1696,6 +1696,88 @@ int mi_stack_push_mosaic(mi_stack_t* s, const void* host_mosaic, size_t row_stri
     return mosaic_push(s, host_mosaic, row_stride_bytes, *cfa, pinned && async);
 }
 
+// ---------------------------------------------------------------- raw development: defect sites, colour matrix, tone curve
+int mi_mosaic_defects_device(int device, void* stream, void* dev_mosaic, int height, int width, int dtype, const int32_t* dev_sites,
+                             int n) {
+    if (!dev_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    if (height < 2 || width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic (got %dx%d)", width, height);
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16 for a mosaic (got %d)", dtype);
+    int rc = sites_check(dev_sites, n, height, width);
+    if (rc) return rc;
+    if (n == 0) return MI_OK;
+    MI_HIP(hipSetDevice(device));
+    defects_launch((hipStream_t)stream, dev_mosaic, height, width, dtype, dev_sites, n);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_develop_device(int device, void* stream, const void* dev_mosaic, void* dev_bgr, int height, int width, int dtype,
+                      const mi_cfa_t* cfa, const mi_develop_t* develop) {
+    int rc = demosaic_check(dev_mosaic, dev_bgr, height, width, dtype, cfa);
+    if (rc || (rc = develop_check(develop))) return rc;
+    MI_HIP(hipSetDevice(device));
+    develop_launch((hipStream_t)stream, dev_mosaic, dev_bgr, height, width, dtype, *cfa, *develop);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_develop(int device, const void* host_mosaic, void* host_bgr, int height, int width, int dtype, const mi_cfa_t* cfa,
+               const int32_t* matrix_q, const void* host_tone, const int32_t* host_sites, int n) {
+    int rc = demosaic_check(host_mosaic, host_bgr, height, width, dtype, cfa);
+    if (rc || (matrix_q && (rc = matrix_check(matrix_q))) || (rc = sites_check(host_sites, n, height, width)) ||
+        (rc = host_sites_check(host_sites, n, height, width)))
+        return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t isz = dtype_size(dtype), nb = (size_t)height * width * isz;
+    mi_develop_t d{};
+    if (matrix_q) {
+        d.flags |= MI_DEVELOP_MATRIX;
+        memcpy(d.matrix_q, matrix_q, sizeof(d.matrix_q));
+    }
+    DevScratch tmp(nullptr);
+    void *src = nullptr, *dst = nullptr, *tone = nullptr;
+    int32_t* sites = nullptr;
+    if ((rc = tmp.upload(&src, host_mosaic, nb)) || (rc = tmp.alloc(&dst, nb * 3))) return rc;
+    if (host_tone) {
+        if ((rc = tmp.upload(&tone, host_tone, (dtype == MI_U8 ? 256 : 65536) * isz))) return rc;
+        d.flags |= MI_DEVELOP_TONE;
+        d.dev_tone = tone;
+    }
+    if (n > 0 && ((rc = tmp.upload(&sites, host_sites, (size_t)n * sizeof(int32_t))) ||
+                  (rc = mi_mosaic_defects_device(device, nullptr, src, height, width, dtype, sites, n))))
+        return rc;
+    if ((rc = mi_develop_device(device, nullptr, src, dst, height, width, dtype, cfa, &d))) return rc;
+    return tmp.download(host_bgr, dst, nb * 3);
+}
+
+int mi_stack_push_mosaic_developed(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa,
+                                   const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!host_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
+    if ((rc = cfa_check(cfa, s->p.in_dtype)) || (rc = develop_check(develop)) ||
+        (rc = sites_check(dev_sites, n_sites, s->p.height, s->p.width)))
+        return rc;
+    const size_t rb = (size_t)s->p.width * dtype_size(s->p.in_dtype);
+    if (row_stride_bytes == 0) row_stride_bytes = rb;
+    if (row_stride_bytes < rb) return fail(MI_ERR_INVALID, "row stride smaller than a row");
+    if (s->idx_exported) return fail(MI_ERR_STATE, "the winner indices were exported (index stride > 1): reset the handle before pushing more frames");
+    if (s->finished) return fail(MI_ERR_STATE, "push after finish; call mi_stack_reset first");
+    MI_HIP(hipSetDevice(s->p.device));
+    const bool async = s->p.impl == MI_IMPL_TILED && !s->f64;
+    if (pinned && async) {
+        if (row_stride_bytes != rb) return fail(MI_ERR_INVALID, "a pinned mosaic must have contiguous rows");
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, host_mosaic) != hipSuccess || at.type != hipMemoryTypeHost) {
+            (void)hipGetLastError();
+            return fail(MI_ERR_INVALID, "mi_stack_push_mosaic_developed: the mosaic is not in pinned host memory (mi_host_alloc / mi_host_register)");
+        }
+    }
+    const mi_develop_t d = *develop;
+    return mosaic_push(s, host_mosaic, row_stride_bytes, *cfa, pinned && async, &d, dev_sites, n_sites);
+}
+
 int mi_host_alloc(void** ptr, size_t bytes) {
     if (!ptr || !bytes) return fail(MI_ERR_INVALID, "bad argument");
     MI_HIP(hipHostMalloc(ptr, bytes, hipHostMallocPortable));

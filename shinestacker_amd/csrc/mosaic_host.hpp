@@ -14,6 +14,9 @@
 //               to the border stream, and tiled_push joins the side streams back into s->stream, so the next demosaic into
 //               `bgr` is ordered behind every reader of the batch -- the two-event handshake tiled_flush keeps with its ring,
 //               here evCopied / evSlotFree per slot and the stream's own order for `bgr`.
+//   develop     mi_stack_push_mosaic_developed: the defect kernel (step 0) on s->stream behind evCopied[slot], in place on the
+//               slot, then the developed demosaic; evSlotFree[slot] follows both, so the copy stream never overwrites a slot
+//               that step 0 still writes.  The caller's device tables (tone, sites) are read by those kernels.
 //   order       frames are fused in call order: the first mosaic after host BGR frames flushes the ring (mosaic_push), and
 //               every call that takes frames of another kind or reads state flushes this stage first (stack_flush in capi.hip).
 #pragma once
@@ -56,6 +59,39 @@ inline int cfa_check(const mi_cfa_t* cfa, int dtype) {
         if (cfa->gain_q[k] > 65535u) return fail(MI_ERR_INVALID, "cfa gain_q[%d] must be <= 65535 (got %u)", k, cfa->gain_q[k]);
     }
     if (cfa->white < 1 || cfa->white > maxv) return fail(MI_ERR_INVALID, "cfa white must be in [1, %d] (got %d)", maxv, cfa->white);
+    return MI_OK;
+}
+
+// argument checks of the development entry points (mi_develop*, mi_mosaic_defects_device, mi_stack_push_mosaic_developed):
+// no device call.  The kernel accumulates step C in int32: that holds while a row's sum of |matrix_q| is at most 32767.
+inline int matrix_check(const int32_t* matrix_q) {
+    for (int i = 0; i < 3; ++i) {
+        int64_t sum = 0;
+        for (int j = 0; j < 3; ++j) sum += std::llabs((long long)matrix_q[3 * i + j]);
+        if (sum > 32767) return fail(MI_ERR_INVALID, "matrix_q row %d: the sum of |entries| must be <= 32767 (got %lld)", i, (long long)sum);
+    }
+    return MI_OK;
+}
+inline int develop_check(const mi_develop_t* d) {
+    if (!d) return fail(MI_ERR_INVALID, "null develop");
+    if (d->flags & ~(MI_DEVELOP_MATRIX | MI_DEVELOP_TONE)) return fail(MI_ERR_INVALID, "unknown develop flags %d", d->flags);
+    if ((d->flags & MI_DEVELOP_TONE) && !d->dev_tone) return fail(MI_ERR_INVALID, "develop: MI_DEVELOP_TONE is set and dev_tone is null");
+    if (d->flags & MI_DEVELOP_MATRIX) return matrix_check(d->matrix_q);
+    return MI_OK;
+}
+inline int sites_check(const int32_t* sites, int n, int height, int width) {
+    if (n < 0) return fail(MI_ERR_INVALID, "the number of sites must be >= 0 (got %d)", n);
+    if (n > 0 && !sites) return fail(MI_ERR_INVALID, "null sites");
+    if (height > 0 && width > 0 && (uint64_t)height * (uint64_t)width >= (1ull << 31)) return fail(MI_ERR_INVALID, "height x width too large");
+    return MI_OK;
+}
+// a list in host memory: every site inside the image, strictly ascending
+inline int host_sites_check(const int32_t* sites, int n, int height, int width) {
+    const int64_t npx = (int64_t)height * width;
+    for (int i = 0; i < n; ++i) {
+        if (sites[i] < 0 || sites[i] >= npx) return fail(MI_ERR_INVALID, "sites[%d] = %d lies outside the %d x %d image", i, sites[i], width, height);
+        if (i && sites[i] <= sites[i - 1]) return fail(MI_ERR_INVALID, "sites must be strictly ascending (sites[%d] = %d follows %d)", i, sites[i], sites[i - 1]);
+    }
     return MI_OK;
 }
 
@@ -120,8 +156,11 @@ inline int mosaic_flush(mi_stack* s) {
     return dispatch_push(s, m->bgr, n, t->frame_bytes);
 }
 
-// One host mosaic (arguments checked by mi_stack_push_mosaic): stage it, start upload and demosaic, return.
-inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t& cfa, bool pinned) {
+// One host mosaic (arguments checked by mi_stack_push_mosaic / mi_stack_push_mosaic_developed): stage it, start upload and
+// demosaic, return.  `dev`: development (null: the plain demosaic, exactly the launches of a handle that never heard of it);
+// with `n_sites` > 0 the defect kernel runs in place on the slot, behind the upload and ahead of the demosaic.
+inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t& cfa, bool pinned,
+                       const mi_develop_t* dev = nullptr, const int32_t* dev_sites = nullptr, int n_sites = 0) {
     TiledState* t = tstate(s);
     int rc = tiled_flush(s);   // call order: host BGR frames staged before this mosaic are fused first
     if (rc) return rc;
@@ -132,7 +171,10 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     if (s->p.impl != MI_IMPL_TILED) {
         // float-64 and MI_IMPL_SIMPLE handles: upload, demosaic, push, wait -- one frame at a time on the handle's stream
         MI_HIP(hipMemcpy2DAsync(m->slot[0], rb, host_mosaic, row_stride_bytes, rb, H, hipMemcpyHostToDevice, s->stream));
-        demosaic_launch(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa);
+        if (dev) {
+            defects_launch(s->stream, m->slot[0], H, W, s->p.in_dtype, dev_sites, n_sites);
+            develop_launch(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa, *dev);
+        } else demosaic_launch(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa);
         MI_HIP(hipGetLastError());
         if ((rc = dispatch_push(s, s->frame_dev, 1, t->frame_bytes))) return rc;
         MI_HIP(hipStreamSynchronize(s->stream));
@@ -175,7 +217,11 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     }
     MI_HIP(hipEventRecord(m->evCopied[si], m->stc));
     MI_HIP(hipStreamWaitEvent(s->stream, m->evCopied[si], 0));
-    demosaic_launch(s->stream, slot, (char*)m->bgr + (size_t)m->pending * t->frame_bytes, H, W, s->p.in_dtype, cfa);
+    void* frame = (char*)m->bgr + (size_t)m->pending * t->frame_bytes;
+    if (dev) {
+        defects_launch(s->stream, slot, H, W, s->p.in_dtype, dev_sites, n_sites);
+        develop_launch(s->stream, slot, frame, H, W, s->p.in_dtype, cfa, *dev);
+    } else demosaic_launch(s->stream, slot, frame, H, W, s->p.in_dtype, cfa);
     MI_HIP(hipGetLastError());
     MI_HIP(hipEventRecord(m->evSlotFree[si], s->stream));
     m->pending++;

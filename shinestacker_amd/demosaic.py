@@ -12,7 +12,17 @@ The arithmetic is integer and exact, the same for uint8 and uint16 (tests/demosa
     step B             Malvar, He, Cutler (ICASSP 2004), the 5 x 5 linear kernels MATLAB's `demosaic` uses, coefficients times 2:
                        out = clamp((sum + 8) >> 4, 0, white), BORDER_REFLECT_101 on the mosaic, H x W x 3 BGR of the input dtype
 
-There is no CPU path: without a GPU or the library `debayer` and its kin raise DeviceError.  `mosaic_of` is host NumPy.
+Raw development around it, `Develop`, each step optional and as exact (tests/develop_restatement.py is the definition):
+
+    step 0, defect sites   on the raw samples, ahead of step A: a listed site becomes (S + (k >> 1)) // k over its k valid
+                           neighbours (y -+ 2, x), (y, x -+ 2) -- same colour, black level and gain; valid: inside the image and
+                           not itself listed; k = 0 leaves the site
+    step C, colour matrix  on step B's output: M_q = round(M * 4096), rows and columns in R, G, B order,
+                           out_i = clamp((sum_j M_q[i][j] * in_j + 2048) >> 12, 0, white); per row sum_j |M_q[i][j]| <= 32767
+    step D, tone curve     out = tone[out], a table of maxv + 1 entries of the frame's dtype (`srgb_tone`, `gamma_tone`)
+
+There is no CPU path: without a GPU or the library `debayer` and its kin raise DeviceError.  `mosaic_of`, `srgb_tone`,
+`gamma_tone` and `defects_from_dark` are host NumPy.
 """
 import math
 
@@ -127,32 +137,246 @@ def mosaic_of(bgr, pattern="RGGB"):
     return out
 
 
-def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None):
-    """debayer() for a mosaic resident in HBM: `dev_mosaic` (h x w) -> `dev_bgr` (h x w x 3).  Queued on `stream`, not waited for."""
+MATRIX_ONE = 4096                               # M_q of 1.0
+MATRIX_ROW_BOUND = 32767                        # per row, sum |M_q|: the kernel's int32 accumulator holds
+
+
+def _tone_from(f, dtype, white):
+    dt = _dtype(dtype)
+    maxv = int(np.iinfo(dt).max)
+    if white is None:
+        white = maxv
+    if isinstance(white, bool) or not isinstance(white, (int, np.integer)) or not 1 <= int(white) <= maxv:
+        raise InvalidOptionError("white", white, f"the white level is an int in [1, {maxv}]")
+    x = np.minimum(np.arange(maxv + 1, dtype=np.float64), float(white)) / float(white)
+    return np.floor(maxv * f(x) + 0.5).astype(dt)
+
+
+def srgb_tone(dtype, white=None):
+    """The sRGB transfer curve as a tone table of `dtype`: round(maxv * srgb(i / white)), i > white as white (float64 NumPy)."""
+    return _tone_from(lambda x: np.where(x <= 0.0031308, 12.92 * x, 1.055 * np.power(x, 1.0 / 2.4) - 0.055), dtype, white)
+
+
+def gamma_tone(dtype, gamma, white=None):
+    """A pure power law as a tone table of `dtype`: round(maxv * (i / white) ** (1 / gamma)), i > white as white."""
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)) or not math.isfinite(gamma) or gamma <= 0:
+        raise InvalidOptionError("gamma", gamma, "a positive finite number is expected")
+    return _tone_from(lambda x: np.power(x, 1.0 / float(gamma)), dtype, white)
+
+
+def defects_from_dark(dark_mosaic, threshold):
+    """The sites of a dark frame (an H x W mosaic taken with the shutter closed) above `threshold`, as an (n, 2) array of
+    (y, x) in ascending order: what Develop(defects=) takes.  Host NumPy."""
+    a = check_mosaic(dark_mosaic)
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not math.isfinite(threshold):
+        raise InvalidOptionError("threshold", threshold, "a finite number is expected")
+    return np.argwhere(a > threshold).astype(np.int32)
+
+
+class Develop:
+    """Raw development around the demosaic: defect sites before it, colour matrix and tone curve behind it.
+
+    matrix   3 x 3 floats, output = matrix @ (R, G, B) of the camera; quantised once, here, as round(m * 4096); the sum of
+             |quantised entries| of a row is at most 32767 (a little under 8.0)
+    tone     a table of 256 uint8 / 65536 uint16 entries, or "srgb", or a float gamma (`srgb_tone`, `gamma_tone` over the
+             dtype's full range, resolved per dtype at first use)
+    defects  an (n, 2) int array of (y, x), or a boolean H x W mask; sorted, made unique and checked against the frame at
+             first use
+
+    The tone table and the site list are uploaded per device (and dtype, frame shape) at first use and held until close().
+    Kernels queued by a Stack read them: the Stack keeps the object until finish / reset / sync / close, and close() here
+    must not come before that."""
+
+    def __init__(self, matrix=None, tone=None, defects=None):
+        self.matrix = self.matrix_q = None
+        if matrix is not None:
+            try:
+                m = np.array(matrix, dtype=np.float64)
+            except (TypeError, ValueError):
+                m = None
+            if m is None or m.shape != (3, 3) or not np.isfinite(m).all():
+                raise InvalidOptionError("matrix", matrix, "3 x 3 finite numbers are expected")
+            q = np.floor(m * float(MATRIX_ONE) + 0.5)
+            if (np.abs(q).sum(axis=1) > MATRIX_ROW_BOUND).any():
+                raise InvalidOptionError("matrix", matrix, f"per row, the sum of |round(m * 4096)| must be <= {MATRIX_ROW_BOUND}")
+            self.matrix, self.matrix_q = m, tuple(int(v) for v in q.reshape(9))
+        self.tone = None
+        if tone is not None:
+            if isinstance(tone, str):
+                if tone.lower() != "srgb":
+                    raise InvalidOptionError("tone", tone, 'a table, "srgb" or a float gamma is expected')
+                self.tone = "srgb"
+            elif isinstance(tone, (int, float, np.integer, np.floating)) and not isinstance(tone, bool):
+                gamma_tone(np.uint8, tone)      # (validates the gamma)
+                self.tone = float(tone)
+            else:
+                t = np.asarray(tone)
+                _dtype(t.dtype)
+                if t.ndim != 1 or t.shape[0] != int(np.iinfo(t.dtype).max) + 1:
+                    raise InvalidOptionError("tone", t.shape, f"a {t.dtype} table has {int(np.iinfo(t.dtype).max) + 1} entries")
+                self.tone = np.ascontiguousarray(t).copy()
+        self.defects = None
+        if defects is not None:
+            d = np.asarray(defects)
+            if d.dtype == np.bool_ and d.ndim == 2:
+                self.defects = d.copy()
+            elif d.ndim == 2 and d.shape[1] == 2 and (d.dtype.kind in "iu" or d.size == 0):
+                self.defects = d.astype(np.int64)
+            else:
+                raise InvalidOptionError("defects", d.shape, "an (n, 2) int array of (y, x) or a boolean H x W mask is expected")
+        self._tones = {}        # dtype -> host table
+        self._sites = {}        # (h, w) -> host int32 list
+        self._dev = {}          # (device, "tone", dtype) / (device, "sites", h, w) -> _lib.DeviceBuffer
+
+    def __repr__(self):
+        tone = self.tone if not isinstance(self.tone, np.ndarray) else f"<{self.tone.dtype} table>"
+        n = None if self.defects is None else (int(self.defects.sum()) if self.defects.dtype == np.bool_ else len(self.defects))
+        return f"Develop(matrix={None if self.matrix is None else self.matrix.tolist()}, tone={tone}, defects={n})"
+
+    def tone_table(self, dtype):
+        """the host tone table for frames of `dtype`, or None"""
+        dt = _dtype(dtype)
+        if self.tone is None:
+            return None
+        if isinstance(self.tone, np.ndarray):
+            if self.tone.dtype != dt:
+                raise BitDepthError(dt, self.tone.dtype)
+            return self.tone
+        if dt not in self._tones:
+            self._tones[dt] = srgb_tone(dt) if self.tone == "srgb" else gamma_tone(dt, self.tone)
+        return self._tones[dt]
+
+    def sites(self, shape):
+        """the defect sites of an H x W frame as linear indices y * W + x: int32, ascending, unique (empty without defects)"""
+        h, w = int(shape[0]), int(shape[1])
+        if (h, w) not in self._sites:
+            if self.defects is None:
+                s = np.zeros(0, np.int64)
+            elif self.defects.dtype == np.bool_:
+                if self.defects.shape != (h, w):
+                    raise InvalidOptionError("defects", self.defects.shape, f"the mask of a {h} x {w} frame has its shape")
+                s = np.flatnonzero(self.defects)
+            else:
+                y, x = self.defects[:, 0], self.defects[:, 1]
+                if len(y) and (y.min() < 0 or y.max() >= h or x.min() < 0 or x.max() >= w):
+                    raise InvalidOptionError("defects", (int(y.max()), int(x.max())), f"a site lies outside the {h} x {w} frame")
+                s = np.unique(y * w + x)
+            if h * w >= 2 ** 31:
+                raise InvalidOptionError("defects", (h, w), "height x width must be below 2^31")
+            self._sites[(h, w)] = s.astype(np.int32)
+        return self._sites[(h, w)]
+
+    def host_args(self, shape, dtype):
+        """(matrix_q as int32[9] or None, tone table or None, sites): what the host form mi_develop takes"""
+        mq = None if self.matrix_q is None else (_lib.C.c_int32 * 9)(*self.matrix_q)
+        return mq, self.tone_table(dtype), self.sites(shape)
+
+    def prepared(self, shape, dtype, device=0):
+        """(mi_develop_t, device pointer of the sites or None, their number) for H x W frames of `dtype` on `device`; uploads
+        the tone table and the site list on first use"""
+        dt = _dtype(dtype)
+        d = _lib.DevelopStruct()
+        if self.matrix_q is not None:
+            d.flags |= _lib.MI_DEVELOP_MATRIX
+            d.matrix_q = (_lib.C.c_int32 * 9)(*self.matrix_q)
+        tone = self.tone_table(dt)
+        sites = self.sites(shape)
+        if tone is not None:
+            d.flags |= _lib.MI_DEVELOP_TONE
+            d.dev_tone = self._resident((device, "tone", dt), tone).ptr
+        ptr = self._resident((device, "sites", int(shape[0]), int(shape[1])), sites).ptr if len(sites) else None
+        return d, ptr, len(sites)
+
+    def _resident(self, key, arr):
+        if key not in self._dev:
+            _lib.require_device()
+            buf = _lib.DeviceBuffer(arr.nbytes, key[0])
+            buf.upload(arr)
+            self._dev[key] = buf
+        return self._dev[key]
+
+    def close(self):
+        """free the device tables (not before every kernel queued with them has run: Stack.finish / sync / reset / close)"""
+        for buf in self._dev.values():
+            buf.free()
+        self._dev = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def check_develop(develop):
+    if not isinstance(develop, Develop):
+        raise InvalidOptionError("develop", develop, "a shinestacker_amd.demosaic.Develop is expected")
+    return develop
+
+
+def require_mosaic(mosaic, develop):
+    """`develop=` only means something beside `mosaic=`"""
+    if develop is not None:
+        if mosaic is None:
+            raise InvalidOptionError("develop", develop, "develop= needs mosaic=: only raw mosaics are developed")
+        check_develop(develop)
+
+
+def defects_device(dev_mosaic, h, w, dtype, develop, device=0, stream=None):
+    """Step 0 alone, in place on a mosaic resident in HBM.  Queued on `stream`, not waited for."""
+    dt = _dtype(dtype)
+    _, sites, n = check_develop(develop).prepared((h, w), dt, device)
+    if n:
+        _lib.check(_lib.load().mi_mosaic_defects_device(device, stream, dev_mosaic, int(h), int(w), _lib.DTYPE_CODE[dt], sites, n))
+
+
+def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None, develop=None):
+    """debayer() for a mosaic resident in HBM: `dev_mosaic` (h x w) -> `dev_bgr` (h x w x 3).  Queued on `stream`, not waited
+    for.  `develop`: a Develop -- its defect sites are repaired IN PLACE in `dev_mosaic` first (no other site is written),
+    then colour matrix and tone curve ride on the demosaic; its device tables must outlive the queued kernels."""
     dt = _dtype(dtype)
     c = _check_cfa(cfa).struct(dt)
     if h < 2 or w < 2:
         raise InvalidOptionError("mosaic", (h, w), "a mosaic is an H x W plane with H, W >= 2")
-    _lib.require_device()
-    _lib.check(_lib.load().mi_demosaic_device(device, stream, dev_mosaic, dev_bgr, int(h), int(w), _lib.DTYPE_CODE[dt],
-                                              _lib.C.byref(c)))
+    if develop is None:
+        _lib.require_device()
+        _lib.check(_lib.load().mi_demosaic_device(device, stream, dev_mosaic, dev_bgr, int(h), int(w), _lib.DTYPE_CODE[dt],
+                                                  _lib.C.byref(c)))
+        return
+    d, sites, n = check_develop(develop).prepared((h, w), dt, device)
+    lib = _lib.load()
+    if n:
+        _lib.check(lib.mi_mosaic_defects_device(device, stream, dev_mosaic, int(h), int(w), _lib.DTYPE_CODE[dt], sites, n))
+    _lib.check(lib.mi_develop_device(device, stream, dev_mosaic, dev_bgr, int(h), int(w), _lib.DTYPE_CODE[dt], _lib.C.byref(c),
+                                     _lib.C.byref(d)))
 
 
-def debayer(mosaic, cfa, device=0):
-    """H x W uint8 / uint16 mosaic -> H x W x 3 BGR array of the same dtype."""
+def debayer(mosaic, cfa, develop=None, device=0):
+    """H x W uint8 / uint16 mosaic -> H x W x 3 BGR array of the same dtype.  `develop`: a Develop (defect sites, colour
+    matrix, tone curve); None: the plain demosaic."""
     a = np.ascontiguousarray(check_mosaic(mosaic))
     c = _check_cfa(cfa).struct(a.dtype)
+    if develop is not None:
+        mq, tone, sites = check_develop(develop).host_args(a.shape, a.dtype)
     _lib.require_device()
     out = np.empty(a.shape + (3,), a.dtype)
-    _lib.check(_lib.load().mi_demosaic(device, a.ctypes.data, out.ctypes.data, a.shape[0], a.shape[1], _lib.DTYPE_CODE[a.dtype],
-                                       _lib.C.byref(c)))
+    if develop is None:
+        _lib.check(_lib.load().mi_demosaic(device, a.ctypes.data, out.ctypes.data, a.shape[0], a.shape[1], _lib.DTYPE_CODE[a.dtype],
+                                           _lib.C.byref(c)))
+        return out
+    _lib.check(_lib.load().mi_develop(device, a.ctypes.data, out.ctypes.data, a.shape[0], a.shape[1], _lib.DTYPE_CODE[a.dtype],
+                                      _lib.C.byref(c), mq, None if tone is None else tone.ctypes.data,
+                                      sites.ctypes.data if len(sites) else None, len(sites)))
     return out
 
 
-def debayer_frames_device(mosaics, dev_out, cfa, device=0):
+def debayer_frames_device(mosaics, dev_out, cfa, device=0, develop=None):
     """Upload the n host mosaics (equal shape and dtype) and demosaic them side by side into `dev_out` (device pointer,
-    n x H x W x 3 of their dtype): exactly what pipeline.align_and_stack_device(dev_frames, ...) takes.  Waits for the device."""
+    n x H x W x 3 of their dtype): exactly what pipeline.align_and_stack_device(dev_frames, ...) takes.  Waits for the device.
+    `develop`: a Develop applied to every frame."""
     _check_cfa(cfa)
+    if develop is not None:
+        check_develop(develop)
     if len(mosaics) == 0:
         raise ValueError("no mosaics")
     first = check_mosaic(mosaics[0])
@@ -163,7 +387,10 @@ def debayer_frames_device(mosaics, dev_out, cfa, device=0):
     try:
         for i, m in enumerate(mosaics):
             stage.upload(check_mosaic(m, first.shape, first.dtype))
-            debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, first.dtype, cfa, device=device)
+            if develop is None:
+                debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, first.dtype, cfa, device=device)
+            else:
+                debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, first.dtype, cfa, device=device, develop=develop)
             # the stage is reused: the null stream's kernel must be through before the next (blocking) upload lands
             _lib.check(_lib.load().mi_device_synchronize(device))
     finally:

@@ -29,7 +29,10 @@ def two_stage(args):
     three pinned bounce buffers and the copy-thread pool.
     `--mosaic`: stage 1 once more in the same process, from the RGGB mosaics of the same frames (`mi_stack_push_mosaic`: a third
     of the bytes over the link, demosaiced on the device behind the upload); the result line carries both stage-1 times, both
-    byte counts and the stage-1 time of the resident BGR frames (`compute_s`) under "mosaic"."""
+    byte counts and the stage-1 time of the resident BGR frames (`compute_s`) under "mosaic".
+    `--develop` (with `--mosaic`): stage 1 a third time, the mosaics developed on the device (`mi_stack_push_mosaic_developed`:
+    camera matrix, sRGB curve, 10 000 defect sites), then the plain mosaic run again; the times sit beside each other under
+    "mosaic"."""
     from shinestacker_amd import _lib as L
     from shinestacker_amd.pipeline import bunches_then_stack
     N, H, W = args.frames, args.height, args.width
@@ -116,11 +119,31 @@ def two_stage(args):
             return info["stage1_s"], info["stage2_s"]
         run_mosaic()
         m1, m2 = run_mosaic()
+        developed = {}
+        if args.develop:
+            # stage 1 once more, developed: a camera matrix, the sRGB curve and 10 000 defect sites ride on the demosaic; then
+            # the plain mosaic run again, so that the two are compared inside one process and in both orders
+            from shinestacker_amd.demosaic import Develop
+            rng = np.random.default_rng(5)
+            sites = np.stack([rng.integers(0, H, 10000), rng.integers(0, W, 10000)], axis=1)
+            with Develop(matrix=[[1.8, -0.6, -0.2], [-0.3, 1.6, -0.3], [0.05, -0.55, 1.5]], tone="srgb", defects=sites) as dv:
+                def run_developed():
+                    info = {}
+                    bunches_then_stack(lambda i: mos[i % ndist], N, H, W, np.uint16, out_dev=out.ptr, stacks=stacks,
+                                       results_buf=results, info=info, zero_copy=not args.pageable, mosaic=cfa, develop=dv)
+                    return info["stage1_s"], info["stage2_s"]
+                run_developed()
+                d1, d2 = run_developed()
+                for s_ in stacks:
+                    s_.sync()
+            m1b, _ = run_mosaic()
+            developed = {"developed_stage1_seconds": d1, "developed_stage2_seconds": d2, "stage1_seconds_again": m1b,
+                         "developed_over_plain_stage1": d1 / m1, "defect_sites": len(dv.sites((H, W)))}
         _, b1, _ = run()        # BGR stage 1 once more, after the mosaic runs: the two are compared inside one process
         extra = {"mosaic": {"stage1_seconds": m1, "stage2_seconds": m2, "bgr_stage1_seconds": s1, "bgr_stage1_seconds_again": b1,
                             "host_to_device_bytes": pushed * per // 3, "bgr_host_to_device_bytes": pushed * per,
                             "host_to_device_GB_per_s": pushed * per / 3 / m1 / 1e9, "upload_s": upload_s / 3, "compute_s": compute_s,
-                            "stage1_Mpixels_per_s": pushed * H * W / m1 / 1e6, "speedup_over_bgr_stage1": s1 / m1}}
+                            "stage1_Mpixels_per_s": pushed * H * W / m1 / 1e6, "speedup_over_bgr_stage1": s1 / m1, **developed}}
     print(json.dumps({"config": f"{N} x {W}x{H} u16 frames from {'pageable' if args.pageable else 'PINNED'} host memory -> "
                                 f"{len(bunches)} bunches of <= 10 (overlap 2) -> one stack over the {len(bunches)} bunch results "
                                 f"(resident, uint16), one GPU",
@@ -147,6 +170,9 @@ def main():
                          "(pipeline.bunches_then_stack)")
     ap.add_argument("--one-handle", action="store_true", help="stage 1 on a single handle (no overlap across bunches)")
     ap.add_argument("--mosaic", action="store_true", help="with --two-stage: stage 1 from the frames' raw mosaics as well")
+    ap.add_argument("--develop", action="store_true",
+                    help="with --two-stage --mosaic: stage 1 once more with raw development (colour matrix, sRGB curve, defect "
+                         "sites) on the demosaic, beside the plain mosaic run")
     ap.add_argument("--pageable", action="store_true", help="host frames in ordinary (pageable) memory: the bounce-copy path")
     args = ap.parse_args()
     if args.two_stage:

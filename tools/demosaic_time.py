@@ -4,6 +4,14 @@ warm runs, beside a device-to-device copy that moves the same bytes (itemsize re
 that copy and the GB/s of the kernel's bytes.
 
     python tools/demosaic_time.py [--runs 20] [--uint8] [--small] [--json FILE]
+
+`--develop`: raw development instead (24 MP uint8 and 50 MP uint16, resident): the developed kernel with the colour matrix only,
+the tone table only and both (mi_develop_device), the defect kernel at 1 000 and at 100 000 sites (mi_mosaic_defects_device,
+which repairs the same mosaic in place over and over: the values settle, the work per launch does not change), and, in the same
+process on the same frame, the plain demosaic_mhc and a device copy of the same bytes.  The frame is uniform random -- the worst
+case for the uint16 tone table's gather -- and the tone variants run once more on a smooth scene with 1 % noise (", scene").  Same method for every line: hipEvents
+around 5 back-to-back launches, 3 warm-up launches, the median of `--runs` windows; the whole list is measured twice and the
+second pass is reported (the first warms clocks and caches).
 """
 import argparse
 import ctypes as C
@@ -22,6 +30,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--runs", type=int, default=20)
 ap.add_argument("--uint8", action="store_true", help="the two shapes at uint8 as well")
 ap.add_argument("--small", action="store_true", help="a 1 MP rehearsal of the whole script")
+ap.add_argument("--develop", action="store_true", help="time raw development: matrix, tone, both, the defect kernel; beside plain and copy")
 ap.add_argument("--json", default=None)
 a = ap.parse_args()
 L.require_device()
@@ -76,7 +85,67 @@ def measure(run):
 
 shapes = [("1 MP", 1000, 1000)] if a.small else [("24 MP", 4000, 6000), ("50 MP", 5792, 8640)]
 cfa = demosaic.Cfa("RGGB", black=256, gains=[1.9, 1.0, 1.0, 1.5])
-for dt in ([np.uint16, np.uint8] if a.uint8 else [np.uint16]):
+
+
+def develop_section():
+    """--develop: every variant on one resident frame per (shape, dtype), two passes, the second reported"""
+    camera = [[1.8, -0.6, -0.2], [-0.3, 1.6, -0.3], [0.05, -0.55, 1.5]]
+    cases = [("1 MP", 1000, 1000, np.uint8), ("1 MP", 1000, 1000, np.uint16)] if a.small else \
+        [("24 MP", 4000, 6000, np.uint8), ("50 MP", 5792, 8640, np.uint16)]
+    for name, h, w, dt in cases:
+        dt = np.dtype(dt)
+        cfa_d = demosaic.Cfa("RGGB", black=1 if dt.itemsize == 1 else 256, gains=[1.9, 1.0, 1.0, 1.5])
+        px = h * w
+        moved = px * 4 * dt.itemsize
+        rng = np.random.default_rng(px)
+        mosaic = L.DeviceBuffer(px * dt.itemsize)
+        mosaic.upload(rng.integers(0, int(np.iinfo(dt).max) + 1, size=(h, w)).astype(dt))
+        # ... and a smooth scene with 1 % noise: neighbouring pixels index neighbouring tone entries, which is what the uint16
+        # table's gather sees on a photograph (the uniform random mosaic is its worst case: 64 cache lines per wave and load)
+        mx = int(np.iinfo(dt).max)
+        scene = L.DeviceBuffer(px * dt.itemsize)
+        smooth = (0.5 + 0.3 * np.sin(np.arange(w) / 230.0)[None, :] * np.cos(np.arange(h) / 170.0)[:, None]) * mx
+        scene.upload(np.clip(smooth + rng.integers(-mx // 100 - 1, mx // 100 + 2, size=(h, w)), 0, mx).astype(dt))
+        del smooth
+        out = L.DeviceBuffer(px * 3 * dt.itemsize)
+        scratch = L.DeviceBuffer(moved)
+        half = moved // 2
+        code = L.DTYPE_CODE[dt]
+
+        def sites(n):
+            return np.stack(np.divmod(np.unique(rng.integers(0, px, size=n)), w), axis=1)   # (a handful fewer where draws repeat)
+
+        devs = {"matrix": demosaic.Develop(matrix=camera), "tone": demosaic.Develop(tone="srgb"),
+                "matrix + tone": demosaic.Develop(matrix=camera, tone="srgb"),
+                "defects 1 000": demosaic.Develop(defects=sites(1000)), "defects 100 000": demosaic.Develop(defects=sites(100000))}
+        runs = [("copy", lambda: L.check(lib.mi_memcpy_d2d_async(0, None, scratch.ptr, scratch.ptr + half, half))),
+                ("plain", lambda: demosaic.debayer_device(mosaic.ptr, out.ptr, h, w, dt, cfa_d))]
+        for key in ("matrix", "tone", "matrix + tone"):
+            d, _, _ = devs[key].prepared((h, w), dt)
+            c = cfa_d.struct(dt)
+            runs.append((key, lambda d=d, c=c: L.check(lib.mi_develop_device(0, None, mosaic.ptr, out.ptr, h, w, code, C.byref(c), C.byref(d)))))
+            if key != "matrix":
+                runs.append((key + ", scene", lambda d=d, c=c: L.check(lib.mi_develop_device(0, None, scene.ptr, out.ptr, h, w, code, C.byref(c), C.byref(d)))))
+        for key in ("defects 1 000", "defects 100 000"):
+            _, ptr, n = devs[key].prepared((h, w), dt)
+            runs.append((key, lambda ptr=ptr, n=n: L.check(lib.mi_mosaic_defects_device(0, None, mosaic.ptr, h, w, code, ptr, n))))
+        for rep in range(2):
+            got = {key: measure(fn) for key, fn in runs}
+        copy_ms, plain_ms = got["copy"][0], got["plain"][0]
+        for key, (ms, best) in got.items():
+            results.append(dict(shape=name, dtype=dt.name, height=h, width=w, what=key, median_ms=ms, best_ms=best, copy_ms=copy_ms,
+                                ratio_to_copy=ms / copy_ms, ratio_to_plain=ms / plain_ms))
+            print(f"{name} {dt.name:6s} {w}x{h} {key:20s}: median {ms:7.4f} ms best {best:7.4f} ms | {ms / plain_ms:5.2f} x plain | "
+                  f"{ms / copy_ms:5.2f} x the copy of {1e-6 * moved:4.0f} MB ({copy_ms:6.4f} ms)", flush=True)
+        for d in devs.values():
+            d.close()
+        for b in (mosaic, scene, out, scratch):
+            b.free()
+
+
+if a.develop:
+    develop_section()
+for dt in ([] if a.develop else [np.uint16, np.uint8] if a.uint8 else [np.uint16]):
     dt = np.dtype(dt)
     for name, h, w in shapes:
         px = h * w
