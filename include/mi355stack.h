@@ -776,6 +776,55 @@ MI_API int mi_develop(int device, const void* host_mosaic, void* host_bgr, int h
 MI_API int mi_stack_push_mosaic_developed(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa,
                                           const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned);
 
+/* ---- raw calibration frames: master dark / flat, the flat's gain table, (raw - dark) * flat_gain (kernels_calib.hpp) ----
+ * Integer and exact, on height x width mosaics of MI_U8 / MI_U16 (height, width >= 2, height * width < 2^31), maxv the dtype's
+ * maximum, pos = 2 (y & 1) + (x & 1); nothing depends on the colour pattern.  tests/calib_restatement.py states it in NumPy.
+ *   master     n exposures, 1 <= n <= 32, 0 <= 2 reject < n.  Per site the samples sorted ascending s[0 .. n - 1],
+ *              m = n - 2 reject, S = s[reject] + ... + s[n - reject - 1], out = (S + (m >> 1)) / m: reject 0 the rounded mean,
+ *              (n - 1) / 2 the median (even n: the rounded mean of the two middle samples), between: min/max rejection.
+ *   flat gain  f = max(F - B, 0) per site, B the flat-dark (a dark frame at the flat's exposure) or cfa.black[pos]; S_p the sum
+ *              of f over the sites of position p and N_p their number.  gain = 16384 where f == 0 or S_p == 0, else
+ *              min(65535, (2 * 16384 * S_p + N_p f) / (2 N_p f)): the position's mean over the site's value in Q14, rounded.
+ *              Normalised per position, so a flat does not change the white balance.  A uint16 table, height x width.
+ *   calibrate  in place on the raw samples, ahead of step 0:  e = max(v - (dark[site] or cfa.black[pos]), 0);
+ *              e' = (e * gain[site] + 8192) >> 14 with a flat, else e;  out = min(maxv, e' + cfa.black[pos]).  The pedestal is
+ *              put back: a calibrated mosaic is an ordinary mosaic for step 0 and steps A to D, which follow in that order.
+ * Of `cfa` only black[] is read, and all of it is checked. */
+enum { MI_CALIB_DARK = 1, MI_CALIB_FLAT = 2 };
+typedef struct mi_calib {
+    int32_t flags;              /* MI_CALIB_* or-ed; 0: nothing is done                                        */
+    const void* dev_dark;       /* height x width of the mosaic's dtype, device memory, read under MI_CALIB_DARK */
+    const uint16_t* dev_gain;   /* height x width Q14 gains, device memory, read under MI_CALIB_FLAT            */
+} mi_calib_t;
+/* MI_ERR_INVALID names the argument; every check comes before the first device call: null pointers, height or width < 2,
+ * another dtype, n outside [1, 32], reject < 0 or 2 reject >= n, unknown flags, a flag whose pointer is null,
+ * height * width >= 2^31.  The device forms enqueue on `stream` and do not wait; the host forms upload, run, download and wait.
+ * mi_mosaic_master_device: `dev_frames` holds the n mosaics one behind the other.  mi_mosaic_master: `host_frames` is a HOST
+ * array of n host pointers.  mi_flat_gain*: the flat-dark may be null.  mi_mosaic_calibrate_device: in place; flags == 0
+ * enqueues nothing and touches no device.  mi_mosaic_calibrate: host_dark / host_gain may each be null; host_out may equal
+ * host_mosaic. */
+MI_API int mi_mosaic_master_device(int device, void* stream, const void* dev_frames, int n, int height, int width, int dtype,
+                                   int reject, void* dev_out);
+MI_API int mi_mosaic_master(int device, const void* const* host_frames, int n, int height, int width, int dtype, int reject,
+                            void* host_out);
+MI_API int mi_flat_gain_device(int device, void* stream, const void* dev_flat, const void* dev_flat_dark, int height, int width,
+                               int dtype, const mi_cfa_t* cfa, uint16_t* dev_gain_out);
+MI_API int mi_flat_gain(int device, const void* host_flat, const void* host_flat_dark, int height, int width, int dtype,
+                        const mi_cfa_t* cfa, uint16_t* host_gain_out);
+MI_API int mi_mosaic_calibrate_device(int device, void* stream, void* dev_mosaic, int height, int width, int dtype,
+                                      const mi_cfa_t* cfa, const mi_calib_t* calib);
+MI_API int mi_mosaic_calibrate(int device, const void* host_mosaic, void* host_out, int height, int width, int dtype,
+                               const mi_cfa_t* cfa, const void* host_dark, const uint16_t* host_gain);
+/* mi_stack_push_mosaic with calibration: the calibration kernel runs on the handle's stream behind the mosaic's upload, in
+ * place on the stage's device slot; step 0 (n_sites > 0) and the demosaic -- developed when `develop` is not null -- follow
+ * it, and the slot is released behind all of them.  `calib` and `develop` are copied by the call; the device tables they and
+ * `dev_sites` point to must stay valid until the handle is synchronised (mi_stack_sync, mi_stack_finish, mi_stack_reset or its
+ * destruction).  Plain, developed and calibrated pushes may mix on one handle, frame by frame.  Everything else as
+ * mi_stack_push_mosaic. */
+MI_API int mi_stack_push_mosaic_calibrated(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa,
+                                           const mi_calib_t* calib, const mi_develop_t* develop, const int32_t* dev_sites,
+                                           int n_sites, int pinned);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

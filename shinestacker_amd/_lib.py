@@ -67,6 +67,14 @@ class DevelopStruct(C.Structure):
     _fields_ = [("flags", C.c_int32), ("matrix_q", C.c_int32 * 9), ("dev_tone", C.c_void_p)]
 
 
+MI_CALIB_DARK, MI_CALIB_FLAT = 1, 2
+
+
+class CalibStruct(C.Structure):
+    """mi_calib_t: what the calibration kernel sees of a demosaic.Calibration"""
+    _fields_ = [("flags", C.c_int32), ("dev_dark", C.c_void_p), ("dev_gain", C.c_void_p)]
+
+
 class DepthMapParams(C.Structure):
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32),
                 ("map_type", C.c_int32), ("energy", C.c_int32), ("kernel_size", C.c_int32),
@@ -253,6 +261,17 @@ SIGNATURES = {
                              C.c_void_p, C.c_int]),
     "mi_stack_push_mosaic_developed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CfaStruct), C.POINTER(DevelopStruct),
                                                  C.c_void_p, C.c_int, C.c_int]),
+    "mi_mosaic_master_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mi_mosaic_master": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mi_flat_gain_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct),
+                                      C.c_void_p]),
+    "mi_flat_gain": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct), C.c_void_p]),
+    "mi_mosaic_calibrate_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct),
+                                             C.POINTER(CalibStruct)]),
+    "mi_mosaic_calibrate": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct), C.c_void_p,
+                                      C.c_void_p]),
+    "mi_stack_push_mosaic_calibrated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CfaStruct), C.POINTER(CalibStruct),
+                                                  C.POINTER(DevelopStruct), C.c_void_p, C.c_int, C.c_int]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }
@@ -487,6 +506,7 @@ class Stack:
         self._h = h
         self._inflight = []     # pinned frames whose zero-copy upload may still be running (push_frame(zero_copy=True))
         self._develops = []     # every demosaic.Develop a queued kernel may still read (push_mosaic(develop=))
+        self._calibrations = []  # ... and every demosaic.Calibration (push_mosaic(calibration=))
         n = C.c_int()
         check(lib.mi_stack_levels(self._h, C.byref(n)))
         self.levels = n.value
@@ -499,6 +519,7 @@ class Stack:
             self._h = None
         self._inflight = []
         self._develops = []
+        self._calibrations = []
 
     def __del__(self):
         try:
@@ -516,6 +537,7 @@ class Stack:
         check(load().mi_stack_reset(self._h))   # synchronises the handle: every upload has completed
         self._inflight = []
         self._develops = []     # ... and every kernel that read a Develop's device tables
+        self._calibrations = []
 
     # -- geometry
     def level_shape(self, level):
@@ -568,20 +590,35 @@ class Stack:
                 check(rc)
         check(load().mi_stack_push_frame(self._h, a.ctypes.data, 0))
 
-    def push_mosaic(self, mosaic, cfa, zero_copy=False, develop=None):
+    def push_mosaic(self, mosaic, cfa, zero_copy=False, develop=None, calibration=None):
         """Push one host frame as its raw Bayer mosaic (H x W samples of the handle's input dtype, `cfa`: a demosaic.Cfa): a
         third of push_frame's bytes cross the host link, and the frame is demosaiced on the device behind its upload.  Frames
         are fused in call order, whichever of push_frame / push_mosaic / push_frames_device brought them.  `zero_copy` as in
         push_frame.  `develop`: a demosaic.Develop -- defect sites, colour matrix and tone curve around the demosaic; the
         handle keeps the object (the queued kernels read its device tables) until finish, reset, sync or close.  None: the
-        plain push, exactly the calls it makes without this argument."""
+        plain push, exactly the calls it makes without this argument.  `calibration`: a demosaic.Calibration -- master dark
+        and flat field applied in place on the uploaded mosaic, ahead of the defect sites and the demosaic; kept by the
+        handle as a Develop is.  None: today's calls, unchanged."""
         a = np.asarray(mosaic)
         if a.shape != (self.height, self.width):
             raise ValueError(f"mosaic shape {a.shape} != {(self.height, self.width)}")
         if a.dtype != self.in_dtype:
             raise ValueError(f"mosaic dtype {a.dtype} != {self.in_dtype}")
         c = cfa.struct(self.in_dtype)
-        if develop is None:
+        if calibration is not None:
+            from .demosaic import check_calibration, check_develop
+            cal = check_calibration(calibration).prepared(a.shape, self.in_dtype, cfa, self.device)
+            d, sites, n_sites = (None, None, 0) if develop is None else check_develop(develop).prepared(a.shape, self.in_dtype, self.device)
+            self._calibrations = getattr(self, "_calibrations", [])
+            if not any(x is calibration for x in self._calibrations):
+                self._calibrations.append(calibration)
+            if develop is not None and not any(x is develop for x in self._develops):
+                self._develops.append(develop)
+
+            def push(ptr, stride, pinned):
+                return load().mi_stack_push_mosaic_calibrated(self._h, ptr, stride, C.byref(c), C.byref(cal),
+                                                              None if d is None else C.byref(d), sites, n_sites, pinned)
+        elif develop is None:
             def push(ptr, stride, pinned):
                 return load().mi_stack_push_mosaic(self._h, ptr, stride, C.byref(c), pinned)
         else:
@@ -625,6 +662,7 @@ class Stack:
         check(load().mi_stack_sync(self._h))
         self._inflight = []
         self._develops = []
+        self._calibrations = []
 
     def sync_level(self, level):
         """wait until the state of `level` covers every pushed frame (level 0: before the coarser levels finish)"""
@@ -635,6 +673,7 @@ class Stack:
         check(load().mi_stack_finish(self._h, out.ctypes.data, 0))
         self._inflight = []      # the result is on the host: every upload it depends on has completed
         self._develops = []
+        self._calibrations = []
         return out
 
     def finish_device(self, dev_ptr=None):

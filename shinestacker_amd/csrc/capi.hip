@@ -1778,6 +1778,145 @@ int mi_stack_push_mosaic_developed(mi_stack_t* s, const void* host_mosaic, size_
     return mosaic_push(s, host_mosaic, row_stride_bytes, *cfa, pinned && async, &d, dev_sites, n_sites);
 }
 
+// ---------------------------------------------------------------- raw calibration frames (kernels_calib.hpp)
+int mi_mosaic_master_device(int device, void* stream, const void* dev_frames, int n, int height, int width, int dtype, int reject,
+                            void* dev_out) {
+    if (!dev_frames) return fail(MI_ERR_INVALID, "null frames");
+    if (!dev_out) return fail(MI_ERR_INVALID, "null master output");
+    int rc = calib_shape_check(height, width, dtype);
+    if (rc || (rc = master_check(n, reject))) return rc;
+    MI_HIP(hipSetDevice(device));
+    master_launch((hipStream_t)stream, dev_frames, n, height, width, dtype, reject, dev_out);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_mosaic_master(int device, const void* const* host_frames, int n, int height, int width, int dtype, int reject, void* host_out) {
+    if (!host_frames) return fail(MI_ERR_INVALID, "null frames");
+    if (!host_out) return fail(MI_ERR_INVALID, "null master output");
+    int rc = calib_shape_check(height, width, dtype);
+    if (rc || (rc = master_check(n, reject))) return rc;
+    for (int i = 0; i < n; ++i)
+        if (!host_frames[i]) return fail(MI_ERR_INVALID, "null frames[%d]", i);
+    if ((rc = open_device(device))) return rc;
+    const size_t nb = (size_t)height * width * dtype_size(dtype);
+    DevScratch tmp(nullptr);
+    char* frames = nullptr;
+    void* out = nullptr;
+    if ((rc = tmp.alloc(&frames, nb * n)) || (rc = tmp.alloc(&out, nb))) return rc;
+    for (int i = 0; i < n; ++i) MI_HIP(hipMemcpyAsync(frames + (size_t)i * nb, host_frames[i], nb, hipMemcpyHostToDevice, nullptr));
+    if ((rc = mi_mosaic_master_device(device, nullptr, frames, n, height, width, dtype, reject, out))) return rc;
+    return tmp.download(host_out, out, nb);
+}
+
+static int flat_check(const void* flat, const void* gain, int height, int width, int dtype, const mi_cfa_t* cfa) {
+    if (!flat) return fail(MI_ERR_INVALID, "null flat");
+    if (!gain) return fail(MI_ERR_INVALID, "null gain output");
+    int rc = calib_shape_check(height, width, dtype);
+    if (rc) return rc;
+    return cfa_check(cfa, dtype);
+}
+
+int mi_flat_gain_device(int device, void* stream, const void* dev_flat, const void* dev_flat_dark, int height, int width, int dtype,
+                        const mi_cfa_t* cfa, uint16_t* dev_gain_out) {
+    int rc = flat_check(dev_flat, dev_gain_out, height, width, dtype, cfa);
+    if (rc) return rc;
+    MI_HIP(hipSetDevice(device));
+    // the four position sums between the two passes: stream-ordered scratch, so the call does not wait
+    unsigned long long* sums = nullptr;
+    MI_HIP(hipMallocAsync((void**)&sums, 4 * sizeof(unsigned long long), (hipStream_t)stream));
+    const hipError_t e = flat_gain_launch((hipStream_t)stream, dev_flat, dev_flat_dark, height, width, dtype, *cfa, sums, dev_gain_out);
+    MI_HIP(hipFreeAsync(sums, (hipStream_t)stream));
+    MI_HIP(e);
+    return MI_OK;
+}
+
+int mi_flat_gain(int device, const void* host_flat, const void* host_flat_dark, int height, int width, int dtype, const mi_cfa_t* cfa,
+                 uint16_t* host_gain_out) {
+    int rc = flat_check(host_flat, host_gain_out, height, width, dtype, cfa);
+    if (rc) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t npx = (size_t)height * width, nb = npx * dtype_size(dtype);
+    DevScratch tmp(nullptr);
+    void *flat = nullptr, *fdark = nullptr;
+    uint16_t* gain = nullptr;
+    if ((rc = tmp.upload(&flat, host_flat, nb)) || (host_flat_dark && (rc = tmp.upload(&fdark, host_flat_dark, nb))) ||
+        (rc = tmp.alloc(&gain, npx * sizeof(uint16_t))) ||
+        (rc = mi_flat_gain_device(device, nullptr, flat, fdark, height, width, dtype, cfa, gain)))
+        return rc;
+    return tmp.download(host_gain_out, gain, npx * sizeof(uint16_t));
+}
+
+int mi_mosaic_calibrate_device(int device, void* stream, void* dev_mosaic, int height, int width, int dtype, const mi_cfa_t* cfa,
+                               const mi_calib_t* calib) {
+    if (!dev_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    int rc = calib_shape_check(height, width, dtype);
+    if (rc || (rc = cfa_check(cfa, dtype)) || (rc = calib_check(calib))) return rc;
+    if (calib->flags == 0) return MI_OK;   // nothing to do, no device call
+    MI_HIP(hipSetDevice(device));
+    calibrate_launch((hipStream_t)stream, dev_mosaic, height, width, dtype, *cfa, *calib);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_mosaic_calibrate(int device, const void* host_mosaic, void* host_out, int height, int width, int dtype, const mi_cfa_t* cfa,
+                        const void* host_dark, const uint16_t* host_gain) {
+    if (!host_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    if (!host_out) return fail(MI_ERR_INVALID, "null mosaic output");
+    int rc = calib_shape_check(height, width, dtype);
+    if (rc || (rc = cfa_check(cfa, dtype))) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t npx = (size_t)height * width, nb = npx * dtype_size(dtype);
+    DevScratch tmp(nullptr);
+    void *m = nullptr, *dark = nullptr;
+    uint16_t* gain = nullptr;
+    mi_calib_t c{};
+    if ((rc = tmp.upload(&m, host_mosaic, nb))) return rc;
+    if (host_dark) {
+        if ((rc = tmp.upload(&dark, host_dark, nb))) return rc;
+        c.flags |= MI_CALIB_DARK;
+        c.dev_dark = dark;
+    }
+    if (host_gain) {
+        if ((rc = tmp.upload(&gain, host_gain, npx * sizeof(uint16_t)))) return rc;
+        c.flags |= MI_CALIB_FLAT;
+        c.dev_gain = gain;
+    }
+    if ((rc = mi_mosaic_calibrate_device(device, nullptr, m, height, width, dtype, cfa, &c))) return rc;
+    return tmp.download(host_out, m, nb);
+}
+
+int mi_stack_push_mosaic_calibrated(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa,
+                                    const mi_calib_t* calib, const mi_develop_t* develop, const int32_t* dev_sites, int n_sites,
+                                    int pinned) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!host_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
+    if ((rc = cfa_check(cfa, s->p.in_dtype)) || (rc = calib_check(calib)) || (develop && (rc = develop_check(develop))) ||
+        (rc = sites_check(dev_sites, n_sites, s->p.height, s->p.width)))
+        return rc;
+    const size_t rb = (size_t)s->p.width * dtype_size(s->p.in_dtype);
+    if (row_stride_bytes == 0) row_stride_bytes = rb;
+    if (row_stride_bytes < rb) return fail(MI_ERR_INVALID, "row stride smaller than a row");
+    if (s->idx_exported) return fail(MI_ERR_STATE, "the winner indices were exported (index stride > 1): reset the handle before pushing more frames");
+    if (s->finished) return fail(MI_ERR_STATE, "push after finish; call mi_stack_reset first");
+    MI_HIP(hipSetDevice(s->p.device));
+    const bool async = s->p.impl == MI_IMPL_TILED && !s->f64;
+    if (pinned && async) {
+        if (row_stride_bytes != rb) return fail(MI_ERR_INVALID, "a pinned mosaic must have contiguous rows");
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, host_mosaic) != hipSuccess || at.type != hipMemoryTypeHost) {
+            (void)hipGetLastError();
+            return fail(MI_ERR_INVALID, "mi_stack_push_mosaic_calibrated: the mosaic is not in pinned host memory (mi_host_alloc / mi_host_register)");
+        }
+    }
+    const mi_calib_t c = *calib;
+    mi_develop_t d{};
+    if (develop) d = *develop;
+    return mosaic_push(s, host_mosaic, row_stride_bytes, *cfa, pinned && async, develop ? &d : nullptr, dev_sites, n_sites, &c);
+}
+
 int mi_host_alloc(void** ptr, size_t bytes) {
     if (!ptr || !bytes) return fail(MI_ERR_INVALID, "bad argument");
     MI_HIP(hipHostMalloc(ptr, bytes, hipHostMallocPortable));

@@ -17,10 +17,14 @@
 //   develop     mi_stack_push_mosaic_developed: the defect kernel (step 0) on s->stream behind evCopied[slot], in place on the
 //               slot, then the developed demosaic; evSlotFree[slot] follows both, so the copy stream never overwrites a slot
 //               that step 0 still writes.  The caller's device tables (tone, sites) are read by those kernels.
+//   calibrate   mi_stack_push_mosaic_calibrated: the calibration kernel (kernels_calib.hpp) on s->stream behind evCopied[slot], in
+//               place on the slot, ahead of the defect kernel and the (developed) demosaic; evSlotFree[slot] follows all of them.
+//               The caller's dark frame and gain table are read by that kernel.
 //   order       frames are fused in call order: the first mosaic after host BGR frames flushes the ring (mosaic_push), and
 //               every call that takes frames of another kind or reads state flushes this stage first (stack_flush in capi.hip).
 #pragma once
 
+#include "kernels_calib.hpp"
 #include "kernels_demosaic.hpp"
 
 namespace mi {
@@ -83,6 +87,27 @@ inline int sites_check(const int32_t* sites, int n, int height, int width) {
     if (n < 0) return fail(MI_ERR_INVALID, "the number of sites must be >= 0 (got %d)", n);
     if (n > 0 && !sites) return fail(MI_ERR_INVALID, "null sites");
     if (height > 0 && width > 0 && (uint64_t)height * (uint64_t)width >= (1ull << 31)) return fail(MI_ERR_INVALID, "height x width too large");
+    return MI_OK;
+}
+// argument checks of the calibration entry points (mi_mosaic_master*, mi_flat_gain*, mi_mosaic_calibrate*,
+// mi_stack_push_mosaic_calibrated): no device call.  The kernels index sites with 31 bits, as the defect list does, and the
+// flat's 64-bit sums hold under the same bound (kernels_calib.hpp).
+inline int calib_shape_check(int height, int width, int dtype) {
+    if (height < 2 || width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic (got %dx%d)", width, height);
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16 for a mosaic (got %d)", dtype);
+    if ((uint64_t)height * (uint64_t)width >= (1ull << 31)) return fail(MI_ERR_INVALID, "height x width too large");
+    return MI_OK;
+}
+inline int master_check(int n, int reject) {
+    if (n < 1 || n > calib::MAX_FRAMES) return fail(MI_ERR_INVALID, "the number of frames must be in [1, %d] (got %d)", calib::MAX_FRAMES, n);
+    if (reject < 0 || 2 * (int64_t)reject >= n) return fail(MI_ERR_INVALID, "reject must be >= 0 with 2 * reject < n (got %d, n = %d)", reject, n);
+    return MI_OK;
+}
+inline int calib_check(const mi_calib_t* c) {
+    if (!c) return fail(MI_ERR_INVALID, "null calib");
+    if (c->flags & ~(MI_CALIB_DARK | MI_CALIB_FLAT)) return fail(MI_ERR_INVALID, "unknown calib flags %d", c->flags);
+    if ((c->flags & MI_CALIB_DARK) && !c->dev_dark) return fail(MI_ERR_INVALID, "calib: MI_CALIB_DARK is set and dev_dark is null");
+    if ((c->flags & MI_CALIB_FLAT) && !c->dev_gain) return fail(MI_ERR_INVALID, "calib: MI_CALIB_FLAT is set and dev_gain is null");
     return MI_OK;
 }
 // a list in host memory: every site inside the image, strictly ascending
@@ -156,11 +181,22 @@ inline int mosaic_flush(mi_stack* s) {
     return dispatch_push(s, m->bgr, n, t->frame_bytes);
 }
 
-// One host mosaic (arguments checked by mi_stack_push_mosaic / mi_stack_push_mosaic_developed): stage it, start upload and
-// demosaic, return.  `dev`: development (null: the plain demosaic, exactly the launches of a handle that never heard of it);
-// with `n_sites` > 0 the defect kernel runs in place on the slot, behind the upload and ahead of the demosaic.
+// the kernels of one mosaic, in place on `slot` and then into `frame`: calibration, defect sites, (developed) demosaic.  Without
+// `cal`, `dev` and sites: the plain demosaic alone, exactly the launches of a handle that never heard of the others.
+inline void mosaic_kernels(hipStream_t st, void* slot, void* frame, int H, int W, int dtype, const mi_cfa_t& cfa,
+                           const mi_calib_t* cal, const mi_develop_t* dev, const int32_t* dev_sites, int n_sites) {
+    if (cal) calibrate_launch(st, slot, H, W, dtype, cfa, *cal);
+    defects_launch(st, slot, H, W, dtype, dev_sites, n_sites);   // (n_sites == 0 launches nothing)
+    if (dev) develop_launch(st, slot, frame, H, W, dtype, cfa, *dev);
+    else demosaic_launch(st, slot, frame, H, W, dtype, cfa);
+}
+
+// One host mosaic (arguments checked by mi_stack_push_mosaic / _developed / _calibrated): stage it, start upload and
+// demosaic, return.  `dev`: development (null: the plain demosaic); with `n_sites` > 0 the defect kernel runs in place on the
+// slot, behind the upload and ahead of the demosaic; `cal`: calibration, in place on the slot ahead of both.
 inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t& cfa, bool pinned,
-                       const mi_develop_t* dev = nullptr, const int32_t* dev_sites = nullptr, int n_sites = 0) {
+                       const mi_develop_t* dev = nullptr, const int32_t* dev_sites = nullptr, int n_sites = 0,
+                       const mi_calib_t* cal = nullptr) {
     TiledState* t = tstate(s);
     int rc = tiled_flush(s);   // call order: host BGR frames staged before this mosaic are fused first
     if (rc) return rc;
@@ -171,10 +207,7 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     if (s->p.impl != MI_IMPL_TILED) {
         // float-64 and MI_IMPL_SIMPLE handles: upload, demosaic, push, wait -- one frame at a time on the handle's stream
         MI_HIP(hipMemcpy2DAsync(m->slot[0], rb, host_mosaic, row_stride_bytes, rb, H, hipMemcpyHostToDevice, s->stream));
-        if (dev) {
-            defects_launch(s->stream, m->slot[0], H, W, s->p.in_dtype, dev_sites, n_sites);
-            develop_launch(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa, *dev);
-        } else demosaic_launch(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa);
+        mosaic_kernels(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
         MI_HIP(hipGetLastError());
         if ((rc = dispatch_push(s, s->frame_dev, 1, t->frame_bytes))) return rc;
         MI_HIP(hipStreamSynchronize(s->stream));
@@ -218,10 +251,7 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     MI_HIP(hipEventRecord(m->evCopied[si], m->stc));
     MI_HIP(hipStreamWaitEvent(s->stream, m->evCopied[si], 0));
     void* frame = (char*)m->bgr + (size_t)m->pending * t->frame_bytes;
-    if (dev) {
-        defects_launch(s->stream, slot, H, W, s->p.in_dtype, dev_sites, n_sites);
-        develop_launch(s->stream, slot, frame, H, W, s->p.in_dtype, cfa, *dev);
-    } else demosaic_launch(s->stream, slot, frame, H, W, s->p.in_dtype, cfa);
+    mosaic_kernels(s->stream, slot, frame, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
     MI_HIP(hipGetLastError());
     MI_HIP(hipEventRecord(m->evSlotFree[si], s->stream));
     m->pending++;

@@ -21,6 +21,16 @@ Raw development around it, `Develop`, each step optional and as exact (tests/dev
                            out_i = clamp((sum_j M_q[i][j] * in_j + 2048) >> 12, 0, white); per row sum_j |M_q[i][j]| <= 32767
     step D, tone curve     out = tone[out], a table of maxv + 1 entries of the frame's dtype (`srgb_tone`, `gamma_tone`)
 
+Calibration frames ahead of all of it, `Calibration`, as exact (csrc/kernels_calib.hpp; tests/calib_restatement.py is the
+definition); pos = 2 (y & 1) + (x & 1), nothing here depends on the colour pattern:
+
+    master frame           K <= 32 exposures, per site sorted s[0..K-1]: out = (S + (n >> 1)) // n over s[reject .. K - reject - 1],
+                           n = K - 2 reject -- the rounded mean (reject 0), the median ((K - 1) // 2), min/max rejection between
+    flat gain table        f = max(F - B, 0), B the flat-dark or black[pos]; per position the sum S_p and count N_p of f;
+                           G_q = 16384 where f == 0 or S_p == 0, else min(65535, (2 * 16384 * S_p + N_p * f) // (2 * N_p * f)), uint16
+    calibrate              in place on the raw samples, ahead of step 0: e = max(v - (dark or black[pos]), 0),
+                           e' = (e * G_q + 8192) >> 14 with a flat, out = min(maxv, e' + black[pos])
+
 There is no CPU path: without a GPU or the library `debayer` and its kin raise DeviceError.  `mosaic_of`, `srgb_tone`,
 `gamma_tone` and `defects_from_dark` are host NumPy.
 """
@@ -34,6 +44,20 @@ from .errors import BitDepthError, InvalidOptionError
 PATTERNS = ("RGGB", "BGGR", "GRBG", "GBRG")     # MI_CFA_*: the 2 x 2 cell at (y & 1, x & 1), row-major
 TILE_H, TILE_W = 16, 128                        # demosaic::TILE_H / TILE_W of csrc/kernels_demosaic.hpp
 GAIN_ONE = 4096                                 # gain_q of gain 1.0
+CALIB_VEC_BYTES = 16                            # calib::VEC_BYTES of csrc/kernels_calib.hpp: one lane's window of a row
+CALIB_TILE_H, CALIB_LANES = 4, 64               # calib::TILE_H / LANES: a workgroup is 4 rows of 64 windows
+CALIB_MAX_FRAMES = 32                           # calib::MAX_FRAMES: exposures of one master
+FLAT_GAIN_ONE = 16384                           # calib::GAIN_ONE: Q14
+
+
+def calib_vec(dtype):
+    """the calibration kernel's vector width in sites for mosaics of `dtype`"""
+    return CALIB_VEC_BYTES // _dtype(dtype).itemsize
+
+
+def calib_tile(dtype):
+    """(rows, sites of a row) of one workgroup of the calibration kernel, for rows that start on a 16-byte boundary"""
+    return CALIB_TILE_H, CALIB_LANES * calib_vec(dtype)
 _BGR = {"B": 0, "G": 1, "R": 2}
 
 
@@ -166,7 +190,8 @@ def gamma_tone(dtype, gamma, white=None):
 
 def defects_from_dark(dark_mosaic, threshold):
     """The sites of a dark frame (an H x W mosaic taken with the shutter closed) above `threshold`, as an (n, 2) array of
-    (y, x) in ascending order: what Develop(defects=) takes.  Host NumPy."""
+    (y, x) in ascending order: what Develop(defects=) takes.  Host NumPy.  (`master_frame` reduces several dark exposures
+    to the one frame this takes.)"""
     a = check_mosaic(dark_mosaic)
     if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not math.isfinite(threshold):
         raise InvalidOptionError("threshold", threshold, "a finite number is expected")
@@ -314,12 +339,218 @@ def check_develop(develop):
     return develop
 
 
-def require_mosaic(mosaic, develop):
-    """`develop=` only means something beside `mosaic=`"""
+def require_mosaic(mosaic, develop, calibration=None):
+    """`develop=` and `calibration=` only mean something beside `mosaic=`"""
     if develop is not None:
         if mosaic is None:
             raise InvalidOptionError("develop", develop, "develop= needs mosaic=: only raw mosaics are developed")
         check_develop(develop)
+    if calibration is not None:
+        if mosaic is None:
+            raise InvalidOptionError("calibration", calibration, "calibration= needs mosaic=: only raw mosaics are calibrated")
+        check_calibration(calibration)
+
+
+# ---------------------------------------------------------------- calibration frames: master dark, flat field
+def _resolve_reject(reject, k):
+    """the number of samples dropped at each end of a site's k sorted samples"""
+    if isinstance(reject, str):
+        if reject.lower() == "mean":
+            return 0
+        if reject.lower() == "median":
+            return (k - 1) // 2
+    elif isinstance(reject, (int, np.integer)) and not isinstance(reject, bool):
+        if reject < 0 or 2 * int(reject) >= k:
+            raise InvalidOptionError("reject", reject, f"0 <= reject and 2 * reject < {k}, the number of frames")
+        return int(reject)
+    raise InvalidOptionError("reject", reject, '"mean", "median" or an int is expected')
+
+
+def _exposures(name, frames):
+    """K mosaics of one shape and dtype, 1 <= K <= 32, as a list of contiguous arrays"""
+    if isinstance(frames, np.ndarray):
+        if frames.ndim != 3:
+            raise InvalidOptionError(name, frames.shape, "K mosaics (K x H x W, or a sequence of H x W planes) are expected")
+        frames = list(frames)
+    try:
+        frames = list(frames)
+    except TypeError:
+        raise InvalidOptionError(name, frames, "a sequence of H x W mosaics is expected") from None
+    if not 1 <= len(frames) <= CALIB_MAX_FRAMES:
+        raise InvalidOptionError(name, len(frames), f"1 to {CALIB_MAX_FRAMES} frames are expected")
+    first = check_mosaic(frames[0])
+    return [np.ascontiguousarray(check_mosaic(f, first.shape, first.dtype)) for f in frames]
+
+
+def master_frame(mosaics, reject="median", device=0):
+    """K <= 32 exposures (H x W mosaics of one shape and dtype) reduced to their master, H x W of that dtype: per site the
+    samples sorted, `reject` dropped at each end and the rest averaged, rounded.  reject: "mean" (0), "median" ((K - 1) // 2) or
+    an int with 2 * reject < K -- min/max rejection, which removes a cosmic-ray hit or a passing insect."""
+    frames = _exposures("mosaics", mosaics)
+    r = _resolve_reject(reject, len(frames))
+    _lib.require_device()
+    h, w = frames[0].shape
+    out = np.empty((h, w), frames[0].dtype)
+    ptrs = (_lib.C.c_void_p * len(frames))(*[f.ctypes.data for f in frames])
+    _lib.check(_lib.load().mi_mosaic_master(device, ptrs, len(frames), h, w, _lib.DTYPE_CODE[out.dtype], r, out.ctypes.data))
+    return out
+
+
+def flat_gain(flat, cfa, flat_dark=None, device=0):
+    """The Q14 gain table of a master flat, uint16 H x W: per cell position the mean of max(flat - B, 0) over the site's value,
+    B the `flat_dark` (a master dark at the flat's exposure) or the Cfa's black level.  Normalised per position: the flat does
+    not change the white balance."""
+    f = np.ascontiguousarray(check_mosaic(flat))
+    c = _check_cfa(cfa).struct(f.dtype)
+    fd = None if flat_dark is None else np.ascontiguousarray(check_mosaic(flat_dark, f.shape, f.dtype))
+    if f.shape[0] * f.shape[1] >= 2 ** 31:
+        raise InvalidOptionError("flat", f.shape, "height x width must be below 2^31")
+    _lib.require_device()
+    out = np.empty(f.shape, np.uint16)
+    _lib.check(_lib.load().mi_flat_gain(device, f.ctypes.data, None if fd is None else fd.ctypes.data, f.shape[0], f.shape[1],
+                                        _lib.DTYPE_CODE[f.dtype], _lib.C.byref(c), out.ctypes.data))
+    return out
+
+
+class Calibration:
+    """Calibration frames of a raw workflow: (raw - dark) * flat_gain per site, before anything else touches the samples.
+
+    dark       the sensor's fixed pattern at the exposure of the frames: one master H x W mosaic, or a sequence (or K x H x W
+               array) of up to 32 exposures reduced with `master_frame` at first use
+    flat       an evenly lit frame: vignetting, dust shadows, per-site gain.  As `dark`.
+    flat_dark  a dark at the flat's exposure, subtracted from the flat; None: the Cfa's black level.  As `dark`.
+    reject     how exposures are reduced: "mean", "median" or an int (`master_frame`)
+
+    The gain table is built at first use against the Cfa it is used with (its black levels).  Masters and table are uploaded
+    per device at first use and held until close().  Kernels queued by a Stack read them: the Stack keeps the object until
+    finish / reset / sync / close, and close() here must not come before that."""
+
+    def __init__(self, dark=None, flat=None, flat_dark=None, reject="median"):
+        _resolve_reject(reject, 2 * CALIB_MAX_FRAMES + 1)     # (the kind of value; against K once the frames are counted)
+        self.reject = reject
+        self._given = {}
+        self.shape = self.dtype = None
+        for name, v in (("dark", dark), ("flat", flat), ("flat_dark", flat_dark)):
+            if v is None:
+                continue
+            if isinstance(v, np.ndarray) and v.ndim == 2:
+                first = np.ascontiguousarray(check_mosaic(v)).copy()
+                self._given[name] = first
+            else:
+                frames = _exposures(name, v)
+                _resolve_reject(reject, len(frames))
+                first = frames[0]
+                self._given[name] = frames
+            if self.shape is None:
+                self.shape, self.dtype = first.shape, first.dtype
+            elif first.shape != self.shape:
+                raise InvalidOptionError(name, first.shape, f"the calibration frames have one shape (so far {self.shape})")
+            elif first.dtype != self.dtype:
+                raise BitDepthError(self.dtype, first.dtype)
+        if flat_dark is not None and flat is None:
+            raise InvalidOptionError("flat_dark", "given", "flat_dark= needs flat=")
+        self._gains = {}        # the Cfa's black levels -> host gain table
+        self._dev = {}          # (device, "dark") / (device, "gain", black) -> _lib.DeviceBuffer
+
+    def __repr__(self):
+        def kind(v):
+            return None if v is None else "master" if isinstance(v, np.ndarray) else f"{len(v)} frames"
+        return (f"Calibration(dark={kind(self._given.get('dark'))}, flat={kind(self._given.get('flat'))}, "
+                f"flat_dark={kind(self._given.get('flat_dark'))}, reject={self.reject!r})")
+
+    def master(self, name):
+        """the master "dark", "flat" or "flat_dark" (reduced at first use), or None"""
+        v = self._given.get(name)
+        if v is not None and not isinstance(v, np.ndarray):
+            v = self._given[name] = master_frame(v, self.reject)
+        return v
+
+    def check_frame(self, shape, dtype):
+        """the calibration frames are those of H x W mosaics of `dtype`"""
+        dt = _dtype(dtype)
+        if self.shape is not None:
+            if tuple(shape) != tuple(self.shape):
+                raise InvalidOptionError("calibration", self.shape, f"the calibration frames of a {tuple(shape)} mosaic have its shape")
+            if dt != self.dtype:
+                raise BitDepthError(dt, self.dtype)
+
+    def gain_table(self, cfa):
+        """the uint16 Q14 gain table against `cfa` (built at first use), or None without a flat"""
+        if "flat" not in self._given:
+            return None
+        key = tuple(_check_cfa(cfa).black)
+        if key not in self._gains:
+            self._gains[key] = flat_gain(self.master("flat"), cfa, self.master("flat_dark"))
+        return self._gains[key]
+
+    def host_tables(self, shape, dtype, cfa):
+        """(master dark or None, gain table or None) for H x W mosaics of `dtype`: what the host form mi_mosaic_calibrate takes"""
+        _check_cfa(cfa)
+        self.check_frame(shape, dtype)
+        return self.master("dark"), self.gain_table(cfa)
+
+    def prepared(self, shape, dtype, cfa, device=0):
+        """mi_calib_t for H x W mosaics of `dtype` on `device`; reduces, builds and uploads the tables on first use"""
+        dark, gain = self.host_tables(shape, dtype, cfa)
+        c = _lib.CalibStruct()
+        if dark is not None:
+            c.flags |= _lib.MI_CALIB_DARK
+            c.dev_dark = self._resident((device, "dark"), dark).ptr
+        if gain is not None:
+            c.flags |= _lib.MI_CALIB_FLAT
+            c.dev_gain = self._resident((device, "gain", tuple(cfa.black)), gain).ptr
+        return c
+
+    def _resident(self, key, arr):
+        if key not in self._dev:
+            _lib.require_device()
+            buf = _lib.DeviceBuffer(arr.nbytes, key[0])
+            buf.upload(arr)
+            self._dev[key] = buf
+        return self._dev[key]
+
+    def close(self):
+        """free the device tables (not before every kernel queued with them has run: Stack.finish / sync / reset / close)"""
+        for buf in self._dev.values():
+            buf.free()
+        self._dev = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def check_calibration(calibration):
+    if not isinstance(calibration, Calibration):
+        raise InvalidOptionError("calibration", calibration, "a shinestacker_amd.demosaic.Calibration is expected")
+    return calibration
+
+
+def calibrate_device(dev_mosaic, h, w, dtype, cfa, calibration, device=0, stream=None):
+    """calibrate() in place on a mosaic resident in HBM.  Queued on `stream`, not waited for; the Calibration's device tables
+    must outlive the queued kernel."""
+    dt = _dtype(dtype)
+    c = _check_cfa(cfa).struct(dt)
+    cal = check_calibration(calibration).prepared((h, w), dt, cfa, device)
+    _lib.check(_lib.load().mi_mosaic_calibrate_device(device, stream, dev_mosaic, int(h), int(w), _lib.DTYPE_CODE[dt], _lib.C.byref(c),
+                                                      _lib.C.byref(cal)))
+
+
+def calibrate(mosaic, cfa, calibration, device=0):
+    """(mosaic - dark) * flat_gain per site with the black pedestal put back: an H x W mosaic of the same dtype, an ordinary
+    mosaic for everything downstream."""
+    a = np.ascontiguousarray(check_mosaic(mosaic))
+    c = _check_cfa(cfa).struct(a.dtype)
+    check_calibration(calibration).check_frame(a.shape, a.dtype)
+    _lib.require_device()
+    dark, gain = calibration.host_tables(a.shape, a.dtype, cfa)
+    out = np.empty_like(a)
+    _lib.check(_lib.load().mi_mosaic_calibrate(device, a.ctypes.data, out.ctypes.data, a.shape[0], a.shape[1], _lib.DTYPE_CODE[a.dtype],
+                                               _lib.C.byref(c), None if dark is None else dark.ctypes.data,
+                                               None if gain is None else gain.ctypes.data))
+    return out
 
 
 def defects_device(dev_mosaic, h, w, dtype, develop, device=0, stream=None):
@@ -330,14 +561,17 @@ def defects_device(dev_mosaic, h, w, dtype, develop, device=0, stream=None):
         _lib.check(_lib.load().mi_mosaic_defects_device(device, stream, dev_mosaic, int(h), int(w), _lib.DTYPE_CODE[dt], sites, n))
 
 
-def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None, develop=None):
+def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None, develop=None, calibration=None):
     """debayer() for a mosaic resident in HBM: `dev_mosaic` (h x w) -> `dev_bgr` (h x w x 3).  Queued on `stream`, not waited
     for.  `develop`: a Develop -- its defect sites are repaired IN PLACE in `dev_mosaic` first (no other site is written),
-    then colour matrix and tone curve ride on the demosaic; its device tables must outlive the queued kernels."""
+    then colour matrix and tone curve ride on the demosaic; its device tables must outlive the queued kernels.
+    `calibration`: a Calibration -- `dev_mosaic` is calibrated IN PLACE ahead of all of that."""
     dt = _dtype(dtype)
     c = _check_cfa(cfa).struct(dt)
     if h < 2 or w < 2:
         raise InvalidOptionError("mosaic", (h, w), "a mosaic is an H x W plane with H, W >= 2")
+    if calibration is not None:
+        calibrate_device(dev_mosaic, h, w, dt, cfa, calibration, device=device, stream=stream)
     if develop is None:
         _lib.require_device()
         _lib.check(_lib.load().mi_demosaic_device(device, stream, dev_mosaic, dev_bgr, int(h), int(w), _lib.DTYPE_CODE[dt],
@@ -351,11 +585,25 @@ def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None,
                                      _lib.C.byref(d)))
 
 
-def debayer(mosaic, cfa, develop=None, device=0):
+def debayer(mosaic, cfa, develop=None, device=0, calibration=None):
     """H x W uint8 / uint16 mosaic -> H x W x 3 BGR array of the same dtype.  `develop`: a Develop (defect sites, colour
-    matrix, tone curve); None: the plain demosaic."""
+    matrix, tone curve); None: the plain demosaic.  `calibration`: a Calibration applied to the mosaic first."""
     a = np.ascontiguousarray(check_mosaic(mosaic))
     c = _check_cfa(cfa).struct(a.dtype)
+    if calibration is not None:
+        check_calibration(calibration).check_frame(a.shape, a.dtype)
+        if develop is not None:
+            check_develop(develop)
+        _lib.require_device()
+        h, w = a.shape
+        stage, bgr = _lib.DeviceBuffer(a.nbytes, device), _lib.DeviceBuffer(a.nbytes * 3, device)
+        try:
+            stage.upload(a)
+            debayer_device(stage.ptr, bgr.ptr, h, w, a.dtype, cfa, device=device, develop=develop, calibration=calibration)
+            return bgr.download((h, w, 3), a.dtype)     # (a blocking copy on the null stream: behind the kernels)
+        finally:
+            stage.free()
+            bgr.free()
     if develop is not None:
         mq, tone, sites = check_develop(develop).host_args(a.shape, a.dtype)
     _lib.require_device()
@@ -370,13 +618,15 @@ def debayer(mosaic, cfa, develop=None, device=0):
     return out
 
 
-def debayer_frames_device(mosaics, dev_out, cfa, device=0, develop=None):
+def debayer_frames_device(mosaics, dev_out, cfa, device=0, develop=None, calibration=None):
     """Upload the n host mosaics (equal shape and dtype) and demosaic them side by side into `dev_out` (device pointer,
     n x H x W x 3 of their dtype): exactly what pipeline.align_and_stack_device(dev_frames, ...) takes.  Waits for the device.
-    `develop`: a Develop applied to every frame."""
+    `develop`: a Develop applied to every frame; `calibration`: a Calibration applied to every mosaic first."""
     _check_cfa(cfa)
     if develop is not None:
         check_develop(develop)
+    if calibration is not None:
+        check_calibration(calibration)
     if len(mosaics) == 0:
         raise ValueError("no mosaics")
     first = check_mosaic(mosaics[0])
@@ -387,7 +637,10 @@ def debayer_frames_device(mosaics, dev_out, cfa, device=0, develop=None):
     try:
         for i, m in enumerate(mosaics):
             stage.upload(check_mosaic(m, first.shape, first.dtype))
-            if develop is None:
+            if calibration is not None:
+                debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, first.dtype, cfa, device=device, develop=develop,
+                               calibration=calibration)
+            elif develop is None:
                 debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, first.dtype, cfa, device=device)
             else:
                 debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, first.dtype, cfa, device=device, develop=develop)

@@ -310,15 +310,17 @@ class PyramidStack(BaseStackAlgo):
         self.print_message(': pyramids fusion completed')
         return stack.finish()
 
-    def focus_stack_arrays(self, frames, mosaic=None, develop=None):
+    def focus_stack_arrays(self, frames, mosaic=None, develop=None, calibration=None):
         """In-memory variant (no file I/O): `frames` is a sequence of H x W x 3 uint8/uint16
         BGR arrays.  Same callbacks as focus_stack, one step per frame per pass.  `mosaic`: a
         `demosaic.Cfa` -- the frames are then raw H x W Bayer mosaics, uploaded as they are and
         demosaiced on the device (demosaic.py).  `develop`: a `demosaic.Develop` beside `mosaic` --
-        defect sites, colour matrix and tone curve around that demosaic."""
-        if develop is not None:
+        defect sites, colour matrix and tone curve around that demosaic.  `calibration`: a
+        `demosaic.Calibration` beside `mosaic` -- master dark and flat field on the raw samples,
+        ahead of both."""
+        if develop is not None or calibration is not None:
             from .demosaic import require_mosaic
-            require_mosaic(mosaic, develop)
+            require_mosaic(mosaic, develop, calibration)
         _lib.require_device()
         n = len(frames)
         if n == 0:
@@ -336,6 +338,8 @@ class PyramidStack(BaseStackAlgo):
         for i, fr in enumerate(frames):
             if mosaic is None:
                 stack.push_frame(fr)
+            elif calibration is not None:
+                stack.push_mosaic(fr, mosaic, develop=develop, calibration=calibration)
             elif develop is None:
                 stack.push_mosaic(fr, mosaic)
             else:

@@ -32,7 +32,10 @@ def two_stage(args):
     byte counts and the stage-1 time of the resident BGR frames (`compute_s`) under "mosaic".
     `--develop` (with `--mosaic`): stage 1 a third time, the mosaics developed on the device (`mi_stack_push_mosaic_developed`:
     camera matrix, sRGB curve, 10 000 defect sites), then the plain mosaic run again; the times sit beside each other under
-    "mosaic"."""
+    "mosaic".
+    `--calibrate` (with `--mosaic`): stage 1 from the mosaics with a `Calibration` (a master dark and a master flat; the gain
+    table is built on the device before the clock starts) and without, three runs of each in turns, so that the two are
+    compared inside one process and the spread from run to run shows; every time is listed under "mosaic"."""
     from shinestacker_amd import _lib as L
     from shinestacker_amd.pipeline import bunches_then_stack
     N, H, W = args.frames, args.height, args.width
@@ -139,6 +142,33 @@ def two_stage(args):
             m1b, _ = run_mosaic()
             developed = {"developed_stage1_seconds": d1, "developed_stage2_seconds": d2, "stage1_seconds_again": m1b,
                          "developed_over_plain_stage1": d1 / m1, "defect_sites": len(dv.sites((H, W)))}
+        if args.calibrate:
+            from shinestacker_amd.demosaic import Calibration
+            rng = np.random.default_rng(7)
+            yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+            fall = 1.0 - 0.7 * (((yy - H / 2) / (H / 2)) ** 2 + ((xx - W / 2) / (W / 2)) ** 2) / 2
+            del yy, xx
+            flat = (40000.0 * fall).astype(np.uint16)
+            del fall
+            dark = rng.integers(0, 512, size=(H, W)).astype(np.uint16)
+            with Calibration(dark=dark, flat=flat) as cb:
+                cb.prepared((H, W), np.uint16, cfa)      # the tables are built and uploaded once per session: not timed
+
+                def run_calibrated():
+                    info = {}
+                    bunches_then_stack(lambda i: mos[i % ndist], N, H, W, np.uint16, out_dev=out.ptr, stacks=stacks,
+                                       results_buf=results, info=info, zero_copy=not args.pageable, mosaic=cfa, calibration=cb)
+                    return info["stage1_s"]
+                run_calibrated()
+                with_c, without = [], []
+                for _ in range(3):
+                    with_c.append(run_calibrated())
+                    without.append(run_mosaic()[0])
+                for s_ in stacks:
+                    s_.sync()
+            developed.update({"calibrated_stage1_seconds": with_c, "plain_stage1_seconds_in_turns": without,
+                              "calibrated_over_plain_stage1": float(np.median(with_c) / np.median(without)),
+                              "plain_stage1_spread": float((max(without) - min(without)) / np.median(without))})
         _, b1, _ = run()        # BGR stage 1 once more, after the mosaic runs: the two are compared inside one process
         extra = {"mosaic": {"stage1_seconds": m1, "stage2_seconds": m2, "bgr_stage1_seconds": s1, "bgr_stage1_seconds_again": b1,
                             "host_to_device_bytes": pushed * per // 3, "bgr_host_to_device_bytes": pushed * per,
@@ -173,6 +203,9 @@ def main():
     ap.add_argument("--develop", action="store_true",
                     help="with --two-stage --mosaic: stage 1 once more with raw development (colour matrix, sRGB curve, defect "
                          "sites) on the demosaic, beside the plain mosaic run")
+    ap.add_argument("--calibrate", action="store_true",
+                    help="with --two-stage --mosaic: stage 1 with a master dark and a flat field applied to every mosaic on the "
+                         "device, in turns with the plain mosaic run")
     ap.add_argument("--pageable", action="store_true", help="host frames in ordinary (pageable) memory: the bounce-copy path")
     args = ap.parse_args()
     if args.two_stage:

@@ -12,6 +12,12 @@ process on the same frame, the plain demosaic_mhc and a device copy of the same 
 case for the uint16 tone table's gather -- and the tone variants run once more on a smooth scene with 1 % noise (", scene").  Same method for every line: hipEvents
 around 5 back-to-back launches, 3 warm-up launches, the median of `--runs` windows; the whole list is measured twice and the
 second pass is reported (the first warms clocks and caches).
+
+`--calibrate`: raw calibration instead (24 MP uint8 and 50 MP uint16, resident), by the same method: the calibration kernel
+(mi_mosaic_calibrate_device, in place) with the dark only, the flat only and both, each beside a device-to-device copy that
+moves the bytes the variant moves (mosaic read and written, dark read, gains read); and mi_mosaic_master_device over K = 16
+frames with reject 0 and reject 7, beside a device copy of the same 16 frames -- a kernel-free read of them, which also writes
+them, so twice the master's traffic.
 """
 import argparse
 import ctypes as C
@@ -31,6 +37,7 @@ ap.add_argument("--runs", type=int, default=20)
 ap.add_argument("--uint8", action="store_true", help="the two shapes at uint8 as well")
 ap.add_argument("--small", action="store_true", help="a 1 MP rehearsal of the whole script")
 ap.add_argument("--develop", action="store_true", help="time raw development: matrix, tone, both, the defect kernel; beside plain and copy")
+ap.add_argument("--calibrate", action="store_true", help="time raw calibration: dark, flat, both, the master kernel; beside copies of the same bytes")
 ap.add_argument("--json", default=None)
 a = ap.parse_args()
 L.require_device()
@@ -143,9 +150,62 @@ def develop_section():
             b.free()
 
 
+def calibrate_section():
+    """--calibrate: every variant on one resident frame per (shape, dtype), two passes, the second reported"""
+    K = 16
+    cases = [("1 MP", 1000, 1000, np.uint8), ("1 MP", 1000, 1000, np.uint16)] if a.small else \
+        [("24 MP", 4000, 6000, np.uint8), ("50 MP", 5792, 8640, np.uint16)]
+    for name, h, w, dt in cases:
+        dt = np.dtype(dt)
+        mx = int(np.iinfo(dt).max)
+        cfa_c = demosaic.Cfa("RGGB", black=1 if dt.itemsize == 1 else 256)
+        c = cfa_c.struct(dt)
+        px, code = h * w, L.DTYPE_CODE[dt]
+        rng = np.random.default_rng(px)
+        frames = L.DeviceBuffer(K * px * dt.itemsize)          # the mosaic under calibration is frame 0
+        first = rng.integers(0, mx + 1, size=(h, w)).astype(dt)
+        for k in range(K):
+            frames.upload(np.roll(first, 977 * k, axis=1), k * px * dt.itemsize)
+        del first
+        dark, gain = L.DeviceBuffer(px * dt.itemsize), L.DeviceBuffer(px * 2)
+        dark.upload(rng.integers(0, mx // 8, size=(h, w)).astype(dt))
+        gain.upload(rng.integers(12000, 45000, size=(h, w)).astype(np.uint16))
+        master = L.DeviceBuffer(px * dt.itemsize)
+        scratch = L.DeviceBuffer(K * px * dt.itemsize)
+        moved = {"dark": 3 * px * dt.itemsize, "flat": 2 * px * dt.itemsize + 2 * px, "dark + flat": 3 * px * dt.itemsize + 2 * px,
+                 "master": (K + 1) * px * dt.itemsize}
+        flags = {"dark": L.MI_CALIB_DARK, "flat": L.MI_CALIB_FLAT, "dark + flat": L.MI_CALIB_DARK | L.MI_CALIB_FLAT}
+        runs = []
+        for key, fl in flags.items():
+            cal = L.CalibStruct(fl, dark.ptr, gain.ptr)
+            half = moved[key] // 2
+            runs.append(("copy for " + key, lambda half=half: L.check(lib.mi_memcpy_d2d_async(0, None, scratch.ptr, scratch.ptr + half, half))))
+            runs.append((key, lambda cal=cal: L.check(lib.mi_mosaic_calibrate_device(0, None, frames.ptr, h, w, code, C.byref(c), C.byref(cal)))))
+        runs.append(("copy of the 16 frames", lambda: L.check(lib.mi_memcpy_d2d_async(0, None, scratch.ptr, frames.ptr, K * px * dt.itemsize))))
+        for reject in (0, 7):
+            runs.append((f"master K=16 reject {reject}",
+                         lambda reject=reject: L.check(lib.mi_mosaic_master_device(0, None, frames.ptr, K, h, w, code, reject, master.ptr))))
+        for rep in range(2):
+            got = {key: measure(fn) for key, fn in runs}
+        for key, (ms, best) in got.items():
+            if key.startswith("copy"):
+                continue
+            ref = "copy of the 16 frames" if key.startswith("master") else "copy for " + key
+            nbytes = moved["master"] if key.startswith("master") else moved[key]
+            copy_ms = got[ref][0]
+            results.append(dict(shape=name, dtype=dt.name, height=h, width=w, what=key, median_ms=ms, best_ms=best, copy_ms=copy_ms,
+                                ratio_to_copy=ms / copy_ms, bytes=nbytes, gbps=1e-6 * nbytes / ms))
+            print(f"{name} {dt.name:6s} {w}x{h} {key:22s}: median {ms:7.4f} ms best {best:7.4f} ms | {1e-6 * nbytes:5.0f} MB at "
+                  f"{1e-6 * nbytes / ms:5.0f} GB/s | {ms / copy_ms:5.2f} x its copy ({ref}: {copy_ms:6.4f} ms)", flush=True)
+        for b in (frames, dark, gain, master, scratch):
+            b.free()
+
+
 if a.develop:
     develop_section()
-for dt in ([] if a.develop else [np.uint16, np.uint8] if a.uint8 else [np.uint16]):
+if a.calibrate:
+    calibrate_section()
+for dt in ([] if a.develop or a.calibrate else [np.uint16, np.uint8] if a.uint8 else [np.uint16]):
     dt = np.dtype(dt)
     for name, h, w in shapes:
         px = h * w
