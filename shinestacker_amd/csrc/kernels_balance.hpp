@@ -137,7 +137,9 @@ __global__ __launch_bounds__(256) void lut_apply_u16(const uint16_t* __restrict_
 // LinearMap (balance.py:87-105) without the host round trip: mean = sum(i * h[i]) / sum(h[i]) over [lo, hi) -- exact
 // integers, one float64 division, as np.average does --, ratio = reference mean / mean, table[i] = trunc(clip(i * ratio, 0,
 // vmax)) in float64.  One workgroup per table; tables below `first_channel` are the identity (the hue channel of HSV / HLS).
-// An empty histogram (np.average raises there) gives ratio 1.
+// An empty histogram (np.average raises there) gives ratio 1.  A product that is NaN -- entry 0 of a black frame: every count in
+// bin 0, mean 0, ratio = reference / 0 = inf, 0 * inf -- writes 0, the value NumPy's astype gives the host path; converting NaN
+// to an integer is undefined, so the kernel never does it.  An infinite product clips to vmax like any large one.
 struct LinRef { double mean[3]; };
 
 template <typename T>
@@ -173,9 +175,8 @@ __global__ __launch_bounds__(256) void lut_linear_build(const uint32_t* __restri
     __syncthreads();
     const double ratio = s_ratio, vmax = (double)(nbins - 1);
     for (int i = tid; i < nbins; i += 256) {
-        double v = (double)i * ratio;
-        v = v < 0.0 ? 0.0 : (v > vmax ? vmax : v);
-        out[i] = (T)v;
+        const double v = (double)i * ratio;
+        out[i] = (T)(v >= 0.0 ? (v > vmax ? vmax : v) : 0.0);   // NaN fails `>=`: 0, never a conversion of NaN
     }
 }
 

@@ -52,7 +52,8 @@ def test_histogram_vs_oracle(L, oracle, dtype, shape):
 @pytest.mark.parametrize("code", [0, 1, 2, 3])
 def test_cvt_color_vs_oracle(L, oracle, code):
     """mi_cvt_color (BGR <-> HSV / HLS, 8-bit) == the oracle's restatement of cv2.cvtColor on every colour of a dense
-    sample of the cube plus random images; 16-bit input is refused like cv2 refuses it."""
+    sample of the cube plus random images; 16-bit input is refused like cv2 refuses it.  (All 256^3 colours, with every hue
+    0..255 on the inverse codes, run in test_gpu_balance_edges.py::test_cvt_color_whole_cube.)"""
     from shinestacker_amd.errors import InvalidOptionError
     rng = np.random.default_rng(code)
     r = np.arange(0, 256, 5, dtype=np.uint8)
@@ -214,7 +215,11 @@ def test_argument_errors(L):
         L.apply_lut(img[..., :2], lut)
     with pytest.raises(ValueError):
         L.apply_lut(img, np.zeros((2, 256), np.uint8))
-    assert b"nlut" in lib.mi_last_error() or True
+    buf, tab = L.DeviceBuffer(img.nbytes), L.DeviceBuffer(2 * 256)
+    assert lib.mi_apply_lut_device(0, None, buf.ptr, buf.ptr, 16 * 16, 0, tab.ptr, 2) == L.MI_ERR_INVALID   # the device form names it
+    assert lib.mi_last_error() == b"nlut must be 1 or 3"
+    buf.free()
+    tab.free()
     # aligner
     h = C.c_void_p()
     with pytest.raises(ValueError):
