@@ -825,6 +825,34 @@ MI_API int mi_stack_push_mosaic_calibrated(mi_stack_t* s, const void* host_mosai
                                            const mi_calib_t* calib, const mi_develop_t* develop, const int32_t* dev_sites,
                                            int n_sites, int pinned);
 
+/* ---- lens correction: radial distortion and lateral chromatic aberration, one remap per frame (kernels_lens.hpp) ----
+ * The radial part of DNG's WarpRectilinear per colour plane, destination -> source, on height x width x 3 BGR frames of
+ * MI_U8 / MI_U16.  tests/lens_restatement.py states it in NumPy.  For the destination pixel (x, y) and plane c, every step in
+ * double and every operation rounded once (nothing fused):
+ *   dx = x - cx, dy = y - cy;  R2 = the largest dx*dx + dy*dy of the four corner pixels;  inv = 1.0 / R2, 0.0 when R2 == 0
+ *   u = (dx*dx + dy*dy) * inv;  s = ((k3*u + k2)*u + k1)*u + k0     with k0..k3 = k[4 * c .. 4 * c + 3]
+ *   px = min(max(cx + dx*s, -1.0), width),  py = min(max(cy + dy*s, -1.0), height)
+ *   X = (int)rint(px * 32), Y = (int)rint(py * 32): 1/32 pixel, the alignment warp's grid;  sx = X >> 5, fx = X & 31, y alike
+ *   v00, v01, v10, v11 = the plane's samples at (sy, sx), (sy, sx+1), (sy+1, sx), (sy+1, sx+1), indices clamped to the frame
+ *   out = (v00*(32-fx)*(32-fy) + v01*fx*(32-fy) + v10*(32-fx)*fy + v11*fx*fy + 512) >> 10
+ * The optional mask (height x width bytes) receives 1 where 0 <= X <= 32 (width - 1) and 0 <= Y <= 32 (height - 1) hold for all
+ * three planes, else 0.  A plane of (1, 0, 0, 0) comes out as it went in, for any centre; a saturated frame stays saturated. */
+typedef struct mi_lens {
+    double k[12];               /* k[4 * c + i], c = B, G, R: the radial polynomial of plane c */
+    double cx;                  /* the optical centre in pixels, column */
+    double cy;                  /* and row */
+} mi_lens_t;
+/* MI_ERR_INVALID names the argument; every check comes before the first device call: a null source, destination or lens,
+ * source == destination (the remap is a gather: distinct buffers), height or width < 1, height * width too large (2^31 pixels
+ * or more, or a side of 2^26 or more: the positions are ints), another dtype, a coefficient that is not finite (its index is
+ * named), a centre that is not finite or lies more than 2^30 pixels from the origin (cx + (x - cx) is then x to far below 1/64
+ * pixel, which is what makes a plane of (1, 0, 0, 0) a copy).  The mask may be null.  mi_lens_remap_device enqueues on `stream`
+ * and does not wait; mi_lens_remap uploads, runs, downloads and waits. */
+MI_API int mi_lens_remap_device(int device, void* stream, const void* dev_src, void* dev_dst, void* dev_mask, int height, int width,
+                                int dtype, const mi_lens_t* lens);
+MI_API int mi_lens_remap(int device, const void* host_src, void* host_dst, void* host_mask, int height, int width, int dtype,
+                         const mi_lens_t* lens);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

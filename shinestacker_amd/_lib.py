@@ -75,6 +75,11 @@ class CalibStruct(C.Structure):
     _fields_ = [("flags", C.c_int32), ("dev_dark", C.c_void_p), ("dev_gain", C.c_void_p)]
 
 
+class LensStruct(C.Structure):
+    """mi_lens_t: what the lens remap sees of a lens.Lens (k[4 * c + i], c = B, G, R; the centre in pixels)"""
+    _fields_ = [("k", C.c_double * 12), ("cx", C.c_double), ("cy", C.c_double)]
+
+
 class DepthMapParams(C.Structure):
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32),
                 ("map_type", C.c_int32), ("energy", C.c_int32), ("kernel_size", C.c_int32),
@@ -272,6 +277,9 @@ SIGNATURES = {
                                       C.c_void_p]),
     "mi_stack_push_mosaic_calibrated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CfaStruct), C.POINTER(CalibStruct),
                                                   C.POINTER(DevelopStruct), C.c_void_p, C.c_int, C.c_int]),
+    "mi_lens_remap_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       C.POINTER(LensStruct)]),
+    "mi_lens_remap": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(LensStruct)]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }

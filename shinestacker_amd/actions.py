@@ -628,6 +628,14 @@ class CombinedActions(StepList, FrameDirectory, _Sharded):
         if img is None:
             raise RuntimeError(f"Invalid file: {self.input_full_path}/{self.filenames[idx]}")
         self.dtype, self.shape = img.dtype, img.shape
+        if not self.step_process:
+            # The input file is the frame as the lens drew it.  A sub-action that changes the frame's GEOMETRY
+            # (`corrects_reference`: LensCorrection) must have seen the reference too, or every corrected frame is fitted to a
+            # distorted one; with step_process the reference is an output file, which has been through the chain already.
+            # (MaskNoise and Vignetting leave the reference as the reference does: INTEGRATION.md.)
+            for a in self._actions:
+                if a.enabled and getattr(a, "corrects_reference", False):
+                    img = a.run_frame(idx, idx, img)
         return img
 
     def run_step(self):

@@ -32,6 +32,7 @@
 #include "kernels_composite.hpp"
 #include "kernels_f64.hpp"
 #include "kernels_steps.hpp"
+#include "kernels_lens.hpp"
 
 using namespace mi;
 
@@ -1884,6 +1885,50 @@ int mi_mosaic_calibrate(int device, const void* host_mosaic, void* host_out, int
     }
     if ((rc = mi_mosaic_calibrate_device(device, nullptr, m, height, width, dtype, cfa, &c))) return rc;
     return tmp.download(host_out, m, nb);
+}
+
+// ---------------------------------------------------------------- lens correction (kernels_lens.hpp)
+static int lens_check(const void* src, const void* dst, int height, int width, int dtype, const mi_lens_t* lens) {
+    if (!src) return fail(MI_ERR_INVALID, "null source frame");
+    if (!dst) return fail(MI_ERR_INVALID, "null destination frame");
+    if (!lens) return fail(MI_ERR_INVALID, "null lens");
+    if (src == dst) return fail(MI_ERR_INVALID, "source and destination must be distinct buffers (the remap is a gather)");
+    if (height < 1 || width < 1) return fail(MI_ERR_INVALID, "height and width must be >= 1 (got %dx%d)", width, height);
+    // (a side below 2^26: positions in 1/32 pixel fit an int)
+    if ((uint64_t)height * (uint64_t)width >= (1ull << 31) || height >= (1 << 26) || width >= (1 << 26))
+        return fail(MI_ERR_INVALID, "height x width too large");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16 for a lens remap (got %d)", dtype);
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(lens->k[i])) return fail(MI_ERR_INVALID, "lens k[%d] must be finite", i);
+    // (a centre within 2^30 pixels of the origin: cx + (x - cx) is then x to far below 1/64 pixel, which makes an identity plane a copy)
+    if (!std::isfinite(lens->cx) || std::fabs(lens->cx) > 1073741824.0) return fail(MI_ERR_INVALID, "lens cx must be finite and at most 2^30 in magnitude");
+    if (!std::isfinite(lens->cy) || std::fabs(lens->cy) > 1073741824.0) return fail(MI_ERR_INVALID, "lens cy must be finite and at most 2^30 in magnitude");
+    return MI_OK;
+}
+
+int mi_lens_remap_device(int device, void* stream, const void* dev_src, void* dev_dst, void* dev_mask, int height, int width,
+                         int dtype, const mi_lens_t* lens) {
+    int rc = lens_check(dev_src, dev_dst, height, width, dtype, lens);
+    if (rc) return rc;
+    MI_HIP(hipSetDevice(device));
+    lens_launch((hipStream_t)stream, dev_src, dev_dst, dev_mask, height, width, dtype, *lens);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_lens_remap(int device, const void* host_src, void* host_dst, void* host_mask, int height, int width, int dtype,
+                  const mi_lens_t* lens) {
+    int rc = lens_check(host_src, host_dst, height, width, dtype, lens);
+    if (rc) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t npx = (size_t)height * width, nb = npx * 3 * dtype_size(dtype);
+    DevScratch tmp(nullptr);
+    void *src = nullptr, *dst = nullptr, *mask = nullptr;
+    if ((rc = tmp.upload(&src, host_src, nb)) || (rc = tmp.alloc(&dst, nb)) || (host_mask && (rc = tmp.alloc(&mask, npx))) ||
+        (rc = mi_lens_remap_device(device, nullptr, src, dst, mask, height, width, dtype, lens)))
+        return rc;
+    if (host_mask && (rc = tmp.download(host_mask, mask, npx))) return rc;
+    return tmp.download(host_dst, dst, nb);
 }
 
 int mi_stack_push_mosaic_calibrated(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa,

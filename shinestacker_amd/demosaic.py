@@ -561,11 +561,37 @@ def defects_device(dev_mosaic, h, w, dtype, develop, device=0, stream=None):
         _lib.check(_lib.load().mi_mosaic_defects_device(device, stream, dev_mosaic, int(h), int(w), _lib.DTYPE_CODE[dt], sites, n))
 
 
-def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None, develop=None, calibration=None):
+def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None, develop=None, calibration=None, lens=None,
+                   lens_scratch=None):
     """debayer() for a mosaic resident in HBM: `dev_mosaic` (h x w) -> `dev_bgr` (h x w x 3).  Queued on `stream`, not waited
     for.  `develop`: a Develop -- its defect sites are repaired IN PLACE in `dev_mosaic` first (no other site is written),
     then colour matrix and tone curve ride on the demosaic; its device tables must outlive the queued kernels.
-    `calibration`: a Calibration -- `dev_mosaic` is calibrated IN PLACE ahead of all of that."""
+    `calibration`: a Calibration -- `dev_mosaic` is calibrated IN PLACE ahead of all of that.
+    `lens`: a lens.Lens -- the demosaic / develop kernel writes one scratch frame and the lens remap (lens.py) takes it to
+    `dev_bgr`.  `lens_scratch`: that frame, a DeviceBuffer of h x w x 3 samples which must outlive the queued kernels; None:
+    one is allocated here, and the call then WAITS for the device before it frees it."""
+    if lens is not None:
+        from .lens import check_lens, correct_device
+        lens = check_lens(lens)
+        dt = _dtype(dtype)
+        own = lens_scratch is None
+        need = int(h) * int(w) * 3 * dt.itemsize
+        if not own and getattr(lens_scratch, "nbytes", 0) < need:
+            raise InvalidOptionError("lens_scratch", getattr(lens_scratch, "nbytes", lens_scratch),
+                                     f"a DeviceBuffer of at least {need} bytes (h x w x 3 samples) is expected")
+        if own:
+            _lib.require_device()
+            lens_scratch = _lib.DeviceBuffer(int(h) * int(w) * 3 * dt.itemsize, device)
+        try:
+            debayer_device(dev_mosaic, lens_scratch.ptr, h, w, dt, cfa, device=device, stream=stream, develop=develop,
+                           calibration=calibration)
+            correct_device(lens_scratch.ptr, dev_bgr, h, w, dt, lens, device=device, stream=stream)
+            if own:
+                _lib.check(_lib.load().mi_device_synchronize(device))
+        finally:
+            if own:
+                lens_scratch.free()
+        return
     dt = _dtype(dtype)
     c = _check_cfa(cfa).struct(dt)
     if h < 2 or w < 2:
@@ -585,25 +611,38 @@ def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None,
                                      _lib.C.byref(d)))
 
 
-def debayer(mosaic, cfa, develop=None, device=0, calibration=None):
+def debayer(mosaic, cfa, develop=None, device=0, calibration=None, lens=None):
     """H x W uint8 / uint16 mosaic -> H x W x 3 BGR array of the same dtype.  `develop`: a Develop (defect sites, colour
-    matrix, tone curve); None: the plain demosaic.  `calibration`: a Calibration applied to the mosaic first."""
+    matrix, tone curve); None: the plain demosaic.  `calibration`: a Calibration applied to the mosaic first.  `lens`: a
+    lens.Lens -- the lens correction behind all of it, on the device: equal to lens.correct(debayer(...), lens)."""
     a = np.ascontiguousarray(check_mosaic(mosaic))
     c = _check_cfa(cfa).struct(a.dtype)
-    if calibration is not None:
-        check_calibration(calibration).check_frame(a.shape, a.dtype)
+    if lens is not None:
+        from .lens import check_lens
+        lens = check_lens(lens)
+    if calibration is not None or lens is not None:
+        if calibration is not None:
+            check_calibration(calibration).check_frame(a.shape, a.dtype)
         if develop is not None:
             check_develop(develop)
         _lib.require_device()
         h, w = a.shape
         stage, bgr = _lib.DeviceBuffer(a.nbytes, device), _lib.DeviceBuffer(a.nbytes * 3, device)
+        scratch = None
         try:
             stage.upload(a)
-            debayer_device(stage.ptr, bgr.ptr, h, w, a.dtype, cfa, device=device, develop=develop, calibration=calibration)
+            if lens is None:
+                debayer_device(stage.ptr, bgr.ptr, h, w, a.dtype, cfa, device=device, develop=develop, calibration=calibration)
+            else:
+                scratch = _lib.DeviceBuffer(a.nbytes * 3, device)
+                debayer_device(stage.ptr, bgr.ptr, h, w, a.dtype, cfa, device=device, develop=develop, calibration=calibration,
+                               lens=lens, lens_scratch=scratch)
             return bgr.download((h, w, 3), a.dtype)     # (a blocking copy on the null stream: behind the kernels)
         finally:
             stage.free()
             bgr.free()
+            if scratch is not None:
+                scratch.free()
     if develop is not None:
         mq, tone, sites = check_develop(develop).host_args(a.shape, a.dtype)
     _lib.require_device()
@@ -618,11 +657,15 @@ def debayer(mosaic, cfa, develop=None, device=0, calibration=None):
     return out
 
 
-def debayer_frames_device(mosaics, dev_out, cfa, device=0, develop=None, calibration=None):
+def debayer_frames_device(mosaics, dev_out, cfa, device=0, develop=None, calibration=None, lens=None):
     """Upload the n host mosaics (equal shape and dtype) and demosaic them side by side into `dev_out` (device pointer,
     n x H x W x 3 of their dtype): exactly what pipeline.align_and_stack_device(dev_frames, ...) takes.  Waits for the device.
-    `develop`: a Develop applied to every frame; `calibration`: a Calibration applied to every mosaic first."""
+    `develop`: a Develop applied to every frame; `calibration`: a Calibration applied to every mosaic first; `lens`: a
+    lens.Lens -- every frame passes through the lens correction behind its demosaic, through one scratch frame."""
     _check_cfa(cfa)
+    if lens is not None:
+        from .lens import check_lens
+        lens = check_lens(lens)
     if develop is not None:
         check_develop(develop)
     if calibration is not None:
@@ -634,10 +677,16 @@ def debayer_frames_device(mosaics, dev_out, cfa, device=0, develop=None, calibra
     frame_bytes = h * w * 3 * first.itemsize
     _lib.require_device()
     stage = _lib.DeviceBuffer(h * w * first.itemsize, device)
+    scratch = None
     try:
+        if lens is not None:
+            scratch = _lib.DeviceBuffer(frame_bytes, device)
         for i, m in enumerate(mosaics):
             stage.upload(check_mosaic(m, first.shape, first.dtype))
-            if calibration is not None:
+            if lens is not None:
+                debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, first.dtype, cfa, device=device, develop=develop,
+                               calibration=calibration, lens=lens, lens_scratch=scratch)
+            elif calibration is not None:
                 debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, first.dtype, cfa, device=device, develop=develop,
                                calibration=calibration)
             elif develop is None:
@@ -648,3 +697,5 @@ def debayer_frames_device(mosaics, dev_out, cfa, device=0, develop=None, calibra
             _lib.check(_lib.load().mi_device_synchronize(device))
     finally:
         stage.free()
+        if scratch is not None:
+            scratch.free()

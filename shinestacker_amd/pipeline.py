@@ -22,11 +22,12 @@ from .errors import AlignmentError, InvalidOptionError
 from .imageio import validate_image
 
 
-def _prestack_steps(mask_noise, vignetting, n_frames, device):
+def _prestack_steps(mask_noise, vignetting, n_frames, device, lens=None):
     """The sub-actions that run on a frame before it is aligned, in the reference's order (constants.py:34 SUB_ACTION_TYPES:
     MaskNoise, Vignetting, AlignFrames, BalanceFrames), from the `mask_noise=` / `vignetting=` option dicts.  `mask_noise`
     takes MaskNoise's options; its `noise_mask` is the mask as an H x W array, or the path of the mask file (there is no
-    working directory here: the path is used as given)."""
+    working directory here: the path is used as given).  `lens`: a lens.Lens, or a dict of LensCorrection's options -- the
+    lens correction, which the reference does not have, comes last: hot pixels are repaired before anything resamples them."""
     steps = []
     if mask_noise is not None:
         from .noise_detection import MaskNoise
@@ -44,6 +45,11 @@ def _prestack_steps(mask_noise, vignetting, n_frames, device):
         vg = Vignetting(device=device, **dict(vignetting))
         vg.begin(None, counts=n_frames)
         steps.append(vg)
+    if lens is not None:
+        from .lens import make_step
+        lc = make_step(lens, device)
+        lc.begin(None, counts=n_frames)
+        steps.append(lc)
     return steps
 
 
@@ -336,7 +342,7 @@ def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_
 def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, feature_config=None,
                     matching_config=None, device=0, batch_frames=16, check_running=None, mask_noise=None, vignetting=None,
                     info=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None, retouch=None,
-                    depth_composite=None, **stack_kwargs):
+                    depth_composite=None, lens=None, **stack_kwargs):
     """Align every frame to frames[ref_idx] (fixed reference, `step_process=False` order,
     stack_framework.py:191-232) and fuse them.  `frames`: sequence of H x W x 3 uint8/uint16 BGR
     arrays.  Returns (fused image, list of n_good_matches).
@@ -345,6 +351,10 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     every frame, the reference frame included, then passes through them, in that order, before it is estimated or warped
     -- the reference's sub-action order.  None (default): the frames are taken as they are.  `info`: an optional dict that
     receives `info["vignetting_corrections"]` (the sub-action's percentile radii per frame).
+
+    `lens`: a `lens.Lens`, or a dict of `LensCorrection`'s options (lens, autoscale): every frame, the reference frame
+    included, passes through the lens correction (lens.py) behind `mask_noise` and `vignetting` and before it is estimated
+    or warped.  None (default): nothing is built, allocated, loaded or called.
 
     `denoise_amount`: the stack actions' option (`_finish`): when positive the fused frame is denoised on the device before
     it is downloaded.  0 (default): nothing is touched.  `white_balance` (an RGB triple) / `unsharp` ((radius, amount,
@@ -386,7 +396,7 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     n = len(frames)
     if n == 0:
         raise ValueError("no frames")
-    pre = _prestack_steps(mask_noise, vignetting, n, device)
+    pre = _prestack_steps(mask_noise, vignetting, n, device, lens)
     if pre:
         fixed = []
         for i, fr in enumerate(frames):
@@ -804,7 +814,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                            balance=None, ecc_batch=16, step_process=False, native_loop=True, handles=None,
                            keep_handles=False, info=None, chain_refine=True, chain_serial=False, mask_noise=None,
                            vignetting=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None,
-                           depth_composite=None, **stack_kwargs):
+                           depth_composite=None, lens=None, **stack_kwargs):
     """BASELINE config 4 with every frame resident in HBM: `dev_frames` is the device address of
     `n_frames` contiguous H x W x 3 frames.  Each frame is registered against frames[ref_idx] by
     the device ECC estimator (mi_aligner_*), warped with the blurred replicate border of
@@ -846,6 +856,10 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     (InvalidOptionError otherwise: the apply pass needs every frame of the contiguous stack 16-byte aligned).  Because the
     corrections overwrite `dev_frames`, a second call on the same buffer
     with the options set would correct the frames a second time: upload the frames again, or leave the options out.
+
+    `lens`: a `lens.Lens`, or a dict of `LensCorrection`'s options (lens, autoscale): the lens correction (lens.py), a third
+    pre-stack step behind those two and under the same terms -- in place in `dev_frames` through one scratch frame, the
+    Python frame loop, no handle reuse.  None (default): nothing is built, allocated, loaded or called.
 
     `step_process=True`: the reference's chained order (see `_align_chains_device`): every frame is registered against
     its already-aligned neighbour; the aligned frames are kept in one extra device buffer (n_frames frames) and fused in
@@ -909,10 +923,10 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     dt = np.dtype(dtype)
     fb = height * width * 3 * dt.itemsize
     lib = _lib.load()
-    pre = _prestack_steps(mask_noise, vignetting, n_frames, device)
+    pre = _prestack_steps(mask_noise, vignetting, n_frames, device, lens)
     if pre:
         if handles is not None or keep_handles:
-            raise InvalidOptionError("handles", "reuse", ": handle reuse is not implemented with mask_noise= / vignetting=")
+            raise InvalidOptionError("handles", "reuse", ": handle reuse is not implemented with mask_noise= / vignetting= / lens=")
         native_loop = False
         for i in range(n_frames):
             for step in pre:
