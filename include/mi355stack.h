@@ -853,6 +853,55 @@ MI_API int mi_lens_remap_device(int device, void* stream, const void* dev_src, v
 MI_API int mi_lens_remap(int device, const void* host_src, void* host_dst, void* host_mask, int height, int width, int dtype,
                          const mi_lens_t* lens);
 
+/* ---- packed raw samples in: a raw file's sample bytes unpacked on the device (kernels_unpack.hpp) ----
+ * A raw file (DNG: a TIFF) stores its mosaic as strips or tiles of 8, 10, 12, 14 or 16-bit samples.  `span` is one contiguous
+ * run of the file's bytes that holds every segment, uploaded as it lies; seg_offsets[k] is the start of segment k inside it
+ * (segments in any order, gaps between them), k = (ys / seg_height) * ceil(image_width / seg_width) + xs / seg_width for the
+ * stored site (ys, xs).  Packing (TIFF FillOrder 1): every row of a segment starts on a byte boundary and takes
+ * ceil(seg_width * bits / 8) bytes; 10, 12 and 14-bit samples follow each other most significant bit first in a big-endian
+ * bit stream; 16-bit samples are two bytes in the file's byte order; edge tiles are stored at full tile size, the last strip
+ * holds the rows that are left.  The output is the crop: height x width samples of `dtype` from (crop_y, crop_x), rows packed.
+ * Per site: v = the sample; with a table v = table[min(v, table_len - 1)]; out = (v << shift) truncated to the dtype.
+ * tests/unpack_restatement.py states it in NumPy. */
+typedef struct mi_raw_layout {
+    int32_t bits;           /* 8, 10, 12, 14 or 16                                                      */
+    int32_t big_endian;     /* 16-bit samples: 1 when the most significant byte comes first             */
+    int32_t image_height;   /* the stored image                                                         */
+    int32_t image_width;
+    int32_t tiled;          /* 0: strips (seg_width == image_width), 1: tiles                           */
+    int32_t seg_height;     /* RowsPerStrip, or TileLength                                              */
+    int32_t seg_width;      /* image_width, or TileWidth                                                */
+    int32_t crop_y;         /* the output's origin in the stored image                                  */
+    int32_t crop_x;
+    int32_t height;         /* the output                                                               */
+    int32_t width;
+    int32_t shift;          /* 0 .. 15                                                                  */
+    int32_t table_len;      /* entries of the linearisation table, 0: none                              */
+    int32_t dtype;          /* of the output: MI_U8 for 8 bits, MI_U16 otherwise                        */
+} mi_raw_layout_t;
+/* MI_ERR_INVALID names the argument; every check comes before the first device call: null pointers, bits outside the five,
+ * a dtype that does not belong to the bits, sizes < 1, a crop outside the stored image, strips narrower than the image,
+ * height * width >= 2^31, span_bytes == 0 or >= 2^32, shift outside [0, 15], table_len outside [0, 65536], a table (uint16
+ * entries) without its pointer or with 8-bit samples.  The host form and mi_stack_push_packed also refuse a segment that ends
+ * outside the span; the device form takes offsets inside the span as its precondition (the kernel reads no byte at or beyond
+ * span_bytes whatever they hold: such a byte counts as 0).  mi_raw_unpack_device enqueues on `stream` and does not wait;
+ * mi_raw_unpack uploads, runs, downloads and waits. */
+MI_API int mi_raw_unpack_device(int device, void* stream, const void* dev_span, size_t span_bytes, const uint32_t* dev_seg_offsets,
+                                const mi_raw_layout_t* layout, const uint16_t* dev_table, void* dev_out);
+MI_API int mi_raw_unpack(int device, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets,
+                         const mi_raw_layout_t* layout, const uint16_t* host_table, void* host_out);
+/* mi_stack_push_mosaic_calibrated with the packed span uploaded instead of the mosaic: layout->height, width and dtype are the
+ * handle's.  The span goes up on the mosaic stage's copy stream into a packed slot beside the stage's mosaic slot (sized on
+ * first use, grown when a later span is larger), the offsets and the table behind it; the unpack kernel writes the mosaic slot
+ * behind the copy, and calibration (`calib` may be null), defect repair and the plain or developed demosaic follow as they do
+ * for a mosaic.  Packed, mosaic and BGR pushes may mix on one handle, frame by frame.  pinned != 0: the SPAN lies in pinned
+ * host memory and is read directly, as in mi_stack_push_mosaic (mi_stack_wait_uploads tells when); seg_offsets and host_table
+ * are copied by the call either way.  Float-64 and MI_IMPL_SIMPLE handles take the synchronous route. */
+MI_API int mi_stack_push_packed(mi_stack_t* s, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets,
+                                const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_cfa_t* cfa,
+                                const mi_calib_t* calib, const mi_develop_t* develop, const int32_t* dev_sites, int n_sites,
+                                int pinned);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

@@ -24,6 +24,7 @@ from . import demosaic  # noqa: F401,E402
 from .demosaic import Calibration, Cfa, Develop, calibrate, debayer, flat_gain, master_frame  # noqa: F401,E402
 from . import lens  # noqa: F401,E402
 from .lens import Lens, LensCorrection  # noqa: F401,E402
+from . import dng  # noqa: F401,E402
 
-__all__ = ["lens", "Lens", "LensCorrection", "AlignFrames", "BalanceFrames", "Vignetting", "MaskNoise", "NoiseDetection", "denoise", "unsharp_mask", "white_balance_from_rgb", "depth_out", "stereo", "retouch", "depth_render", "Stroke", "demosaic", "Cfa", "Develop", "debayer", "Calibration", "master_frame", "flat_gain", "calibrate", "align_images", "PyramidStack", "DepthMapStack", "BaseStackAlgo", "StackJob", "FocusStack", "FocusStackBunch",
+__all__ = ["dng", "lens", "Lens", "LensCorrection", "AlignFrames", "BalanceFrames", "Vignetting", "MaskNoise", "NoiseDetection", "denoise", "unsharp_mask", "white_balance_from_rgb", "depth_out", "stereo", "retouch", "depth_render", "Stroke", "demosaic", "Cfa", "Develop", "debayer", "Calibration", "master_frame", "flat_gain", "calibrate", "align_images", "PyramidStack", "DepthMapStack", "BaseStackAlgo", "StackJob", "FocusStack", "FocusStackBunch",
            "CombinedActions", "SubAction", "get_bunches", "constants"]

@@ -80,6 +80,14 @@ class LensStruct(C.Structure):
     _fields_ = [("k", C.c_double * 12), ("cx", C.c_double), ("cy", C.c_double)]
 
 
+class RawLayoutStruct(C.Structure):
+    """mi_raw_layout_t: how the samples of a raw file lie in its uploaded span (dng.RawLayout.struct)"""
+    _fields_ = [("bits", C.c_int32), ("big_endian", C.c_int32), ("image_height", C.c_int32), ("image_width", C.c_int32),
+                ("tiled", C.c_int32), ("seg_height", C.c_int32), ("seg_width", C.c_int32), ("crop_y", C.c_int32),
+                ("crop_x", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("shift", C.c_int32),
+                ("table_len", C.c_int32), ("dtype", C.c_int32)]
+
+
 class DepthMapParams(C.Structure):
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32),
                 ("map_type", C.c_int32), ("energy", C.c_int32), ("kernel_size", C.c_int32),
@@ -280,6 +288,12 @@ SIGNATURES = {
     "mi_lens_remap_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(LensStruct)]),
     "mi_lens_remap": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(LensStruct)]),
+    "mi_raw_unpack_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p,
+                                       C.c_void_p]),
+    "mi_raw_unpack": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p, C.c_void_p]),
+    "mi_stack_push_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p,
+                                       C.POINTER(CfaStruct), C.POINTER(CalibStruct), C.POINTER(DevelopStruct), C.c_void_p, C.c_int,
+                                       C.c_int]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }
@@ -653,6 +667,52 @@ class Stack:
             if rc != MI_ERR_INVALID:     # MI_ERR_INVALID: the library does not see pinned memory there (stale record)
                 check(rc)
         check(push(a.ctypes.data, 0, 0))
+
+    def push_packed(self, frame, zero_copy=False, develop=None, calibration=None):
+        """Push one host frame as the packed sample bytes of its raw file (`frame`: a dng.DngFrame whose cropped size and
+        dtype are the handle's): the span crosses the host link as it lies in the file -- 0.75 of a uint16 mosaic's bytes at
+        12 bits -- and is unpacked on the device behind its upload, then calibrated, repaired and demosaiced with the frame's
+        own Cfa exactly as push_mosaic does.  `develop`, `calibration`: as in push_mosaic (None: that step is not run).
+        `zero_copy`: the frame's span must then lie in pinned memory (a file mapping is not: it takes the copying path)."""
+        lay = frame.layout
+        if (lay.height, lay.width) != (self.height, self.width):
+            raise ValueError(f"mosaic shape {(lay.height, lay.width)} != {(self.height, self.width)}")
+        if lay.dtype != self.in_dtype:
+            raise ValueError(f"mosaic dtype {lay.dtype} != {self.in_dtype}")
+        c = frame.cfa.struct(self.in_dtype)
+        L, offsets, table = lay.struct(), lay.offsets, lay.table
+        cal = d = sites = None
+        n_sites = 0
+        if calibration is not None:
+            from .demosaic import check_calibration
+            cal = check_calibration(calibration).prepared((lay.height, lay.width), self.in_dtype, frame.cfa, self.device)
+            if not any(x is calibration for x in self._calibrations):
+                self._calibrations.append(calibration)
+        if develop is not None:
+            from .demosaic import check_develop
+            d, sites, n_sites = check_develop(develop).prepared((lay.height, lay.width), self.in_dtype, self.device)
+            if not any(x is develop for x in self._develops):
+                self._develops.append(develop)
+        span = frame.span
+        if self.float_type == MI_F64 or self.params.impl == IMPL_SIMPLE:
+            from .dng import host_span
+            span = host_span(frame)     # the synchronous route uploads straight out of the caller's memory
+
+        def push(pinned):
+            return load().mi_stack_push_packed(self._h, span.ctypes.data, span.nbytes, offsets.ctypes.data, C.byref(L),
+                                               None if table is None else table.ctypes.data, C.byref(c),
+                                               None if cal is None else C.byref(cal), None if d is None else C.byref(d), sites,
+                                               n_sites, pinned)
+        if zero_copy and is_pinned(span):
+            rc = push(1)
+            if rc == MI_OK:
+                self._inflight.append(span)
+                if len(self._inflight) > 64:
+                    self.wait_uploads(32)
+                return
+            if rc != MI_ERR_INVALID:     # MI_ERR_INVALID: the library does not see pinned memory there (stale record)
+                check(rc)
+        check(push(0))
 
     def wait_uploads(self, max_outstanding=0):
         """block until at most `max_outstanding` of the pinned frames pushed so far are still being uploaded: a producer that

@@ -145,7 +145,13 @@ class FrameDirectory:
 
     def __init__(self, name, input_path='', output_path='', working_path='',
                  plot_path=constants.DEFAULT_PLOTS_PATH, scratch_output_dir=True, resample=1,
-                 reverse_order=constants.DEFAULT_FILE_REVERSE_ORDER, **_kwargs):
+                 reverse_order=constants.DEFAULT_FILE_REVERSE_ORDER, raw=None, **_kwargs):
+        # raw (extension; None: off): a dng.Raw -- the folder scan also accepts `.dng` files, they are read through dng.py and
+        # every output named after one is written as .tif
+        if raw is not None:
+            from .dng import check_raw
+            check_raw(raw)
+        self.raw = raw
         self.name = name
         self.working_path = working_path
         self.plot_path = plot_path
@@ -164,13 +170,48 @@ class FrameDirectory:
 
     def folder_filelist(self):
         _dirpath, _, names = next(os.walk(self.input_full_path))
+        extensions = constants.EXTENSIONS
+        if self.raw is not None:
+            from .dng import EXTENSIONS as raw_extensions
+            extensions = set(extensions) | raw_extensions
         files = sorted(n for n in names
-                       if os.path.splitext(n)[-1][1:].lower() in constants.EXTENSIONS)
+                       if os.path.splitext(n)[-1][1:].lower() in extensions)
         if self.reverse_order:
             files.reverse()
         if self.resample > 1:
             files = files[0::self.resample]
         return files
+
+    def _is_raw_name(self, name):
+        if self.raw is None:
+            return False
+        from .dng import is_dng
+        return is_dng(name)
+
+    def output_name(self, name):
+        """the file name an output derived from the input `name` gets: a `.dng` input (raw=) is written as .tif"""
+        return name if not self._is_raw_name(name) else name[:len(name) - len(name.split(".")[-1])] + "tif"
+
+    def read_frame(self, path):
+        """the H x W x 3 BGR frame of an input file: read_img, or with raw= a `.dng` path through dng.develop"""
+        if not self._is_raw_name(path):
+            return read_img(path)
+        return self._develop_raw(self._parse_input(path))
+
+    def _parse_input(self, path):
+        """the host half of read_frame (codec or TIFF structure; safe on a worker thread): a frame, or a dng.DngFrame"""
+        if not self._is_raw_name(path):
+            return read_img(path)
+        from . import dng
+        return dng.read(path)
+
+    def _develop_raw(self, frame):
+        from . import dng
+        if not isinstance(frame, dng.DngFrame):
+            return frame
+        stacker = getattr(self, "stack_algo", None)
+        return dng.develop(frame, develop=self.raw.develop, lens=self.raw.lens, calibration=self.raw.calibration,
+                           device=getattr(stacker, "device", getattr(self, "device", 0)))
 
     def set_filelist(self):
         self.filenames = self.folder_filelist()
@@ -256,6 +297,11 @@ class _FocusStackCommon(FrameDirectory):
                 raise InvalidOptionError("denoise_amount", self.denoise_amount,
                                          f"the amount is also the template window size: integral, at most {MAX_TEMPLATE_WINDOW}")
         self.plot_stack = kwargs.pop('plot_stack', constants.DEFAULT_PLOT_STACK)
+        # raw (extension; None: off): the dng.Raw FrameDirectory took -- the stacker reads the `.dng` files itself
+        if kwargs.pop('raw', None) is not None:
+            if not hasattr(stack_algo, "raw"):
+                raise InvalidOptionError("raw", self.raw, f"the stacker {stack_algo.name()} does not read raw files")
+            stack_algo.raw = self.raw
         # depth_map_path (extension; None: off): every output also gets {working_path}/{depth_map_path}/{prefix}{name}.png, the
         # stacker's depth_map() as 16-bit grey (depth_out.quantize); depth_map_sigma None: the stacker's own default
         self.depth_map_path = kwargs.pop('depth_map_path', None)
@@ -316,7 +362,7 @@ class _FocusStackCommon(FrameDirectory):
 
         def frames():
             for path in img_files:
-                img = read_img(path)
+                img = self.read_frame(path)
                 if img is None:
                     raise RuntimeError(f"Invalid file: {path}")
                 yield img
@@ -340,7 +386,7 @@ class _FocusStackCommon(FrameDirectory):
                 if not -len(img_files) <= s.source < len(img_files):
                     raise InvalidOptionError("source", s.source, f"the stack has {len(img_files)} frames")
                 path = img_files[s.source]
-            img = read_img(path)
+            img = self.read_frame(path)
             if img is None:
                 raise RuntimeError(f"Invalid file: {path}")
             if img.dtype != stacked.dtype:
@@ -355,7 +401,7 @@ class _FocusStackCommon(FrameDirectory):
         self.sub_message_r(': reading input files')
         img_files = sorted(os.path.join(self.input_full_path, n) for n in filenames)
         stacked = self.stack_algo.focus_stack(img_files)
-        parts = filenames[0].split(".")
+        parts = self.output_name(filenames[0]).split(".")
         out_filename = f"{self.output_dir}/{self.prefix}{parts[0]}." + '.'.join(parts[1:])
         composite = None
         if self.depth_composite_path is not None:
@@ -541,7 +587,7 @@ class CombinedActions(StepList, FrameDirectory, _Sharded):
     (stack_framework.py:191-232 FramesRefActions + :246-302 CombinedActions)."""
 
     def __init__(self, name, actions=None, enabled=True, ref_idx=-1, step_process=False,
-                 io_threads=2, shard=None, **kwargs):
+                 io_threads=2, shard=None, raw=None, **kwargs):
         # SURVEY.md 8(e), alignment: without step_process every frame depends on the reference frame only, so
         # the frames split over processes like bunches do (shard=(rank, world) or 'env'; every rank reads the
         # reference frame itself, no collective); with step_process the frames form two serial chains
@@ -549,7 +595,12 @@ class CombinedActions(StepList, FrameDirectory, _Sharded):
         self._shard_setup(shard, kwargs, self._actions)
         if self.world > 1 and step_process:
             raise InvalidOptionError("shard", shard, "step_process chains frames; they cannot be sharded")
-        FrameDirectory.__init__(self, name, **kwargs)
+        FrameDirectory.__init__(self, name, raw=raw, **kwargs)
+        # raw (extension; None: off): a `.dng` frame is read through dng.develop, so the sub-actions see an ordinary BGR frame.
+        # A lens the raw reading applies ("auto": each file's own opcode) beside a LensCorrection sub-action would correct twice.
+        if raw is not None and raw.lens is not None and any(getattr(a, "corrects_reference", False) for a in self._actions):
+            raise InvalidOptionError("raw", raw, "raw.lens is active and a LensCorrection sub-action is present: the frames would be "
+                                                 "corrected twice; set Raw(lens=None) or drop the sub-action")
         StepList.__init__(self, name, enabled)
         self.ref_idx = ref_idx
         self.step_process = step_process
@@ -606,7 +657,9 @@ class CombinedActions(StepList, FrameDirectory, _Sharded):
     def _read_input(self, idx):
         fut = self._ahead.pop(idx, None)
         path = f"{self.input_full_path}/{self.filenames[idx]}"
-        return fut.result() if fut is not None else read_img(path)
+        if self.raw is None:
+            return fut.result() if fut is not None else read_img(path)
+        return self._develop_raw(fut.result() if fut is not None else self._parse_input(path))
 
     def _decode_next(self, idx, idx_step):
         """Start decoding the file the next step will ask for (same order as run_step)."""
@@ -620,11 +673,14 @@ class CombinedActions(StepList, FrameDirectory, _Sharded):
         if self.world > 1 and nxt not in self._block:
             return
         if 0 <= nxt < n and nxt not in self._ahead and not (self.step_process and nxt == self.ref_idx):
-            self._ahead[nxt] = pool.submit(read_img, f"{self.input_full_path}/{self.filenames[nxt]}")
+            self._ahead[nxt] = pool.submit(read_img if self.raw is None else self._parse_input,
+                                           f"{self.input_full_path}/{self.filenames[nxt]}")
 
     def img_ref(self, idx):
         base = self.output_dir if self.step_process else self.input_full_path
-        img = read_img(f"{base}/{self.filenames[idx]}")
+        # (with step_process the reference is an OUTPUT file: it carries the output's name)
+        img = read_img(f"{base}/{self.output_name(self.filenames[idx])}") if self.step_process else \
+            self.read_frame(f"{base}/{self.filenames[idx]}")
         if img is None:
             raise RuntimeError(f"Invalid file: {self.input_full_path}/{self.filenames[idx]}")
         self.dtype, self.shape = img.dtype, img.shape
@@ -683,11 +739,11 @@ class CombinedActions(StepList, FrameDirectory, _Sharded):
             out = np.ascontiguousarray(img)
             pool = self._io_pool()
             if pool is None or self.step_process:
-                write_img(self.output_dir + "/" + filename, out)
+                write_img(self.output_dir + "/" + self.output_name(filename), out)
             else:
                 if len(self._writes) >= 2 * int(self.io_threads):
                     self._writes.pop(0).result()
-                self._writes.append(pool.submit(write_img, self.output_dir + "/" + filename, out))
+                self._writes.append(pool.submit(write_img, self.output_dir + "/" + self.output_name(filename), out))
         else:
             self.print_message("No output file resulted from processing input file: "
                                f"{self.input_full_path}/{filename}", level=logging.WARNING)

@@ -1962,6 +1962,119 @@ int mi_stack_push_mosaic_calibrated(mi_stack_t* s, const void* host_mosaic, size
     return mosaic_push(s, host_mosaic, row_stride_bytes, *cfa, pinned && async, develop ? &d : nullptr, dev_sites, n_sites, &c);
 }
 
+// ---------------------------------------------------------------- packed raw samples (kernels_unpack.hpp)
+// argument checks of mi_raw_unpack*, mi_stack_push_packed: no device call
+static int raw_layout_check(const void* span, size_t span_bytes, const uint32_t* seg_offsets, const mi_raw_layout_t* L,
+                            const uint16_t* table, const void* out) {
+    if (!span) return fail(MI_ERR_INVALID, "null span");
+    if (!seg_offsets) return fail(MI_ERR_INVALID, "null seg_offsets");
+    if (!L) return fail(MI_ERR_INVALID, "null layout");
+    if (!out) return fail(MI_ERR_INVALID, "null output");
+    if (L->bits != 8 && L->bits != 10 && L->bits != 12 && L->bits != 14 && L->bits != 16)
+        return fail(MI_ERR_INVALID, "layout bits must be 8, 10, 12, 14 or 16 (got %d)", L->bits);
+    if (L->dtype != (L->bits == 8 ? MI_U8 : MI_U16))
+        return fail(MI_ERR_INVALID, "layout dtype must be MI_U8 for 8 bits and MI_U16 otherwise (got dtype %d for %d bits)", L->dtype, L->bits);
+    if (L->image_height < 1 || L->image_width < 1)
+        return fail(MI_ERR_INVALID, "layout image_height and image_width must be >= 1 (got %dx%d)", L->image_width, L->image_height);
+    if (L->seg_height < 1 || L->seg_width < 1)
+        return fail(MI_ERR_INVALID, "layout seg_height and seg_width must be >= 1 (got %dx%d)", L->seg_width, L->seg_height);
+    if (!L->tiled && L->seg_width != L->image_width)
+        return fail(MI_ERR_INVALID, "layout seg_width of strips must be image_width (got %d for %d)", L->seg_width, L->image_width);
+    if (L->height < 1 || L->width < 1) return fail(MI_ERR_INVALID, "layout height and width must be >= 1 (got %dx%d)", L->width, L->height);
+    if (L->crop_y < 0 || L->crop_x < 0 || (int64_t)L->crop_y + L->height > L->image_height || (int64_t)L->crop_x + L->width > L->image_width)
+        return fail(MI_ERR_INVALID, "layout crop (%d, %d) + %dx%d lies outside the %dx%d image", L->crop_x, L->crop_y, L->width, L->height,
+                    L->image_width, L->image_height);
+    if ((uint64_t)L->height * (uint64_t)L->width >= (1ull << 31)) return fail(MI_ERR_INVALID, "layout height x width too large");
+    if (span_bytes == 0 || (uint64_t)span_bytes >= (1ull << 32))
+        return fail(MI_ERR_INVALID, "span_bytes must be in [1, 2^32) (got %llu)", (unsigned long long)span_bytes);
+    if (L->shift < 0 || L->shift > 15) return fail(MI_ERR_INVALID, "layout shift must be in [0, 15] (got %d)", L->shift);
+    if (L->table_len < 0 || L->table_len > unpack::MAX_TABLE)
+        return fail(MI_ERR_INVALID, "layout table_len must be in [0, %d] (got %d)", unpack::MAX_TABLE, L->table_len);
+    if (L->table_len > 0 && !table) return fail(MI_ERR_INVALID, "layout table_len is %d and the table is null", L->table_len);
+    if (L->table_len > 0 && L->bits == 8) return fail(MI_ERR_INVALID, "layout table_len must be 0 for 8-bit samples (the table holds uint16)");
+    return MI_OK;
+}
+// offsets in host memory: every segment ends inside the span
+static int raw_segments_check(size_t span_bytes, const uint32_t* seg_offsets, const mi_raw_layout_t* L) {
+    const int nsx = unpack_nsx(*L), nsy = cdiv(L->image_height, L->seg_height);
+    const uint64_t rowb = unpack_row_bytes(*L);
+    for (int sy = 0; sy < nsy; ++sy) {
+        const int rows = L->tiled ? L->seg_height : std::min(L->seg_height, L->image_height - sy * L->seg_height);
+        for (int sx = 0; sx < nsx; ++sx) {
+            const uint64_t a = seg_offsets[sy * nsx + sx], e = a + rowb * (uint64_t)rows;
+            if (e > span_bytes)
+                return fail(MI_ERR_INVALID, "seg_offsets[%d] = %llu: the segment ends at %llu, outside the span of %llu bytes", sy * nsx + sx,
+                            (unsigned long long)a, (unsigned long long)e, (unsigned long long)span_bytes);
+        }
+    }
+    return MI_OK;
+}
+
+int mi_raw_unpack_device(int device, void* stream, const void* dev_span, size_t span_bytes, const uint32_t* dev_seg_offsets,
+                         const mi_raw_layout_t* layout, const uint16_t* dev_table, void* dev_out) {
+    int rc = raw_layout_check(dev_span, span_bytes, dev_seg_offsets, layout, dev_table, dev_out);
+    if (rc) return rc;
+    // (the kernel fetches aligned dwords of the span and 16-byte windows of the output)
+    if ((uintptr_t)dev_span & 3) return fail(MI_ERR_INVALID, "dev_span must be 4-byte aligned");
+    if ((uintptr_t)dev_out & (dtype_size(layout->dtype) - 1)) return fail(MI_ERR_INVALID, "dev_out must be aligned to its samples");
+    MI_HIP(hipSetDevice(device));
+    unpack_launch((hipStream_t)stream, dev_span, span_bytes, dev_seg_offsets, *layout, dev_table, dev_out);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_raw_unpack(int device, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets, const mi_raw_layout_t* layout,
+                  const uint16_t* host_table, void* host_out) {
+    int rc = raw_layout_check(host_span, span_bytes, seg_offsets, layout, host_table, host_out);
+    if (rc || (rc = raw_segments_check(span_bytes, seg_offsets, layout))) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t nb = (size_t)layout->height * layout->width * dtype_size(layout->dtype);
+    DevScratch tmp(nullptr);
+    void *span = nullptr, *out = nullptr;
+    uint32_t* seg = nullptr;
+    uint16_t* table = nullptr;
+    if ((rc = tmp.upload(&span, host_span, span_bytes)) || (rc = tmp.upload(&seg, seg_offsets, (size_t)unpack_nsegs(*layout) * sizeof(uint32_t))) ||
+        (layout->table_len > 0 && (rc = tmp.upload(&table, host_table, (size_t)layout->table_len * sizeof(uint16_t)))) ||
+        (rc = tmp.alloc(&out, nb)) || (rc = mi_raw_unpack_device(device, nullptr, span, span_bytes, seg, layout, table, out)))
+        return rc;
+    return tmp.download(host_out, out, nb);
+}
+
+int mi_stack_push_packed(mi_stack_t* s, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets,
+                         const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_cfa_t* cfa, const mi_calib_t* calib,
+                         const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if ((rc = raw_layout_check(host_span, span_bytes, seg_offsets, layout, host_table, s)) ||
+        (rc = raw_segments_check(span_bytes, seg_offsets, layout)))
+        return rc;
+    if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
+    if (layout->height != s->p.height || layout->width != s->p.width || layout->dtype != s->p.in_dtype)
+        return fail(MI_ERR_INVALID, "layout height, width and dtype must be the handle's (got %dx%d dtype %d for %dx%d dtype %d)", layout->width,
+                    layout->height, layout->dtype, s->p.width, s->p.height, s->p.in_dtype);
+    if ((rc = cfa_check(cfa, s->p.in_dtype)) || (calib && (rc = calib_check(calib))) || (develop && (rc = develop_check(develop))) ||
+        (rc = sites_check(dev_sites, n_sites, s->p.height, s->p.width)))
+        return rc;
+    if (s->idx_exported) return fail(MI_ERR_STATE, "the winner indices were exported (index stride > 1): reset the handle before pushing more frames");
+    if (s->finished) return fail(MI_ERR_STATE, "push after finish; call mi_stack_reset first");
+    MI_HIP(hipSetDevice(s->p.device));
+    const bool async = s->p.impl == MI_IMPL_TILED && !s->f64;
+    if (pinned && async) {
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, host_span) != hipSuccess || at.type != hipMemoryTypeHost) {
+            (void)hipGetLastError();
+            return fail(MI_ERR_INVALID, "mi_stack_push_packed: the span is not in pinned host memory (mi_host_alloc / mi_host_register)");
+        }
+    }
+    mi_calib_t c{};
+    if (calib) c = *calib;
+    mi_develop_t d{};
+    if (develop) d = *develop;
+    const mi_raw_layout_t L = *layout;
+    const PackedSrc pk{host_span, span_bytes, seg_offsets, unpack_nsegs(L), &L, host_table};
+    return mosaic_push(s, nullptr, 0, *cfa, pinned && async, develop ? &d : nullptr, dev_sites, n_sites, calib && c.flags ? &c : nullptr, &pk);
+}
+
 int mi_host_alloc(void** ptr, size_t bytes) {
     if (!ptr || !bytes) return fail(MI_ERR_INVALID, "bad argument");
     MI_HIP(hipHostMalloc(ptr, bytes, hipHostMallocPortable));

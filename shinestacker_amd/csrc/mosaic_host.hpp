@@ -20,12 +20,20 @@
 //   calibrate   mi_stack_push_mosaic_calibrated: the calibration kernel (kernels_calib.hpp) on s->stream behind evCopied[slot], in
 //               place on the slot, ahead of the defect kernel and the (developed) demosaic; evSlotFree[slot] follows all of them.
 //               The caller's dark frame and gain table are read by that kernel.
+//   packed      mi_stack_push_packed: the frame arrives as the packed sample bytes of a raw file (kernels_unpack.hpp), 0.75 of a
+//               uint16 mosaic's bytes at 12 bits.  The span is uploaded on stc into pslot[slot], a packed slot beside the mosaic
+//               slot laid out [span | segment offsets | table], the offsets and the table out of the pinned meta[slot]; the
+//               unpack kernel runs on s->stream behind evCopied[slot] and writes slot[slot], and calibration, defect repair
+//               and the demosaic follow as for a mosaic.  evSlotFree[slot] is behind all of them, so it guards both slots.
+//               The packed slots belong to the stage (not to s->allocs): they grow when a later span is larger, after a wait
+//               for both streams.
 //   order       frames are fused in call order: the first mosaic after host BGR frames flushes the ring (mosaic_push), and
 //               every call that takes frames of another kind or reads state flushes this stage first (stack_flush in capi.hip).
 #pragma once
 
 #include "kernels_calib.hpp"
 #include "kernels_demosaic.hpp"
+#include "kernels_unpack.hpp"
 
 namespace mi {
 
@@ -46,7 +54,27 @@ struct MosaicStage {
     long slot_no = 0, pin_no = 0, up_no = 0;
     long frames_up_seen = 0;                  // TiledState::up_no at the most recent pinned mosaic
     long run = 0;                             // pinned mosaics since the most recent pinned BGR frame
+    // packed spans (mi_stack_push_packed)
+    void* pslot[NSLOT] = {};                  // [span | segment offsets | table] on the device, each part 256-byte aligned
+    size_t pslot_cap = 0;
+    void* meta[NSLOT] = {};                   // pinned: the offsets and the table that go with pslot[i]
+    size_t meta_cap = 0;
+    void* ppin[NPIN] = {nullptr, nullptr, nullptr};         // bounce buffers of spans that are not pinned
+    hipEvent_t evPPin[NPIN] = {nullptr, nullptr, nullptr};  // the upload out of ppin[i] finished
+    size_t ppin_cap = 0;
+    long ppin_no = 0;
 };
+
+// what mi_stack_push_packed brings in place of a mosaic (arguments checked by the caller)
+struct PackedSrc {
+    const void* span;
+    size_t span_bytes;
+    const uint32_t* seg;        // host
+    int nseg;
+    const mi_raw_layout_t* layout;
+    const uint16_t* table;      // host, layout->table_len entries, or null
+};
+inline size_t packed_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
 inline MosaicStage* mstage(const mi_stack* s) { return reinterpret_cast<MosaicStage*>(s->mosaic); }
 
@@ -153,6 +181,15 @@ inline void mosaic_destroy(mi_stack* s) {
         if (m->pin[i]) (void)hipHostFree(m->pin[i]);
         if (m->evPin[i]) (void)hipEventDestroy(m->evPin[i]);
     }
+    for (int i = 0; i < MosaicStage::NPIN; ++i) {
+        if (m->ppin[i]) (void)hipHostFree(m->ppin[i]);
+        if (m->evPPin[i]) (void)hipEventDestroy(m->evPPin[i]);
+    }
+    if (m->pslot[0]) (void)hipStreamSynchronize(s->stream);   // (the unpack kernels read the packed slots)
+    for (int i = 0; i < MosaicStage::NSLOT; ++i) {
+        if (m->meta[i]) (void)hipHostFree(m->meta[i]);
+        if (m->pslot[i]) (void)hipFree(m->pslot[i]);
+    }
     for (int i = 0; i < MosaicStage::NUP; ++i)
         if (m->evUp[i]) (void)hipEventDestroy(m->evUp[i]);
     for (int i = 0; i < MosaicStage::NSLOT; ++i) {
@@ -191,12 +228,48 @@ inline void mosaic_kernels(hipStream_t st, void* slot, void* frame, int H, int W
     else demosaic_launch(st, slot, frame, H, W, dtype, cfa);
 }
 
+// room for a span of `span_bytes` with `meta_bytes` of offsets and table behind it, in every packed slot the handle uses.
+// Growing waits for both streams first: nothing reads what is freed.
+inline int packed_reserve(mi_stack* s, size_t span_bytes, size_t meta_bytes) {
+    MosaicStage* m = mstage(s);
+    const int nslot = s->p.impl == MI_IMPL_TILED ? MosaicStage::NSLOT : 1;
+    const size_t need = packed_align(span_bytes) + meta_bytes;
+    if (need <= m->pslot_cap && meta_bytes <= m->meta_cap) return MI_OK;
+    if (m->stc) MI_HIP(hipStreamSynchronize(m->stc));
+    MI_HIP(hipStreamSynchronize(s->stream));
+    if (need > m->pslot_cap) {
+        for (int i = 0; i < nslot; ++i) {
+            if (m->pslot[i]) (void)hipFree(m->pslot[i]);
+            m->pslot[i] = nullptr;
+        }
+        m->pslot_cap = 0;
+        for (int i = 0; i < nslot; ++i)
+            if (hipMalloc(&m->pslot[i], need) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(MI_ERR_NOMEM, "out of device memory");
+            }
+        m->pslot_cap = need;
+    }
+    if (meta_bytes > m->meta_cap) {
+        for (int i = 0; i < nslot; ++i) {
+            if (m->meta[i]) (void)hipHostFree(m->meta[i]);
+            m->meta[i] = nullptr;
+        }
+        m->meta_cap = 0;
+        for (int i = 0; i < nslot; ++i) MI_HIP(hipHostMalloc(&m->meta[i], meta_bytes, hipHostMallocDefault));
+        m->meta_cap = meta_bytes;
+    }
+    return MI_OK;
+}
+
 // One host mosaic (arguments checked by mi_stack_push_mosaic / _developed / _calibrated): stage it, start upload and
 // demosaic, return.  `dev`: development (null: the plain demosaic); with `n_sites` > 0 the defect kernel runs in place on the
-// slot, behind the upload and ahead of the demosaic; `cal`: calibration, in place on the slot ahead of both.
+// slot, behind the upload and ahead of the demosaic; `cal`: calibration, in place on the slot ahead of both.  `pk`: the frame
+// comes as a packed span (mi_stack_push_packed) -- `host_mosaic` is not read, the span is uploaded into the packed slot and
+// the unpack kernel writes the mosaic slot ahead of everything else.
 inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t& cfa, bool pinned,
                        const mi_develop_t* dev = nullptr, const int32_t* dev_sites = nullptr, int n_sites = 0,
-                       const mi_calib_t* cal = nullptr) {
+                       const mi_calib_t* cal = nullptr, const PackedSrc* pk = nullptr) {
     TiledState* t = tstate(s);
     int rc = tiled_flush(s);   // call order: host BGR frames staged before this mosaic are fused first
     if (rc) return rc;
@@ -204,6 +277,25 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     MosaicStage* m = mstage(s);
     const int H = s->p.height, W = s->p.width;
     const size_t rb = (size_t)W * dtype_size(s->p.in_dtype);
+    // a packed span's device layout: [span | offsets | table]
+    const size_t seg_bytes = pk ? packed_align((size_t)pk->nseg * sizeof(uint32_t)) : 0;
+    const size_t table_bytes = pk ? (size_t)pk->layout->table_len * sizeof(uint16_t) : 0;
+    const size_t seg_at = pk ? packed_align(pk->span_bytes) : 0, table_at = seg_at + seg_bytes;
+    if (pk && (rc = packed_reserve(s, pk->span_bytes, seg_bytes + table_bytes))) return rc;
+    if (pk && s->p.impl != MI_IMPL_TILED) {
+        // the synchronous route of a packed span: upload, unpack, then as a mosaic below
+        char* ps = (char*)m->pslot[0];
+        MI_HIP(hipMemcpyAsync(ps, pk->span, pk->span_bytes, hipMemcpyHostToDevice, s->stream));
+        MI_HIP(hipMemcpyAsync(ps + seg_at, pk->seg, (size_t)pk->nseg * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+        if (table_bytes) MI_HIP(hipMemcpyAsync(ps + table_at, pk->table, table_bytes, hipMemcpyHostToDevice, s->stream));
+        unpack_launch(s->stream, ps, pk->span_bytes, (const uint32_t*)(ps + seg_at), *pk->layout, (const uint16_t*)(ps + table_at),
+                      m->slot[0]);
+        mosaic_kernels(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
+        MI_HIP(hipGetLastError());
+        rc = dispatch_push(s, s->frame_dev, 1, t->frame_bytes);
+        MI_HIP(hipStreamSynchronize(s->stream));   // (also on failure: the copies read the caller's arrays)
+        return rc;
+    }
     if (s->p.impl != MI_IMPL_TILED) {
         // float-64 and MI_IMPL_SIMPLE handles: upload, demosaic, push, wait -- one frame at a time on the handle's stream
         MI_HIP(hipMemcpy2DAsync(m->slot[0], rb, host_mosaic, row_stride_bytes, rb, H, hipMemcpyHostToDevice, s->stream));
@@ -217,15 +309,52 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     void* slot = m->slot[si];
     if (m->slot_no >= MosaicStage::NSLOT) MI_HIP(hipStreamWaitEvent(m->stc, m->evSlotFree[si], 0));
     m->slot_no++;
+    char* ps = pk ? (char*)m->pslot[si] : nullptr;
+    if (pk) {
+        // offsets and table through the slot's pinned block: its previous upload is through once evCopied[si] is
+        MI_HIP(hipEventSynchronize(m->evCopied[si]));   // (no-op on an event never recorded)
+        char* mb = (char*)m->meta[si];
+        memcpy(mb, pk->seg, (size_t)pk->nseg * sizeof(uint32_t));
+        if (table_bytes) memcpy(mb + seg_bytes, pk->table, table_bytes);
+        MI_HIP(hipMemcpyAsync(ps + seg_at, mb, seg_bytes + table_bytes, hipMemcpyHostToDevice, m->stc));
+    }
     if (pinned) {
         hipEvent_t& ev = m->evUp[m->up_no % MosaicStage::NUP];
         if (!ev) MI_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         else MI_HIP(hipEventSynchronize(ev));   // (only when more than NUP uploads are in flight)
-        MI_HIP(hipMemcpyAsync(slot, host_mosaic, m->mosaic_bytes, hipMemcpyHostToDevice, m->stc));
+        if (pk) MI_HIP(hipMemcpyAsync(ps, pk->span, pk->span_bytes, hipMemcpyHostToDevice, m->stc));
+        else MI_HIP(hipMemcpyAsync(slot, host_mosaic, m->mosaic_bytes, hipMemcpyHostToDevice, m->stc));
         MI_HIP(hipEventRecord(ev, m->stc));
         if (m->frames_up_seen != t->up_no) { m->frames_up_seen = t->up_no; m->run = 0; }
         m->run++;
         m->up_no++;
+    } else if (pk) {
+        if (pk->span_bytes > m->ppin_cap) {
+            MI_HIP(hipStreamSynchronize(m->stc));   // (no upload reads a bounce buffer that is freed)
+            for (int i = 0; i < MosaicStage::NPIN; ++i) {
+                if (m->ppin[i]) (void)hipHostFree(m->ppin[i]);
+                m->ppin[i] = nullptr;
+            }
+            m->ppin_cap = 0;
+            for (int i = 0; i < MosaicStage::NPIN; ++i) {
+                MI_HIP(hipHostMalloc(&m->ppin[i], pk->span_bytes, hipHostMallocDefault));
+                if (!m->evPPin[i]) MI_HIP(hipEventCreateWithFlags(&m->evPPin[i], hipEventDisableTiming));
+            }
+            m->ppin_cap = pk->span_bytes;
+        }
+        const int k = (int)(m->ppin_no++ % MosaicStage::NPIN);
+        MI_HIP(hipEventSynchronize(m->evPPin[k]));   // bounce buffer free again? (no-op when unused)
+        char* pb = (char*)m->ppin[k];
+        const size_t nb = pk->span_bytes;
+        const int nthr = nb >= ((size_t)32 << 20) ? 4 : 1;
+        const std::function<void(int)> band = [&](int j) {
+            const size_t a = nb * (size_t)j / nthr, b = nb * (size_t)(j + 1) / nthr;
+            memcpy(pb + a, (const char*)pk->span + a, b - a);
+        };
+        if (nthr == 1) band(0);
+        else CopyPool::get().run(nthr, band);
+        MI_HIP(hipMemcpyAsync(ps, pb, nb, hipMemcpyHostToDevice, m->stc));
+        MI_HIP(hipEventRecord(m->evPPin[k], m->stc));
     } else {
         if (!m->pin[0])
             for (int i = 0; i < MosaicStage::NPIN; ++i) {
@@ -251,6 +380,8 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     MI_HIP(hipEventRecord(m->evCopied[si], m->stc));
     MI_HIP(hipStreamWaitEvent(s->stream, m->evCopied[si], 0));
     void* frame = (char*)m->bgr + (size_t)m->pending * t->frame_bytes;
+    if (pk)
+        unpack_launch(s->stream, ps, pk->span_bytes, (const uint32_t*)(ps + seg_at), *pk->layout, (const uint16_t*)(ps + table_at), slot);
     mosaic_kernels(s->stream, slot, frame, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
     MI_HIP(hipGetLastError());
     MI_HIP(hipEventRecord(m->evSlotFree[si], s->stream));

@@ -1,0 +1,569 @@
+"""DNG raw files in: the TIFF structure parsed on the host, the packed samples unpacked on the MI355X (csrc/kernels_unpack.hpp).
+
+The reference reads developed frames and never opens a raw file, so this has no reference counterpart.  DNG is the documented
+raw container and it is a TIFF: `read` walks the IFDs with `struct` and NumPy alone and never touches the sample data -- it
+maps the file and hands out `span`, one contiguous uint8 view from the lowest segment offset to the end of the highest, which
+is uploaded as it lies.  A 12-bit mosaic is 1.5 bytes per site in the file and 2 once unpacked: the file's bytes are 0.75 of
+the mosaic's over the host link, and the host never shuffles a bit.
+
+What a `DngFrame` carries: `layout` (a RawLayout: how samples lie in the span), `cfa` (a demosaic.Cfa from CFAPattern,
+BlackLevel, WhiteLevel and AsShotNeutral), `develop` (a demosaic.Develop from the colour matrix, or None), `lens` (a lens.Lens
+from the WarpRectilinear opcode, or None), `orientation` (reported, not applied) and `ignored`: the names of every tag and
+opcode in the file that carries a correction this reader does NOT apply -- nothing is dropped silently.
+
+Refused, each with the tag's name and value, before any device call: compressed samples (lossless JPEG, deflate, lossy
+JPEG), more than one sample per pixel, a CFA repeat other than 2 x 2, a CFALayout other than 1, bit depths other than 8, 10,
+12, 14 and 16, truncated segments, and a TIFF without a CFA IFD.
+
+The tag numbers and the opcode layout are written from memory of the DNG specification: this reader is UNPINNED against a
+real DNG -- it has met only the files its own tests write (tests/dng_cases.py, written from the format description).
+
+The sample arithmetic is integer and exact (tests/unpack_restatement.py is its definition):
+
+    v = the sample's bits;  v = table[min(v, len - 1)] with a LinearizationTable;  out = v << shift
+    shift = max(0, bits of the dtype - bit_length(WhiteLevel)): a 12-bit sensor fills the top of uint16, so that the Cfa's
+    gains (white balance times maxv / (white - black)) stay below 16; black and white move with it
+
+There is no CPU path: without a GPU or the library `unpack` and its kin raise DeviceError.  `read` is host Python.
+"""
+import os
+import struct
+
+import numpy as np
+
+from . import _lib
+from .demosaic import PATTERNS, Cfa, Develop, debayer, debayer_device, srgb_tone
+from .errors import ImageLoadError, InvalidOptionError
+
+EXTENSIONS = frozenset(["dng"])
+BITS = (8, 10, 12, 14, 16)
+MAX_TABLE = 65536                               # unpack::MAX_TABLE of csrc/kernels_unpack.hpp
+XYZ_FROM_SRGB = np.array([[0.4124564, 0.3575761, 0.1804375],
+                          [0.2126729, 0.7151522, 0.0721750],
+                          [0.0193339, 0.1191920, 0.9503041]], np.float64)
+D65 = 21                                        # CalibrationIlluminant: D65
+
+TAG_NAMES = {254: "NewSubFileType", 256: "ImageWidth", 257: "ImageLength", 258: "BitsPerSample", 259: "Compression",
+             262: "PhotometricInterpretation", 273: "StripOffsets", 274: "Orientation", 277: "SamplesPerPixel",
+             278: "RowsPerStrip", 279: "StripByteCounts", 284: "PlanarConfiguration", 322: "TileWidth", 323: "TileLength",
+             324: "TileOffsets", 325: "TileByteCounts", 330: "SubIFDs", 33421: "CFARepeatPatternDim", 33422: "CFAPattern",
+             50706: "DNGVersion", 50710: "CFAPlaneColor", 50711: "CFALayout", 50712: "LinearizationTable",
+             50713: "BlackLevelRepeatDim", 50714: "BlackLevel", 50715: "BlackLevelDeltaH", 50716: "BlackLevelDeltaV",
+             50717: "WhiteLevel", 50718: "DefaultScale", 50719: "DefaultCropOrigin", 50720: "DefaultCropSize",
+             50721: "ColorMatrix1", 50722: "ColorMatrix2", 50727: "AnalogBalance", 50728: "AsShotNeutral",
+             50778: "CalibrationIlluminant1", 50779: "CalibrationIlluminant2", 50829: "ActiveArea", 51008: "OpcodeList1",
+             51009: "OpcodeList2", 51022: "OpcodeList3"}
+# tags that carry a correction this reader does not apply: reported in DngFrame.ignored when present
+IGNORED_TAGS = (50715, 50716, 50718, 50719, 50720, 50727)
+OPCODE_NAMES = {1: "WarpRectilinear", 2: "WarpFisheye", 3: "FixVignetteRadial", 4: "FixBadPixelsConstant", 5: "FixBadPixelsList",
+                6: "TrimBounds", 7: "MapTable", 8: "MapPolynomial", 9: "GainMap", 10: "DeltaPerRow", 11: "DeltaPerColumn",
+                12: "ScalePerRow", 13: "ScalePerColumn"}
+COMPRESSION_NAMES = {7: "lossless JPEG", 8: "deflate", 34892: "lossy JPEG"}
+CFA_PHOTOMETRIC = 32803
+_TYPES = {1: ("B", 1), 2: ("c", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8), 6: ("b", 1), 7: ("B", 1), 8: ("h", 2), 9: ("i", 4),
+          10: ("ii", 8), 11: ("f", 4), 12: ("d", 8), 13: ("I", 4)}
+
+
+class RawLayout:
+    """How the samples of a raw IFD lie in `DngFrame.span` (mi_raw_layout_t plus the offsets and the table).
+
+    bits                        8, 10, 12, 14 or 16 bits per sample
+    big_endian                  the file's byte order; it matters for 16-bit samples only (10, 12 and 14-bit samples are packed
+                                most significant bit first whatever the file's order: TIFF FillOrder 1)
+    image_height, image_width   the stored image
+    tiled                       False: strips of seg_height = RowsPerStrip rows, seg_width == image_width; True: tiles of
+                                seg_height x seg_width = TileLength x TileWidth, edge tiles stored at full size
+    offsets                     uint32, one per segment, row-major over the segment grid, rebased to the start of the span
+    crop_y, crop_x, height, width   the ActiveArea (or the whole image): what comes out
+    shift                       every sample is shifted left by it
+    table                       the LinearizationTable (uint16) or None
+    dtype                       uint8 for 8-bit files, uint16 otherwise
+    """
+
+    def __init__(self, bits, big_endian, image_height, image_width, tiled, seg_height, seg_width, offsets, crop_y=0, crop_x=0,
+                 height=None, width=None, shift=0, table=None):
+        self.bits, self.big_endian = int(bits), bool(big_endian)
+        self.image_height, self.image_width = int(image_height), int(image_width)
+        self.tiled, self.seg_height, self.seg_width = bool(tiled), int(seg_height), int(seg_width)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        self.crop_y, self.crop_x = int(crop_y), int(crop_x)
+        self.height = self.image_height - self.crop_y if height is None else int(height)
+        self.width = self.image_width - self.crop_x if width is None else int(width)
+        self.shift = int(shift)
+        self.table = None if table is None else np.ascontiguousarray(table, dtype=np.uint16)
+        self.dtype = np.dtype(np.uint8 if self.bits == 8 else np.uint16)
+
+    def __repr__(self):
+        seg = f"tiles {self.seg_height}x{self.seg_width}" if self.tiled else f"strips of {self.seg_height} rows"
+        return (f"RawLayout({self.bits} bit{', big-endian' if self.big_endian else ''}, {self.image_height}x{self.image_width}, {seg}, "
+                f"crop ({self.crop_y}, {self.crop_x}) {self.height}x{self.width}, shift {self.shift}, "
+                f"table {None if self.table is None else len(self.table)})")
+
+    @property
+    def row_bytes(self):
+        """bytes of one row of a segment: every row starts on a byte boundary"""
+        return (self.seg_width * self.bits + 7) // 8
+
+    @property
+    def grid(self):
+        """(segments down, segments across)"""
+        return -(-self.image_height // self.seg_height), -(-self.image_width // self.seg_width)
+
+    def segment_bytes(self, k):
+        """the stored bytes of segment k: a tile is always whole, the last strip holds the rows that are left"""
+        sy = k // self.grid[1]
+        rows = self.seg_height if self.tiled else min(self.seg_height, self.image_height - sy * self.seg_height)
+        return rows * self.row_bytes
+
+    def struct(self):
+        """mi_raw_layout_t"""
+        return _lib.RawLayoutStruct(self.bits, int(self.big_endian), self.image_height, self.image_width, int(self.tiled),
+                                    self.seg_height, self.seg_width, self.crop_y, self.crop_x, self.height, self.width, self.shift,
+                                    0 if self.table is None else len(self.table), _lib.DTYPE_CODE[self.dtype])
+
+
+class DngFrame:
+    """One parsed DNG file (see the module's docstring).  `span` is a read-only view of the file's mapping: the frame keeps
+    the mapping alive."""
+
+    def __init__(self, path, layout, span, cfa, develop, lens, orientation, ignored):
+        self.path, self.layout, self.span, self.cfa = path, layout, span, cfa
+        self.develop, self.lens, self.orientation, self.ignored = develop, lens, orientation, tuple(ignored)
+
+    @property
+    def shape(self):
+        return self.layout.height, self.layout.width
+
+    @property
+    def dtype(self):
+        return self.layout.dtype
+
+    def __repr__(self):
+        return f"DngFrame({self.path!r}, {self.layout!r}, {self.cfa!r}, ignored={list(self.ignored)})"
+
+
+class Raw:
+    """How FocusStack, FocusStackBunch, CombinedActions and PyramidStack take `.dng` input (their `raw=` option).
+
+    develop      "auto": each file's own `DngFrame.develop` (its colour matrix and the sRGB curve); None: the plain demosaic;
+                 a demosaic.Develop: that one for every file
+    lens         "auto": the file's WarpRectilinear opcode; None: no lens correction; a lens.Lens: that one
+    calibration  a demosaic.Calibration applied to every unpacked mosaic, or None
+    """
+
+    def __init__(self, develop="auto", lens="auto", calibration=None):
+        from .demosaic import check_calibration, check_develop
+        from .lens import check_lens
+        if not (isinstance(develop, str) and develop == "auto") and develop is not None:
+            check_develop(develop)
+        if not (isinstance(lens, str) and lens == "auto") and lens is not None:
+            lens = check_lens(lens)
+        if calibration is not None:
+            check_calibration(calibration)
+        self.develop, self.lens, self.calibration = develop, lens, calibration
+
+    def __repr__(self):
+        return f"Raw(develop={self.develop!r}, lens={self.lens!r}, calibration={self.calibration!r})"
+
+    def develop_for(self, frame):
+        return frame.develop if isinstance(self.develop, str) else self.develop
+
+    def lens_for(self, frame):
+        return frame.lens if isinstance(self.lens, str) else self.lens
+
+
+def check_raw(raw):
+    if not isinstance(raw, Raw):
+        raise InvalidOptionError("raw", raw, "a shinestacker_amd.dng.Raw is expected")
+    return raw
+
+
+def is_dng(path):
+    return str(path).split(".")[-1].lower() in EXTENSIONS
+
+
+# ---------------------------------------------------------------- the TIFF structure
+class _Tiff:
+    def __init__(self, path, data):
+        self.path, self.data = path, data
+        head = bytes(data[:8])
+        if len(head) < 8 or head[:2] not in (b"II", b"MM"):
+            raise ImageLoadError(path, "not a TIFF (no II / MM byte-order mark)")
+        self.e = "<" if head[:2] == b"II" else ">"
+        if struct.unpack(self.e + "H", head[2:4])[0] != 42:
+            raise ImageLoadError(path, "not a TIFF (the magic number is not 42)")
+        self.first = struct.unpack(self.e + "I", head[4:8])[0]
+
+    def bytes_at(self, off, n):
+        if off < 0 or off + n > len(self.data):
+            raise ImageLoadError(self.path, f"truncated: {n} bytes at offset {off} lie outside the {len(self.data)}-byte file")
+        return bytes(self.data[off:off + n])
+
+    def ifd(self, off):
+        """{tag: (type, count, where the value's bytes lie)} and the offset of the next IFD"""
+        n = struct.unpack(self.e + "H", self.bytes_at(off, 2))[0]
+        tags = {}
+        for i in range(n):
+            at = off + 2 + 12 * i
+            tag, typ, cnt = struct.unpack(self.e + "HHI", self.bytes_at(at, 8))
+            if typ not in _TYPES:
+                continue
+            nbytes = _TYPES[typ][1] * cnt
+            tags[tag] = (typ, cnt, at + 8 if nbytes <= 4 else struct.unpack(self.e + "I", self.bytes_at(at + 8, 4))[0])
+        return tags, struct.unpack(self.e + "I", self.bytes_at(off + 2 + 12 * n, 4))[0]
+
+    def raw(self, entry):
+        typ, cnt, at = entry
+        return self.bytes_at(at, _TYPES[typ][1] * cnt)
+
+    def values(self, entry):
+        """the entry's values: ints, floats (RATIONAL and SRATIONAL as numerator / denominator), or bytes for ASCII"""
+        typ, cnt, _ = entry
+        raw = self.raw(entry)
+        if typ == 2:
+            return raw
+        fmt = _TYPES[typ][0]
+        vals = struct.unpack(self.e + fmt * cnt, raw)
+        if typ in (5, 10):
+            return tuple(vals[2 * i] / vals[2 * i + 1] if vals[2 * i + 1] else 0.0 for i in range(cnt))
+        return vals
+
+
+def _one(t, tags, tag, default):
+    return t.values(tags[tag])[0] if tag in tags else default
+
+
+def _opcodes(blob, name, path):
+    """[(id, data)] of an opcode list: always big-endian -- uint32 count, then per opcode id, version, flags, byte count, data"""
+    if len(blob) < 4:
+        raise ImageLoadError(path, f"{name} is shorter than its count")
+    n = struct.unpack(">I", blob[:4])[0]
+    out, at = [], 4
+    for _ in range(n):
+        if at + 16 > len(blob):
+            raise ImageLoadError(path, f"{name} is truncated at opcode {len(out)}")
+        oid, _ver, _flags, nb = struct.unpack(">IIII", blob[at:at + 16])
+        if at + 16 + nb > len(blob):
+            raise ImageLoadError(path, f"{name} is truncated inside opcode {len(out)}")
+        out.append((oid, blob[at + 16:at + 16 + nb]))
+        at += 16 + nb
+    return out
+
+
+def colour_matrix(color_matrix):
+    """camera RGB -> linear sRGB from a DNG ColorMatrix (XYZ -> camera), dcraw's construction:
+    cam_from_srgb = ColorMatrix @ XYZ_from_sRGB, every row divided by its sum (camera white maps to sRGB white), inverted."""
+    cm = np.asarray(color_matrix, np.float64).reshape(3, 3)
+    cam = cm @ XYZ_FROM_SRGB
+    cam = cam / cam.sum(axis=1, keepdims=True)
+    return np.linalg.inv(cam)
+
+
+def permute_pattern(pattern, crop_y, crop_x):
+    """the 2 x 2 pattern seen from a crop origin: rows swap when crop_y is odd, columns when crop_x is odd"""
+    cell = [[pattern[0], pattern[1]], [pattern[2], pattern[3]]]
+    return "".join(cell[(py + crop_y) & 1][(px + crop_x) & 1] for py in range(2) for px in range(2))
+
+
+def read(path):
+    """Parse the DNG at `path` into a DngFrame.  TIFF structure only: the sample data is mapped (np.memmap, read-only), not
+    read.  The raw IFD is the one with PhotometricInterpretation 32803 (CFA) and NewSubFileType 0, IFD0 or one of its
+    SubIFDs; colour tags are looked up in the raw IFD first and in IFD0 after it.
+
+    The colour matrix is the ColorMatrix whose CalibrationIlluminant is 21 (D65), else ColorMatrix2, else ColorMatrix1: the
+    two matrices are NOT interpolated between their illuminants."""
+    path = os.fspath(path)
+    if not os.path.isfile(path):
+        raise RuntimeError("File does not exist: " + path)
+    if os.path.getsize(path) < 8:
+        raise ImageLoadError(path, "not a TIFF (shorter than its header)")
+    data = np.memmap(path, dtype=np.uint8, mode="r")
+    t = _Tiff(path, data)
+    ifd0, _ = t.ifd(t.first)
+    cands = [ifd0] + [t.ifd(off)[0] for off in (t.values(ifd0[330]) if 330 in ifd0 else ())]
+    rawifd = next((c for c in cands if _one(t, c, 262, None) == CFA_PHOTOMETRIC and _one(t, c, 254, 0) == 0), None)
+    if rawifd is None:
+        raise ImageLoadError(path, "no CFA IFD: no IFD with PhotometricInterpretation 32803 and NewSubFileType 0")
+
+    def get(tag, default=None):
+        for c in (rawifd, ifd0):
+            if tag in c:
+                return t.values(c[tag])
+        return default
+
+    comp = _one(t, rawifd, 259, 1)
+    if comp != 1:
+        kind = COMPRESSION_NAMES.get(comp)
+        raise InvalidOptionError("Compression", comp, ("compressed samples are not read" if kind is None else
+                                                       f"{kind} compressed samples are not read") + ": only uncompressed DNGs")
+    spp = _one(t, rawifd, 277, 1)
+    if spp != 1:
+        raise InvalidOptionError("SamplesPerPixel", spp, "a CFA mosaic has one sample per pixel")
+    bits = _one(t, rawifd, 258, 1)
+    if bits not in BITS:
+        raise InvalidOptionError("BitsPerSample", bits, "valid values are " + ", ".join(map(str, BITS)))
+    rep = tuple(t.values(rawifd[33421])) if 33421 in rawifd else (2, 2)
+    if rep != (2, 2):
+        raise InvalidOptionError("CFARepeatPatternDim", rep, "only 2 x 2 Bayer patterns are read")
+    lay = _one(t, rawifd, 50711, 1)
+    if lay != 1:
+        raise InvalidOptionError("CFALayout", lay, "only the rectangular layout 1 is read")
+    planes = tuple(get(50710, (0, 1, 2)))
+    if planes != (0, 1, 2):
+        raise InvalidOptionError("CFAPlaneColor", planes, "only red, green, blue (0, 1, 2) is read")
+    if 33422 not in rawifd:
+        raise ImageLoadError(path, "the CFA IFD has no CFAPattern")
+    pat = tuple(t.values(rawifd[33422]))
+    pattern = "".join("RGB"[v] if 0 <= v <= 2 else "?" for v in pat)
+    if pattern not in PATTERNS:
+        raise InvalidOptionError("CFAPattern", pat, "valid patterns are " + ", ".join(PATTERNS) + " with 0 = R, 1 = G, 2 = B")
+    if 256 not in rawifd or 257 not in rawifd:
+        raise ImageLoadError(path, "the CFA IFD has no ImageWidth / ImageLength")
+    iw, ih = _one(t, rawifd, 256, 0), _one(t, rawifd, 257, 0)
+    if iw < 1 or ih < 1:
+        raise InvalidOptionError("ImageWidth", (iw, ih), "the stored image is empty")
+    dt = np.dtype(np.uint8 if bits == 8 else np.uint16)
+    maxv = int(np.iinfo(dt).max)
+
+    # segments
+    tiled = 324 in rawifd
+    if tiled:
+        sw, sh = _one(t, rawifd, 322, 0), _one(t, rawifd, 323, 0)
+        if sw < 1 or sh < 1:
+            raise InvalidOptionError("TileWidth", (sw, sh), "TileOffsets without a tile size")
+        off_tag, cnt_tag = 324, 325
+    else:
+        if 273 not in rawifd:
+            raise ImageLoadError(path, "the CFA IFD has neither StripOffsets nor TileOffsets")
+        sw, sh = iw, min(_one(t, rawifd, 278, ih), ih)
+        if sh < 1:
+            raise InvalidOptionError("RowsPerStrip", sh, "a strip has at least one row")
+        off_tag, cnt_tag = 273, 279
+    offs = np.array(t.values(rawifd[off_tag]), np.int64)
+    layout = RawLayout(bits, t.e == ">", ih, iw, tiled, sh, sw, np.zeros(0, np.uint32))
+    nseg = layout.grid[0] * layout.grid[1]
+    if len(offs) != nseg:
+        raise InvalidOptionError(TAG_NAMES[off_tag], len(offs), f"{nseg} segments are expected for a {ih} x {iw} image")
+    need = np.array([layout.segment_bytes(k) for k in range(nseg)], np.int64)
+    if cnt_tag in rawifd:
+        cnts = np.array(t.values(rawifd[cnt_tag]), np.int64)
+        if len(cnts) != nseg or (cnts < need).any():
+            k = 0 if len(cnts) != nseg else int(np.flatnonzero(cnts < need)[0])
+            raise ImageLoadError(path, f"truncated segment: {TAG_NAMES[cnt_tag]}[{k}] = {cnts[k] if k < len(cnts) else None}, "
+                                       f"{need[k]} bytes are needed")
+    if ((offs + need) > len(data)).any():
+        k = int(np.flatnonzero((offs + need) > len(data))[0])
+        raise ImageLoadError(path, f"truncated segment: {TAG_NAMES[off_tag]}[{k}] = {offs[k]} with {need[k]} bytes ends outside the "
+                                   f"{len(data)}-byte file")
+    lo, hi = int(offs.min()), int((offs + need).max())
+    if hi - lo >= 2 ** 32:
+        raise InvalidOptionError(TAG_NAMES[off_tag], hi - lo, "the segments span 2^32 bytes or more")
+    layout.offsets = (offs - lo).astype(np.uint32)
+    span = data[lo:hi]
+
+    # crop
+    if 50829 in rawifd:
+        top, left, bottom, right = (int(v) for v in t.values(rawifd[50829]))
+        if not (0 <= top < bottom <= ih and 0 <= left < right <= iw):
+            raise InvalidOptionError("ActiveArea", (top, left, bottom, right), f"it lies outside the {ih} x {iw} image")
+        layout.crop_y, layout.crop_x, layout.height, layout.width = top, left, bottom - top, right - left
+
+    # levels
+    white = int(round(get(50717, ((1 << bits) - 1,))[0]))
+    if not 1 <= white <= maxv:
+        raise InvalidOptionError("WhiteLevel", white, f"it lies outside [1, {maxv}]")
+    shift = max(0, 8 * dt.itemsize - white.bit_length())
+    layout.shift = shift
+    if 50712 in rawifd:
+        if bits == 8:
+            raise InvalidOptionError("LinearizationTable", "present", "a table on 8-bit samples is not read (its entries are 16-bit)")
+        table = np.array(t.values(rawifd[50712]), np.int64)
+        if not 1 <= len(table) <= MAX_TABLE or table.min() < 0 or table.max() > 65535:
+            raise InvalidOptionError("LinearizationTable", len(table), f"1 to {MAX_TABLE} entries of 16 bits are expected")
+        layout.table = table.astype(np.uint16)
+    brep = tuple(get(50713, (1, 1)))
+    if brep not in ((1, 1), (2, 2)):
+        raise InvalidOptionError("BlackLevelRepeatDim", brep, "1 x 1 or 2 x 2 is read")
+    bl = [int(np.floor(float(v) + 0.5)) for v in get(50714, (0,) * (brep[0] * brep[1]))]
+    if len(bl) != brep[0] * brep[1]:
+        raise InvalidOptionError("BlackLevel", bl, f"{brep[0] * brep[1]} values are expected")
+    black = bl * 4 if len(bl) == 1 else bl       # (its origin is the ActiveArea's: already in the crop's coordinates)
+    if min(black) < 0 or max(black) >= white:
+        raise InvalidOptionError("BlackLevel", black, f"it lies outside [0, WhiteLevel = {white})")
+
+    # colour
+    pattern = permute_pattern(pattern, layout.crop_y, layout.crop_x)
+    neutral = get(50728)
+    if neutral is not None and (len(neutral) != 3 or min(neutral) <= 0):
+        raise InvalidOptionError("AsShotNeutral", tuple(neutral), "three positive values are expected")
+    gains = []
+    for pos in range(4):
+        wb = 1.0 if neutral is None else float(neutral[1]) / float(neutral["RGB".index(pattern[pos])])
+        gains.append(wb * maxv / float((white - black[pos]) << shift))
+    cfa = Cfa(pattern, black=[b << shift for b in black], gains=gains, white=None)
+    mats = {k: get(tag) for k, tag in ((1, 50721), (2, 50722))}
+    ill = {1: _one(t, ifd0, 50778, _one(t, rawifd, 50778, None)), 2: _one(t, ifd0, 50779, _one(t, rawifd, 50779, None))}
+    pick = next((k for k in (1, 2) if mats[k] is not None and ill[k] == D65), None)
+    if pick is None:
+        pick = 2 if mats[2] is not None else 1 if mats[1] is not None else None
+    develop = None
+    if pick is not None:
+        if len(mats[pick]) != 9:
+            raise InvalidOptionError(f"ColorMatrix{pick}", len(mats[pick]), "a 3 x 3 matrix is expected")
+        develop = Develop(matrix=colour_matrix(mats[pick]), tone=srgb_tone(dt))
+
+    # what is in the file and not applied
+    ignored = [TAG_NAMES[tag] for tag in IGNORED_TAGS if tag in rawifd or tag in ifd0]
+    lens = None
+    for tag in (51008, 51009, 51022):
+        if tag not in rawifd and tag not in ifd0:
+            continue
+        name = TAG_NAMES[tag]
+        ops = _opcodes(t.raw((rawifd if tag in rawifd else ifd0)[tag]), name, path)
+        if tag != 51022:
+            ignored.append(name)
+        for oid, body in ops:
+            oname = OPCODE_NAMES.get(oid, f"Opcode{oid}")
+            if tag == 51022 and oid == 1 and lens is None:
+                lens = _warp_rectilinear(body, layout.height, layout.width, path)
+                if lens is not None:
+                    continue
+                oname = "WarpRectilinear (tangential terms)"
+            ignored.append(oname)
+    orientation = int(_one(t, ifd0, 274, _one(t, rawifd, 274, 1)))
+    return DngFrame(path, layout, span, cfa, develop, lens, orientation, ignored)
+
+
+def _warp_rectilinear(body, h, w, path):
+    """the opcode's data -- uint32 planes, six doubles per plane (kr0..kr3, kt0, kt1), the centre as two doubles in [0, 1] of
+    the image -- as a lens.Lens; None when a tangential term is not 0 (not modelled)"""
+    from .lens import Lens
+    if len(body) < 4:
+        raise ImageLoadError(path, "WarpRectilinear is shorter than its plane count")
+    n = struct.unpack(">I", body[:4])[0]
+    if n not in (1, 3) or len(body) < 4 + 8 * (6 * n + 2):
+        raise ImageLoadError(path, f"WarpRectilinear with {n} planes in {len(body)} bytes")
+    vals = struct.unpack(f">{6 * n + 2}d", body[4:4 + 8 * (6 * n + 2)])
+    planes = [vals[6 * i:6 * i + 6] for i in range(n)]
+    if any(p[4] != 0.0 or p[5] != 0.0 for p in planes):
+        return None
+    cx, cy = vals[6 * n], vals[6 * n + 1]
+    return Lens.from_warp_rectilinear(planes[0] if n == 1 else planes, centre=(cx * (w - 1), cy * (h - 1)))
+
+
+# ---------------------------------------------------------------- the device side
+def host_span(frame):
+    """the frame's span as memory a plain (pageable) upload may read: a read-only file mapping is copied once on the host --
+    the runtime pins what it uploads, and read-only pages do not pin.  (Stack.push_packed on an asynchronous handle needs no
+    such copy: there the library copies the mapping into its own pinned bounce buffer.)"""
+    return frame.span if frame.span.flags.writeable else np.array(frame.span)
+
+
+def _check_frame(frame):
+    if not isinstance(frame, DngFrame):
+        raise InvalidOptionError("frame", frame, "a shinestacker_amd.dng.DngFrame (dng.read) is expected")
+    return frame
+
+
+def unpack(frame, device=0):
+    """The cropped H x W mosaic of a DngFrame as a NumPy array of its dtype: span up, raw_unpack, mosaic down."""
+    lay = _check_frame(frame).layout
+    _lib.require_device()
+    out = np.empty((lay.height, lay.width), lay.dtype)
+    L = lay.struct()
+    span = host_span(frame)
+    _lib.check(_lib.load().mi_raw_unpack(device, span.ctypes.data, span.nbytes, lay.offsets.ctypes.data, _lib.C.byref(L),
+                                         None if lay.table is None else lay.table.ctypes.data, out.ctypes.data))
+    return out
+
+
+def unpack_device(layout, dev_span, span_bytes, dev_offsets, dev_table, dev_out, device=0, stream=None):
+    """raw_unpack on buffers resident in HBM: the span (`span_bytes` of it, 4-byte aligned), the uint32 segment offsets, the
+    uint16 table (or None) -> `dev_out`, layout.height x layout.width samples.  Queued on `stream`, not waited for."""
+    _lib.require_device()
+    L = layout.struct()
+    _lib.check(_lib.load().mi_raw_unpack_device(device, stream, dev_span, int(span_bytes), dev_offsets, _lib.C.byref(L), dev_table, dev_out))
+
+
+class _Staged:
+    """a frame's span, offsets and table in one device buffer"""
+
+    def __init__(self, frame, device):
+        lay = frame.layout
+        self.seg_at = (frame.span.nbytes + 255) & ~255
+        self.table_at = self.seg_at + ((lay.offsets.nbytes + 255) & ~255)
+        self.buf = _lib.DeviceBuffer(self.table_at + (0 if lay.table is None else lay.table.nbytes), device)
+        self.buf.upload(host_span(frame))
+        self.buf.upload(lay.offsets, self.seg_at)
+        if lay.table is not None:
+            self.buf.upload(lay.table, self.table_at)
+        self.span_bytes = frame.span.nbytes
+        self.table = None if lay.table is None else self.buf.ptr + self.table_at
+
+    def unpack_into(self, layout, dev_out, device, stream=None):
+        unpack_device(layout, self.buf.ptr, self.span_bytes, self.buf.ptr + self.seg_at, self.table, dev_out, device, stream)
+
+
+def _resolve(frame, develop, lens):
+    from .demosaic import check_develop
+    from .lens import check_lens
+    if isinstance(develop, str):
+        if develop != "auto":
+            raise InvalidOptionError("develop", develop, '"auto", None or a demosaic.Develop is expected')
+        develop = frame.develop
+    elif develop is not None:
+        check_develop(develop)
+    if isinstance(lens, str):
+        if lens != "auto":
+            raise InvalidOptionError("lens", lens, '"auto", None or a lens.Lens is expected')
+        lens = frame.lens
+    elif lens is not None:
+        lens = check_lens(lens)
+    return develop, lens
+
+
+def develop(frame, develop="auto", lens="auto", calibration=None, device=0):
+    """A DngFrame -> H x W x 3 BGR of its dtype: unpack, then `debayer` with the frame's own Cfa.  `develop`, `lens`: "auto"
+    takes frame.develop / frame.lens, None switches the step off, an object overrides it.  `calibration`: a
+    demosaic.Calibration applied to the unpacked mosaic first."""
+    dev, ln = _resolve(_check_frame(frame), develop, lens)
+    return debayer(unpack(frame, device), frame.cfa, develop=dev, device=device, calibration=calibration, lens=ln)
+
+
+def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None, device=0):
+    """Read the n DNG files (equal cropped shape and dtype), upload their spans and unpack and demosaic them side by side
+    into `dev_out` (device pointer, n x H x W x 3 of their dtype): exactly what pipeline.align_and_stack_device(dev_frames,
+    ...) takes, as demosaic.debayer_frames_device does for mosaics.  Waits for the device.  Returns (H, W, dtype)."""
+    if len(paths) == 0:
+        raise ValueError("no files")
+    _lib.require_device()
+    first = None
+    stage = scratch = None
+    try:
+        for i, p in enumerate(paths):
+            frame = read(p)
+            if first is None:
+                first = frame
+                h, w = frame.shape
+                frame_bytes = h * w * 3 * frame.dtype.itemsize
+                stage = _lib.DeviceBuffer(h * w * frame.dtype.itemsize, device)
+            elif frame.shape != first.shape or frame.dtype != first.dtype:
+                raise InvalidOptionError("paths", p, f"a {frame.shape} {frame.dtype} frame among {first.shape} {first.dtype} ones")
+            dev, ln = _resolve(frame, develop, lens)
+            if ln is not None and scratch is None:
+                scratch = _lib.DeviceBuffer(frame_bytes, device)
+            up = _Staged(frame, device)
+            try:
+                up.unpack_into(frame.layout, stage.ptr, device)
+                debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, frame.dtype, frame.cfa, device=device, develop=dev,
+                               calibration=calibration, lens=ln, lens_scratch=scratch)
+                # the stage and the staged span are reused / freed: the null stream's kernels must be through first
+                _lib.check(_lib.load().mi_device_synchronize(device))
+            finally:
+                up.buf.free()
+    finally:
+        if stage is not None:
+            stage.free()
+        if scratch is not None:
+            scratch.free()
+    return h, w, first.dtype

@@ -1171,7 +1171,8 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
 def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constants.DEFAULT_FRAMES,
                        overlap=constants.DEFAULT_OVERLAP, device=0, out_dev=None, on_bunch=None, on_final=None,
                        check_running=None, stacks=None, results_buf=None, info=None, zero_copy=False, denoise_amount=0,
-                       white_balance=None, unsharp=None, mosaic=None, develop=None, calibration=None, **stack_kwargs):
+                       white_balance=None, unsharp=None, mosaic=None, develop=None, calibration=None, packed=False,
+                       **stack_kwargs):
     """BASELINE config 5's two-stage flow in memory (the reference's `FocusStackBunch` followed by `FocusStack`,
     stack.py:61-113, examples/stack-from-frames): the frames are fused in bunches of `frames` with `overlap` shared
     (`get_bunches`), every bunch result is the stacker's OUTPUT type -- truncated to the input dtype exactly as the file
@@ -1198,13 +1199,17 @@ def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constan
     the bytes over the host link, demosaiced on the device behind the upload) and stage 2 is what it is without it: bunch
     results are BGR on the device.  None (default): nothing of that is called.  `develop`: a `demosaic.Develop` beside `mosaic`
     -- defect sites, colour matrix and tone curve around stage 1's demosaic; it must stay open until this returns.  `calibration`: a `demosaic.Calibration` beside `mosaic` -- master dark and flat field
-    on the raw samples of stage 1, ahead of both; it too stays open until this returns.  Returns the fused image (or None when `out_dev` is given) and the list of
+    on the raw samples of stage 1, ahead of both; it too stays open until this returns.  `packed`: `get_frame(i)` returns a
+    `dng.DngFrame` and stage 1 pushes its packed span (`Stack.push_packed`: the file's sample bytes as they lie, unpacked on the
+    device, demosaiced with the frame's own Cfa; `develop` and `calibration` apply as beside `mosaic`).  Returns the fused image (or None when `out_dev` is given) and the list of
     bunches (frame indices)."""
     from .actions import get_bunches
     _check_denoise_amount(denoise_amount)
     if white_balance is not None or unsharp is not None:
         _check_retouch(white_balance, unsharp, dtype)
-    if develop is not None or calibration is not None:
+    if packed and mosaic is not None:
+        raise InvalidOptionError("packed", packed, "a packed frame carries its own Cfa: mosaic= does not go with it")
+    if (develop is not None or calibration is not None) and not packed:
         from .demosaic import require_mosaic
         require_mosaic(mosaic, develop, calibration)
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
@@ -1236,7 +1241,9 @@ def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constan
             st = stage1[k % len(stage1)]
             st.reset()      # a handle serves every other bunch, as one stacker object serves FocusStackBunch (stack.py:94-97)
             for i in bunch:
-                if mosaic is None:
+                if packed:
+                    st.push_packed(get_frame(i), zero_copy=zero_copy, develop=develop, calibration=calibration)
+                elif mosaic is None:
                     st.push_frame(get_frame(i), zero_copy=zero_copy)
                 elif calibration is not None:
                     st.push_mosaic(get_frame(i), mosaic, zero_copy=zero_copy, develop=develop, calibration=calibration)

@@ -27,8 +27,13 @@ import numpy as np
 
 from . import _lib, depth_out
 from .defaults import constants, resolve_arith
-from .errors import ImageLoadError, InvalidOptionError, RunStopException
+from .errors import BitDepthError, ImageLoadError, InvalidOptionError, RunStopException, ShapeError
 from .imageio import get_img_metadata, read_img, validate_image
+
+
+def _is_dng(path):
+    from .dng import is_dng
+    return is_dng(path)
 
 
 def _cyan(msg):
@@ -73,12 +78,19 @@ class BaseStackAlgo:
             validate_image(img, *metadata)
         return img, metadata, updated
 
+    def _read_file(self, path):
+        """with `raw=` set: a `.dng` path is parsed by dng.read (the header only: a DngFrame whose span is the file's mapping),
+        every other path is decoded as ever"""
+        from . import dng
+        return dng.read(path) if dng.is_dng(path) else read_img(path)
+
     def _decode_ahead(self, filenames):
         """(path, future-or-None) in file order.  With decode_threads > 1 the files are decoded on a
         thread pool a few frames ahead of the consumer (image codecs release the GIL): a 24 MP JPEG
         takes the host far longer to decode than the GPU needs to fuse it.  Errors surface in order,
         at the file that caused them, as in the sequential loop (pyramid.py:155-169)."""
         n = int(self.decode_threads or 0)
+        reader = read_img if getattr(self, "raw", None) is None else self._read_file
         if n <= 1 or len(filenames) <= 1:
             for p in filenames:
                 yield p, None
@@ -89,14 +101,14 @@ class BaseStackAlgo:
             window = deque()
             it = iter(filenames)
             for p in it:
-                window.append((p, pool.submit(read_img, p)))
+                window.append((p, pool.submit(reader, p)))
                 if len(window) >= 2 * n:
                     break
             while window:
                 p, fut = window.popleft()
                 nxt = next(it, None)
                 if nxt is not None:
-                    window.append((nxt, pool.submit(read_img, nxt)))
+                    window.append((nxt, pool.submit(reader, nxt)))
                 try:
                     yield p, fut
                 except GeneratorExit:
@@ -110,8 +122,16 @@ class PyramidStack(BaseStackAlgo):
                  kernel_size=constants.DEFAULT_PY_KERNEL_SIZE,
                  gen_kernel=constants.DEFAULT_PY_GEN_KERNEL,
                  float_type=constants.DEFAULT_PY_FLOAT, *, device=0, use_fma=True,
-                 impl=_lib.IMPL_AUTO, batch_frames=0, decode_threads=8, arith=None):
+                 impl=_lib.IMPL_AUTO, batch_frames=0, decode_threads=8, arith=None, raw=None):
         super().__init__("pyramid", 2, float_type)
+        # raw (keyword-only extension): a dng.Raw -- focus_stack then takes `.dng` paths: each is parsed on the decode-ahead
+        # pool (dng.read), its packed samples are uploaded as they lie in the file and unpacked, demosaiced and developed on
+        # the device (Stack.push_packed).  None: a `.dng` path is an unknown extension, as ever.
+        if raw is not None:
+            from .dng import check_raw
+            check_raw(raw)
+        self.raw = raw
+        self._raw_develops = {}     # quantised colour matrix -> the Develop every file with that matrix shares
         # arith (keyword-only extension; the reference has one evaluation order):
         #   "separable" = MI_ARITH_SEPARABLE, the 5 + 5 tap form of the same stencils: within the stated float-32 tolerance
         #                 of the reference's float-64 mode, ~1.3x the throughput -- the default since round 4
@@ -295,6 +315,21 @@ class PyramidStack(BaseStackAlgo):
         # validation error still aborts the whole stack before any result exists.
         for i, (img_path, decoded) in enumerate(self._decode_ahead(filenames)):
             self.print_message(f": validating file {img_path.split('/')[-1]}")
+            if self.raw is not None and _is_dng(img_path):
+                frame = decoded.result() if decoded is not None else self._read_file(img_path)
+                updated = metadata is None
+                if updated:
+                    metadata = (frame.shape, frame.dtype)
+                elif frame.shape != metadata[0][:2]:
+                    raise ShapeError(metadata[0], frame.shape)
+                elif frame.dtype != metadata[1]:
+                    raise BitDepthError(metadata[1], frame.dtype)
+                if updated:
+                    self._set_dtype(metadata[1])
+                    stack = self._handle(metadata[0], metadata[1])
+                self._push_raw(stack, frame)
+                self._step(i)
+                continue
             img, metadata, updated = self.read_image_and_update_metadata(
                 img_path, metadata, decoded.result() if decoded is not None else None)
             if updated:
@@ -309,6 +344,34 @@ class PyramidStack(BaseStackAlgo):
             self._step(i + n)
         self.print_message(': pyramids fusion completed')
         return stack.finish()
+
+    def _push_raw(self, stack, frame):
+        """one DngFrame into the stack under self.raw.  Without a lens: Stack.push_packed.  With one (the push has no lens
+        path): the frame is unpacked, demosaiced and lens-corrected on the device, then pushed from there, before it is fused."""
+        raw = self.raw
+        dev, ln = raw.develop_for(frame), raw.lens_for(frame)
+        if dev is not None and dev is frame.develop:     # files of one camera share one Develop: one tone table on the device
+            dev = self._raw_develops.setdefault(dev.matrix_q, dev)
+        if ln is None:
+            stack.push_packed(frame, develop=dev, calibration=raw.calibration)
+            return
+        from .demosaic import debayer_device
+        from .dng import _Staged
+        h, w = frame.shape
+        nb = h * w * frame.dtype.itemsize
+        up = _Staged(frame, self.device)
+        mosaic, bgr, scratch = (_lib.DeviceBuffer(nb, self.device), _lib.DeviceBuffer(3 * nb, self.device),
+                                _lib.DeviceBuffer(3 * nb, self.device))
+        try:
+            up.unpack_into(frame.layout, mosaic.ptr, self.device)
+            debayer_device(mosaic.ptr, bgr.ptr, h, w, frame.dtype, frame.cfa, device=self.device, develop=dev,
+                           calibration=raw.calibration, lens=ln, lens_scratch=scratch)
+            _lib.check(_lib.load().mi_device_synchronize(self.device))   # the null stream's kernels, ahead of the handle's
+            stack.push_frames_device(bgr.ptr, 1)
+            stack.sync()                                                 # ... and the handle's, ahead of the buffers' release
+        finally:
+            for b in (up.buf, mosaic, bgr, scratch):
+                b.free()
 
     def focus_stack_arrays(self, frames, mosaic=None, develop=None, calibration=None):
         """In-memory variant (no file I/O): `frames` is a sequence of H x W x 3 uint8/uint16

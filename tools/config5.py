@@ -33,6 +33,8 @@ def two_stage(args):
     `--develop` (with `--mosaic`): stage 1 a third time, the mosaics developed on the device (`mi_stack_push_mosaic_developed`:
     camera matrix, sRGB curve, 10 000 defect sites), then the plain mosaic run again; the times sit beside each other under
     "mosaic".
+    `--packed BITS` (with `--mosaic`): stage 1 from packed spans of the same frames (`mi_stack_push_packed`: BITS / 16 of the
+    mosaic's bytes over the link, unpacked on the device), in turns with the mosaic run on the same samples.
     `--calibrate` (with `--mosaic`): stage 1 from the mosaics with a `Calibration` (a master dark and a master flat; the gain
     table is built on the device before the clock starts) and without, three runs of each in turns, so that the two are
     compared inside one process and the spread from run to run shows; every time is listed under "mosaic"."""
@@ -169,6 +171,63 @@ def two_stage(args):
             developed.update({"calibrated_stage1_seconds": with_c, "plain_stage1_seconds_in_turns": without,
                               "calibrated_over_plain_stage1": float(np.median(with_c) / np.median(without)),
                               "plain_stage1_spread": float((max(without) - min(without)) / np.median(without))})
+        if args.packed:
+            # stage 1 from packed spans of the SAME frames (the mosaics' top `--packed` bits, stored as a raw file stores them:
+            # strips of 64 rows, rows packed most significant bit first), in turns with the mosaic run.  The mosaics pushed
+            # beside them are the unpacked spans, so both runs fuse the same samples.
+            from shinestacker_amd import dng
+            bits = args.packed
+            rowb = (W * bits + 7) // 8
+            rps = 64
+            offsets = np.arange(-(-H // rps), dtype=np.uint32) * np.uint32(rps * rowb)
+            lay = dng.RawLayout(bits, False, H, W, False, rps, W, offsets, shift=16 - bits)
+            pk, same = [], []
+            for m in mos:
+                v = (np.asarray(m) >> (16 - bits)).astype(np.uint16)
+                if bits == 16:
+                    span = v.view(np.uint8).reshape(-1)
+                elif bits == 12 and W % 2 == 0:      # two samples are three bytes
+                    a_, b_ = v[:, 0::2], v[:, 1::2]
+                    span = np.stack([a_ >> 4, (a_ & 15) << 4 | b_ >> 8, b_ & 255], axis=2).astype(np.uint8).reshape(-1)
+                else:
+                    bit = np.unpackbits(v.byteswap().view(np.uint8).reshape(H, W, 2), axis=2)[:, :, 16 - bits:].reshape(H, W * bits)
+                    bit = np.concatenate([bit, np.zeros((H, rowb * 8 - W * bits), np.uint8)], axis=1)
+                    span = np.packbits(bit, axis=1).reshape(-1)
+                    del bit
+                if not args.pageable:
+                    pin = L.host_alloc(span.shape, np.uint8)
+                    pin[...] = span
+                    span = pin
+                pk.append(dng.DngFrame("<memory>", lay, span, cfa, None, None, 1, ()))
+                low = (v << (16 - bits)).astype(np.uint16)
+                if not args.pageable:
+                    pin = L.host_alloc((H, W), np.uint16)
+                    pin[...] = low
+                    low = pin
+                same.append(low)
+
+            def run_packed():
+                info = {}
+                bunches_then_stack(lambda i: pk[i % ndist], N, H, W, np.uint16, out_dev=out.ptr, stacks=stacks, results_buf=results,
+                                   info=info, zero_copy=not args.pageable, packed=True)
+                return info["stage1_s"]
+
+            def run_same():
+                info = {}
+                bunches_then_stack(lambda i: same[i % ndist], N, H, W, np.uint16, out_dev=out.ptr, stacks=stacks, results_buf=results,
+                                   info=info, zero_copy=not args.pageable, mosaic=cfa)
+                return info["stage1_s"]
+            run_packed()
+            with_p, without = [], []
+            for _ in range(3):
+                with_p.append(run_packed())
+                without.append(run_same())
+            for s_ in stacks:
+                s_.sync()
+            developed.update({"packed_bits": bits, "packed_stage1_seconds": with_p, "mosaic_stage1_seconds_in_turns": without,
+                              "packed_over_mosaic_stage1": float(np.median(with_p) / np.median(without)),
+                              "packed_host_to_device_bytes": pushed * int(pk[0].span.nbytes),
+                              "packed_bytes_over_mosaic_bytes": pk[0].span.nbytes / (H * W * 2)})
         _, b1, _ = run()        # BGR stage 1 once more, after the mosaic runs: the two are compared inside one process
         extra = {"mosaic": {"stage1_seconds": m1, "stage2_seconds": m2, "bgr_stage1_seconds": s1, "bgr_stage1_seconds_again": b1,
                             "host_to_device_bytes": pushed * per // 3, "bgr_host_to_device_bytes": pushed * per,
@@ -206,6 +265,9 @@ def main():
     ap.add_argument("--calibrate", action="store_true",
                     help="with --two-stage --mosaic: stage 1 with a master dark and a flat field applied to every mosaic on the "
                          "device, in turns with the plain mosaic run")
+    ap.add_argument("--packed", type=int, default=0, choices=(0, 10, 12, 14, 16),
+                    help="with --two-stage --mosaic: stage 1 from packed spans of that many bits (the file's bytes, unpacked on the "
+                         "device), in turns with the mosaic run on the same samples")
     ap.add_argument("--pageable", action="store_true", help="host frames in ordinary (pageable) memory: the bounce-copy path")
     args = ap.parse_args()
     if args.two_stage:
