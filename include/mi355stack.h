@@ -902,6 +902,55 @@ MI_API int mi_stack_push_packed(mi_stack_t* s, const void* host_span, size_t spa
                                 const mi_calib_t* calib, const mi_develop_t* develop, const int32_t* dev_sites, int n_sites,
                                 int pinned);
 
+/* ---- lossless-JPEG raw samples in: DNG Compression 7 decoded on the device (kernels_ljpeg.hpp) ----
+ * Every strip or tile of such a file is one JPEG stream (ITU-T T.81 lossless, Huffman coded, SOF3).  The host reads the
+ * stream's headers into one descriptor per segment, in grid order (k as for mi_raw_layout_t); the span is uploaded as it lies
+ * and the kernel decodes the entropy-coded data: Huffman categories, differences, prediction per component (Ra: the sample
+ * ncomp columns to the left, Rb: above, Rc: above-left; the first sample is predicted by 2^(precision-1), the rest of the
+ * first line by Ra, the first sample of every other line by Rb), value = (prediction + difference) mod 2^16.  The sample of
+ * line r, x, component c lands at segment row r, column x * ncomp + c; table, shift and crop then apply as in raw_unpack.
+ * `layout` describes the grid, the crop and the output exactly as for mi_raw_unpack; its `bits` is the file's BitsPerSample
+ * and only picks the dtype.  tests/ljpeg_restatement.py states all of it in Python. */
+typedef struct mi_ljpeg_seg {
+    uint32_t scan_off;      /* the entropy-coded data: its first byte in the span ...                   */
+    uint32_t scan_bytes;    /* ... and its length; a marker inside it ends it earlier                   */
+    int32_t x;              /* samples per line of one component: x * ncomp == the segment's columns    */
+    int32_t y;              /* lines: the segment's rows                                                */
+    uint8_t ncomp;          /* 1 or 2                                                                   */
+    uint8_t predictor;      /* 1 .. 7                                                                   */
+    uint8_t precision;      /* 2 .. 16                                                                  */
+    uint8_t reserved;
+    uint8_t counts[2][16];  /* per component: the number of codes of length 1 .. 16                     */
+    uint8_t values[2][17];  /* per component: the categories (0 .. 16) in code order                    */
+    uint8_t pad[10];        /* to 96 bytes                                                              */
+} mi_ljpeg_seg_t;
+#define MI_LJPEG_NOCODE 1u      /* status bit 0: a 16-bit prefix matched no code                             */
+#define MI_LJPEG_OVERRUN 2u     /* status bit 1: the last sample needed bits from beyond the end of the data */
+#define MI_LJPEG_UNDECODED 4u   /* status bit 2: a descriptor in device memory that the host forms refuse    */
+#define MI_LJPEG_MAX_LINE 24576 /* predictors 2 .. 7 keep the line above on chip: segments up to this wide   */
+/* Status: one uint32 per segment.  A flagged segment's samples are unspecified, but every one of them is written inside the
+ * output; all other segments are exact.  Argument checks are those of mi_raw_unpack (the offsets array is replaced by `segs`:
+ * "null segs") and, where the descriptors lie in host memory, per segment: ncomp 1 or 2, predictor 1 .. 7, precision 2 ..
+ * layout->bits, x * ncomp and y equal to the segment's columns and rows, a predictor other than 1 only on segments of at most
+ * MI_LJPEG_MAX_LINE columns, counts that fit the code space with at most 17 values none above 16, scan_off + scan_bytes
+ * inside the span.  dev_span must be 4-byte aligned, dev_segs 16-byte, dev_out to its samples, dev_status to 4 bytes.
+ * mi_raw_ljpeg_device enqueues on `stream` and does not wait; dev_status (one word per segment) may be null.  mi_raw_ljpeg
+ * uploads, runs, downloads and waits; it returns MI_OK with the flags in status_out (may be null). */
+MI_API int mi_raw_ljpeg_device(int device, void* stream, const void* dev_span, size_t span_bytes, const mi_ljpeg_seg_t* dev_segs,
+                               const mi_raw_layout_t* layout, const uint16_t* dev_table, void* dev_out, uint32_t* dev_status);
+MI_API int mi_raw_ljpeg(int device, const void* host_span, size_t span_bytes, const mi_ljpeg_seg_t* segs,
+                        const mi_raw_layout_t* layout, const uint16_t* host_table, void* host_out, uint32_t* status_out);
+/* mi_stack_push_packed for a lossless-JPEG span: the packed slot holds [span | descriptors | table], raw_ljpeg takes the place
+ * of raw_unpack, and everything else -- routes, the pinned rule, the kernels behind it -- is the same.  Packed, compressed,
+ * mosaic and BGR pushes may mix on one handle.  The stage ORs every frame's status flags into one device word of its own:
+ * mi_stack_ljpeg_status waits for the stage, returns that word in *flags and clears it (0 on a handle that never took a
+ * compressed frame). */
+MI_API int mi_stack_push_ljpeg(mi_stack_t* s, const void* host_span, size_t span_bytes, const mi_ljpeg_seg_t* segs,
+                               const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_cfa_t* cfa,
+                               const mi_calib_t* calib, const mi_develop_t* develop, const int32_t* dev_sites, int n_sites,
+                               int pinned);
+MI_API int mi_stack_ljpeg_status(mi_stack_t* s, uint32_t* flags);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

@@ -88,6 +88,27 @@ class RawLayoutStruct(C.Structure):
                 ("table_len", C.c_int32), ("dtype", C.c_int32)]
 
 
+class LjpegSeg(C.Structure):
+    """mi_ljpeg_seg_t: one lossless-JPEG segment of a raw file, read from its stream's headers (dng.read)"""
+    _fields_ = [("scan_off", C.c_uint32), ("scan_bytes", C.c_uint32), ("x", C.c_int32), ("y", C.c_int32), ("ncomp", C.c_uint8),
+                ("predictor", C.c_uint8), ("precision", C.c_uint8), ("reserved", C.c_uint8), ("counts", (C.c_uint8 * 16) * 2),
+                ("values", (C.c_uint8 * 17) * 2), ("pad", C.c_uint8 * 10)]
+
+
+# the same as a NumPy record: dng.RawLayout.segments is an array of these
+LJPEG_SEG_DTYPE = np.dtype([("scan_off", "<u4"), ("scan_bytes", "<u4"), ("x", "<i4"), ("y", "<i4"), ("ncomp", "u1"), ("predictor", "u1"),
+                            ("precision", "u1"), ("reserved", "u1"), ("counts", "u1", (2, 16)), ("values", "u1", (2, 17)),
+                            ("pad", "u1", (10,))])
+LJPEG_NOCODE, LJPEG_OVERRUN, LJPEG_UNDECODED = 1, 2, 4
+LJPEG_MAX_LINE = 24576
+LJPEG_FLAG_NAMES = {LJPEG_NOCODE: "a 16-bit prefix matched no Huffman code", LJPEG_OVERRUN: "the data ended before the last sample",
+                    LJPEG_UNDECODED: "a descriptor the decoder does not take"}
+
+
+def ljpeg_flag_text(flags):
+    return ", ".join(t for b, t in LJPEG_FLAG_NAMES.items() if flags & b) or "no flag"
+
+
 class DepthMapParams(C.Structure):
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32),
                 ("map_type", C.c_int32), ("energy", C.c_int32), ("kernel_size", C.c_int32),
@@ -294,6 +315,14 @@ SIGNATURES = {
     "mi_stack_push_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p,
                                        C.POINTER(CfaStruct), C.POINTER(CalibStruct), C.POINTER(DevelopStruct), C.c_void_p, C.c_int,
                                        C.c_int]),
+    "mi_raw_ljpeg_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "mi_raw_ljpeg": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+    "mi_stack_push_ljpeg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p,
+                                      C.POINTER(CfaStruct), C.POINTER(CalibStruct), C.POINTER(DevelopStruct), C.c_void_p, C.c_int,
+                                      C.c_int]),
+    "mi_stack_ljpeg_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }
@@ -670,7 +699,8 @@ class Stack:
 
     def push_packed(self, frame, zero_copy=False, develop=None, calibration=None):
         """Push one host frame as the packed sample bytes of its raw file (`frame`: a dng.DngFrame whose cropped size and
-        dtype are the handle's): the span crosses the host link as it lies in the file -- 0.75 of a uint16 mosaic's bytes at
+        dtype are the handle's; uncompressed, or lossless JPEG -- then `ljpeg_status()` tells whether every stream decoded):
+        the span crosses the host link as it lies in the file -- 0.75 of a uint16 mosaic's bytes at
         12 bits -- and is unpacked on the device behind its upload, then calibrated, repaired and demosaiced with the frame's
         own Cfa exactly as push_mosaic does.  `develop`, `calibration`: as in push_mosaic (None: that step is not run).
         `zero_copy`: the frame's span must then lie in pinned memory (a file mapping is not: it takes the copying path)."""
@@ -680,7 +710,10 @@ class Stack:
         if lay.dtype != self.in_dtype:
             raise ValueError(f"mosaic dtype {lay.dtype} != {self.in_dtype}")
         c = frame.cfa.struct(self.in_dtype)
-        L, offsets, table = lay.struct(), lay.offsets, lay.table
+        L, table = lay.struct(), lay.table
+        compressed = getattr(lay, "compression", 1) == 7
+        offsets = lay.segments if compressed else lay.offsets     # (descriptors stand where the offsets do)
+        entry = load().mi_stack_push_ljpeg if compressed else load().mi_stack_push_packed
         cal = d = sites = None
         n_sites = 0
         if calibration is not None:
@@ -699,10 +732,9 @@ class Stack:
             span = host_span(frame)     # the synchronous route uploads straight out of the caller's memory
 
         def push(pinned):
-            return load().mi_stack_push_packed(self._h, span.ctypes.data, span.nbytes, offsets.ctypes.data, C.byref(L),
-                                               None if table is None else table.ctypes.data, C.byref(c),
-                                               None if cal is None else C.byref(cal), None if d is None else C.byref(d), sites,
-                                               n_sites, pinned)
+            return entry(self._h, span.ctypes.data, span.nbytes, offsets.ctypes.data, C.byref(L),
+                         None if table is None else table.ctypes.data, C.byref(c), None if cal is None else C.byref(cal),
+                         None if d is None else C.byref(d), sites, n_sites, pinned)
         if zero_copy and is_pinned(span):
             rc = push(1)
             if rc == MI_OK:
@@ -713,6 +745,13 @@ class Stack:
             if rc != MI_ERR_INVALID:     # MI_ERR_INVALID: the library does not see pinned memory there (stale record)
                 check(rc)
         check(push(0))
+
+    def ljpeg_status(self):
+        """the status flags (LJPEG_NOCODE, LJPEG_OVERRUN, ...) of every lossless-JPEG frame pushed since the last call, ORed:
+        waits for the frames' decode kernels, returns the word and clears it.  0: every compressed frame decoded exactly."""
+        flags = C.c_uint32(0)
+        check(load().mi_stack_ljpeg_status(self._h, C.byref(flags)))
+        return int(flags.value)
 
     def wait_uploads(self, max_outstanding=0):
         """block until at most `max_outstanding` of the pinned frames pushed so far are still being uploaded: a producer that

@@ -2040,6 +2040,88 @@ int mi_raw_unpack(int device, const void* host_span, size_t span_bytes, const ui
     return tmp.download(host_out, out, nb);
 }
 
+// descriptors in host memory (mi_raw_ljpeg, mi_stack_push_ljpeg): what the kernel would flag or mis-decode is refused here
+static int ljpeg_segs_check(size_t span_bytes, const mi_ljpeg_seg_t* segs, const mi_raw_layout_t* L) {
+    const int nsx = unpack_nsx(*L), nsy = cdiv(L->image_height, L->seg_height);
+    for (int k = 0; k < nsx * nsy; ++k) {
+        const mi_ljpeg_seg_t& S = segs[k];
+        const int rows = L->tiled ? L->seg_height : std::min(L->seg_height, L->image_height - (k / nsx) * L->seg_height);
+        if (S.ncomp != 1 && S.ncomp != 2) return fail(MI_ERR_INVALID, "segs[%d].ncomp must be 1 or 2 (got %d)", k, S.ncomp);
+        if (S.predictor < 1 || S.predictor > 7) return fail(MI_ERR_INVALID, "segs[%d].predictor must be in [1, 7] (got %d)", k, S.predictor);
+        if (S.precision < 2 || S.precision > L->bits)
+            return fail(MI_ERR_INVALID, "segs[%d].precision must be in [2, layout bits = %d] (got %d)", k, L->bits, S.precision);
+        if (S.x < 1 || (int64_t)S.x * S.ncomp != L->seg_width || S.y != rows)
+            return fail(MI_ERR_INVALID, "segs[%d]: a frame of %d lines of %d x %d samples does not match its segment of %d x %d", k, S.y, S.x,
+                        S.ncomp, rows, L->seg_width);
+        if (S.predictor != 1 && L->seg_width > ljpeg::MAX_LINE)
+            return fail(MI_ERR_INVALID, "segs[%d].predictor %d keeps the line above: layout seg_width must be <= %d for it (got %d)", k,
+                        S.predictor, ljpeg::MAX_LINE, L->seg_width);
+        for (int c = 0; c < S.ncomp; ++c) {
+            uint32_t code = 0, total = 0;
+            for (int l = 1; l <= 16; ++l) {
+                code += S.counts[c][l - 1];
+                total += S.counts[c][l - 1];
+                if (code > (1u << l)) return fail(MI_ERR_INVALID, "segs[%d].counts[%d] overflow the code space at length %d", k, c, l);
+                code <<= 1;
+            }
+            if (total < 1 || total > 17) return fail(MI_ERR_INVALID, "segs[%d].counts[%d] must sum to 1 .. 17 (got %u)", k, c, total);
+            for (uint32_t i = 0; i < total; ++i)
+                if (S.values[c][i] > 16) return fail(MI_ERR_INVALID, "segs[%d].values[%d][%u] must be <= 16 (got %d)", k, c, i, S.values[c][i]);
+        }
+        const uint64_t e = (uint64_t)S.scan_off + S.scan_bytes;
+        if (e > span_bytes)
+            return fail(MI_ERR_INVALID, "segs[%d].scan_off = %u: the data ends at %llu, outside the span of %llu bytes", k, S.scan_off,
+                        (unsigned long long)e, (unsigned long long)span_bytes);
+    }
+    return MI_OK;
+}
+// raw_layout_check for the lossless-JPEG entry points: the descriptors stand where the offsets do
+static int ljpeg_layout_check(const void* span, size_t span_bytes, const mi_ljpeg_seg_t* segs, const mi_raw_layout_t* L, const uint16_t* table,
+                              const void* out) {
+    if (span && !segs) return fail(MI_ERR_INVALID, "null segs");
+    return raw_layout_check(span, span_bytes, (const uint32_t*)segs, L, table, out);
+}
+
+int mi_raw_ljpeg_device(int device, void* stream, const void* dev_span, size_t span_bytes, const mi_ljpeg_seg_t* dev_segs,
+                        const mi_raw_layout_t* layout, const uint16_t* dev_table, void* dev_out, uint32_t* dev_status) {
+    int rc = ljpeg_layout_check(dev_span, span_bytes, dev_segs, layout, dev_table, dev_out);
+    if (rc) return rc;
+    // (the kernel stages aligned dwords of the span and reads the descriptors as structs)
+    if ((uintptr_t)dev_span & 3) return fail(MI_ERR_INVALID, "dev_span must be 4-byte aligned");
+    if ((uintptr_t)dev_segs & 15) return fail(MI_ERR_INVALID, "dev_segs must be 16-byte aligned");
+    if ((uintptr_t)dev_out & (dtype_size(layout->dtype) - 1)) return fail(MI_ERR_INVALID, "dev_out must be aligned to its samples");
+    if ((uintptr_t)dev_status & 3) return fail(MI_ERR_INVALID, "dev_status must be 4-byte aligned");
+    MI_HIP(hipSetDevice(device));
+    ljpeg_launch((hipStream_t)stream, dev_span, span_bytes, dev_segs, *layout, dev_table, dev_out, dev_status, nullptr);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_raw_ljpeg(int device, const void* host_span, size_t span_bytes, const mi_ljpeg_seg_t* segs, const mi_raw_layout_t* layout,
+                 const uint16_t* host_table, void* host_out, uint32_t* status_out) {
+    int rc = ljpeg_layout_check(host_span, span_bytes, segs, layout, host_table, host_out);
+    if (rc || (rc = ljpeg_segs_check(span_bytes, segs, layout))) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t nb = (size_t)layout->height * layout->width * dtype_size(layout->dtype);
+    const size_t nseg = (size_t)unpack_nsegs(*layout);
+    DevScratch tmp(nullptr);
+    void *span = nullptr, *out = nullptr;
+    mi_ljpeg_seg_t* seg = nullptr;
+    uint16_t* table = nullptr;
+    uint32_t* status = nullptr;
+    if ((rc = tmp.upload(&span, host_span, span_bytes)) || (rc = tmp.upload(&seg, segs, nseg * sizeof(mi_ljpeg_seg_t))) ||
+        (layout->table_len > 0 && (rc = tmp.upload(&table, host_table, (size_t)layout->table_len * sizeof(uint16_t)))) ||
+        (rc = tmp.alloc(&out, nb)) || (rc = tmp.alloc(&status, nseg * sizeof(uint32_t))) ||
+        (rc = mi_raw_ljpeg_device(device, nullptr, span, span_bytes, seg, layout, table, out, status)))
+        return rc;
+    if (status_out && (rc = tmp.download(status_out, status, nseg * sizeof(uint32_t)))) return rc;
+    return tmp.download(host_out, out, nb);
+}
+
+static int packed_push(mi_stack_t* s, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets, const mi_ljpeg_seg_t* segs,
+                       const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_cfa_t* cfa, const mi_calib_t* calib,
+                       const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned);
+
 int mi_stack_push_packed(mi_stack_t* s, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets,
                          const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_cfa_t* cfa, const mi_calib_t* calib,
                          const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned) {
@@ -2048,6 +2130,39 @@ int mi_stack_push_packed(mi_stack_t* s, const void* host_span, size_t span_bytes
     if ((rc = raw_layout_check(host_span, span_bytes, seg_offsets, layout, host_table, s)) ||
         (rc = raw_segments_check(span_bytes, seg_offsets, layout)))
         return rc;
+    return packed_push(s, host_span, span_bytes, seg_offsets, nullptr, layout, host_table, cfa, calib, develop, dev_sites, n_sites, pinned);
+}
+
+int mi_stack_push_ljpeg(mi_stack_t* s, const void* host_span, size_t span_bytes, const mi_ljpeg_seg_t* segs, const mi_raw_layout_t* layout,
+                        const uint16_t* host_table, const mi_cfa_t* cfa, const mi_calib_t* calib, const mi_develop_t* develop,
+                        const int32_t* dev_sites, int n_sites, int pinned) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if ((rc = ljpeg_layout_check(host_span, span_bytes, segs, layout, host_table, s)) || (rc = ljpeg_segs_check(span_bytes, segs, layout)))
+        return rc;
+    return packed_push(s, host_span, span_bytes, nullptr, segs, layout, host_table, cfa, calib, develop, dev_sites, n_sites, pinned);
+}
+
+int mi_stack_ljpeg_status(mi_stack_t* s, uint32_t* flags) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (!flags) return fail(MI_ERR_INVALID, "null flags");
+    *flags = 0;
+    MosaicStage* m = mstage(s);
+    if (!m || !m->ljstatus) return MI_OK;
+    MI_HIP(hipSetDevice(s->p.device));
+    if ((rc = mosaic_sync(s))) return rc;
+    MI_HIP(hipStreamSynchronize(s->stream));   // (the decode kernels run on the handle's stream behind their uploads)
+    MI_HIP(hipMemcpy(flags, m->ljstatus, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    MI_HIP(hipMemsetAsync(m->ljstatus, 0, sizeof(uint32_t), s->stream));   // (in order with the next frame's decode kernel)
+    return MI_OK;
+}
+
+// the part of mi_stack_push_packed and mi_stack_push_ljpeg behind the span's checks
+static int packed_push(mi_stack_t* s, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets, const mi_ljpeg_seg_t* segs,
+                       const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_cfa_t* cfa, const mi_calib_t* calib,
+                       const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned) {
+    int rc;
     if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
     if (layout->height != s->p.height || layout->width != s->p.width || layout->dtype != s->p.in_dtype)
         return fail(MI_ERR_INVALID, "layout height, width and dtype must be the handle's (got %dx%d dtype %d for %dx%d dtype %d)", layout->width,
@@ -2063,7 +2178,8 @@ int mi_stack_push_packed(mi_stack_t* s, const void* host_span, size_t span_bytes
         hipPointerAttribute_t at{};
         if (hipPointerGetAttributes(&at, host_span) != hipSuccess || at.type != hipMemoryTypeHost) {
             (void)hipGetLastError();
-            return fail(MI_ERR_INVALID, "mi_stack_push_packed: the span is not in pinned host memory (mi_host_alloc / mi_host_register)");
+            return fail(MI_ERR_INVALID, "%s: the span is not in pinned host memory (mi_host_alloc / mi_host_register)",
+                        segs ? "mi_stack_push_ljpeg" : "mi_stack_push_packed");
         }
     }
     mi_calib_t c{};
@@ -2071,7 +2187,7 @@ int mi_stack_push_packed(mi_stack_t* s, const void* host_span, size_t span_bytes
     mi_develop_t d{};
     if (develop) d = *develop;
     const mi_raw_layout_t L = *layout;
-    const PackedSrc pk{host_span, span_bytes, seg_offsets, unpack_nsegs(L), &L, host_table};
+    const PackedSrc pk{host_span, span_bytes, seg_offsets, segs, unpack_nsegs(L), &L, host_table};
     return mosaic_push(s, nullptr, 0, *cfa, pinned && async, develop ? &d : nullptr, dev_sites, n_sites, calib && c.flags ? &c : nullptr, &pk);
 }
 

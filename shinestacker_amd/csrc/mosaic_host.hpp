@@ -27,12 +27,16 @@
 //               and the demosaic follow as for a mosaic.  evSlotFree[slot] is behind all of them, so it guards both slots.
 //               The packed slots belong to the stage (not to s->allocs): they grow when a later span is larger, after a wait
 //               for both streams.
+//   ljpeg       mi_stack_push_ljpeg: the same route with a lossless-JPEG span (kernels_ljpeg.hpp): the packed slot holds [span |
+//               descriptors | table], raw_ljpeg takes raw_unpack's place and ORs every segment's status flags into `ljstatus`,
+//               one device word of the stage (mi_stack_ljpeg_status reads and clears it).
 //   order       frames are fused in call order: the first mosaic after host BGR frames flushes the ring (mosaic_push), and
 //               every call that takes frames of another kind or reads state flushes this stage first (stack_flush in capi.hip).
 #pragma once
 
 #include "kernels_calib.hpp"
 #include "kernels_demosaic.hpp"
+#include "kernels_ljpeg.hpp"
 #include "kernels_unpack.hpp"
 
 namespace mi {
@@ -63,18 +67,22 @@ struct MosaicStage {
     hipEvent_t evPPin[NPIN] = {nullptr, nullptr, nullptr};  // the upload out of ppin[i] finished
     size_t ppin_cap = 0;
     long ppin_no = 0;
+    uint32_t* ljstatus = nullptr;             // lossless-JPEG spans: every frame's status flags ORed (in s->allocs)
 };
 
 // what mi_stack_push_packed brings in place of a mosaic (arguments checked by the caller)
 struct PackedSrc {
     const void* span;
     size_t span_bytes;
-    const uint32_t* seg;        // host
+    const uint32_t* seg;        // host: the segment offsets, or null ...
+    const mi_ljpeg_seg_t* ljseg;    // ... when the span is lossless JPEG: host, one descriptor per segment
     int nseg;
     const mi_raw_layout_t* layout;
     const uint16_t* table;      // host, layout->table_len entries, or null
 };
 inline size_t packed_align(size_t n) { return (n + 255) & ~(size_t)255; }
+inline const void* packed_seg(const PackedSrc& pk) { return pk.ljseg ? (const void*)pk.ljseg : (const void*)pk.seg; }
+inline size_t packed_seg_bytes(const PackedSrc& pk) { return (size_t)pk.nseg * (pk.ljseg ? sizeof(mi_ljpeg_seg_t) : sizeof(uint32_t)); }
 
 inline MosaicStage* mstage(const mi_stack* s) { return reinterpret_cast<MosaicStage*>(s->mosaic); }
 
@@ -228,6 +236,15 @@ inline void mosaic_kernels(hipStream_t st, void* slot, void* frame, int H, int W
     else demosaic_launch(st, slot, frame, H, W, dtype, cfa);
 }
 
+// the kernel that turns the packed slot `ps` ([span | offsets or descriptors | table]) into the mosaic `slot`
+inline void packed_launch(hipStream_t st, const PackedSrc& pk, const char* ps, size_t seg_at, size_t table_at, void* slot, uint32_t* ljstatus) {
+    if (pk.ljseg)
+        ljpeg_launch(st, ps, pk.span_bytes, (const mi_ljpeg_seg_t*)(ps + seg_at), *pk.layout, (const uint16_t*)(ps + table_at), slot, nullptr,
+                     ljstatus);
+    else
+        unpack_launch(st, ps, pk.span_bytes, (const uint32_t*)(ps + seg_at), *pk.layout, (const uint16_t*)(ps + table_at), slot);
+}
+
 // room for a span of `span_bytes` with `meta_bytes` of offsets and table behind it, in every packed slot the handle uses.
 // Growing waits for both streams first: nothing reads what is freed.
 inline int packed_reserve(mi_stack* s, size_t span_bytes, size_t meta_bytes) {
@@ -278,18 +295,21 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     const int H = s->p.height, W = s->p.width;
     const size_t rb = (size_t)W * dtype_size(s->p.in_dtype);
     // a packed span's device layout: [span | offsets | table]
-    const size_t seg_bytes = pk ? packed_align((size_t)pk->nseg * sizeof(uint32_t)) : 0;
+    const size_t seg_bytes = pk ? packed_align(packed_seg_bytes(*pk)) : 0;
     const size_t table_bytes = pk ? (size_t)pk->layout->table_len * sizeof(uint16_t) : 0;
     const size_t seg_at = pk ? packed_align(pk->span_bytes) : 0, table_at = seg_at + seg_bytes;
     if (pk && (rc = packed_reserve(s, pk->span_bytes, seg_bytes + table_bytes))) return rc;
+    if (pk && pk->ljseg && !m->ljstatus) {
+        if ((rc = dev_alloc(s, (void**)&m->ljstatus, sizeof(uint32_t)))) return rc;
+        MI_HIP(hipMemsetAsync(m->ljstatus, 0, sizeof(uint32_t), s->stream));
+    }
     if (pk && s->p.impl != MI_IMPL_TILED) {
         // the synchronous route of a packed span: upload, unpack, then as a mosaic below
         char* ps = (char*)m->pslot[0];
         MI_HIP(hipMemcpyAsync(ps, pk->span, pk->span_bytes, hipMemcpyHostToDevice, s->stream));
-        MI_HIP(hipMemcpyAsync(ps + seg_at, pk->seg, (size_t)pk->nseg * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+        MI_HIP(hipMemcpyAsync(ps + seg_at, packed_seg(*pk), packed_seg_bytes(*pk), hipMemcpyHostToDevice, s->stream));
         if (table_bytes) MI_HIP(hipMemcpyAsync(ps + table_at, pk->table, table_bytes, hipMemcpyHostToDevice, s->stream));
-        unpack_launch(s->stream, ps, pk->span_bytes, (const uint32_t*)(ps + seg_at), *pk->layout, (const uint16_t*)(ps + table_at),
-                      m->slot[0]);
+        packed_launch(s->stream, *pk, ps, seg_at, table_at, m->slot[0], m->ljstatus);
         mosaic_kernels(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
         MI_HIP(hipGetLastError());
         rc = dispatch_push(s, s->frame_dev, 1, t->frame_bytes);
@@ -314,7 +334,7 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
         // offsets and table through the slot's pinned block: its previous upload is through once evCopied[si] is
         MI_HIP(hipEventSynchronize(m->evCopied[si]));   // (no-op on an event never recorded)
         char* mb = (char*)m->meta[si];
-        memcpy(mb, pk->seg, (size_t)pk->nseg * sizeof(uint32_t));
+        memcpy(mb, packed_seg(*pk), packed_seg_bytes(*pk));
         if (table_bytes) memcpy(mb + seg_bytes, pk->table, table_bytes);
         MI_HIP(hipMemcpyAsync(ps + seg_at, mb, seg_bytes + table_bytes, hipMemcpyHostToDevice, m->stc));
     }
@@ -380,8 +400,7 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     MI_HIP(hipEventRecord(m->evCopied[si], m->stc));
     MI_HIP(hipStreamWaitEvent(s->stream, m->evCopied[si], 0));
     void* frame = (char*)m->bgr + (size_t)m->pending * t->frame_bytes;
-    if (pk)
-        unpack_launch(s->stream, ps, pk->span_bytes, (const uint32_t*)(ps + seg_at), *pk->layout, (const uint16_t*)(ps + table_at), slot);
+    if (pk) packed_launch(s->stream, *pk, ps, seg_at, table_at, slot, m->ljstatus);
     mosaic_kernels(s->stream, slot, frame, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
     MI_HIP(hipGetLastError());
     MI_HIP(hipEventRecord(m->evSlotFree[si], s->stream));

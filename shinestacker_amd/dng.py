@@ -1,4 +1,5 @@
-"""DNG raw files in: the TIFF structure parsed on the host, the packed samples unpacked on the MI355X (csrc/kernels_unpack.hpp).
+"""DNG raw files in: the TIFF structure parsed on the host, the samples -- packed (csrc/kernels_unpack.hpp) or lossless JPEG
+(Compression 7, csrc/kernels_ljpeg.hpp) -- unpacked or decoded on the MI355X.
 
 The reference reads developed frames and never opens a raw file, so this has no reference counterpart.  DNG is the documented
 raw container and it is a TIFF: `read` walks the IFDs with `struct` and NumPy alone and never touches the sample data -- it
@@ -11,8 +12,17 @@ BlackLevel, WhiteLevel and AsShotNeutral), `develop` (a demosaic.Develop from th
 from the WarpRectilinear opcode, or None), `orientation` (reported, not applied) and `ignored`: the names of every tag and
 opcode in the file that carries a correction this reader does NOT apply -- nothing is dropped silently.
 
-Refused, each with the tag's name and value, before any device call: compressed samples (lossless JPEG, deflate, lossy
-JPEG), more than one sample per pixel, a CFA repeat other than 2 x 2, a CFALayout other than 1, bit depths other than 8, 10,
+Lossless JPEG (ITU-T T.81, SOF3, Huffman coded: what most cameras and converters write): every strip or tile is one JPEG
+stream; `read` parses each stream's markers out of the mapping -- headers only, a few hundred bytes a tile -- into one
+descriptor per segment (`RawLayout.segments`), and the kernel decodes the entropy-coded data.  The compressed bytes are the
+smallest form of the frame that can cross the host link.  Accepted: one or two components whose samples interleave along the
+segment's rows (X * Nf == the segment's columns), Y equal to the segment's rows, 2 <= P <= BitsPerSample, predictors 1 to 7,
+no point transform, no restart interval, one scan.  `unpack` raises ImageLoadError when a stream ends early or holds bits that
+match no code; a stack asks its handle (`Stack.ljpeg_status`).
+
+Refused, each with the tag's name and value, before any device call: deflate and lossy JPEG samples, a lossless-JPEG
+segment outside the above (each as InvalidOptionError("Compression", 7, "lossless JPEG: segment k: ...")), more than one sample
+per pixel, a CFA repeat other than 2 x 2, a CFALayout other than 1, bit depths other than 8, 10,
 12, 14 and 16, truncated segments, and a TIFF without a CFA IFD.
 
 The tag numbers and the opcode layout are written from memory of the DNG specification: this reader is UNPINNED against a
@@ -74,6 +84,10 @@ class RawLayout:
     tiled                       False: strips of seg_height = RowsPerStrip rows, seg_width == image_width; True: tiles of
                                 seg_height x seg_width = TileLength x TileWidth, edge tiles stored at full size
     offsets                     uint32, one per segment, row-major over the segment grid, rebased to the start of the span
+    compression                 1: packed samples; 7: every segment is a lossless-JPEG stream
+    segments                    compression 7: one _lib.LJPEG_SEG_DTYPE record (mi_ljpeg_seg_t) per segment, its scan_off
+                                rebased to the start of the span; else None
+    counts                      compression 7: the file's byte count of every segment
     crop_y, crop_x, height, width   the ActiveArea (or the whole image): what comes out
     shift                       every sample is shifted left by it
     table                       the LinearizationTable (uint16) or None
@@ -81,7 +95,7 @@ class RawLayout:
     """
 
     def __init__(self, bits, big_endian, image_height, image_width, tiled, seg_height, seg_width, offsets, crop_y=0, crop_x=0,
-                 height=None, width=None, shift=0, table=None):
+                 height=None, width=None, shift=0, table=None, compression=1, segments=None, counts=None):
         self.bits, self.big_endian = int(bits), bool(big_endian)
         self.image_height, self.image_width = int(image_height), int(image_width)
         self.tiled, self.seg_height, self.seg_width = bool(tiled), int(seg_height), int(seg_width)
@@ -92,10 +106,14 @@ class RawLayout:
         self.shift = int(shift)
         self.table = None if table is None else np.ascontiguousarray(table, dtype=np.uint16)
         self.dtype = np.dtype(np.uint8 if self.bits == 8 else np.uint16)
+        self.compression = int(compression)
+        self.segments = None if segments is None else np.ascontiguousarray(segments, dtype=_lib.LJPEG_SEG_DTYPE)
+        self.counts = None if counts is None else np.ascontiguousarray(counts, dtype=np.int64)
 
     def __repr__(self):
         seg = f"tiles {self.seg_height}x{self.seg_width}" if self.tiled else f"strips of {self.seg_height} rows"
-        return (f"RawLayout({self.bits} bit{', big-endian' if self.big_endian else ''}, {self.image_height}x{self.image_width}, {seg}, "
+        return (f"RawLayout({self.bits} bit{', big-endian' if self.big_endian else ''}{', lossless JPEG' if self.compression == 7 else ''}, "
+                f"{self.image_height}x{self.image_width}, {seg}, "
                 f"crop ({self.crop_y}, {self.crop_x}) {self.height}x{self.width}, shift {self.shift}, "
                 f"table {None if self.table is None else len(self.table)})")
 
@@ -110,10 +128,15 @@ class RawLayout:
         return -(-self.image_height // self.seg_height), -(-self.image_width // self.seg_width)
 
     def segment_bytes(self, k):
-        """the stored bytes of segment k: a tile is always whole, the last strip holds the rows that are left"""
+        """the stored bytes of segment k: a tile is always whole, the last strip holds the rows that are left; of a
+        compressed layout the file's byte count"""
+        if self.compression == 7:
+            return int(self.counts[k])
+        return self.segment_rows(k) * self.row_bytes
+
+    def segment_rows(self, k):
         sy = k // self.grid[1]
-        rows = self.seg_height if self.tiled else min(self.seg_height, self.image_height - sy * self.seg_height)
-        return rows * self.row_bytes
+        return self.seg_height if self.tiled else min(self.seg_height, self.image_height - sy * self.seg_height)
 
     def struct(self):
         """mi_raw_layout_t"""
@@ -292,7 +315,7 @@ def read(path):
         return default
 
     comp = _one(t, rawifd, 259, 1)
-    if comp != 1:
+    if comp not in (1, 7):
         kind = COMPRESSION_NAMES.get(comp)
         raise InvalidOptionError("Compression", comp, ("compressed samples are not read" if kind is None else
                                                        f"{kind} compressed samples are not read") + ": only uncompressed DNGs")
@@ -340,12 +363,26 @@ def read(path):
             raise InvalidOptionError("RowsPerStrip", sh, "a strip has at least one row")
         off_tag, cnt_tag = 273, 279
     offs = np.array(t.values(rawifd[off_tag]), np.int64)
-    layout = RawLayout(bits, t.e == ">", ih, iw, tiled, sh, sw, np.zeros(0, np.uint32))
+    layout = RawLayout(bits, t.e == ">", ih, iw, tiled, sh, sw, np.zeros(0, np.uint32), compression=comp)
     nseg = layout.grid[0] * layout.grid[1]
     if len(offs) != nseg:
         raise InvalidOptionError(TAG_NAMES[off_tag], len(offs), f"{nseg} segments are expected for a {ih} x {iw} image")
+    if comp == 7:
+        if cnt_tag not in rawifd:
+            raise InvalidOptionError("Compression", 7, f"lossless JPEG: {TAG_NAMES[cnt_tag]} is missing: the length of a compressed "
+                                                       "segment is only known from it")
+        cnts = np.array(t.values(rawifd[cnt_tag]), np.int64)
+        if len(cnts) != nseg:
+            raise InvalidOptionError("Compression", 7, f"lossless JPEG: {TAG_NAMES[cnt_tag]} has {len(cnts)} entries for {nseg} segments")
+        layout.counts = cnts
     need = np.array([layout.segment_bytes(k) for k in range(nseg)], np.int64)
-    if cnt_tag in rawifd:
+    if comp == 7:
+        bad = np.flatnonzero((need < 1) | ((offs + need) > len(data)))
+        if len(bad):
+            k = int(bad[0])
+            raise InvalidOptionError("Compression", 7, f"lossless JPEG: segment {k} ({TAG_NAMES[off_tag]}[{k}] = {offs[k]}, {need[k]} bytes) ends "
+                                                       f"outside the {len(data)}-byte file")
+    elif cnt_tag in rawifd:
         cnts = np.array(t.values(rawifd[cnt_tag]), np.int64)
         if len(cnts) != nseg or (cnts < need).any():
             k = 0 if len(cnts) != nseg else int(np.flatnonzero(cnts < need)[0])
@@ -360,6 +397,10 @@ def read(path):
         raise InvalidOptionError(TAG_NAMES[off_tag], hi - lo, "the segments span 2^32 bytes or more")
     layout.offsets = (offs - lo).astype(np.uint32)
     span = data[lo:hi]
+    if comp == 7:
+        layout.segments = np.zeros(nseg, _lib.LJPEG_SEG_DTYPE)
+        for k in range(nseg):
+            _ljpeg_segment(layout.segments[k:k + 1], k, span, int(layout.offsets[k]), int(need[k]), bits, layout.segment_rows(k), sw)
 
     # crop
     if 50829 in rawifd:
@@ -451,6 +492,104 @@ def _warp_rectilinear(body, h, w, path):
     return Lens.from_warp_rectilinear(planes[0] if n == 1 else planes, centre=(cx * (w - 1), cy * (h - 1)))
 
 
+# ---------------------------------------------------------------- lossless JPEG: the headers of one segment
+SOF_NAMES = {0xC0: "SOF0 baseline DCT", 0xC1: "SOF1 extended sequential DCT", 0xC2: "SOF2 progressive DCT", 0xC5: "SOF5 differential DCT",
+             0xC6: "SOF6 differential progressive DCT", 0xC7: "SOF7 differential lossless", 0xC9: "SOF9 arithmetic DCT",
+             0xCA: "SOF10 arithmetic progressive DCT", 0xCB: "SOF11 arithmetic lossless", 0xCD: "SOF13 differential arithmetic DCT",
+             0xCE: "SOF14 differential arithmetic progressive DCT", 0xCF: "SOF15 differential arithmetic lossless"}
+LJPEG_HEADER_MAX = 65536           # (markers are looked for this far into a segment: headers are a few hundred bytes)
+
+
+def _ljpeg_segment(rec, k, span, off, count, bits, rows, seg_w):
+    """Fill the descriptor `rec` (a one-element LJPEG_SEG_DTYPE view) of segment k, the `count` bytes of `span` from `off`,
+    from the stream's markers: SOI, DHT / DRI / anything with a length, SOF3, SOS.  Only the markers are read out of the
+    mapping, four bytes and then the marker's own length at a time: the sample data is not touched.  The entropy-coded data
+    is everything behind the SOS header up to the segment's end: the decoder stops at the first marker inside it."""
+    def refuse(what):
+        raise InvalidOptionError("Compression", 7, f"lossless JPEG: segment {k}: {what}")
+
+    def take(a, n):     # n bytes from byte a of the segment, fewer at its end
+        return bytes(span[off + a:off + min(a + n, count)])
+    if take(0, 2) != b"\xff\xd8":
+        refuse("it does not start with SOI (FF D8): found " + (take(0, 2).hex(" ").upper() or "nothing"))
+    at, dht, frame = 2, {}, None
+    while True:
+        h4 = take(at, 4)
+        if len(h4) < 4 or at > LJPEG_HEADER_MAX:
+            refuse(f"the headers end at byte {at} without a scan (SOS)")
+        if h4[0] != 0xFF:
+            refuse(f"byte {h4[0]:#04x} at {at} where a marker is expected")
+        m = h4[1]
+        if m == 0xFF:           # fill
+            at += 1
+            continue
+        n = h4[2] << 8 | h4[3]
+        body = take(at + 4, n - 2) if n >= 2 else b""
+        if n < 2 or len(body) != n - 2:
+            refuse(f"marker FF {m:02X} at {at} with length {n} runs past the segment")
+        if m == 0xC4:
+            i = 0
+            while i < len(body):
+                counts = list(body[i + 1:i + 17])
+                values = list(body[i + 17:i + 17 + sum(counts)])
+                if len(counts) != 16 or len(values) != sum(counts):
+                    refuse(f"a DHT at {at} is cut short")
+                code = 0
+                for length, c in enumerate(counts, 1):
+                    code += c
+                    if code > 1 << length:
+                        refuse(f"the DHT of table {body[i] & 15} overflows the code space at length {length}")
+                    code <<= 1
+                if not 1 <= len(values) <= 17:
+                    refuse(f"the DHT of table {body[i] & 15} holds {len(values)} values (1 to 17 are expected)")
+                if max(values) > 16:
+                    refuse(f"the DHT of table {body[i] & 15} holds the category {max(values)} (at most 16)")
+                if body[i] >> 4 == 0:
+                    dht[body[i] & 15] = (counts, values)
+                i += 17 + len(values)
+        elif m == 0xC3:
+            if len(body) < 6 or len(body) < 6 + 3 * body[5]:
+                refuse("SOF3 is cut short")
+            frame = (body[0], body[1] << 8 | body[2], body[3] << 8 | body[4], body[5], [body[6 + 3 * i] for i in range(body[5])])
+        elif m in SOF_NAMES:
+            refuse(f"the frame is {SOF_NAMES[m]}, not SOF3 lossless")
+        elif m == 0xDD:
+            if len(body) >= 2 and (body[0] << 8 | body[1]) != 0:
+                refuse(f"DRI with a restart interval of {body[0] << 8 | body[1]} (restart intervals are not read)")
+        elif m == 0xDA:
+            break
+        at += 2 + n
+    if frame is None:
+        refuse("SOS without a frame (SOF3) in front of it")
+    prec, lines, x, nf, ids = frame
+    if nf not in (1, 2):
+        refuse(f"Nf = {nf} components (1 or 2 are read)")
+    if x * nf != seg_w or lines != rows:
+        refuse(f"a frame of {lines} lines of {x} x {nf} samples does not match its segment of {rows} x {seg_w}")
+    if not 2 <= prec <= bits:
+        refuse(f"P = {prec} with BitsPerSample = {bits} (2 <= P <= BitsPerSample)")
+    if len(body) < 1 or body[0] != nf or len(body) < 4 + 2 * nf:
+        refuse(f"a scan of Ns = {body[0] if body else None} components for Nf = {nf} (one scan with Ns == Nf is read)")
+    sel = {body[1 + 2 * i]: body[2 + 2 * i] >> 4 for i in range(nf)}
+    pred, al = body[1 + 2 * nf], body[3 + 2 * nf] & 15
+    if al != 0:
+        refuse(f"Al = {al} (point transforms are not read)")
+    if not 1 <= pred <= 7:
+        refuse(f"predictor Ss = {pred} (1 to 7)")
+    if pred != 1 and seg_w > _lib.LJPEG_MAX_LINE:
+        refuse(f"predictor Ss = {pred} on a segment of {seg_w} columns (predictors 2 to 7 are read up to {_lib.LJPEG_MAX_LINE})")
+    r = rec[0]
+    for c, cid in enumerate(ids):
+        if cid not in sel or sel[cid] not in dht:
+            refuse(f"component {cid} selects table {sel.get(cid)}, which no DHT defines")
+        counts, values = dht[sel[cid]]
+        r["counts"][c, :] = counts
+        r["values"][c, :len(values)] = values
+    scan = at + 2 + n
+    r["scan_off"], r["scan_bytes"] = off + scan, count - scan
+    r["x"], r["y"], r["ncomp"], r["predictor"], r["precision"] = x, lines, nf, pred, prec
+
+
 # ---------------------------------------------------------------- the device side
 def host_span(frame):
     """the frame's span as memory a plain (pageable) upload may read: a read-only file mapping is copied once on the host --
@@ -466,42 +605,74 @@ def _check_frame(frame):
 
 
 def unpack(frame, device=0):
-    """The cropped H x W mosaic of a DngFrame as a NumPy array of its dtype: span up, raw_unpack, mosaic down."""
+    """The cropped H x W mosaic of a DngFrame as a NumPy array of its dtype: span up, raw_unpack or raw_ljpeg, mosaic down.
+    A lossless-JPEG frame one of whose streams did not decode raises ImageLoadError."""
     lay = _check_frame(frame).layout
     _lib.require_device()
     out = np.empty((lay.height, lay.width), lay.dtype)
     L = lay.struct()
     span = host_span(frame)
+    if lay.compression == 7:
+        status = np.zeros(len(lay.segments), np.uint32)
+        _lib.check(_lib.load().mi_raw_ljpeg(device, span.ctypes.data, span.nbytes, lay.segments.ctypes.data, _lib.C.byref(L),
+                                            None if lay.table is None else lay.table.ctypes.data, out.ctypes.data, status.ctypes.data))
+        check_ljpeg_status(frame.path, status)
+        return out
     _lib.check(_lib.load().mi_raw_unpack(device, span.ctypes.data, span.nbytes, lay.offsets.ctypes.data, _lib.C.byref(L),
                                          None if lay.table is None else lay.table.ctypes.data, out.ctypes.data))
     return out
 
 
-def unpack_device(layout, dev_span, span_bytes, dev_offsets, dev_table, dev_out, device=0, stream=None):
+def check_ljpeg_status(path, status):
+    """ImageLoadError naming the first flagged segment of `status` (one word per segment, or one word for a whole stack)"""
+    status = np.atleast_1d(np.asarray(status))
+    bad = np.flatnonzero(status)
+    if len(bad):
+        k = int(bad[0])
+        where = f"segment {k}" if len(status) > 1 or k else "a segment"
+        raise ImageLoadError(path, f"lossless JPEG: {where} did not decode (status {int(status[k])}: {_lib.ljpeg_flag_text(int(status[k]))})")
+
+
+def unpack_device(layout, dev_span, span_bytes, dev_offsets, dev_table, dev_out, device=0, stream=None, dev_status=None):
     """raw_unpack on buffers resident in HBM: the span (`span_bytes` of it, 4-byte aligned), the uint32 segment offsets, the
-    uint16 table (or None) -> `dev_out`, layout.height x layout.width samples.  Queued on `stream`, not waited for."""
+    uint16 table (or None) -> `dev_out`, layout.height x layout.width samples.  Queued on `stream`, not waited for.  A
+    lossless-JPEG layout: `dev_offsets` holds its descriptors (layout.segments, 16-byte aligned) and raw_ljpeg runs, which
+    leaves one status word per segment at `dev_status` (or None)."""
     _lib.require_device()
     L = layout.struct()
+    if layout.compression == 7:
+        _lib.check(_lib.load().mi_raw_ljpeg_device(device, stream, dev_span, int(span_bytes), dev_offsets, _lib.C.byref(L), dev_table, dev_out,
+                                                   dev_status))
+        return
     _lib.check(_lib.load().mi_raw_unpack_device(device, stream, dev_span, int(span_bytes), dev_offsets, _lib.C.byref(L), dev_table, dev_out))
 
 
 class _Staged:
-    """a frame's span, offsets and table in one device buffer"""
+    """a frame's span, offsets (or lossless-JPEG descriptors and status words) and table in one device buffer"""
 
     def __init__(self, frame, device):
         lay = frame.layout
+        segs = lay.segments if lay.compression == 7 else lay.offsets
+        self.path, self.nseg = frame.path, len(segs)
         self.seg_at = (frame.span.nbytes + 255) & ~255
-        self.table_at = self.seg_at + ((lay.offsets.nbytes + 255) & ~255)
+        self.status_at = self.seg_at + ((segs.nbytes + 255) & ~255)
+        self.table_at = self.status_at + (((4 * self.nseg + 255) & ~255) if lay.compression == 7 else 0)
         self.buf = _lib.DeviceBuffer(self.table_at + (0 if lay.table is None else lay.table.nbytes), device)
         self.buf.upload(host_span(frame))
-        self.buf.upload(lay.offsets, self.seg_at)
+        self.buf.upload(segs, self.seg_at)
+        self.status = self.buf.ptr + self.status_at if lay.compression == 7 else None
         if lay.table is not None:
             self.buf.upload(lay.table, self.table_at)
         self.span_bytes = frame.span.nbytes
         self.table = None if lay.table is None else self.buf.ptr + self.table_at
 
     def unpack_into(self, layout, dev_out, device, stream=None):
-        unpack_device(layout, self.buf.ptr, self.span_bytes, self.buf.ptr + self.seg_at, self.table, dev_out, device, stream)
+        unpack_device(layout, self.buf.ptr, self.span_bytes, self.buf.ptr + self.seg_at, self.table, dev_out, device, stream, self.status)
+
+    def check_status(self):
+        """after a wait for the kernel: ImageLoadError when a lossless-JPEG segment did not decode"""
+        if self.status is not None:
+            check_ljpeg_status(self.path, self.buf.download((self.nseg,), np.uint32, self.status_at))
 
 
 def _resolve(frame, develop, lens):
@@ -559,6 +730,7 @@ def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None,
                                calibration=calibration, lens=ln, lens_scratch=scratch)
                 # the stage and the staged span are reused / freed: the null stream's kernels must be through first
                 _lib.check(_lib.load().mi_device_synchronize(device))
+                up.check_status()
             finally:
                 up.buf.free()
     finally:

@@ -1259,6 +1259,9 @@ def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constan
             st.finish_device(results.ptr + k * fb)
         for st in stage1:
             st.sync()
+            if packed and st.ljpeg_status():
+                from .errors import ImageLoadError
+                raise ImageLoadError("stage 1", "lossless JPEG: a segment of a pushed frame did not decode")
     except BaseException:
         for st in stage1:
             try:                # the cleanup must not mask the exception that brought us here

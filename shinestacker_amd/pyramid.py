@@ -343,6 +343,11 @@ class PyramidStack(BaseStackAlgo):
             self.print_message(f": processing file {img_path.split('/')[-1]}")
             self._step(i + n)
         self.print_message(': pyramids fusion completed')
+        if self.raw is not None:
+            flags = stack.ljpeg_status()    # (0 at once on a stack that took no lossless-JPEG frame)
+            if flags:
+                from .dng import check_ljpeg_status
+                check_ljpeg_status(f"{filenames[0]} .. {filenames[-1]}", [flags])
         return stack.finish()
 
     def _push_raw(self, stack, frame):
@@ -367,6 +372,7 @@ class PyramidStack(BaseStackAlgo):
             debayer_device(mosaic.ptr, bgr.ptr, h, w, frame.dtype, frame.cfa, device=self.device, develop=dev,
                            calibration=raw.calibration, lens=ln, lens_scratch=scratch)
             _lib.check(_lib.load().mi_device_synchronize(self.device))   # the null stream's kernels, ahead of the handle's
+            up.check_status()
             stack.push_frames_device(bgr.ptr, 1)
             stack.sync()                                                 # ... and the handle's, ahead of the buffers' release
         finally:

@@ -35,6 +35,9 @@ def two_stage(args):
     "mosaic".
     `--packed BITS` (with `--mosaic`): stage 1 from packed spans of the same frames (`mi_stack_push_packed`: BITS / 16 of the
     mosaic's bytes over the link, unpacked on the device), in turns with the mosaic run on the same samples.
+    `--ljpeg` (with `--mosaic --packed BITS`): stage 1 a further time from the same samples as lossless-JPEG spans
+    (`mi_stack_push_ljpeg`: 256 x 256 tiles, two components, predictor 1, written by tools/ljpeg_encode.py; decoded on the device
+    by raw_ljpeg), in turns with the packed and the mosaic runs; the handles' decode status is asserted to be 0.
     `--calibrate` (with `--mosaic`): stage 1 from the mosaics with a `Calibration` (a master dark and a master flat; the gain
     table is built on the device before the clock starts) and without, three runs of each in turns, so that the two are
     compared inside one process and the spread from run to run shows; every time is listed under "mosaic"."""
@@ -181,9 +184,21 @@ def two_stage(args):
             rps = 64
             offsets = np.arange(-(-H // rps), dtype=np.uint32) * np.uint32(rps * rowb)
             lay = dng.RawLayout(bits, False, H, W, False, rps, W, offsets, shift=16 - bits)
-            pk, same = [], []
+            pk, same, lj = [], [], []
+            if args.ljpeg:
+                sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+                import ljpeg_encode
             for m in mos:
                 v = (np.asarray(m) >> (16 - bits)).astype(np.uint16)
+                if args.ljpeg:
+                    cspan, segs = ljpeg_encode.encode_frame(v, bits, 256, 256, True)
+                    if not args.pageable:
+                        pin = L.host_alloc(cspan.shape, np.uint8)
+                        pin[...] = cspan
+                        cspan = pin
+                    clay = dng.RawLayout(bits, False, H, W, True, 256, 256, np.zeros(len(segs), np.uint32), shift=16 - bits, compression=7,
+                                         segments=segs)
+                    lj.append(dng.DngFrame("<memory>", clay, cspan, cfa, None, None, 1, ()))
                 if bits == 16:
                     span = v.view(np.uint8).reshape(-1)
                 elif bits == 12 and W % 2 == 0:      # two samples are three bytes
@@ -224,6 +239,26 @@ def two_stage(args):
                 without.append(run_same())
             for s_ in stacks:
                 s_.sync()
+            if args.ljpeg:
+                def run_ljpeg():
+                    info = {}
+                    bunches_then_stack(lambda i: lj[i % ndist], N, H, W, np.uint16, out_dev=out.ptr, stacks=stacks, results_buf=results,
+                                       info=info, zero_copy=not args.pageable, packed=True)
+                    return info["stage1_s"]
+                run_ljpeg()
+                with_l, with_p2, without2 = [], [], []
+                for _ in range(3):
+                    with_l.append(run_ljpeg())
+                    with_p2.append(run_packed())
+                    without2.append(run_same())
+                for s_ in stacks:
+                    s_.sync()
+                    assert s_.ljpeg_status() == 0
+                developed.update({"ljpeg_stage1_seconds": with_l, "packed_stage1_seconds_in_turns": with_p2,
+                                  "mosaic_stage1_seconds_in_turns_with_ljpeg": without2,
+                                  "ljpeg_over_packed_stage1": float(np.median(with_l) / np.median(with_p2)),
+                                  "ljpeg_host_to_device_bytes": pushed * int(np.mean([f.span.nbytes for f in lj])),
+                                  "ljpeg_bytes_over_mosaic_bytes": float(np.mean([f.span.nbytes for f in lj]) / (H * W * 2))})
             developed.update({"packed_bits": bits, "packed_stage1_seconds": with_p, "mosaic_stage1_seconds_in_turns": without,
                               "packed_over_mosaic_stage1": float(np.median(with_p) / np.median(without)),
                               "packed_host_to_device_bytes": pushed * int(pk[0].span.nbytes),
@@ -268,6 +303,8 @@ def main():
     ap.add_argument("--packed", type=int, default=0, choices=(0, 10, 12, 14, 16),
                     help="with --two-stage --mosaic: stage 1 from packed spans of that many bits (the file's bytes, unpacked on the "
                          "device), in turns with the mosaic run on the same samples")
+    ap.add_argument("--ljpeg", action="store_true",
+                    help="with --two-stage --mosaic --packed BITS: stage 1 from lossless-JPEG spans of the same samples as well")
     ap.add_argument("--pageable", action="store_true", help="host frames in ordinary (pageable) memory: the bounce-copy path")
     args = ap.parse_args()
     if args.two_stage:
