@@ -951,6 +951,74 @@ MI_API int mi_stack_push_ljpeg(mi_stack_t* s, const void* host_span, size_t span
                                int pinned);
 MI_API int mi_stack_ljpeg_status(mi_stack_t* s, uint32_t* flags);
 
+/* ---- site corrections: the per-site corrections a raw file carries for its own samples (kernels_sitecorr.hpp) ----
+ * DNG's BlackLevelDeltaH/V, GainMap, FixBadPixelsList and FixBadPixelsConstant, resolved on the host into integer tables.
+ * Integer and exact, in place on height x width mosaics of MI_U8 / MI_U16 (height, width >= 2, height * width < 2^31), maxv the
+ * dtype's maximum, pos = 2 (y & 1) + (x & 1); nothing depends on the colour pattern.  tests/sitecorr_restatement.py states it
+ * in NumPy.  The steps run in this order, each under its flag, ahead of calibration and of step 0:
+ *   bad list   MI_SITE_BAD_LIST: step 0's rule (mi_mosaic_defects_device) on `bad_sites`: linear indices, strictly ascending.
+ *   bad const  MI_SITE_BAD_CONST: every site of the positions in `bad_phase_mask` (bit pos) whose value equals `bad_constant`
+ *              becomes (S + (k >> 1)) / k over its valid neighbours (y -+ 2, x), (y, x -+ 2): inside the image and not
+ *              themselves such a site, judged on the mosaic as it is when the step begins; k = 0 leaves the site.
+ *   correct    b = cfa.black[pos] + delta_h[x] + delta_v[y] (each table under its flag, else 0), 0 <= b <= maxv for every site;
+ *              e = max(v - b, 0).  Gain g in Q12: 4096 for a position whose gain[pos].nodes is null or without MI_SITE_GAIN,
+ *              else with the row's axis entry (i, a) = row_axis[y], the column's (j, b) = col_axis[x], i1 = min(i + 1, mv - 1),
+ *              j1 = min(j + 1, mh - 1) over the position's mv x mh nodes n:
+ *                g = ((256 - a) * ((256 - b) * n[i][j] + b * n[i][j1]) + a * ((256 - b) * n[i1][j] + b * n[i1][j1]) + 32768) >> 16
+ *              e' = (e * g + 2048) >> 12;  out = min(maxv, e' + cfa.black[pos]).  The pedestal is put back, as calibration
+ *              does: the result is an ordinary mosaic for everything behind it.
+ * Of `cfa` only black[] is read, and all of it is checked.  A position's axis tables have height and width entries; only the
+ * entries of the position's own rows and columns are read.  Positions may share tables. */
+enum { MI_SITE_DELTA_H = 1, MI_SITE_DELTA_V = 2, MI_SITE_GAIN = 4, MI_SITE_BAD_LIST = 8, MI_SITE_BAD_CONST = 16 };
+typedef struct mi_site_axis {
+    uint16_t node;              /* the first of the two nodes a row or column lies between, < mv or mh         */
+    uint16_t weight;            /* of the second node, 0 .. 256                                                */
+} mi_site_axis_t;
+typedef struct mi_site_gain {
+    const uint16_t* nodes;              /* mv x mh Q12 gains, row-major; NULL: the position has no map         */
+    const mi_site_axis_t* row_axis;     /* height entries                                                      */
+    const mi_site_axis_t* col_axis;     /* width entries                                                       */
+    int32_t mv;                         /* node rows, 1 .. 4096                                                */
+    int32_t mh;                         /* node columns, 1 .. 4096                                             */
+} mi_site_gain_t;
+typedef struct mi_site_correct {
+    int32_t flags;                      /* MI_SITE_* or-ed; 0: nothing is done                                 */
+    const int16_t* delta_h;             /* width entries, read under MI_SITE_DELTA_H                           */
+    const int16_t* delta_v;             /* height entries, read under MI_SITE_DELTA_V                          */
+    mi_site_gain_t gain[4];             /* per position, read under MI_SITE_GAIN (at least one with nodes)     */
+    const int32_t* bad_sites;           /* n_bad sites, read under MI_SITE_BAD_LIST                            */
+    int32_t n_bad;
+    int32_t bad_constant;               /* 0 .. maxv, read under MI_SITE_BAD_CONST                             */
+    int32_t bad_phase_mask;             /* 1 .. 15                                                             */
+    void* dev_scratch;                  /* device form, under MI_SITE_BAD_CONST: 8 * ceil(height * width / 64)  */
+                                        /* bytes of device memory, the bit plane between the step's two passes */
+} mi_site_correct_t;
+/* MI_ERR_INVALID names the argument; every check comes before the first device call: null pointers, height or width < 2,
+ * another dtype, height * width >= 2^31, unknown flags, a flag without its table, mv or mh outside [1, 4096], n_bad < 0, a
+ * constant outside [0, maxv], a mask outside [1, 15], MI_SITE_BAD_CONST without dev_scratch (device forms; the host form and a
+ * handle's stage bring their own and ignore the member).  Where the tables lie in host memory (mi_mosaic_site_correct,
+ * mi_stack_set_site_correction) also: a weight above 256, a node index outside its grid, b outside [0, maxv], a bad-site list
+ * that is not strictly ascending or lies outside the image.  The device form takes those as its precondition (the kernel reads
+ * no node outside a grid whatever an entry holds).
+ * mi_mosaic_site_correct_device: every pointer of `sc` is device memory; enqueues on `stream`, does not wait; flags == 0
+ * enqueues nothing and touches no device.  mi_mosaic_site_correct: every pointer of `sc` is host memory; uploads, runs,
+ * downloads and waits; host_out may equal host_mosaic.  mi_mosaic_defects_const_device: the bad-const step alone, `dev_scratch`
+ * as in the struct; enqueued, not waited for.  The scratch must stay valid until the kernels have run, and two streams must
+ * not share one. */
+MI_API int mi_mosaic_site_correct_device(int device, void* stream, void* dev_mosaic, int height, int width, int dtype,
+                                         const mi_cfa_t* cfa, const mi_site_correct_t* sc);
+MI_API int mi_mosaic_site_correct(int device, const void* host_mosaic, void* host_out, int height, int width, int dtype,
+                                  const mi_cfa_t* cfa, const mi_site_correct_t* sc);
+MI_API int mi_mosaic_defects_const_device(int device, void* stream, void* dev_mosaic, int height, int width, int dtype,
+                                          int constant, int phase_mask, void* dev_scratch);
+/* The site corrections of a handle's mosaic stage: `sc` (host memory, or NULL to clear) is checked against the handle's
+ * height, width and in_dtype and copied by the call, tables included.  From then on every mi_stack_push_mosaic*,
+ * mi_stack_push_packed and mi_stack_push_ljpeg uploads the tables into the stage's slot beside the mosaic (or the span, its
+ * offsets and its linearisation table), and the steps above run on the handle's stream behind the upload or the unpack and
+ * ahead of calibration, step 0 and the demosaic, with the push's own cfa.black.  It holds until it is replaced or cleared;
+ * frames pushed before the call are not touched.  Float-64 and MI_IMPL_SIMPLE handles take the synchronous route. */
+MI_API int mi_stack_set_site_correction(mi_stack_t* s, const mi_site_correct_t* sc);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

@@ -75,6 +75,22 @@ class CalibStruct(C.Structure):
     _fields_ = [("flags", C.c_int32), ("dev_dark", C.c_void_p), ("dev_gain", C.c_void_p)]
 
 
+MI_SITE_DELTA_H, MI_SITE_DELTA_V, MI_SITE_GAIN, MI_SITE_BAD_LIST, MI_SITE_BAD_CONST = 1, 2, 4, 8, 16
+SITE_AXIS_DTYPE = np.dtype([("node", "<u2"), ("weight", "<u2")])     # mi_site_axis_t as a NumPy record
+
+
+class SiteGainStruct(C.Structure):
+    """mi_site_gain_t: one position's gain map as the site-correction kernel sees it"""
+    _fields_ = [("nodes", C.c_void_p), ("row_axis", C.c_void_p), ("col_axis", C.c_void_p), ("mv", C.c_int32), ("mh", C.c_int32)]
+
+
+class SiteCorrectStruct(C.Structure):
+    """mi_site_correct_t: what the site-correction kernels see of a dng.SiteCorrections (its quantised tables)"""
+    _fields_ = [("flags", C.c_int32), ("delta_h", C.c_void_p), ("delta_v", C.c_void_p), ("gain", SiteGainStruct * 4),
+                ("bad_sites", C.c_void_p), ("n_bad", C.c_int32), ("bad_constant", C.c_int32), ("bad_phase_mask", C.c_int32),
+                ("dev_scratch", C.c_void_p)]
+
+
 class LensStruct(C.Structure):
     """mi_lens_t: what the lens remap sees of a lens.Lens (k[4 * c + i], c = B, G, R; the centre in pixels)"""
     _fields_ = [("k", C.c_double * 12), ("cx", C.c_double), ("cy", C.c_double)]
@@ -306,6 +322,13 @@ SIGNATURES = {
                                       C.c_void_p]),
     "mi_stack_push_mosaic_calibrated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CfaStruct), C.POINTER(CalibStruct),
                                                   C.POINTER(DevelopStruct), C.c_void_p, C.c_int, C.c_int]),
+    "mi_mosaic_site_correct_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct),
+                                                C.POINTER(SiteCorrectStruct)]),
+    "mi_mosaic_site_correct": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct),
+                                         C.POINTER(SiteCorrectStruct)]),
+    "mi_mosaic_defects_const_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p]),
+    "mi_stack_set_site_correction": (C.c_int, [C.c_void_p, C.POINTER(SiteCorrectStruct)]),
     "mi_lens_remap_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(LensStruct)]),
     "mi_lens_remap": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(LensStruct)]),
@@ -641,7 +664,38 @@ class Stack:
                 check(rc)
         check(load().mi_stack_push_frame(self._h, a.ctypes.data, 0))
 
-    def push_mosaic(self, mosaic, cfa, zero_copy=False, develop=None, calibration=None):
+    def set_site_correction(self, corrections):
+        """The site corrections (a dng.SiteCorrections, or None to clear) every later push_mosaic / push_packed of this
+        handle applies behind its upload or unpack and ahead of calibration: the tables are copied by the library and go up
+        with each frame.  It holds until it is replaced or cleared.  A set whose tables equal the current ones is not sent
+        again (the library waits for the stage's uploads before it replaces its copy)."""
+        tables = None
+        if corrections is not None:
+            tables = corrections.quantised((self.height, self.width), self.in_dtype)
+            if tables.flags == 0:
+                tables = None
+        cur = getattr(self, "_site_tables", None)
+        if tables is None:
+            if cur is not None:
+                check(load().mi_stack_set_site_correction(self._h, None))
+            self._site_tables = None
+            return
+        if cur is not None and (cur is tables or cur.same(tables)):
+            return
+        sc = tables.host_struct()
+        check(load().mi_stack_set_site_correction(self._h, C.byref(sc)))
+        self._site_tables = tables
+
+    def _site_for(self, corrections, cfa):
+        """push_mosaic / push_packed(corrections=): None leaves whatever set_site_correction holds; an object is set for this
+        and the following pushes"""
+        if corrections is not None:
+            from .demosaic import _check_site_black
+            from .dng import check_corrections
+            _check_site_black(cfa, check_corrections(corrections).quantised((self.height, self.width), self.in_dtype), self.in_dtype)
+            self.set_site_correction(corrections)
+
+    def push_mosaic(self, mosaic, cfa, zero_copy=False, develop=None, calibration=None, corrections=None):
         """Push one host frame as its raw Bayer mosaic (H x W samples of the handle's input dtype, `cfa`: a demosaic.Cfa): a
         third of push_frame's bytes cross the host link, and the frame is demosaiced on the device behind its upload.  Frames
         are fused in call order, whichever of push_frame / push_mosaic / push_frames_device brought them.  `zero_copy` as in
@@ -649,13 +703,16 @@ class Stack:
         handle keeps the object (the queued kernels read its device tables) until finish, reset, sync or close.  None: the
         plain push, exactly the calls it makes without this argument.  `calibration`: a demosaic.Calibration -- master dark
         and flat field applied in place on the uploaded mosaic, ahead of the defect sites and the demosaic; kept by the
-        handle as a Develop is.  None: today's calls, unchanged."""
+        handle as a Develop is.  None: today's calls, unchanged.  `corrections`: a dng.SiteCorrections -- set on the handle
+        (set_site_correction) for this and the following pushes, ahead of the calibration; None: the handle's current
+        setting, which is nothing unless one was set."""
         a = np.asarray(mosaic)
         if a.shape != (self.height, self.width):
             raise ValueError(f"mosaic shape {a.shape} != {(self.height, self.width)}")
         if a.dtype != self.in_dtype:
             raise ValueError(f"mosaic dtype {a.dtype} != {self.in_dtype}")
         c = cfa.struct(self.in_dtype)
+        self._site_for(corrections, cfa)
         if calibration is not None:
             from .demosaic import check_calibration, check_develop
             cal = check_calibration(calibration).prepared(a.shape, self.in_dtype, cfa, self.device)
@@ -697,19 +754,27 @@ class Stack:
                 check(rc)
         check(push(a.ctypes.data, 0, 0))
 
-    def push_packed(self, frame, zero_copy=False, develop=None, calibration=None):
+    def push_packed(self, frame, zero_copy=False, develop=None, calibration=None, corrections=None):
         """Push one host frame as the packed sample bytes of its raw file (`frame`: a dng.DngFrame whose cropped size and
         dtype are the handle's; uncompressed, or lossless JPEG -- then `ljpeg_status()` tells whether every stream decoded):
         the span crosses the host link as it lies in the file -- 0.75 of a uint16 mosaic's bytes at
         12 bits -- and is unpacked on the device behind its upload, then calibrated, repaired and demosaiced with the frame's
         own Cfa exactly as push_mosaic does.  `develop`, `calibration`: as in push_mosaic (None: that step is not run).
-        `zero_copy`: the frame's span must then lie in pinned memory (a file mapping is not: it takes the copying path)."""
+        `zero_copy`: the frame's span must then lie in pinned memory (a file mapping is not: it takes the copying path).
+        `corrections`: "auto" -- the frame's own site corrections (frame.corrections; cleared on the handle when the frame has
+        none) -- or a dng.SiteCorrections, set on the handle as push_mosaic does; None: the handle's current setting."""
         lay = frame.layout
         if (lay.height, lay.width) != (self.height, self.width):
             raise ValueError(f"mosaic shape {(lay.height, lay.width)} != {(self.height, self.width)}")
         if lay.dtype != self.in_dtype:
             raise ValueError(f"mosaic dtype {lay.dtype} != {self.in_dtype}")
         c = frame.cfa.struct(self.in_dtype)
+        if isinstance(corrections, str):
+            from .dng import resolve_corrections
+            corrections = resolve_corrections(frame, corrections)
+            if corrections is None:
+                self.set_site_correction(None)
+        self._site_for(corrections, frame.cfa)
         L, table = lay.struct(), lay.table
         compressed = getattr(lay, "compression", 1) == 7
         offsets = lay.segments if compressed else lay.offsets     # (descriptors stand where the offsets do)

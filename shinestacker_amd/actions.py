@@ -211,7 +211,7 @@ class FrameDirectory:
             return frame
         stacker = getattr(self, "stack_algo", None)
         return dng.develop(frame, develop=self.raw.develop, lens=self.raw.lens, calibration=self.raw.calibration,
-                           device=getattr(stacker, "device", getattr(self, "device", 0)))
+                           corrections=self.raw.corrections, device=getattr(stacker, "device", getattr(self, "device", 0)))
 
     def set_filelist(self):
         self.filenames = self.folder_filelist()

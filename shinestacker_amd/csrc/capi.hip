@@ -1887,6 +1887,92 @@ int mi_mosaic_calibrate(int device, const void* host_mosaic, void* host_out, int
     return tmp.download(host_out, m, nb);
 }
 
+// ---------------------------------------------------------------- site corrections (kernels_sitecorr.hpp)
+int mi_mosaic_defects_const_device(int device, void* stream, void* dev_mosaic, int height, int width, int dtype, int constant,
+                                   int phase_mask, void* dev_scratch) {
+    if (!dev_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    int rc = calib_shape_check(height, width, dtype);
+    if (rc) return rc;
+    mi_site_correct_t c{};
+    c.flags = MI_SITE_BAD_CONST;
+    c.bad_constant = constant;
+    c.bad_phase_mask = phase_mask;
+    c.dev_scratch = dev_scratch;
+    if ((rc = site_check(&c, dtype, true))) return rc;
+    MI_HIP(hipSetDevice(device));
+    defects_const_launch((hipStream_t)stream, dev_mosaic, height, width, dtype, constant, phase_mask, (unsigned long long*)dev_scratch);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_mosaic_site_correct_device(int device, void* stream, void* dev_mosaic, int height, int width, int dtype, const mi_cfa_t* cfa,
+                                  const mi_site_correct_t* sc) {
+    if (!dev_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    int rc = calib_shape_check(height, width, dtype);
+    if (rc || (rc = cfa_check(cfa, dtype)) || (rc = site_check(sc, dtype, true))) return rc;
+    if (sc->flags == 0) return MI_OK;   // nothing to do, no device call
+    MI_HIP(hipSetDevice(device));
+    site_kernels((hipStream_t)stream, dev_mosaic, height, width, dtype, *cfa, *sc, (unsigned long long*)sc->dev_scratch);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_mosaic_site_correct(int device, const void* host_mosaic, void* host_out, int height, int width, int dtype, const mi_cfa_t* cfa,
+                           const mi_site_correct_t* sc) {
+    if (!host_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    if (!host_out) return fail(MI_ERR_INVALID, "null mosaic output");
+    int rc = calib_shape_check(height, width, dtype);
+    if (rc || (rc = cfa_check(cfa, dtype)) || (rc = site_check(sc, dtype))) return rc;
+    int64_t dmin[4], dmax[4];
+    if ((rc = site_host_check(sc, height, width, dmin, dmax)) || (rc = site_black_check(cfa->black, dmin, dmax, dtype))) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t nb = (size_t)height * width * dtype_size(dtype);
+    DevScratch tmp(nullptr);
+    void* m = nullptr;
+    mi_site_correct_t d = *sc;
+    if ((rc = tmp.upload(&m, host_mosaic, nb))) return rc;
+    const auto up = [&tmp](auto& field, const void* src, size_t bytes) {     // a table up, its device pointer into the descriptor
+        void* q = nullptr;
+        const int r = tmp.upload(&q, src, bytes);
+        field = (std::remove_reference_t<decltype(field)>)q;
+        return r;
+    };
+    if ((sc->flags & MI_SITE_DELTA_H) && (rc = up(d.delta_h, sc->delta_h, (size_t)width * sizeof(int16_t)))) return rc;
+    if ((sc->flags & MI_SITE_DELTA_V) && (rc = up(d.delta_v, sc->delta_v, (size_t)height * sizeof(int16_t)))) return rc;
+    if (sc->flags & MI_SITE_GAIN)
+        for (int p = 0; p < 4; ++p) {
+            const mi_site_gain_t& g = sc->gain[p];
+            if (!g.nodes) continue;
+            if ((rc = up(d.gain[p].nodes, g.nodes, (size_t)g.mv * g.mh * sizeof(uint16_t))) ||
+                (rc = up(d.gain[p].row_axis, g.row_axis, (size_t)height * sizeof(mi_site_axis_t))) ||
+                (rc = up(d.gain[p].col_axis, g.col_axis, (size_t)width * sizeof(mi_site_axis_t))))
+                return rc;
+        }
+    if ((sc->flags & MI_SITE_BAD_LIST) && sc->n_bad > 0 && (rc = up(d.bad_sites, sc->bad_sites, (size_t)sc->n_bad * sizeof(int32_t))))
+        return rc;
+    if ((sc->flags & MI_SITE_BAD_CONST) && (rc = tmp.alloc(&d.dev_scratch, defects_const_scratch_bytes(height, width)))) return rc;
+    if ((rc = mi_mosaic_site_correct_device(device, nullptr, m, height, width, dtype, cfa, &d))) return rc;
+    return tmp.download(host_out, m, nb);
+}
+
+int mi_stack_set_site_correction(mi_stack_t* s, const mi_site_correct_t* sc) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    int64_t dmin[4] = {}, dmax[4] = {};
+    if (sc) {
+        if ((rc = calib_shape_check(s->p.height, s->p.width, s->p.in_dtype)) || (rc = site_check(sc, s->p.in_dtype)) ||
+            (rc = site_host_check(sc, s->p.height, s->p.width, dmin, dmax)))
+            return rc;
+        // (black is the push's own: every level the handle's dtype allows must leave room for the deltas somewhere)
+        const int maxv = s->p.in_dtype == MI_U8 ? 255 : 65535;
+        for (int p = 0; p < 4; ++p)
+            if (dmax[p] - dmin[p] > maxv)
+                return fail(MI_ERR_INVALID, "site correction: delta_h + delta_v spans %lld .. %lld at position %d: no black level keeps it inside [0, %d]",
+                            (long long)dmin[p], (long long)dmax[p], p, maxv);
+    }
+    return mosaic_set_site(s, sc, dmin, dmax);
+}
+
 // ---------------------------------------------------------------- lens correction (kernels_lens.hpp)
 static int lens_check(const void* src, const void* dst, int height, int width, int dtype, const mi_lens_t* lens) {
     if (!src) return fail(MI_ERR_INVALID, "null source frame");

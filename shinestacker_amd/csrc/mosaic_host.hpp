@@ -30,6 +30,11 @@
 //   ljpeg       mi_stack_push_ljpeg: the same route with a lossless-JPEG span (kernels_ljpeg.hpp): the packed slot holds [span |
 //               descriptors | table], raw_ljpeg takes raw_unpack's place and ORs every segment's status flags into `ljstatus`,
 //               one device word of the stage (mi_stack_ljpeg_status reads and clears it).
+//   site corr   mi_stack_set_site_correction: the file's own per-site corrections (kernels_sitecorr.hpp).  The setter copies
+//               every table into one pinned block of the stage, laid out as it will lie on the device; every later push
+//               uploads the block on stc into cslot[slot] ahead of evCopied[slot], and the bad-site kernels and
+//               mosaic_site_correct run on s->stream behind the upload (or the unpack) and ahead of calibration.  The block is
+//               replaced only after a wait for stc; the device slots grow after a wait for both streams.
 //   order       frames are fused in call order: the first mosaic after host BGR frames flushes the ring (mosaic_push), and
 //               every call that takes frames of another kind or reads state flushes this stage first (stack_flush in capi.hip).
 #pragma once
@@ -37,6 +42,7 @@
 #include "kernels_calib.hpp"
 #include "kernels_demosaic.hpp"
 #include "kernels_ljpeg.hpp"
+#include "kernels_sitecorr.hpp"
 #include "kernels_unpack.hpp"
 
 namespace mi {
@@ -68,6 +74,15 @@ struct MosaicStage {
     size_t ppin_cap = 0;
     long ppin_no = 0;
     uint32_t* ljstatus = nullptr;             // lossless-JPEG spans: every frame's status flags ORed (in s->allocs)
+    // site corrections (mi_stack_set_site_correction)
+    bool sc_on = false;
+    mi_site_correct_t sc = {};                // its pointers hold OFFSETS into the block
+    void* sc_host = nullptr;                  // pinned: every table, each part 256-byte aligned
+    size_t sc_bytes = 0, sc_host_cap = 0;
+    void* cslot[NSLOT] = {};                  // the block on the device, one per mosaic slot
+    size_t cslot_cap = 0;
+    unsigned long long* sc_bits = nullptr;    // the constant repair's bit plane (in s->allocs; kernels of one stream share it)
+    int64_t sc_dmin[4] = {}, sc_dmax[4] = {}; // per position, the range of delta_h[x] + delta_v[y]
 };
 
 // what mi_stack_push_packed brings in place of a mosaic (arguments checked by the caller)
@@ -156,6 +171,88 @@ inline int host_sites_check(const int32_t* sites, int n, int height, int width) 
     return MI_OK;
 }
 
+// argument checks of the site-correction entry points (mi_mosaic_site_correct*, mi_stack_set_site_correction): no device call,
+// no table is read
+inline int site_check(const mi_site_correct_t* c, int dtype, bool need_scratch = false) {
+    if (!c) return fail(MI_ERR_INVALID, "null site correction");
+    const int all = MI_SITE_DELTA_H | MI_SITE_DELTA_V | MI_SITE_GAIN | MI_SITE_BAD_LIST | MI_SITE_BAD_CONST;
+    if (c->flags & ~all) return fail(MI_ERR_INVALID, "unknown site correction flags %d", c->flags);
+    if ((c->flags & MI_SITE_DELTA_H) && !c->delta_h) return fail(MI_ERR_INVALID, "site correction: MI_SITE_DELTA_H is set and delta_h is null");
+    if ((c->flags & MI_SITE_DELTA_V) && !c->delta_v) return fail(MI_ERR_INVALID, "site correction: MI_SITE_DELTA_V is set and delta_v is null");
+    if (c->flags & MI_SITE_GAIN) {
+        int maps = 0;
+        for (int p = 0; p < 4; ++p) {
+            const mi_site_gain_t& g = c->gain[p];
+            if (!g.nodes) continue;
+            ++maps;
+            if (!g.row_axis) return fail(MI_ERR_INVALID, "site correction: gain[%d] has nodes and row_axis is null", p);
+            if (!g.col_axis) return fail(MI_ERR_INVALID, "site correction: gain[%d] has nodes and col_axis is null", p);
+            if (g.mv < 1 || g.mv > sitecorr::MAX_NODES) return fail(MI_ERR_INVALID, "site correction: gain[%d].mv must be in [1, %d] (got %d)", p, sitecorr::MAX_NODES, g.mv);
+            if (g.mh < 1 || g.mh > sitecorr::MAX_NODES) return fail(MI_ERR_INVALID, "site correction: gain[%d].mh must be in [1, %d] (got %d)", p, sitecorr::MAX_NODES, g.mh);
+        }
+        if (!maps) return fail(MI_ERR_INVALID, "site correction: MI_SITE_GAIN is set and every gain[].nodes is null");
+    }
+    if (c->flags & MI_SITE_BAD_LIST) {
+        if (c->n_bad < 0) return fail(MI_ERR_INVALID, "site correction: n_bad must be >= 0 (got %d)", c->n_bad);
+        if (c->n_bad > 0 && !c->bad_sites) return fail(MI_ERR_INVALID, "site correction: MI_SITE_BAD_LIST is set and bad_sites is null");
+    }
+    if (c->flags & MI_SITE_BAD_CONST) {
+        const int maxv = dtype == MI_U8 ? 255 : 65535;
+        if (c->bad_constant < 0 || c->bad_constant > maxv) return fail(MI_ERR_INVALID, "site correction: bad_constant must be in [0, %d] (got %d)", maxv, c->bad_constant);
+        if (c->bad_phase_mask < 1 || c->bad_phase_mask > 15) return fail(MI_ERR_INVALID, "site correction: bad_phase_mask must be in [1, 15] (got %d)", c->bad_phase_mask);
+        if (need_scratch && !c->dev_scratch) return fail(MI_ERR_INVALID, "site correction: MI_SITE_BAD_CONST is set and dev_scratch is null");
+    }
+    return MI_OK;
+}
+// tables in host memory: weights, node indices, the bad-site list; dmin / dmax receive, per position, the range of
+// delta_h[x] + delta_v[y] over the position's sites
+inline int site_host_check(const mi_site_correct_t* c, int height, int width, int64_t* dmin, int64_t* dmax) {
+    int64_t hlo[2] = {0, 0}, hhi[2] = {0, 0}, vlo[2] = {0, 0}, vhi[2] = {0, 0};
+    if (c->flags & MI_SITE_DELTA_H)
+        for (int px = 0; px < 2; ++px) {
+            hlo[px] = 32767; hhi[px] = -32768;
+            for (int x = px; x < width; x += 2) { hlo[px] = std::min<int64_t>(hlo[px], c->delta_h[x]); hhi[px] = std::max<int64_t>(hhi[px], c->delta_h[x]); }
+        }
+    if (c->flags & MI_SITE_DELTA_V)
+        for (int py = 0; py < 2; ++py) {
+            vlo[py] = 32767; vhi[py] = -32768;
+            for (int y = py; y < height; y += 2) { vlo[py] = std::min<int64_t>(vlo[py], c->delta_v[y]); vhi[py] = std::max<int64_t>(vhi[py], c->delta_v[y]); }
+        }
+    for (int p = 0; p < 4; ++p) { dmin[p] = hlo[p & 1] + vlo[p >> 1]; dmax[p] = hhi[p & 1] + vhi[p >> 1]; }
+    if (c->flags & MI_SITE_GAIN)
+        for (int p = 0; p < 4; ++p) {
+            const mi_site_gain_t& g = c->gain[p];
+            if (!g.nodes) continue;
+            for (int y = p >> 1; y < height; y += 2) {
+                if (g.row_axis[y].weight > sitecorr::MAX_WEIGHT) return fail(MI_ERR_INVALID, "site correction: gain[%d].row_axis[%d].weight must be <= 256 (got %d)", p, y, g.row_axis[y].weight);
+                if (g.row_axis[y].node >= g.mv) return fail(MI_ERR_INVALID, "site correction: gain[%d].row_axis[%d].node = %d lies outside the %d rows of its grid", p, y, g.row_axis[y].node, g.mv);
+            }
+            for (int x = p & 1; x < width; x += 2) {
+                if (g.col_axis[x].weight > sitecorr::MAX_WEIGHT) return fail(MI_ERR_INVALID, "site correction: gain[%d].col_axis[%d].weight must be <= 256 (got %d)", p, x, g.col_axis[x].weight);
+                if (g.col_axis[x].node >= g.mh) return fail(MI_ERR_INVALID, "site correction: gain[%d].col_axis[%d].node = %d lies outside the %d columns of its grid", p, x, g.col_axis[x].node, g.mh);
+            }
+        }
+    if (c->flags & MI_SITE_BAD_LIST) return host_sites_check(c->bad_sites, c->n_bad, height, width);
+    return MI_OK;
+}
+// b = black[pos] + delta_h[x] + delta_v[y] inside [0, maxv] for every site
+inline int site_black_check(const int32_t* black, const int64_t* dmin, const int64_t* dmax, int dtype) {
+    const int maxv = dtype == MI_U8 ? 255 : 65535;
+    for (int p = 0; p < 4; ++p)
+        if (black[p] + dmin[p] < 0 || black[p] + dmax[p] > maxv)
+            return fail(MI_ERR_INVALID, "site correction: black[%d] + delta_h + delta_v must stay inside [0, %d] (it spans %lld .. %lld)", p, maxv,
+                        (long long)(black[p] + dmin[p]), (long long)(black[p] + dmax[p]));
+    return MI_OK;
+}
+
+// the site-correction kernels of one mosaic, in place (arguments checked by the caller); `bits`: the constant repair's scratch
+inline void site_kernels(hipStream_t st, void* mosaic, int H, int W, int dtype, const mi_cfa_t& cfa, const mi_site_correct_t& c,
+                         unsigned long long* bits) {
+    if (c.flags & MI_SITE_BAD_LIST) defects_launch(st, mosaic, H, W, dtype, c.bad_sites, c.n_bad);
+    if (c.flags & MI_SITE_BAD_CONST) defects_const_launch(st, mosaic, H, W, dtype, c.bad_constant, c.bad_phase_mask, bits);
+    site_correct_launch(st, mosaic, H, W, dtype, cfa, c);
+}
+
 inline int mosaic_create(mi_stack* s) {
     auto* m = new MosaicStage();
     s->mosaic = m;
@@ -204,9 +301,106 @@ inline void mosaic_destroy(mi_stack* s) {
         if (m->evCopied[i]) (void)hipEventDestroy(m->evCopied[i]);
         if (m->evSlotFree[i]) (void)hipEventDestroy(m->evSlotFree[i]);
     }
+    if (m->cslot[0]) (void)hipStreamSynchronize(s->stream);   // (the site kernels read the table slots)
+    for (int i = 0; i < MosaicStage::NSLOT; ++i)
+        if (m->cslot[i]) (void)hipFree(m->cslot[i]);
+    if (m->sc_host) (void)hipHostFree(m->sc_host);
     if (m->stc) (void)hipStreamDestroy(m->stc);
     delete m;   // (the device buffers are in s->allocs)
     s->mosaic = nullptr;
+}
+
+// mi_stack_set_site_correction behind its checks (site_check, site_host_check): copy every table of `c` into the stage's
+// pinned block, or clear.  The stage is created here when no mosaic came before.
+inline int mosaic_set_site(mi_stack* s, const mi_site_correct_t* c, const int64_t* dmin, const int64_t* dmax) {
+    int rc;
+    if (!c && !mstage(s)) return MI_OK;
+    if (!mstage(s) && (rc = mosaic_create(s))) return rc;
+    MosaicStage* m = mstage(s);
+    if (!c || c->flags == 0) {
+        m->sc_on = false;
+        return MI_OK;
+    }
+    const int H = s->p.height, W = s->p.width;
+    const int nslot = s->p.impl == MI_IMPL_TILED ? MosaicStage::NSLOT : 1;
+    // the block's layout: [delta_h | delta_v | per position: nodes, row axis, column axis | bad sites], each part aligned
+    mi_site_correct_t d = *c;
+    size_t at = 0;
+    struct Part { const void* src; size_t off, bytes; };
+    std::vector<Part> parts;
+    const auto place = [&](const void* src, size_t bytes) {
+        parts.push_back(Part{src, at, bytes});
+        const size_t off = at;
+        at += packed_align(bytes ? bytes : 1);
+        return off;
+    };
+    d.delta_h = d.delta_v = nullptr;
+    d.bad_sites = nullptr;
+    if (c->flags & MI_SITE_DELTA_H) d.delta_h = (const int16_t*)place(c->delta_h, (size_t)W * sizeof(int16_t));
+    if (c->flags & MI_SITE_DELTA_V) d.delta_v = (const int16_t*)place(c->delta_v, (size_t)H * sizeof(int16_t));
+    for (int p = 0; p < 4; ++p) {
+        d.gain[p] = mi_site_gain_t{};
+        const mi_site_gain_t& g = c->gain[p];
+        if (!(c->flags & MI_SITE_GAIN) || !g.nodes) continue;
+        d.gain[p].mv = g.mv;
+        d.gain[p].mh = g.mh;
+        d.gain[p].nodes = (const uint16_t*)place(g.nodes, (size_t)g.mv * g.mh * sizeof(uint16_t));
+        d.gain[p].row_axis = (const mi_site_axis_t*)place(g.row_axis, (size_t)H * sizeof(mi_site_axis_t));
+        d.gain[p].col_axis = (const mi_site_axis_t*)place(g.col_axis, (size_t)W * sizeof(mi_site_axis_t));
+    }
+    if ((c->flags & MI_SITE_BAD_LIST) && c->n_bad > 0) d.bad_sites = (const int32_t*)place(c->bad_sites, (size_t)c->n_bad * sizeof(int32_t));
+    const size_t bytes = at ? at : 256;
+    MI_HIP(hipSetDevice(s->p.device));
+    if (m->stc) MI_HIP(hipStreamSynchronize(m->stc));      // no upload reads the block that is rewritten
+    else MI_HIP(hipStreamSynchronize(s->stream));          // (the synchronous route uploads on the handle's stream)
+    if (bytes > m->sc_host_cap) {
+        if (m->sc_host) (void)hipHostFree(m->sc_host);
+        m->sc_host = nullptr;
+        m->sc_host_cap = 0;
+        MI_HIP(hipHostMalloc(&m->sc_host, bytes, hipHostMallocDefault));
+        m->sc_host_cap = bytes;
+    }
+    if (bytes > m->cslot_cap) {
+        MI_HIP(hipStreamSynchronize(s->stream));           // nothing reads what is freed
+        for (int i = 0; i < nslot; ++i) {
+            if (m->cslot[i]) (void)hipFree(m->cslot[i]);
+            m->cslot[i] = nullptr;
+        }
+        m->cslot_cap = 0;
+        for (int i = 0; i < nslot; ++i)
+            if (hipMalloc(&m->cslot[i], bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(MI_ERR_NOMEM, "out of device memory");
+            }
+        m->cslot_cap = bytes;
+    }
+    if ((c->flags & MI_SITE_BAD_CONST) && !m->sc_bits && (rc = dev_alloc(s, (void**)&m->sc_bits, defects_const_scratch_bytes(H, W)))) return rc;
+    memset(m->sc_host, 0, bytes);
+    for (const Part& q : parts) memcpy((char*)m->sc_host + q.off, q.src, q.bytes);
+    m->sc = d;
+    m->sc_bytes = bytes;
+    for (int p = 0; p < 4; ++p) { m->sc_dmin[p] = dmin[p]; m->sc_dmax[p] = dmax[p]; }
+    m->sc_on = true;
+    return MI_OK;
+}
+
+// the stage's descriptor with its offsets turned into pointers into the device block `base`
+inline mi_site_correct_t site_at(const MosaicStage* m, const char* base) {
+    mi_site_correct_t d = m->sc;
+    const auto fix = [&](const auto*& p, bool on) {
+        using P = std::remove_reference_t<decltype(p)>;
+        p = on ? (P)(base + (size_t)(uintptr_t)p) : nullptr;
+    };
+    fix(d.delta_h, (d.flags & MI_SITE_DELTA_H) != 0);
+    fix(d.delta_v, (d.flags & MI_SITE_DELTA_V) != 0);
+    for (int p = 0; p < 4; ++p) {
+        const bool on = d.gain[p].mv > 0;
+        fix(d.gain[p].nodes, on);
+        fix(d.gain[p].row_axis, on);
+        fix(d.gain[p].col_axis, on);
+    }
+    fix(d.bad_sites, (d.flags & MI_SITE_BAD_LIST) != 0 && d.n_bad > 0);
+    return d;
 }
 
 // mi_stack_reset: the stage is empty again and keeps its buffers (the caller has waited for its stream and the handle's)
@@ -294,6 +488,8 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     MosaicStage* m = mstage(s);
     const int H = s->p.height, W = s->p.width;
     const size_t rb = (size_t)W * dtype_size(s->p.in_dtype);
+    const bool sc = m->sc_on;      // site corrections: the stage's tables go up with this frame
+    if (sc && (rc = site_black_check(cfa.black, m->sc_dmin, m->sc_dmax, s->p.in_dtype))) return rc;
     // a packed span's device layout: [span | offsets | table]
     const size_t seg_bytes = pk ? packed_align(packed_seg_bytes(*pk)) : 0;
     const size_t table_bytes = pk ? (size_t)pk->layout->table_len * sizeof(uint16_t) : 0;
@@ -310,6 +506,10 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
         MI_HIP(hipMemcpyAsync(ps + seg_at, packed_seg(*pk), packed_seg_bytes(*pk), hipMemcpyHostToDevice, s->stream));
         if (table_bytes) MI_HIP(hipMemcpyAsync(ps + table_at, pk->table, table_bytes, hipMemcpyHostToDevice, s->stream));
         packed_launch(s->stream, *pk, ps, seg_at, table_at, m->slot[0], m->ljstatus);
+        if (sc) {
+            MI_HIP(hipMemcpyAsync(m->cslot[0], m->sc_host, m->sc_bytes, hipMemcpyHostToDevice, s->stream));
+            site_kernels(s->stream, m->slot[0], H, W, s->p.in_dtype, cfa, site_at(m, (const char*)m->cslot[0]), m->sc_bits);
+        }
         mosaic_kernels(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
         MI_HIP(hipGetLastError());
         rc = dispatch_push(s, s->frame_dev, 1, t->frame_bytes);
@@ -319,6 +519,10 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     if (s->p.impl != MI_IMPL_TILED) {
         // float-64 and MI_IMPL_SIMPLE handles: upload, demosaic, push, wait -- one frame at a time on the handle's stream
         MI_HIP(hipMemcpy2DAsync(m->slot[0], rb, host_mosaic, row_stride_bytes, rb, H, hipMemcpyHostToDevice, s->stream));
+        if (sc) {
+            MI_HIP(hipMemcpyAsync(m->cslot[0], m->sc_host, m->sc_bytes, hipMemcpyHostToDevice, s->stream));
+            site_kernels(s->stream, m->slot[0], H, W, s->p.in_dtype, cfa, site_at(m, (const char*)m->cslot[0]), m->sc_bits);
+        }
         mosaic_kernels(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
         MI_HIP(hipGetLastError());
         if ((rc = dispatch_push(s, s->frame_dev, 1, t->frame_bytes))) return rc;
@@ -330,6 +534,7 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     if (m->slot_no >= MosaicStage::NSLOT) MI_HIP(hipStreamWaitEvent(m->stc, m->evSlotFree[si], 0));
     m->slot_no++;
     char* ps = pk ? (char*)m->pslot[si] : nullptr;
+    if (sc) MI_HIP(hipMemcpyAsync(m->cslot[si], m->sc_host, m->sc_bytes, hipMemcpyHostToDevice, m->stc));   // ahead of evCopied[si]
     if (pk) {
         // offsets and table through the slot's pinned block: its previous upload is through once evCopied[si] is
         MI_HIP(hipEventSynchronize(m->evCopied[si]));   // (no-op on an event never recorded)
@@ -401,6 +606,7 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
     MI_HIP(hipStreamWaitEvent(s->stream, m->evCopied[si], 0));
     void* frame = (char*)m->bgr + (size_t)m->pending * t->frame_bytes;
     if (pk) packed_launch(s->stream, *pk, ps, seg_at, table_at, slot, m->ljstatus);
+    if (sc) site_kernels(s->stream, slot, H, W, s->p.in_dtype, cfa, site_at(m, (const char*)m->cslot[si]), m->sc_bits);
     mosaic_kernels(s->stream, slot, frame, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
     MI_HIP(hipGetLastError());
     MI_HIP(hipEventRecord(m->evSlotFree[si], s->stream));

@@ -553,6 +553,46 @@ def calibrate(mosaic, cfa, calibration, device=0):
     return out
 
 
+def correct_sites_device(dev_mosaic, h, w, dtype, cfa, corrections, device=0, stream=None):
+    """correct_sites() in place on a mosaic resident in HBM.  Queued on `stream`, not waited for; the SiteCorrections' device
+    tables must outlive the queued kernels."""
+    from .dng import check_corrections
+    dt = _dtype(dtype)
+    c = _check_cfa(cfa).struct(dt)
+    _check_site_black(cfa, check_corrections(corrections).quantised((h, w), dt), dt)
+    sc = corrections.prepared((h, w), dt, device)
+    _lib.check(_lib.load().mi_mosaic_site_correct_device(device, stream, dev_mosaic, int(h), int(w), _lib.DTYPE_CODE[dt], _lib.C.byref(c),
+                                                         _lib.C.byref(sc)))
+
+
+def _check_site_black(cfa, q, dt):
+    """black[pos] + black_h[x] + black_v[y] stays inside [0, maxv]: what the kernel is promised"""
+    maxv = int(np.iinfo(dt).max)
+    for pos in range(4):
+        lo = hi = cfa.black[pos]
+        for d, sl in ((q.dh, slice(pos & 1, None, 2)), (q.dv, slice(pos >> 1, None, 2))):
+            if d is not None:
+                lo, hi = lo + int(d[sl].min()), hi + int(d[sl].max())
+        if lo < 0 or hi > maxv:
+            raise InvalidOptionError("corrections", (lo, hi), f"black level plus deltas leaves [0, {maxv}] at position {pos}")
+
+
+def correct_sites(mosaic, cfa, corrections, device=0):
+    """The site corrections of a raw frame (dng.SiteCorrections: bad sites, black deltas, gain maps) applied to an H x W
+    mosaic: a mosaic of the same dtype with the black pedestal in place, an ordinary mosaic for everything downstream."""
+    from .dng import check_corrections
+    a = np.ascontiguousarray(check_mosaic(mosaic))
+    c = _check_cfa(cfa).struct(a.dtype)
+    q = check_corrections(corrections).quantised(a.shape, a.dtype)
+    _check_site_black(cfa, q, a.dtype)
+    _lib.require_device()
+    sc = q.host_struct()
+    out = np.empty_like(a)
+    _lib.check(_lib.load().mi_mosaic_site_correct(device, a.ctypes.data, out.ctypes.data, a.shape[0], a.shape[1], _lib.DTYPE_CODE[a.dtype],
+                                                  _lib.C.byref(c), _lib.C.byref(sc)))
+    return out
+
+
 def defects_device(dev_mosaic, h, w, dtype, develop, device=0, stream=None):
     """Step 0 alone, in place on a mosaic resident in HBM.  Queued on `stream`, not waited for."""
     dt = _dtype(dtype)
@@ -562,14 +602,17 @@ def defects_device(dev_mosaic, h, w, dtype, develop, device=0, stream=None):
 
 
 def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None, develop=None, calibration=None, lens=None,
-                   lens_scratch=None):
+                   lens_scratch=None, corrections=None):
     """debayer() for a mosaic resident in HBM: `dev_mosaic` (h x w) -> `dev_bgr` (h x w x 3).  Queued on `stream`, not waited
     for.  `develop`: a Develop -- its defect sites are repaired IN PLACE in `dev_mosaic` first (no other site is written),
     then colour matrix and tone curve ride on the demosaic; its device tables must outlive the queued kernels.
     `calibration`: a Calibration -- `dev_mosaic` is calibrated IN PLACE ahead of all of that.
     `lens`: a lens.Lens -- the demosaic / develop kernel writes one scratch frame and the lens remap (lens.py) takes it to
     `dev_bgr`.  `lens_scratch`: that frame, a DeviceBuffer of h x w x 3 samples which must outlive the queued kernels; None:
-    one is allocated here, and the call then WAITS for the device before it frees it."""
+    one is allocated here, and the call then WAITS for the device before it frees it.
+    `corrections`: a dng.SiteCorrections -- `dev_mosaic` is corrected IN PLACE ahead of the calibration."""
+    if corrections is not None:
+        correct_sites_device(dev_mosaic, h, w, dtype, cfa, corrections, device=device, stream=stream)
     if lens is not None:
         from .lens import check_lens, correct_device
         lens = check_lens(lens)
@@ -611,10 +654,13 @@ def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None,
                                      _lib.C.byref(d)))
 
 
-def debayer(mosaic, cfa, develop=None, device=0, calibration=None, lens=None):
+def debayer(mosaic, cfa, develop=None, device=0, calibration=None, lens=None, corrections=None):
     """H x W uint8 / uint16 mosaic -> H x W x 3 BGR array of the same dtype.  `develop`: a Develop (defect sites, colour
     matrix, tone curve); None: the plain demosaic.  `calibration`: a Calibration applied to the mosaic first.  `lens`: a
-    lens.Lens -- the lens correction behind all of it, on the device: equal to lens.correct(debayer(...), lens)."""
+    lens.Lens -- the lens correction behind all of it, on the device: equal to lens.correct(debayer(...), lens).
+    `corrections`: a dng.SiteCorrections applied ahead of the calibration: equal to debayer(correct_sites(...), ...)."""
+    if corrections is not None:
+        mosaic = correct_sites(mosaic, cfa, corrections, device=device)
     a = np.ascontiguousarray(check_mosaic(mosaic))
     c = _check_cfa(cfa).struct(a.dtype)
     if lens is not None:

@@ -25,8 +25,21 @@ segment outside the above (each as InvalidOptionError("Compression", 7, "lossles
 per pixel, a CFA repeat other than 2 x 2, a CFALayout other than 1, bit depths other than 8, 10,
 12, 14 and 16, truncated segments, and a TIFF without a CFA IFD.
 
-The tag numbers and the opcode layout are written from memory of the DNG specification: this reader is UNPINNED against a
-real DNG -- it has met only the files its own tests write (tests/dng_cases.py, written from the format description).
+The tag numbers and the opcode layouts (WarpRectilinear, GainMap, FixBadPixelsConstant, FixBadPixelsList) are written from
+memory of the DNG specification: this reader is UNPINNED against a real DNG -- it has met only the files its own tests write
+(tests/dng_cases.py, written from the format description).  The one formula that places a pixel in an opcode's relative
+coordinates is `relative`.
+
+Site corrections (`SiteCorrections`, `DngFrame.corrections`; csrc/kernels_sitecorr.hpp, tests/sitecorr_restatement.py is the
+definition): the per-site corrections the file carries for its own samples -- BlackLevelDeltaH/V and, from OpcodeList2, GainMap,
+FixBadPixelsList and FixBadPixelsConstant -- applied to the unpacked mosaic on the device, integer and exact, in this order:
+
+    raw_unpack / raw_ljpeg -> file bad sites (list, constant) -> file black deltas + gain maps -> Calibration -> step 0 -> ...
+
+They are OFF unless asked for (`corrections="auto"` on Raw, unpack, develop, frames_device, Stack.push_packed): `ignored` lists
+them whether or not they can be applied, `DngFrame.remaining(corrections)` is what is still not applied with them.  A
+correction that cannot be used is recorded in `corrections.skipped` with its reason and stays in `ignored`.  Opcode
+coordinates in OpcodeList2 are taken as those of the active area, the cropped mosaic.
 
 The sample arithmetic is integer and exact (tests/unpack_restatement.py is its definition):
 
@@ -36,6 +49,7 @@ The sample arithmetic is integer and exact (tests/unpack_restatement.py is its d
 
 There is no CPU path: without a GPU or the library `unpack` and its kin raise DeviceError.  `read` is host Python.
 """
+import math
 import os
 import struct
 
@@ -149,9 +163,24 @@ class DngFrame:
     """One parsed DNG file (see the module's docstring).  `span` is a read-only view of the file's mapping: the frame keeps
     the mapping alive."""
 
-    def __init__(self, path, layout, span, cfa, develop, lens, orientation, ignored):
+    def __init__(self, path, layout, span, cfa, develop, lens, orientation, ignored, corrections=None):
         self.path, self.layout, self.span, self.cfa = path, layout, span, cfa
         self.develop, self.lens, self.orientation, self.ignored = develop, lens, orientation, tuple(ignored)
+        self.corrections = corrections      # a SiteCorrections, or None when the file carries none
+
+    def remaining(self, corrections="auto"):
+        """`ignored` minus what `corrections` ("auto": the file's own, None: nothing, or a SiteCorrections) applies: one entry
+        leaves per applied tag or opcode, and "OpcodeList2" with them when every opcode of that list is applied"""
+        c = resolve_corrections(self, corrections)
+        left = list(self.ignored)
+        if c is None:
+            return tuple(left)
+        for name in c.applies:
+            if name in left:
+                left.remove(name)
+        if c.whole_list2 and "OpcodeList2" in left:
+            left.remove("OpcodeList2")
+        return tuple(left)
 
     @property
     def shape(self):
@@ -172,9 +201,11 @@ class Raw:
                  a demosaic.Develop: that one for every file
     lens         "auto": the file's WarpRectilinear opcode; None: no lens correction; a lens.Lens: that one
     calibration  a demosaic.Calibration applied to every unpacked mosaic, or None
+    corrections  None: the file's site corrections are not applied (`DngFrame.ignored` lists them); "auto": each file's own
+                 `DngFrame.corrections`; a SiteCorrections: that one for every file.  Ahead of `calibration`.
     """
 
-    def __init__(self, develop="auto", lens="auto", calibration=None):
+    def __init__(self, develop="auto", lens="auto", calibration=None, corrections=None):
         from .demosaic import check_calibration, check_develop
         from .lens import check_lens
         if not (isinstance(develop, str) and develop == "auto") and develop is not None:
@@ -183,10 +214,16 @@ class Raw:
             lens = check_lens(lens)
         if calibration is not None:
             check_calibration(calibration)
-        self.develop, self.lens, self.calibration = develop, lens, calibration
+        if not (isinstance(corrections, str) and corrections == "auto") and corrections is not None:
+            check_corrections(corrections)
+        self.develop, self.lens, self.calibration, self.corrections = develop, lens, calibration, corrections
 
     def __repr__(self):
-        return f"Raw(develop={self.develop!r}, lens={self.lens!r}, calibration={self.calibration!r})"
+        tail = "" if self.corrections is None else f", corrections={self.corrections!r}"
+        return f"Raw(develop={self.develop!r}, lens={self.lens!r}, calibration={self.calibration!r}{tail})"
+
+    def corrections_for(self, frame):
+        return frame.corrections if isinstance(self.corrections, str) else self.corrections
 
     def develop_for(self, frame):
         return frame.develop if isinstance(self.develop, str) else self.develop
@@ -203,6 +240,435 @@ def check_raw(raw):
 
 def is_dng(path):
     return str(path).split(".")[-1].lower() in EXTENSIONS
+
+
+# ---------------------------------------------------------------- site corrections
+SITE_MAX_NODES = 4096                           # sitecorr::MAX_NODES of csrc/kernels_sitecorr.hpp: mv, mh of one grid
+SITE_GAIN_ONE = 4096                            # Q12
+SITE_MAX_BAD = 1 << 20                          # sites a file's bad-pixel list may expand to
+SITE_VEC_BYTES = 16                             # sitecorr::VEC_BYTES: one lane's window of a row
+SITE_TILE_H, SITE_LANES = 4, 64                 # sitecorr::TILE_H / LANES: a workgroup is 4 rows of 64 windows
+
+
+def site_vec(dtype):
+    """the site-correction kernel's vector width in sites for mosaics of `dtype`"""
+    return SITE_VEC_BYTES // np.dtype(dtype).itemsize
+
+
+def site_tile(dtype):
+    """(rows, sites of a row) of one workgroup of the site-correction kernel, for rows that start on a 16-byte boundary"""
+    return SITE_TILE_H, SITE_LANES * site_vec(dtype)
+
+
+def relative(k, n):
+    """Row or column k of an n-pixel image in an opcode's relative coordinates (0.0: the image's first edge, 1.0: its last):
+    the pixel's centre.  The ONE place the formula stands: pinning the reader against a real DNG changes this line."""
+    return (np.asarray(k, np.float64) + 0.5) / float(n)
+
+
+def _half_up(x):
+    return np.floor(np.asarray(x, np.float64) + 0.5)
+
+
+class GainMap:
+    """One gain map: `nodes` (mv x mh float64, each finite and in [0, 16)), `spacing` (vertical, horizontal) and `origin`
+    (vertical, horizontal) of the node grid in relative coordinates (`relative`).  Between nodes the gain is bilinear; outside
+    the grid the edge node holds."""
+
+    def __init__(self, nodes, spacing=(1.0, 1.0), origin=(0.0, 0.0)):
+        n = np.array(nodes, np.float64)
+        if n.ndim != 2 or not 1 <= n.shape[0] <= SITE_MAX_NODES or not 1 <= n.shape[1] <= SITE_MAX_NODES:
+            raise InvalidOptionError("nodes", n.shape, f"a grid of 1 to {SITE_MAX_NODES} nodes each way is expected")
+        if not np.isfinite(n).all() or n.min() < 0.0 or n.max() >= 16.0:
+            raise InvalidOptionError("nodes", "values", "every node is finite and lies in [0, 16)")
+        sp, og = tuple(float(v) for v in spacing), tuple(float(v) for v in origin)
+        if len(sp) != 2 or len(og) != 2 or not all(math.isfinite(v) for v in sp + og) or min(sp) < 0.0:
+            raise InvalidOptionError("spacing", (spacing, origin), "two finite numbers each, the spacing not negative")
+        self.nodes, self.spacing, self.origin = n, sp, og
+
+    def __repr__(self):
+        return f"GainMap({self.nodes.shape[0]} x {self.nodes.shape[1]}, spacing={self.spacing}, origin={self.origin})"
+
+    def nodes_q(self):
+        """the nodes in Q12, uint16: round-half-up(node * 4096), at most 65535"""
+        return np.minimum(_half_up(self.nodes * float(SITE_GAIN_ONE)), 65535.0).astype(np.uint16)
+
+    @staticmethod
+    def axis(n_sites, n_nodes, spacing, origin):
+        """one axis entry (node, weight) per row or column: t = (relative(k, n) - origin) / spacing clamped to the grid,
+        node = floor(t), weight = round-half-up(256 (t - node)) of the node behind it"""
+        out = np.zeros(n_sites, _lib.SITE_AXIS_DTYPE)
+        if n_nodes > 1 and spacing > 0.0:
+            t = np.clip((relative(np.arange(n_sites), n_sites) - origin) / spacing, 0.0, float(n_nodes - 1))
+            i = np.minimum(np.floor(t), n_nodes - 1)
+            out["node"] = i.astype(np.uint16)
+            out["weight"] = _half_up((t - i) * 256.0).astype(np.uint16)
+        return out
+
+    def axes(self, shape):
+        """(row axis, column axis) over an H x W image"""
+        return (self.axis(int(shape[0]), self.nodes.shape[0], self.spacing[0], self.origin[0]),
+                self.axis(int(shape[1]), self.nodes.shape[1], self.spacing[1], self.origin[1]))
+
+
+class SiteTables:
+    """The integer tables the site-correction kernels take (SiteCorrections.quantised): `dh` / `dv` int16 or None, `gains` four
+    entries of None or (nodes uint16 mv x mh, row axis, column axis), `bad_sites` int32 ascending, `bad_constant` (value, mask)
+    or None."""
+
+    def __init__(self, dh, dv, gains, bad_sites, bad_constant):
+        self.dh, self.dv, self.gains, self.bad_sites, self.bad_constant = dh, dv, gains, bad_sites, bad_constant
+
+    @property
+    def flags(self):
+        return ((_lib.MI_SITE_DELTA_H if self.dh is not None else 0) | (_lib.MI_SITE_DELTA_V if self.dv is not None else 0) |
+                (_lib.MI_SITE_GAIN if any(g is not None for g in self.gains) else 0) |
+                (_lib.MI_SITE_BAD_LIST if len(self.bad_sites) else 0) | (_lib.MI_SITE_BAD_CONST if self.bad_constant is not None else 0))
+
+    def arrays(self):
+        """every table, in a fixed order, each named: what struct() points into"""
+        out = []
+        if self.dh is not None:
+            out.append(("dh", self.dh))
+        if self.dv is not None:
+            out.append(("dv", self.dv))
+        for p, g in enumerate(self.gains):
+            if g is not None:
+                out += [(f"nodes{p}", g[0]), (f"row{p}", g[1]), (f"col{p}", g[2])]
+        if len(self.bad_sites):
+            out.append(("bad", self.bad_sites))
+        return out
+
+    def same(self, other):
+        a, b = self.arrays(), other.arrays()
+        return (self.bad_constant == other.bad_constant and [n for n, _ in a] == [n for n, _ in b] and
+                all(x.shape == y.shape and x.dtype == y.dtype and np.array_equal(x, y) for (_, x), (_, y) in zip(a, b)))
+
+    def struct(self, address):
+        """mi_site_correct_t whose pointers are address(name, array): host addresses, or those of resident copies"""
+        c = _lib.SiteCorrectStruct()
+        c.flags = self.flags
+        if self.dh is not None:
+            c.delta_h = address("dh", self.dh)
+        if self.dv is not None:
+            c.delta_v = address("dv", self.dv)
+        for p, g in enumerate(self.gains):
+            if g is not None:
+                c.gain[p].nodes, c.gain[p].row_axis, c.gain[p].col_axis = (address(f"nodes{p}", g[0]), address(f"row{p}", g[1]),
+                                                                           address(f"col{p}", g[2]))
+                c.gain[p].mv, c.gain[p].mh = g[0].shape
+        if len(self.bad_sites):
+            c.bad_sites, c.n_bad = address("bad", self.bad_sites), len(self.bad_sites)
+        if self.bad_constant is not None:
+            c.bad_constant, c.bad_phase_mask = self.bad_constant
+        return c
+
+    def host_struct(self):
+        return self.struct(lambda name, a: a.ctypes.data)
+
+
+class SiteCorrections:
+    """The per-site corrections of a raw frame, applied to the unpacked mosaic ahead of everything else (see the module's
+    docstring for the order; csrc/kernels_sitecorr.hpp for the arithmetic).
+
+    black_h, black_v   integer arrays of W and H entries in the mosaic's scale, added to the black level per column and per row
+                       (a file's BlackLevelDeltaH/V: round-half-up of the delta times 2^shift), or None
+    gains              None, one GainMap for every position, or four entries (None or a GainMap) for the positions
+                       2 (y & 1) + (x & 1)
+    bad_sites          linear indices y * W + x into the cropped mosaic, or an (n, 2) array of (y, x) with `shape`; kept
+                       ascending and unique, int32
+    bad_constant       (value, mask): every site of the positions in the 4-bit `mask` (bit pos) that holds `value` is repaired
+    skipped            a tuple of (name, reason): what a file carried and this object does not apply
+    applies            the names, as `DngFrame.ignored` spells them, of what this object applies (None: derived from the above)
+
+    `quantised(shape, dtype)` is the one function that turns geometry into the kernel's axis entries.  The device tables of
+    `prepared` are uploaded per device at first use and held until close()."""
+
+    def __init__(self, black_h=None, black_v=None, gains=None, bad_sites=None, bad_constant=None, skipped=(), applies=None,
+                 whole_list2=False):
+        def delta(name, v):
+            if v is None:
+                return None
+            a = np.asarray(v)
+            if a.ndim != 1 or a.dtype.kind not in "iu" or len(a) < 2:
+                raise InvalidOptionError(name, getattr(a, "shape", v), "a one-dimensional integer array is expected")
+            a = a.astype(np.int64)
+            if a.min() < -32768 or a.max() > 32767:
+                raise InvalidOptionError(name, (int(a.min()), int(a.max())), "the deltas fit 16 bits")
+            return a
+        self.black_h, self.black_v = delta("black_h", black_h), delta("black_v", black_v)
+        if gains is None:
+            self.gains = (None,) * 4
+        elif isinstance(gains, GainMap):
+            self.gains = (gains,) * 4
+        else:
+            g = tuple(gains)
+            if len(g) != 4 or not all(m is None or isinstance(m, GainMap) for m in g):
+                raise InvalidOptionError("gains", gains, "one GainMap, or four entries (a GainMap or None per position)")
+            self.gains = g
+        self.bad_sites = np.zeros(0, np.int32)
+        if bad_sites is not None:
+            b = np.asarray(bad_sites)
+            if b.size and (b.ndim != 1 or b.dtype.kind not in "iu" or b.min() < 0 or b.max() >= 2 ** 31):
+                raise InvalidOptionError("bad_sites", b.shape, "a one-dimensional array of linear indices y * W + x is expected")
+            self.bad_sites = np.unique(b.astype(np.int64)).astype(np.int32)
+        self.bad_constant = None
+        if bad_constant is not None:
+            try:
+                value, mask = (int(v) for v in bad_constant)
+            except (TypeError, ValueError):
+                raise InvalidOptionError("bad_constant", bad_constant, "a (value, mask) pair of ints is expected") from None
+            if not 0 <= value <= 65535 or not 1 <= mask <= 15:
+                raise InvalidOptionError("bad_constant", bad_constant, "the value lies in [0, 65535], the position mask in [1, 15]")
+            self.bad_constant = (value, mask)
+        self.skipped = tuple((str(n), str(r)) for n, r in skipped)
+        if applies is None:
+            maps = []
+            for m in self.gains:
+                if m is not None and not any(m is x for x in maps):
+                    maps.append(m)
+            applies = ((["BlackLevelDeltaH"] if self.black_h is not None else []) + (["BlackLevelDeltaV"] if self.black_v is not None else []) +
+                       (["FixBadPixelsList"] if len(self.bad_sites) else []) + (["FixBadPixelsConstant"] if self.bad_constant else []) +
+                       ["GainMap"] * len(maps))
+        self.applies, self.whole_list2 = tuple(applies), bool(whole_list2)
+        self._quant = {}        # (h, w, dtype) -> SiteTables
+        self._dev = {}          # (device, h, w, dtype) -> (mi_site_correct_t, [DeviceBuffer])
+
+    def __repr__(self):
+        maps = [None if m is None else f"{m.nodes.shape[0]}x{m.nodes.shape[1]}" for m in self.gains]
+        return (f"SiteCorrections(black_h={None if self.black_h is None else len(self.black_h)}, "
+                f"black_v={None if self.black_v is None else len(self.black_v)}, gains={maps}, bad_sites={len(self.bad_sites)}, "
+                f"bad_constant={self.bad_constant}, skipped={list(self.skipped)})")
+
+    @property
+    def empty(self):
+        return (self.black_h is None and self.black_v is None and all(m is None for m in self.gains) and len(self.bad_sites) == 0 and
+                self.bad_constant is None)
+
+    def quantised(self, shape, dtype):
+        """The SiteTables for H x W mosaics of `dtype`: the deltas as int16, every map's nodes in Q12 with one axis entry per
+        row and per column (GainMap.axis), the bad sites, the constant.  Checked against the frame: table lengths, sites
+        inside it, a constant the dtype holds."""
+        h, w = int(shape[0]), int(shape[1])
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            from .errors import BitDepthError
+            raise BitDepthError("uint8 or uint16", dt)
+        key = (h, w, dt)
+        if key not in self._quant:
+            if h < 2 or w < 2 or h * w >= 2 ** 31:
+                raise InvalidOptionError("shape", (h, w), "a mosaic is H x W with H, W >= 2 and H * W < 2^31")
+            if self.black_h is not None and len(self.black_h) != w:
+                raise InvalidOptionError("black_h", len(self.black_h), f"a {h} x {w} mosaic has {w} columns")
+            if self.black_v is not None and len(self.black_v) != h:
+                raise InvalidOptionError("black_v", len(self.black_v), f"a {h} x {w} mosaic has {h} rows")
+            if len(self.bad_sites) and int(self.bad_sites[-1]) >= h * w:
+                raise InvalidOptionError("bad_sites", int(self.bad_sites[-1]), f"a site lies outside the {h} x {w} mosaic")
+            if self.bad_constant is not None and self.bad_constant[0] > int(np.iinfo(dt).max):
+                raise InvalidOptionError("bad_constant", self.bad_constant, f"the value exceeds the maximum of {dt}")
+            done, gains = [], []
+            for m in self.gains:        # positions that share a map share its tables
+                hit = next((t for x, t in done if x is m), None)
+                if m is not None and hit is None:
+                    ra, ca = m.axes((h, w))
+                    hit = (np.ascontiguousarray(m.nodes_q()), ra, ca)
+                    done.append((m, hit))
+                gains.append(hit)
+            self._quant[key] = SiteTables(None if self.black_h is None else self.black_h.astype(np.int16),
+                                          None if self.black_v is None else self.black_v.astype(np.int16), tuple(gains),
+                                          self.bad_sites, self.bad_constant)
+        return self._quant[key]
+
+    def prepared(self, shape, dtype, device=0):
+        """mi_site_correct_t whose tables are resident on `device` (uploaded at first use, held until close()).  With a
+        constant it carries one scratch plane: kernels queued with it on two streams at once would share that plane."""
+        q = self.quantised(shape, dtype)
+        key = (device, int(shape[0]), int(shape[1]), np.dtype(dtype))
+        if key not in self._dev:
+            _lib.require_device()
+            bufs, seen = [], {}
+
+            def resident(name, a):
+                if id(a) not in seen:
+                    buf = _lib.DeviceBuffer(a.nbytes, device)
+                    buf.upload(a)
+                    bufs.append(buf)
+                    seen[id(a)] = buf.ptr
+                return seen[id(a)]
+            sc = q.struct(resident)
+            if q.bad_constant is not None:      # the bit plane between the constant repair's two passes
+                bufs.append(_lib.DeviceBuffer(8 * (-(-key[1] * key[2] // 64)), device))
+                sc.dev_scratch = bufs[-1].ptr
+            self._dev[key] = (sc, bufs)
+        return self._dev[key][0]
+
+    def close(self):
+        """free the device tables (not before every kernel queued with them has run)"""
+        for _, bufs in self._dev.values():
+            for buf in bufs:
+                buf.free()
+        self._dev = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def check_corrections(corrections):
+    if not isinstance(corrections, SiteCorrections):
+        raise InvalidOptionError("corrections", corrections, '"auto", None or a shinestacker_amd.dng.SiteCorrections is expected')
+    return corrections
+
+
+def resolve_corrections(frame, corrections):
+    """None, the frame's own ("auto") or the given SiteCorrections; one that holds nothing counts as None"""
+    if isinstance(corrections, str):
+        if corrections != "auto":
+            raise InvalidOptionError("corrections", corrections, '"auto", None or a dng.SiteCorrections is expected')
+        corrections = None if frame is None else frame.corrections
+    elif corrections is not None:
+        check_corrections(corrections)
+    return None if corrections is None or corrections.empty else corrections
+
+
+def _gain_map(body, h, w):
+    """a GainMap opcode's data -> (positions, GainMap), or a str: the reason it is skipped.  Layout: Top, Left, Bottom, Right,
+    Plane, Planes, RowPitch, ColPitch, MapPointsV, MapPointsH (uint32), MapSpacingV, MapSpacingH, MapOriginV, MapOriginH
+    (double), MapPlanes (uint32) -- 76 bytes -- then MapPointsV x MapPointsH x MapPlanes float32, all big-endian."""
+    if len(body) < 76:
+        return f"a body of {len(body)} bytes is shorter than its 76-byte header"
+    top, left, bottom, right, _plane, planes, rp, cp, mv, mh = struct.unpack(">10I", body[:40])
+    sv, sh, ov, oh = struct.unpack(">4d", body[40:72])
+    mplanes = struct.unpack(">I", body[72:76])[0]
+    if mv == 0 or mh == 0:
+        return "zero map points"
+    if planes != 1 or mplanes != 1:
+        return f"Planes = {planes}, MapPlanes = {mplanes}: one plane is read"
+    if mv > SITE_MAX_NODES or mh > SITE_MAX_NODES:
+        return f"{mv} x {mh} map points: at most {SITE_MAX_NODES} each way"
+    if len(body) < 76 + 4 * mv * mh:
+        return f"a body of {len(body)} bytes is shorter than its {mv} x {mh} map points"
+    if rp not in (1, 2) or cp not in (1, 2):
+        return f"RowPitch = {rp}, ColPitch = {cp}: a pitch of 1 or 2 is read"
+    last_y, last_x = (h - 1) - ((h - 1 - top) % rp) if top < h else -1, (w - 1) - ((w - 1 - left) % cp) if left < w else -1
+    if top >= rp or left >= cp or bottom <= last_y or right <= last_x:
+        return f"the rectangle ({top}, {left}, {bottom}, {right}) does not span the {h} x {w} image"
+    if not all(math.isfinite(v) for v in (sv, sh, ov, oh)) or sv < 0.0 or sh < 0.0:
+        return "a spacing or origin that is not finite, or a negative spacing"
+    nodes = np.array(struct.unpack(f">{mv * mh}f", body[76:76 + 4 * mv * mh]), np.float64).reshape(mv, mh)
+    if not np.isfinite(nodes).all():
+        return "a map point that is not finite"
+    if nodes.min() < 0.0:
+        return "a negative map point"
+    if nodes.max() >= 16.0:
+        return "a map point of 16 or more"
+    rows = (0, 1) if rp == 1 else (top & 1,)
+    cols = (0, 1) if cp == 1 else (left & 1,)
+    return [2 * py + px for py in rows for px in cols], GainMap(nodes, (sv, sh), (ov, oh))
+
+
+def _bad_list(body, h, w):
+    """a FixBadPixelsList opcode's data -> ascending linear indices inside the H x W image, or a str: the reason it is skipped.
+    Layout: BayerPhase, BadPointCount, BadRectCount (uint32), the points as (row, column), the rectangles as (top, left,
+    bottom, right), all uint32 big-endian."""
+    if len(body) < 12:
+        return f"a body of {len(body)} bytes is shorter than its 12-byte header"
+    _phase, npts, nrect = struct.unpack(">3I", body[:12])
+    if len(body) < 12 + 8 * npts + 16 * nrect:
+        return f"a body of {len(body)} bytes is shorter than its {npts} points and {nrect} rectangles"
+    pts = np.array(struct.unpack(f">{2 * npts}I", body[12:12 + 8 * npts]), np.int64).reshape(npts, 2)
+    rects = np.array(struct.unpack(f">{4 * nrect}I", body[12 + 8 * npts:12 + 8 * npts + 16 * nrect]), np.int64).reshape(nrect, 4)
+    t, l = np.clip(rects[:, 0], 0, h), np.clip(rects[:, 1], 0, w)
+    b, r = np.clip(rects[:, 2], t, h), np.clip(rects[:, 3], l, w)
+    total = npts + int((np.maximum(rects[:, 2] - rects[:, 0], 0) * np.maximum(rects[:, 3] - rects[:, 1], 0)).sum())   # as the file states them
+    if total > SITE_MAX_BAD:
+        return f"the list expands to {total} sites: at most 2^20 are read"
+    inside = pts[(pts[:, 0] < h) & (pts[:, 1] < w)]
+    sites = [inside[:, 0] * w + inside[:, 1]]
+    for k in range(nrect):
+        yy, xx = np.mgrid[t[k]:b[k], l[k]:r[k]]
+        sites.append((yy * w + xx).reshape(-1))
+    return np.unique(np.concatenate(sites)).astype(np.int32)
+
+
+def _site_corrections(t, rawifd, ifd0, ops2, layout, black, path):
+    """the SiteCorrections of a file, or None when it carries none: BlackLevelDeltaH/V of the raw IFD (or IFD0) and the
+    GainMap, FixBadPixelsConstant and FixBadPixelsList opcodes `ops2` of OpcodeList2.  black: the four levels, unshifted."""
+    h, w, shift = layout.height, layout.width, layout.shift
+    maxv = int(np.iinfo(layout.dtype).max)
+    skipped, applies, seen = [], [], False
+    deltas = {}
+    for tag, n in ((50715, w), (50716, h)):
+        c = rawifd if tag in rawifd else ifd0 if tag in ifd0 else None
+        if c is None:
+            continue
+        seen = True
+        vals = np.array(t.values(c[tag]), np.float64)
+        if len(vals) != n:
+            skipped.append((TAG_NAMES[tag], f"{len(vals)} entries for a crop of {n} {'columns' if tag == 50715 else 'rows'}"))
+            continue
+        if not np.isfinite(vals).all() or np.abs(vals).max() * (1 << shift) > 32767:
+            skipped.append((TAG_NAMES[tag], "a delta that does not fit 16 bits in the mosaic's scale"))
+            continue
+        deltas[tag] = _half_up(vals * float(1 << shift)).astype(np.int64)
+    if deltas:
+        dh, dv = deltas.get(50715, np.zeros(w, np.int64)), deltas.get(50716, np.zeros(h, np.int64))
+        for pos in range(4):
+            lo = (black[pos] << shift) + dh[pos & 1::2].min() + dv[pos >> 1::2].min()
+            hi = (black[pos] << shift) + dh[pos & 1::2].max() + dv[pos >> 1::2].max()
+            if lo < 0 or hi > maxv:
+                for tag in sorted(deltas):
+                    skipped.append((TAG_NAMES[tag], f"black level plus deltas spans {lo} .. {hi} at position {pos}: outside [0, {maxv}]"))
+                deltas = {}
+                break
+    applies += [TAG_NAMES[tag] for tag in sorted(deltas)]
+    gains, bad, const, applied2 = [None] * 4, [], None, 0
+    for oid, body in ops2:
+        name = OPCODE_NAMES.get(oid)
+        if oid == 9:
+            seen = True
+            got = _gain_map(body, h, w)
+            if not isinstance(got, str) and any(gains[p] is not None for p in got[0]):
+                got = f"a second map for position {next(p for p in got[0] if gains[p] is not None)}"
+            if isinstance(got, str):
+                skipped.append((name, got))
+                continue
+            for p in got[0]:
+                gains[p] = got[1]
+        elif oid == 5:
+            seen = True
+            got = _bad_list(body, h, w)
+            if isinstance(got, str):
+                skipped.append((name, got))
+                continue
+            bad.append(got)
+        elif oid == 4:
+            seen = True
+            if len(body) < 8:
+                skipped.append((name, f"a body of {len(body)} bytes is shorter than its 8"))
+                continue
+            value = struct.unpack(">I", body[:4])[0]
+            if layout.table is not None:
+                skipped.append((name, "the file has a LinearizationTable: the constant is a stored value, the mosaic holds table entries"))
+                continue
+            if const is not None:
+                skipped.append((name, "a second constant"))
+                continue
+            if (value << shift) > maxv:
+                skipped.append((name, f"the constant {value} lies outside the samples' range"))
+                continue
+            const = (value << shift, 15)
+        else:
+            continue
+        applies.append(name)
+        applied2 += 1
+    if not seen:
+        return None
+    sites = np.unique(np.concatenate(bad)) if bad else None
+    return SiteCorrections(deltas.get(50715), deltas.get(50716), gains if any(g is not None for g in gains) else None, sites, const,
+                           skipped=skipped, applies=applies, whole_list2=len(ops2) > 0 and applied2 == len(ops2))
 
 
 # ---------------------------------------------------------------- the TIFF structure
@@ -455,12 +921,14 @@ def read(path):
 
     # what is in the file and not applied
     ignored = [TAG_NAMES[tag] for tag in IGNORED_TAGS if tag in rawifd or tag in ifd0]
-    lens = None
+    lens, ops2 = None, []
     for tag in (51008, 51009, 51022):
         if tag not in rawifd and tag not in ifd0:
             continue
         name = TAG_NAMES[tag]
         ops = _opcodes(t.raw((rawifd if tag in rawifd else ifd0)[tag]), name, path)
+        if tag == 51009:
+            ops2 = ops
         if tag != 51022:
             ignored.append(name)
         for oid, body in ops:
@@ -472,7 +940,8 @@ def read(path):
                 oname = "WarpRectilinear (tangential terms)"
             ignored.append(oname)
     orientation = int(_one(t, ifd0, 274, _one(t, rawifd, 274, 1)))
-    return DngFrame(path, layout, span, cfa, develop, lens, orientation, ignored)
+    corrections = _site_corrections(t, rawifd, ifd0, ops2, layout, black, path)
+    return DngFrame(path, layout, span, cfa, develop, lens, orientation, ignored, corrections)
 
 
 def _warp_rectilinear(body, h, w, path):
@@ -604,9 +1073,14 @@ def _check_frame(frame):
     return frame
 
 
-def unpack(frame, device=0):
+def unpack(frame, device=0, corrections=None):
     """The cropped H x W mosaic of a DngFrame as a NumPy array of its dtype: span up, raw_unpack or raw_ljpeg, mosaic down.
-    A lossless-JPEG frame one of whose streams did not decode raises ImageLoadError."""
+    A lossless-JPEG frame one of whose streams did not decode raises ImageLoadError.  `corrections`: None, "auto" (the
+    frame's own) or a SiteCorrections, applied to the unpacked mosaic (demosaic.correct_sites)."""
+    sc = resolve_corrections(_check_frame(frame), corrections)
+    if sc is not None:
+        from .demosaic import correct_sites
+        return correct_sites(unpack(frame, device), frame.cfa, sc, device=device)
     lay = _check_frame(frame).layout
     _lib.require_device()
     out = np.empty((lay.height, lay.width), lay.dtype)
@@ -693,18 +1167,23 @@ def _resolve(frame, develop, lens):
     return develop, lens
 
 
-def develop(frame, develop="auto", lens="auto", calibration=None, device=0):
+def develop(frame, develop="auto", lens="auto", calibration=None, device=0, corrections=None):
     """A DngFrame -> H x W x 3 BGR of its dtype: unpack, then `debayer` with the frame's own Cfa.  `develop`, `lens`: "auto"
     takes frame.develop / frame.lens, None switches the step off, an object overrides it.  `calibration`: a
-    demosaic.Calibration applied to the unpacked mosaic first."""
+    demosaic.Calibration applied to the unpacked mosaic first.  `corrections`: None, "auto" or a SiteCorrections -- the
+    file's site corrections, ahead of the calibration."""
     dev, ln = _resolve(_check_frame(frame), develop, lens)
+    sc = resolve_corrections(frame, corrections)
+    if sc is not None:
+        return debayer(unpack(frame, device), frame.cfa, develop=dev, device=device, calibration=calibration, lens=ln, corrections=sc)
     return debayer(unpack(frame, device), frame.cfa, develop=dev, device=device, calibration=calibration, lens=ln)
 
 
-def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None, device=0):
+def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None, device=0, corrections=None):
     """Read the n DNG files (equal cropped shape and dtype), upload their spans and unpack and demosaic them side by side
     into `dev_out` (device pointer, n x H x W x 3 of their dtype): exactly what pipeline.align_and_stack_device(dev_frames,
-    ...) takes, as demosaic.debayer_frames_device does for mosaics.  Waits for the device.  Returns (H, W, dtype)."""
+    ...) takes, as demosaic.debayer_frames_device does for mosaics.  Waits for the device.  Returns (H, W, dtype).
+    `corrections`: None, "auto" (each file's own) or a SiteCorrections, applied in place behind the unpack."""
     if len(paths) == 0:
         raise ValueError("no files")
     _lib.require_device()
@@ -726,6 +1205,10 @@ def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None,
             up = _Staged(frame, device)
             try:
                 up.unpack_into(frame.layout, stage.ptr, device)
+                sc = resolve_corrections(frame, corrections)
+                if sc is not None:
+                    from .demosaic import correct_sites_device
+                    correct_sites_device(stage.ptr, h, w, frame.dtype, frame.cfa, sc, device=device)
                 debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, frame.dtype, frame.cfa, device=device, develop=dev,
                                calibration=calibration, lens=ln, lens_scratch=scratch)
                 # the stage and the staged span are reused / freed: the null stream's kernels must be through first
@@ -733,6 +1216,8 @@ def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None,
                 up.check_status()
             finally:
                 up.buf.free()
+                if isinstance(corrections, str) and frame.corrections is not None:
+                    frame.corrections.close()     # (the device was waited for above, or nothing was queued)
     finally:
         if stage is not None:
             stage.free()

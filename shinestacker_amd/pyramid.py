@@ -357,7 +357,11 @@ class PyramidStack(BaseStackAlgo):
         dev, ln = raw.develop_for(frame), raw.lens_for(frame)
         if dev is not None and dev is frame.develop:     # files of one camera share one Develop: one tone table on the device
             dev = self._raw_develops.setdefault(dev.matrix_q, dev)
+        from .dng import resolve_corrections
+        sc = resolve_corrections(frame, raw.corrections)
         if ln is None:
+            if raw.corrections is not None:
+                stack.set_site_correction(sc)       # (None clears what an earlier file of the folder set)
             stack.push_packed(frame, develop=dev, calibration=raw.calibration)
             return
         from .demosaic import debayer_device
@@ -369,8 +373,12 @@ class PyramidStack(BaseStackAlgo):
                                 _lib.DeviceBuffer(3 * nb, self.device))
         try:
             up.unpack_into(frame.layout, mosaic.ptr, self.device)
-            debayer_device(mosaic.ptr, bgr.ptr, h, w, frame.dtype, frame.cfa, device=self.device, develop=dev,
-                           calibration=raw.calibration, lens=ln, lens_scratch=scratch)
+            if sc is None:
+                debayer_device(mosaic.ptr, bgr.ptr, h, w, frame.dtype, frame.cfa, device=self.device, develop=dev,
+                               calibration=raw.calibration, lens=ln, lens_scratch=scratch)
+            else:
+                debayer_device(mosaic.ptr, bgr.ptr, h, w, frame.dtype, frame.cfa, device=self.device, develop=dev,
+                               calibration=raw.calibration, lens=ln, lens_scratch=scratch, corrections=sc)
             _lib.check(_lib.load().mi_device_synchronize(self.device))   # the null stream's kernels, ahead of the handle's
             up.check_status()
             stack.push_frames_device(bgr.ptr, 1)
@@ -378,6 +386,8 @@ class PyramidStack(BaseStackAlgo):
         finally:
             for b in (up.buf, mosaic, bgr, scratch):
                 b.free()
+            if sc is not None and sc is frame.corrections:
+                sc.close()      # (the file's own tables: nothing queued reads them any more)
 
     def focus_stack_arrays(self, frames, mosaic=None, develop=None, calibration=None):
         """In-memory variant (no file I/O): `frames` is a sequence of H x W x 3 uint8/uint16

@@ -38,6 +38,8 @@ def two_stage(args):
     `--ljpeg` (with `--mosaic --packed BITS`): stage 1 a further time from the same samples as lossless-JPEG spans
     (`mi_stack_push_ljpeg`: 256 x 256 tiles, two components, predictor 1, written by tools/ljpeg_encode.py; decoded on the device
     by raw_ljpeg), in turns with the packed and the mosaic runs; the handles' decode status is asserted to be 0.
+    `--sitecorr` (with `--mosaic --packed BITS`): the packed stage 1 with site corrections (dng.SiteCorrections: black deltas
+    and four 17 x 13 gain maps) set on every stage-1 handle, in turns with the packed run without them.
     `--calibrate` (with `--mosaic`): stage 1 from the mosaics with a `Calibration` (a master dark and a master flat; the gain
     table is built on the device before the clock starts) and without, three runs of each in turns, so that the two are
     compared inside one process and the spread from run to run shows; every time is listed under "mosaic"."""
@@ -239,6 +241,31 @@ def two_stage(args):
                 without.append(run_same())
             for s_ in stacks:
                 s_.sync()
+            if args.sitecorr:
+                # the packed run once more with site corrections set on every stage-1 handle (black deltas and four 17 x 13
+                # gain maps: what a phone's DNG carries), in turns with the packed run without them
+                def _map(seed):
+                    n = np.random.default_rng(seed).uniform(0.8, 1.6, size=(13, 17))
+                    return dng.GainMap(n, spacing=(1.0 / 12, 1.0 / 16))
+                sc = dng.SiteCorrections(black_h=np.arange(W) % 3 - 1, black_v=1 - np.arange(H) % 3, gains=[_map(k) for k in range(4)])
+
+                def run_corrected():
+                    for s_ in stacks:
+                        s_.set_site_correction(sc)
+                    try:
+                        return run_packed()
+                    finally:
+                        for s_ in stacks:
+                            s_.set_site_correction(None)
+                run_corrected()
+                with_s, plain_p = [], []
+                for _ in range(3):
+                    with_s.append(run_corrected())
+                    plain_p.append(run_packed())
+                for s_ in stacks:
+                    s_.sync()
+                developed.update({"sitecorr_packed_stage1_seconds": with_s, "packed_stage1_seconds_in_turns_sitecorr": plain_p,
+                                  "sitecorr_over_packed_stage1": float(np.median(with_s) / np.median(plain_p))})
             if args.ljpeg:
                 def run_ljpeg():
                     info = {}
@@ -300,6 +327,9 @@ def main():
     ap.add_argument("--calibrate", action="store_true",
                     help="with --two-stage --mosaic: stage 1 with a master dark and a flat field applied to every mosaic on the "
                          "device, in turns with the plain mosaic run")
+    ap.add_argument("--sitecorr", action="store_true",
+                    help="with --two-stage --mosaic --packed BITS: the packed stage 1 once more with site corrections (black deltas, "
+                         "four gain maps) set on the handles, in turns with the packed run without them")
     ap.add_argument("--packed", type=int, default=0, choices=(0, 10, 12, 14, 16),
                     help="with --two-stage --mosaic: stage 1 from packed spans of that many bits (the file's bytes, unpacked on the "
                          "device), in turns with the mosaic run on the same samples")
