@@ -1019,6 +1019,36 @@ MI_API int mi_mosaic_defects_const_device(int device, void* stream, void* dev_mo
  * frames pushed before the call are not touched.  Float-64 and MI_IMPL_SIMPLE handles take the synchronous route. */
 MI_API int mi_stack_set_site_correction(mi_stack_t* s, const mi_site_correct_t* sc);
 
+/* ---- finishing a raw frame (csrc/kernels_finish.hpp; tests/finish_restatement.py is the definition) ----
+ * A radial gain on the H x W mosaic (a DNG's FixVignetteRadial), in place, integer and exact: the centre in HALF pixels,
+ * d2 = (2x - cx2)^2 + (2y - cy2)^2, D the largest d2 of the four corner sites, u = d2 / D looked up in `table`:
+ * MI_RADIAL_NODES uint16 Q12 gains at u = i / 1024, blended with an 8-bit weight; out = min(maxv, (((v - black[pos]) g + 2048)
+ * >> 12) + black[pos]), v - black clamped at 0.  The library derives D and the multiplier and shift that replace the
+ * division from (height, width, cx2, cy2).  Refused before any device call: |cx2|, |cy2| above 2^24, D outside [1, 2^40), a
+ * black level above the dtype's maximum. */
+#define MI_RADIAL_NODES 1025
+typedef struct mi_radial_gain {
+    int32_t cx2;             /* the centre, half pixels */
+    int32_t cy2;
+    const uint16_t* table;   /* MI_RADIAL_NODES entries, Q12 */
+} mi_radial_gain_t;
+/* mi_mosaic_radial_gain_device: `rg->table` is device memory; enqueues on `stream`, does not wait.  mi_mosaic_radial_gain: the
+ * table is host memory; uploads, runs, downloads and waits; host_out may equal host_mosaic. */
+MI_API int mi_mosaic_radial_gain_device(int device, void* stream, void* dev_mosaic, int height, int width, int dtype,
+                                        const mi_cfa_t* cfa, const mi_radial_gain_t* rg);
+MI_API int mi_mosaic_radial_gain(int device, const void* host_mosaic, void* host_out, int height, int width, int dtype,
+                                 const mi_cfa_t* cfa, const mi_radial_gain_t* rg);
+/* Crop and orientation of a developed frame, out of place: src (height x width x 3, MI_U8 / MI_U16) -> dst, the crop
+ * a[y, x] = src[crop_y + y, crop_x + x] (crop_h x crop_w) turned by the TIFF `orientation` 1..8:
+ *   1: a  2: a[:, ::-1]  3: a[::-1, ::-1]  4: a[::-1]  (dst is crop_h x crop_w x 3)
+ *   5: a transposed  6: a turned 90 degrees clockwise  7: a[::-1, ::-1] transposed  8: a turned 90 degrees anticlockwise
+ *   (dst is crop_w x crop_h x 3).  The samples of a pixel keep their order.  src and dst must not overlap; 3 x height x width
+ *   stays below 2^31.  The _device form enqueues on `stream` and does not wait; the host form uploads, runs, downloads, waits. */
+MI_API int mi_frame_finish_device(int device, void* stream, const void* dev_src, void* dev_dst, int height, int width, int dtype,
+                                  int crop_y, int crop_x, int crop_h, int crop_w, int orientation);
+MI_API int mi_frame_finish(int device, const void* host_src, void* host_dst, int height, int width, int dtype, int crop_y,
+                           int crop_x, int crop_h, int crop_w, int orientation);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

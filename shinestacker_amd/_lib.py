@@ -96,6 +96,14 @@ class LensStruct(C.Structure):
     _fields_ = [("k", C.c_double * 12), ("cx", C.c_double), ("cy", C.c_double)]
 
 
+RADIAL_NODES = 1025                               # MI_RADIAL_NODES
+
+
+class RadialGainStruct(C.Structure):
+    """mi_radial_gain_t: what the radial-gain kernel sees of a dng.RadialGain (the centre in half pixels, the Q12 table)"""
+    _fields_ = [("cx2", C.c_int32), ("cy2", C.c_int32), ("table", C.c_void_p)]
+
+
 class RawLayoutStruct(C.Structure):
     """mi_raw_layout_t: how the samples of a raw file lie in its uploaded span (dng.RawLayout.struct)"""
     _fields_ = [("bits", C.c_int32), ("big_endian", C.c_int32), ("image_height", C.c_int32), ("image_width", C.c_int32),
@@ -332,6 +340,14 @@ SIGNATURES = {
     "mi_lens_remap_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.POINTER(LensStruct)]),
     "mi_lens_remap": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(LensStruct)]),
+    "mi_mosaic_radial_gain_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct),
+                                               C.POINTER(RadialGainStruct)]),
+    "mi_mosaic_radial_gain": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct),
+                                        C.POINTER(RadialGainStruct)]),
+    "mi_frame_finish_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_int]),
+    "mi_frame_finish": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_int]),
     "mi_raw_unpack_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p,
                                        C.c_void_p]),
     "mi_raw_unpack": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p, C.c_void_p]),

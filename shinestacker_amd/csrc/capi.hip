@@ -33,6 +33,7 @@
 #include "kernels_f64.hpp"
 #include "kernels_steps.hpp"
 #include "kernels_lens.hpp"
+#include "kernels_finish.hpp"
 
 using namespace mi;
 
@@ -2015,6 +2016,92 @@ int mi_lens_remap(int device, const void* host_src, void* host_dst, void* host_m
         return rc;
     if (host_mask && (rc = tmp.download(host_mask, mask, npx))) return rc;
     return tmp.download(host_dst, dst, nb);
+}
+
+// ---------------------------------------------------------------- finishing a raw frame (kernels_finish.hpp)
+// argument checks of mi_mosaic_radial_gain*: no device call, the table is not read
+static int radial_check(const void* mosaic, int height, int width, int dtype, const mi_cfa_t* cfa, const mi_radial_gain_t* rg) {
+    if (!mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    int rc = calib_shape_check(height, width, dtype);
+    if (rc || (rc = cfa_check(cfa, dtype))) return rc;
+    if (!rg) return fail(MI_ERR_INVALID, "null radial gain");
+    if (!rg->table) return fail(MI_ERR_INVALID, "radial gain: null table");
+    const int maxv = dtype == MI_U8 ? 255 : 65535;
+    for (int k = 0; k < 4; ++k)
+        if (cfa->black[k] > maxv) return fail(MI_ERR_INVALID, "cfa black[%d] must be <= %d (got %d)", k, maxv, cfa->black[k]);
+    if (rg->cx2 < -finish::CENTRE_MAX || rg->cx2 > finish::CENTRE_MAX || rg->cy2 < -finish::CENTRE_MAX || rg->cy2 > finish::CENTRE_MAX)
+        return fail(MI_ERR_INVALID, "radial gain: the centre (%d, %d) half pixels must be at most 2^24 in magnitude", rg->cx2, rg->cy2);
+    const long long D = radial_d2max(height, width, rg->cx2, rg->cy2);
+    if (D < 1 || D >= finish::D2_MAX)
+        return fail(MI_ERR_INVALID, "radial gain: the farthest corner lies %lld half pixels squared from the centre (1 to 2^40 - 1)", D);
+    return MI_OK;
+}
+
+int mi_mosaic_radial_gain_device(int device, void* stream, void* dev_mosaic, int height, int width, int dtype, const mi_cfa_t* cfa,
+                                 const mi_radial_gain_t* rg) {
+    int rc = radial_check(dev_mosaic, height, width, dtype, cfa, rg);
+    if (rc) return rc;
+    MI_HIP(hipSetDevice(device));
+    radial_gain_launch((hipStream_t)stream, dev_mosaic, height, width, dtype, cfa->black, *rg);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_mosaic_radial_gain(int device, const void* host_mosaic, void* host_out, int height, int width, int dtype, const mi_cfa_t* cfa,
+                          const mi_radial_gain_t* rg) {
+    if (!host_out) return fail(MI_ERR_INVALID, "null mosaic output");
+    int rc = radial_check(host_mosaic, height, width, dtype, cfa, rg);
+    if (rc) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t nb = (size_t)height * width * dtype_size(dtype);
+    DevScratch tmp(nullptr);
+    void *m = nullptr, *table = nullptr;
+    mi_radial_gain_t d = *rg;
+    if ((rc = tmp.upload(&m, host_mosaic, nb)) || (rc = tmp.upload(&table, rg->table, MI_RADIAL_NODES * sizeof(uint16_t)))) return rc;
+    d.table = (const uint16_t*)table;
+    if ((rc = mi_mosaic_radial_gain_device(device, nullptr, m, height, width, dtype, cfa, &d))) return rc;
+    return tmp.download(host_out, m, nb);
+}
+
+// argument checks of mi_frame_finish*: no device call
+static int finish_check(const void* src, const void* dst, int height, int width, int dtype, int crop_y, int crop_x, int crop_h,
+                        int crop_w, int orientation) {
+    if (!src) return fail(MI_ERR_INVALID, "null source frame");
+    if (!dst) return fail(MI_ERR_INVALID, "null destination frame");
+    if (src == dst) return fail(MI_ERR_INVALID, "source and destination must be distinct buffers (the finish is out of place)");
+    if (height < 1 || width < 1) return fail(MI_ERR_INVALID, "height and width must be >= 1 (got %dx%d)", width, height);
+    // (the kernels count a row's SAMPLES in an int: three per pixel)
+    if (3 * (uint64_t)height * (uint64_t)width >= (1ull << 31)) return fail(MI_ERR_INVALID, "height x width too large (3 x height x width must be below 2^31)");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16 for a frame finish (got %d)", dtype);
+    if (crop_y < 0 || crop_x < 0 || crop_h < 1 || crop_w < 1 || (int64_t)crop_y + crop_h > height || (int64_t)crop_x + crop_w > width)
+        return fail(MI_ERR_INVALID, "the crop (y %d, x %d, %d x %d) must be a rectangle inside the %d x %d frame", crop_y, crop_x, crop_h,
+                    crop_w, height, width);
+    if (orientation < 1 || orientation > 8) return fail(MI_ERR_INVALID, "orientation must be in [1, 8] (got %d)", orientation);
+    return MI_OK;
+}
+
+int mi_frame_finish_device(int device, void* stream, const void* dev_src, void* dev_dst, int height, int width, int dtype, int crop_y,
+                           int crop_x, int crop_h, int crop_w, int orientation) {
+    int rc = finish_check(dev_src, dev_dst, height, width, dtype, crop_y, crop_x, crop_h, crop_w, orientation);
+    if (rc) return rc;
+    MI_HIP(hipSetDevice(device));
+    frame_finish_launch((hipStream_t)stream, dev_src, dev_dst, width, dtype, crop_y, crop_x, crop_h, crop_w, orientation);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_frame_finish(int device, const void* host_src, void* host_dst, int height, int width, int dtype, int crop_y, int crop_x,
+                    int crop_h, int crop_w, int orientation) {
+    int rc = finish_check(host_src, host_dst, height, width, dtype, crop_y, crop_x, crop_h, crop_w, orientation);
+    if (rc) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t nb = (size_t)height * width * 3 * dtype_size(dtype), ob = (size_t)crop_h * crop_w * 3 * dtype_size(dtype);
+    DevScratch tmp(nullptr);
+    void *src = nullptr, *dst = nullptr;
+    if ((rc = tmp.upload(&src, host_src, nb)) || (rc = tmp.alloc(&dst, ob)) ||
+        (rc = mi_frame_finish_device(device, nullptr, src, dst, height, width, dtype, crop_y, crop_x, crop_h, crop_w, orientation)))
+        return rc;
+    return tmp.download(host_dst, dst, ob);
 }
 
 int mi_stack_push_mosaic_calibrated(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa,

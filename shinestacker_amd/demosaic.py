@@ -593,6 +593,71 @@ def correct_sites(mosaic, cfa, corrections, device=0):
     return out
 
 
+def _check_radial(gain, cfa, dt):
+    from .dng import RadialGain
+    if not isinstance(gain, RadialGain):
+        raise InvalidOptionError("vignette", gain, "a shinestacker_amd.dng.RadialGain is expected")
+    maxv = int(np.iinfo(dt).max)
+    if max(_check_cfa(cfa).black) > maxv:
+        raise InvalidOptionError("cfa", tuple(cfa.black), f"a black level exceeds the maximum of {dt}")
+    return gain
+
+
+def radial_gain_device(dev_mosaic, h, w, dtype, cfa, gain, device=0, stream=None, lens=None):
+    """radial_gain() in place on a mosaic resident in HBM.  Queued on `stream`, not waited for; the RadialGain's device table
+    must outlive the queued kernel.  `lens`: the lens.Lens applied to the developed frame later, or None (dng.RadialGain)."""
+    dt = _dtype(dtype)
+    if h < 2 or w < 2:
+        raise InvalidOptionError("mosaic", (h, w), "a mosaic is an H x W plane with H, W >= 2")
+    c = _check_cfa(cfa).struct(dt)
+    rg = _check_radial(gain, cfa, dt).prepared((h, w), device, lens)
+    _lib.check(_lib.load().mi_mosaic_radial_gain_device(device, stream, dev_mosaic, int(h), int(w), _lib.DTYPE_CODE[dt], _lib.C.byref(c),
+                                                        _lib.C.byref(rg)))
+
+
+def radial_gain(mosaic, cfa, gain, device=0, lens=None):
+    """A dng.RadialGain (a DNG's FixVignetteRadial) applied to an H x W mosaic: (v - black) * g(r^2) with the black pedestal
+    put back, a mosaic of the same dtype (csrc/kernels_finish.hpp; integer and exact: tests/finish_restatement.py)."""
+    a = np.ascontiguousarray(check_mosaic(mosaic))
+    c = _check_cfa(cfa).struct(a.dtype)
+    rg, _table = _check_radial(gain, cfa, a.dtype).struct(a.shape, lens)
+    _lib.require_device()
+    out = np.empty_like(a)
+    _lib.check(_lib.load().mi_mosaic_radial_gain(device, a.ctypes.data, out.ctypes.data, a.shape[0], a.shape[1], _lib.DTYPE_CODE[a.dtype],
+                                                 _lib.C.byref(c), _lib.C.byref(rg)))
+    return out
+
+
+def _check_finish_frame(shape, dtype, finish):
+    """(dtype, (y, x, h, w), orientation) of dng.Finish `finish` on an H x W x 3 frame"""
+    from .dng import check_finish
+    if len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
+        raise InvalidOptionError("frame", tuple(shape), "an H x W x 3 BGR frame is expected")
+    dt = _dtype(dtype)
+    return dt, check_finish(finish).crop_for(shape[:2]), finish.orientation
+
+
+def finish_frame_device(dev_src, dev_dst, h, w, dtype, finish, device=0, stream=None):
+    """finish_frame() for a frame resident in HBM: `dev_src` (h x w x 3) -> `dev_dst` (H' x W' x 3, finish.finished_shape; a
+    distinct buffer).  Queued on `stream`, not waited for."""
+    dt, (cy, cx, ch, cw), orientation = _check_finish_frame((h, w, 3), dtype, finish)
+    _lib.require_device()
+    _lib.check(_lib.load().mi_frame_finish_device(device, stream, dev_src, dev_dst, int(h), int(w), _lib.DTYPE_CODE[dt], cy, cx, ch, cw,
+                                                  orientation))
+
+
+def finish_frame(frame, finish, device=0):
+    """Crop and orientation of a dng.Finish applied to an H x W x 3 uint8 / uint16 BGR frame: the H' x W' x 3 frame (its
+    vignette is not touched here: it belongs on the mosaic, `radial_gain`)."""
+    a = np.ascontiguousarray(frame)
+    dt, (cy, cx, ch, cw), orientation = _check_finish_frame(a.shape, a.dtype, finish)
+    _lib.require_device()
+    out = np.empty(finish.finished_shape(a.shape[:2]) + (3,), dt)
+    _lib.check(_lib.load().mi_frame_finish(device, a.ctypes.data, out.ctypes.data, a.shape[0], a.shape[1], _lib.DTYPE_CODE[dt], cy, cx, ch,
+                                           cw, orientation))
+    return out
+
+
 def defects_device(dev_mosaic, h, w, dtype, develop, device=0, stream=None):
     """Step 0 alone, in place on a mosaic resident in HBM.  Queued on `stream`, not waited for."""
     dt = _dtype(dtype)
@@ -602,7 +667,7 @@ def defects_device(dev_mosaic, h, w, dtype, develop, device=0, stream=None):
 
 
 def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None, develop=None, calibration=None, lens=None,
-                   lens_scratch=None, corrections=None):
+                   lens_scratch=None, corrections=None, finish=None, finish_scratch=None):
     """debayer() for a mosaic resident in HBM: `dev_mosaic` (h x w) -> `dev_bgr` (h x w x 3).  Queued on `stream`, not waited
     for.  `develop`: a Develop -- its defect sites are repaired IN PLACE in `dev_mosaic` first (no other site is written),
     then colour matrix and tone curve ride on the demosaic; its device tables must outlive the queued kernels.
@@ -610,9 +675,37 @@ def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None,
     `lens`: a lens.Lens -- the demosaic / develop kernel writes one scratch frame and the lens remap (lens.py) takes it to
     `dev_bgr`.  `lens_scratch`: that frame, a DeviceBuffer of h x w x 3 samples which must outlive the queued kernels; None:
     one is allocated here, and the call then WAITS for the device before it frees it.
-    `corrections`: a dng.SiteCorrections -- `dev_mosaic` is corrected IN PLACE ahead of the calibration."""
+    `corrections`: a dng.SiteCorrections -- `dev_mosaic` is corrected IN PLACE ahead of the calibration.
+    `finish`: a dng.Finish -- its vignette gain is applied IN PLACE to `dev_mosaic` behind the corrections and ahead of the
+    calibration; its crop and orientation are the last stage: everything above writes one scratch frame and frame_finish
+    takes it to `dev_bgr`, which is then H' x W' x 3 (finish.finished_shape).  `finish_scratch`: that frame, as
+    `lens_scratch` (a second one: the lens remap is out of place too)."""
     if corrections is not None:
         correct_sites_device(dev_mosaic, h, w, dtype, cfa, corrections, device=device, stream=stream)
+    if finish is not None:
+        from .dng import check_finish
+        dt = _dtype(dtype)
+        if check_finish(finish).vignette is not None:
+            radial_gain_device(dev_mosaic, h, w, dt, cfa, finish.vignette, device=device, stream=stream, lens=lens)
+        if finish.geometry((h, w)):
+            own = finish_scratch is None
+            need = int(h) * int(w) * 3 * dt.itemsize
+            if not own and getattr(finish_scratch, "nbytes", 0) < need:
+                raise InvalidOptionError("finish_scratch", getattr(finish_scratch, "nbytes", finish_scratch),
+                                         f"a DeviceBuffer of at least {need} bytes (h x w x 3 samples) is expected")
+            if own:
+                _lib.require_device()
+                finish_scratch = _lib.DeviceBuffer(need, device)
+            try:
+                debayer_device(dev_mosaic, finish_scratch.ptr, h, w, dt, cfa, device=device, stream=stream, develop=develop,
+                               calibration=calibration, lens=lens, lens_scratch=lens_scratch)
+                finish_frame_device(finish_scratch.ptr, dev_bgr, h, w, dt, finish, device=device, stream=stream)
+                if own:
+                    _lib.check(_lib.load().mi_device_synchronize(device))
+            finally:
+                if own:
+                    finish_scratch.free()
+            return
     if lens is not None:
         from .lens import check_lens, correct_device
         lens = check_lens(lens)
@@ -654,11 +747,13 @@ def debayer_device(dev_mosaic, dev_bgr, h, w, dtype, cfa, device=0, stream=None,
                                      _lib.C.byref(d)))
 
 
-def debayer(mosaic, cfa, develop=None, device=0, calibration=None, lens=None, corrections=None):
+def debayer(mosaic, cfa, develop=None, device=0, calibration=None, lens=None, corrections=None, finish=None):
     """H x W uint8 / uint16 mosaic -> H x W x 3 BGR array of the same dtype.  `develop`: a Develop (defect sites, colour
     matrix, tone curve); None: the plain demosaic.  `calibration`: a Calibration applied to the mosaic first.  `lens`: a
     lens.Lens -- the lens correction behind all of it, on the device: equal to lens.correct(debayer(...), lens).
-    `corrections`: a dng.SiteCorrections applied ahead of the calibration: equal to debayer(correct_sites(...), ...)."""
+    `corrections`: a dng.SiteCorrections applied ahead of the calibration: equal to debayer(correct_sites(...), ...).
+    `finish`: a dng.Finish -- equal to finish_frame(debayer(radial_gain(...), ...), finish): the vignette gain on the mosaic
+    behind the corrections, crop and orientation last; the result is H' x W' x 3."""
     if corrections is not None:
         mosaic = correct_sites(mosaic, cfa, corrections, device=device)
     a = np.ascontiguousarray(check_mosaic(mosaic))
@@ -666,6 +761,26 @@ def debayer(mosaic, cfa, develop=None, device=0, calibration=None, lens=None, co
     if lens is not None:
         from .lens import check_lens
         lens = check_lens(lens)
+    if finish is not None:
+        from .dng import check_finish
+        if calibration is not None:
+            check_calibration(calibration).check_frame(a.shape, a.dtype)
+        if develop is not None:
+            check_develop(develop)
+        oh, ow = check_finish(finish).finished_shape(a.shape)
+        _lib.require_device()
+        h, w = a.shape
+        bufs = [_lib.DeviceBuffer(a.nbytes, device), _lib.DeviceBuffer(oh * ow * 3 * a.itemsize, device), _lib.DeviceBuffer(a.nbytes * 3, device)]
+        try:
+            if lens is not None:
+                bufs.append(_lib.DeviceBuffer(a.nbytes * 3, device))
+            bufs[0].upload(a)
+            debayer_device(bufs[0].ptr, bufs[1].ptr, h, w, a.dtype, cfa, device=device, develop=develop, calibration=calibration, lens=lens,
+                           lens_scratch=bufs[3] if lens is not None else None, finish=finish, finish_scratch=bufs[2])
+            return bufs[1].download((oh, ow, 3), a.dtype)     # (a blocking copy on the null stream: behind the kernels)
+        finally:
+            for b in bufs:
+                b.free()
     if calibration is not None or lens is not None:
         if calibration is not None:
             check_calibration(calibration).check_frame(a.shape, a.dtype)

@@ -9,8 +9,9 @@ the mosaic's over the host link, and the host never shuffles a bit.
 
 What a `DngFrame` carries: `layout` (a RawLayout: how samples lie in the span), `cfa` (a demosaic.Cfa from CFAPattern,
 BlackLevel, WhiteLevel and AsShotNeutral), `develop` (a demosaic.Develop from the colour matrix, or None), `lens` (a lens.Lens
-from the WarpRectilinear opcode, or None), `orientation` (reported, not applied) and `ignored`: the names of every tag and
-opcode in the file that carries a correction this reader does NOT apply -- nothing is dropped silently.
+from the WarpRectilinear opcode, or None), `orientation` (reported; applied by `finish`), `finish` (a Finish: the file's
+FixVignetteRadial, default crop and orientation, applied only when asked for) and `ignored`: the names of every tag and
+opcode in the file that carries a correction a default read does NOT apply -- nothing is dropped silently.
 
 Lossless JPEG (ITU-T T.81, SOF3, Huffman coded: what most cameras and converters write): every strip or tile is one JPEG
 stream; `read` parses each stream's markers out of the mapping -- headers only, a few hundred bytes a tile -- into one
@@ -40,6 +41,15 @@ They are OFF unless asked for (`corrections="auto"` on Raw, unpack, develop, fra
 them whether or not they can be applied, `DngFrame.remaining(corrections)` is what is still not applied with them.  A
 correction that cannot be used is recorded in `corrections.skipped` with its reason and stays in `ignored`.  Opcode
 coordinates in OpcodeList2 are taken as those of the active area, the cropped mosaic.
+
+Finish (`Finish`, `RadialGain`, `DngFrame.finish`; csrc/kernels_finish.hpp, tests/finish_restatement.py is the definition):
+FixVignetteRadial of OpcodeList3 as a radial gain on the linear mosaic, DefaultCropOrigin / DefaultCropSize and Orientation
+as one last pass over the developed frame.  OFF unless asked for (`finish="auto"` on Raw, unpack, develop, frames_device):
+
+    ... -> file black deltas + gain maps -> radial gain -> Calibration -> step 0 -> demosaic / develop -> lens -> crop + orientation
+
+What cannot be used is recorded in `finish.skipped` with its reason and stays in `ignored`; `DngFrame.remaining(corrections,
+finish)` is what is left with both options.  An Orientation outside 1 to 8 is refused.
 
 The sample arithmetic is integer and exact (tests/unpack_restatement.py is its definition):
 
@@ -163,24 +173,31 @@ class DngFrame:
     """One parsed DNG file (see the module's docstring).  `span` is a read-only view of the file's mapping: the frame keeps
     the mapping alive."""
 
-    def __init__(self, path, layout, span, cfa, develop, lens, orientation, ignored, corrections=None):
+    def __init__(self, path, layout, span, cfa, develop, lens, orientation, ignored, corrections=None, finish=None):
         self.path, self.layout, self.span, self.cfa = path, layout, span, cfa
         self.develop, self.lens, self.orientation, self.ignored = develop, lens, orientation, tuple(ignored)
         self.corrections = corrections      # a SiteCorrections, or None when the file carries none
+        self.finish = Finish(orientation=orientation) if finish is None else finish    # the file's own Finish
 
-    def remaining(self, corrections="auto"):
-        """`ignored` minus what `corrections` ("auto": the file's own, None: nothing, or a SiteCorrections) applies: one entry
-        leaves per applied tag or opcode, and "OpcodeList2" with them when every opcode of that list is applied"""
+    def remaining(self, corrections="auto", finish=None):
+        """`ignored` minus what `corrections` ("auto": the file's own, None: nothing, or a SiteCorrections) and `finish` ("auto",
+        None or a Finish) apply: one entry leaves per applied tag or opcode, and "OpcodeList2" with them when every opcode of
+        that list is applied.  (OpcodeList3 itself is never listed: only its opcodes are, and FixVignetteRadial leaves with a
+        finish that applies it.)"""
         c = resolve_corrections(self, corrections)
+        f = resolve_finish(self, finish)
         left = list(self.ignored)
-        if c is None:
-            return tuple(left)
-        for name in c.applies:
+        for name in (() if c is None else c.applies) + (() if f is None else f.applies):
             if name in left:
                 left.remove(name)
-        if c.whole_list2 and "OpcodeList2" in left:
+        if c is not None and c.whole_list2 and "OpcodeList2" in left:
             left.remove("OpcodeList2")
         return tuple(left)
+
+    def finished_shape(self, finish="auto"):
+        """(H', W') of the developed frame under `finish` ("auto": the file's own, None, or a Finish)"""
+        f = resolve_finish(self, finish)
+        return self.shape if f is None else f.finished_shape(self.shape)
 
     @property
     def shape(self):
@@ -203,9 +220,13 @@ class Raw:
     calibration  a demosaic.Calibration applied to every unpacked mosaic, or None
     corrections  None: the file's site corrections are not applied (`DngFrame.ignored` lists them); "auto": each file's own
                  `DngFrame.corrections`; a SiteCorrections: that one for every file.  Ahead of `calibration`.
+    finish       None: vignette, default crop and orientation of the file are not applied (the frame comes out as stored);
+                 "auto": each file's own `DngFrame.finish`; a Finish: that one for every file.  The vignette gain follows
+                 the site corrections, crop and orientation are the last stage: the stack, its depth map and everything
+                 derived from them come out in the finished geometry.
     """
 
-    def __init__(self, develop="auto", lens="auto", calibration=None, corrections=None):
+    def __init__(self, develop="auto", lens="auto", calibration=None, corrections=None, finish=None):
         from .demosaic import check_calibration, check_develop
         from .lens import check_lens
         if not (isinstance(develop, str) and develop == "auto") and develop is not None:
@@ -216,14 +237,21 @@ class Raw:
             check_calibration(calibration)
         if not (isinstance(corrections, str) and corrections == "auto") and corrections is not None:
             check_corrections(corrections)
-        self.develop, self.lens, self.calibration, self.corrections = develop, lens, calibration, corrections
+        if not (isinstance(finish, str) and finish == "auto") and finish is not None:
+            check_finish(finish)
+        self.develop, self.lens, self.calibration, self.corrections, self.finish = develop, lens, calibration, corrections, finish
 
     def __repr__(self):
         tail = "" if self.corrections is None else f", corrections={self.corrections!r}"
+        tail += "" if self.finish is None else f", finish={self.finish!r}"
         return f"Raw(develop={self.develop!r}, lens={self.lens!r}, calibration={self.calibration!r}{tail})"
 
     def corrections_for(self, frame):
         return frame.corrections if isinstance(self.corrections, str) else self.corrections
+
+    def finish_for(self, frame):
+        """the Finish applied to `frame`, or None when there is nothing to apply"""
+        return resolve_finish(frame, self.finish)
 
     def develop_for(self, frame):
         return frame.develop if isinstance(self.develop, str) else self.develop
@@ -671,6 +699,296 @@ def _site_corrections(t, rawifd, ifd0, ops2, layout, black, path):
                            skipped=skipped, applies=applies, whole_list2=len(ops2) > 0 and applied2 == len(ops2))
 
 
+# ---------------------------------------------------------------- finish: vignette, crop, orientation
+RADIAL_NODES = _lib.RADIAL_NODES                # finish::NODES of csrc/kernels_finish.hpp: u = i / 1024
+RADIAL_D2_MAX = 1 << 40                         # finish::D2_MAX
+RADIAL_CENTRE_MAX = 1 << 24                     # finish::CENTRE_MAX, half pixels
+_INVERT_SAMPLES = 1 << 16                       # intervals of [0, 1] over which a warp's radial map is inverted
+
+
+def radial_d2max(h, w, cx2, cy2):
+    """the largest d2 = (2x - cx2)^2 + (2y - cy2)^2 of the four corner sites of an H x W mosaic: what the kernel's radius is
+    normalised by"""
+    return max((2 * x - cx2) ** 2 + (2 * y - cy2) ** 2 for x in (0, w - 1) for y in (0, h - 1))
+
+
+class RadialGain:
+    """A radial gain on the linear mosaic: g(u) = 1 + k0 u + k1 u^2 + k2 u^3 + k3 u^4 + k4 u^5 with u = r^2, r the distance
+    from `centre` normalised to 1 at the farthest corner site, as lens.Lens normalises its radius (a DNG's
+    FixVignetteRadial: 1 + k0 r^2 + ... + k4 r^10).
+
+    k           (k0, k1, k2, k3, k4), finite, with 0 < g < 16 on [0, 1]
+    centre      (cx, cy) in pixels; the kernel takes it rounded to half pixels
+    after_warp  the polynomial is stated in the lens-corrected frame (the opcode stands behind a WarpRectilinear).  The
+                gain is applied to the mosaic, ahead of the lens remap, so when a lens IS applied the table is built over
+                the SOURCE radius: table(u_src) = g(u_dst(u_src)), where u_src = u_dst s(u_dst)^2 is GREEN's radial map
+                (lens.Lens, destination -> source, about the same centre), inverted numerically in float64.  A map that is
+                not strictly increasing on [0, 1] is refused.  Red and blue have their own magnifications (lateral CA) and
+                get green's table: the differing CA magnifications are IGNORED here.  A plane whose own map puts a site at
+                u_dst + du gets the gain of u_dst, off by at most max|g'| du: for the tests' polynomial (0.3, 0.1, 0, 0, 0),
+                max|g'| = 0.5, under planes of 1.01 / 1.0 / 0.99 (the largest CA the tests write) du <= 0.0204 and the
+                gain error is at most 0.0102, one percent of the gain (tests/test_finish_host.py computes both)."""
+
+    def __init__(self, k, centre, after_warp=False):
+        try:
+            kk = tuple(float(v) for v in k)
+            c = tuple(float(v) for v in centre)
+        except (TypeError, ValueError):
+            raise InvalidOptionError("vignette", (k, centre), "five numbers (k0..k4) and a centre (cx, cy) are expected") from None
+        if len(kk) != 5 or len(c) != 2:
+            raise InvalidOptionError("vignette", (k, centre), "five numbers (k0..k4) and a centre (cx, cy) are expected")
+        if not all(math.isfinite(v) for v in kk + c):
+            raise InvalidOptionError("vignette", (k, centre), "the coefficients and the centre must be finite")
+        if max(abs(v) for v in c) > RADIAL_CENTRE_MAX // 2:
+            raise InvalidOptionError("vignette", centre, "the centre lies at most 2^23 pixels from the origin")
+        self.k, self.centre, self.after_warp = kk, c, bool(after_warp)
+        lo, hi = self.range()
+        if not lo > 0.0 or not hi < 16.0:
+            raise InvalidOptionError("vignette", k, f"the gain spans {lo} .. {hi} on [0, 1]: it must stay inside (0, 16)")
+        self._dev = {}          # (device, lens key) -> DeviceBuffer of the table
+
+    def __repr__(self):
+        return f"RadialGain(k={list(self.k)}, centre={self.centre}{', after_warp=True' if self.after_warp else ''})"
+
+    def gain(self, u):
+        """g(u), float64"""
+        u = np.asarray(u, np.float64)
+        k0, k1, k2, k3, k4 = self.k
+        return 1.0 + u * (k0 + u * (k1 + u * (k2 + u * (k3 + u * k4))))
+
+    def range(self):
+        """(min, max) of g over 4097 points of [0, 1]"""
+        g = self.gain(np.linspace(0.0, 1.0, 4097))
+        return float(g.min()), float(g.max())
+
+    def centre2(self):
+        """the centre in half pixels: round-half-up(2 cx), round-half-up(2 cy)"""
+        return int(_half_up(2.0 * self.centre[0])), int(_half_up(2.0 * self.centre[1]))
+
+    @staticmethod
+    def source_map(lens):
+        """(u_dst, u_src) over [0, 1]: green's radial map u_src = u_dst s(u_dst)^2 on _INVERT_SAMPLES intervals; raises
+        InvalidOptionError when it is not strictly increasing"""
+        from .lens import check_lens
+        k0, k1, k2, k3 = check_lens(lens).k[1]
+        ud = np.linspace(0.0, 1.0, _INVERT_SAMPLES + 1)
+        s = ((k3 * ud + k2) * ud + k1) * ud + k0
+        us = ud * s * s
+        if not (s > 0.0).all() or not (np.diff(us) > 0.0).all():
+            raise InvalidOptionError("lens", lens, "green's radial map is not monotone on [0, 1]: the vignette cannot be moved in front of it")
+        return ud, us
+
+    def table(self, lens=None):
+        """the RADIAL_NODES Q12 uint16 nodes at u = i / 1024: round-half-up(4096 g(u)), at most 65535.  `lens`: the lens.Lens
+        applied behind the gain, or None; it matters only with `after_warp` (see the class)."""
+        u = np.arange(RADIAL_NODES, dtype=np.float64) / float(RADIAL_NODES - 1)
+        if lens is not None and self.after_warp:
+            ud, us = self.source_map(lens)
+            u = np.interp(u, us, ud)        # (a source radius whose destination lies outside the frame takes the corner's gain)
+        return np.minimum(_half_up(self.gain(u) * float(SITE_GAIN_ONE)), 65535.0).astype(np.uint16)
+
+    def check_shape(self, shape):
+        """the centre against an H x W mosaic: the farthest corner within the kernel's range"""
+        h, w = int(shape[0]), int(shape[1])
+        cx2, cy2 = self.centre2()
+        d = radial_d2max(h, w, cx2, cy2)
+        if not 1 <= d < RADIAL_D2_MAX:
+            raise InvalidOptionError("vignette", self.centre, f"the farthest corner of a {h} x {w} mosaic lies {d} half pixels squared away (1 to 2^40 - 1)")
+        return cx2, cy2
+
+    def struct(self, shape, lens=None):
+        """(mi_radial_gain_t over host memory, the table it points into)"""
+        cx2, cy2 = self.check_shape(shape)
+        t = np.ascontiguousarray(self.table(lens))
+        return _lib.RadialGainStruct(cx2, cy2, t.ctypes.data), t
+
+    def prepared(self, shape, device=0, lens=None):
+        """mi_radial_gain_t whose table is resident on `device` (uploaded at first use, held until close())"""
+        cx2, cy2 = self.check_shape(shape)
+        from .lens import check_lens
+        key = (device, None if lens is None or not self.after_warp else check_lens(lens).k[1])
+        if key not in self._dev:
+            _lib.require_device()
+            t = np.ascontiguousarray(self.table(lens))
+            buf = _lib.DeviceBuffer(t.nbytes, device)
+            buf.upload(t)
+            self._dev[key] = buf
+        return _lib.RadialGainStruct(cx2, cy2, self._dev[key].ptr)
+
+    def close(self):
+        """free the device tables (not before every kernel queued with them has run)"""
+        for buf in self._dev.values():
+            buf.free()
+        self._dev = {}
+
+
+class Finish:
+    """What a raw file says about the finished picture (csrc/kernels_finish.hpp; tests/finish_restatement.py is the definition):
+
+    vignette     None or a RadialGain, applied to the linear mosaic behind the site corrections and ahead of the calibration
+                 -- not to the developed frame: Develop's tone curve is not linear, a gain behind it would be wrong
+    crop         None or (y, x, h, w) in the coordinates of the unpacked mosaic (a DNG's DefaultCropOrigin / DefaultCropSize)
+    orientation  the TIFF orientation 1..8, applied to the cropped frame:  1: a  2: a[:, ::-1]  3: a[::-1, ::-1]  4: a[::-1]
+                 5: a.transpose(1, 0, 2)  6: np.rot90(a, -1)  7: a[::-1, ::-1].transpose(1, 0, 2)  8: np.rot90(a, 1)
+    skipped      a tuple of (name, reason): what a file carried and this object does not apply
+    applies      the names, as `DngFrame.ignored` spells them, of what this object applies (None: derived from the above)
+
+    Crop and orientation are the LAST stage, behind the lens correction: one out-of-place pass over the developed frame."""
+
+    def __init__(self, vignette=None, crop=None, orientation=1, skipped=(), applies=None):
+        if vignette is not None and not isinstance(vignette, RadialGain):
+            raise InvalidOptionError("vignette", vignette, "None or a shinestacker_amd.dng.RadialGain is expected")
+        if crop is not None:
+            try:
+                c = tuple(crop)
+            except TypeError:
+                c = ()
+            if len(c) != 4 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in c):
+                raise InvalidOptionError("crop", crop, "None or four ints (y, x, h, w) are expected")
+            crop = tuple(int(v) for v in c)
+            if crop[0] < 0 or crop[1] < 0 or crop[2] < 1 or crop[3] < 1:
+                raise InvalidOptionError("crop", crop, "the origin is not negative and the size at least 1 x 1")
+        if isinstance(orientation, bool) or not isinstance(orientation, (int, np.integer)) or not 1 <= orientation <= 8:
+            raise InvalidOptionError("orientation", orientation, "a TIFF orientation 1 to 8 is expected")
+        self.vignette, self.crop, self.orientation = vignette, crop, int(orientation)
+        self.skipped = tuple((str(n), str(r)) for n, r in skipped)
+        if applies is None:
+            applies = (["FixVignetteRadial"] if vignette is not None else []) + (["DefaultCropOrigin", "DefaultCropSize"] if crop is not None else [])
+        self.applies = tuple(applies)
+
+    def __repr__(self):
+        return f"Finish(vignette={self.vignette!r}, crop={self.crop}, orientation={self.orientation}, skipped={list(self.skipped)})"
+
+    @property
+    def empty(self):
+        return self.vignette is None and self.crop is None and self.orientation == 1
+
+    def crop_for(self, shape):
+        """(y, x, h, w) on an H x W frame: the crop checked against it, or the whole frame"""
+        h, w = int(shape[0]), int(shape[1])
+        if self.crop is None:
+            return 0, 0, h, w
+        y, x, ch, cw = self.crop
+        if y + ch > h or x + cw > w:
+            raise InvalidOptionError("crop", self.crop, f"it lies outside the {h} x {w} frame")
+        return self.crop
+
+    def geometry(self, shape):
+        """True when crop and orientation change an H x W frame at all"""
+        return self.orientation != 1 or self.crop_for(shape) != (0, 0, int(shape[0]), int(shape[1]))
+
+    def finished_shape(self, shape):
+        """(H', W') of an H x W frame behind crop and orientation"""
+        _, _, ch, cw = self.crop_for(shape)
+        return (cw, ch) if self.orientation >= 5 else (ch, cw)
+
+    def close(self):
+        if self.vignette is not None:
+            self.vignette.close()
+
+
+def check_finish(finish):
+    if not isinstance(finish, Finish):
+        raise InvalidOptionError("finish", finish, '"auto", None or a shinestacker_amd.dng.Finish is expected')
+    return finish
+
+
+def resolve_finish(frame, finish):
+    """None, the frame's own ("auto") or the given Finish; one that holds nothing counts as None"""
+    if isinstance(finish, str):
+        if finish != "auto":
+            raise InvalidOptionError("finish", finish, '"auto", None or a dng.Finish is expected')
+        finish = None if frame is None else frame.finish
+    elif finish is not None:
+        check_finish(finish)
+    return None if finish is None or finish.empty else finish
+
+
+def _fix_vignette_radial(body, h, w):
+    """a FixVignetteRadial opcode's data -- seven big-endian doubles k0..k4, cx, cy, the centre in [0, 1] of the image placed as
+    `_warp_rectilinear` places its own -- as a RadialGain, or a str: the reason it is skipped"""
+    if len(body) < 56:
+        return f"a body of {len(body)} bytes is shorter than its seven doubles"
+    vals = struct.unpack(">7d", body[:56])
+    if not all(math.isfinite(v) for v in vals):
+        return "a coefficient or the centre is not finite"
+    try:
+        return RadialGain(vals[:5], (vals[5] * (w - 1), vals[6] * (h - 1)))
+    except InvalidOptionError as exc:
+        return str(exc)
+
+
+def _file_finish(t, rawifd, ifd0, ops3, layout, lens, orientation):
+    """the Finish of a file: FixVignetteRadial of OpcodeList3 (`ops3`), DefaultCropOrigin / DefaultCropSize, Orientation"""
+    h, w = layout.height, layout.width
+    skipped = []
+
+    def get(tag):
+        for c in (rawifd, ifd0):
+            if tag in c:
+                return t.values(c[tag])
+        return None
+
+    vignette = None
+    where = [i for i, (oid, _) in enumerate(ops3) if oid == 3]
+    warps = [i for i, (oid, _) in enumerate(ops3) if oid == 1]
+    if where:
+        name = OPCODE_NAMES[3]
+        scale = get(50718)
+        got = _fix_vignette_radial(ops3[where[0]][1], h, w)
+        if len(where) > 1:
+            got = "a second FixVignetteRadial is present"
+        elif scale is not None and any(float(v) != 1.0 for v in scale):
+            got = f"the file has DefaultScale = {tuple(scale)}: the radius is stated for the scaled frame"
+        elif not isinstance(got, str) and any(i > where[0] for i in warps):
+            got = "it stands before the WarpRectilinear: the gain is stated for a frame this reader never holds"
+        elif not isinstance(got, str) and warps:
+            got.after_warp = True
+            if lens is not None:
+                lc = lens.resolved_centre(h, w)
+                if max(abs(lc[0] - got.centre[0]), abs(lc[1] - got.centre[1])) > 0.5:
+                    got = f"its centre {got.centre} is not the WarpRectilinear's {lc}: the warp is inverted about one centre"
+                else:
+                    try:
+                        got.source_map(lens)
+                    except InvalidOptionError:
+                        got = "the WarpRectilinear's radial map is not monotone on [0, 1]: the gain cannot be moved in front of it"
+        if not isinstance(got, str):
+            try:
+                got.check_shape((h, w))
+            except InvalidOptionError as exc:
+                got = str(exc)
+        if isinstance(got, str):
+            skipped.append((name, got))
+        else:
+            vignette = got
+    crop = None
+    origin, size = get(50719), get(50720)
+    if size is not None or origin is not None:
+        names = [TAG_NAMES[tag] for tag, v in ((50719, origin), (50720, size)) if v is not None]
+        why = None
+        if size is None:
+            why = "DefaultCropOrigin without a DefaultCropSize"
+        else:
+            origin = (0, 0) if origin is None else origin
+            vals = [float(v) for v in tuple(origin) + tuple(size)]
+            if len(origin) != 2 or len(size) != 2:
+                why = f"{len(origin)} and {len(size)} values: two each (horizontal, vertical) are expected"
+            elif not all(math.isfinite(v) and v == math.floor(v) for v in vals):
+                why = f"origin {tuple(origin)}, size {tuple(size)}: a value that is not integral"
+            else:
+                x, y, cw, ch = (int(v) for v in vals)
+                if x < 0 or y < 0 or cw < 1 or ch < 1 or x + cw > w or y + ch > h:
+                    why = f"the rectangle (x {x}, y {y}, {cw} x {ch}) lies outside the {h} x {w} frame"
+                else:
+                    crop = (y, x, ch, cw)
+        if why is not None:
+            skipped += [(n, why) for n in names]
+    applies = ([OPCODE_NAMES[3]] if vignette is not None else []) + ([TAG_NAMES[tag] for tag, v in ((50719, get(50719)), (50720, size)) if v is not None]
+                                                                   if crop is not None else [])
+    return Finish(vignette, crop, orientation, skipped=skipped, applies=applies)
+
+
 # ---------------------------------------------------------------- the TIFF structure
 class _Tiff:
     def __init__(self, path, data):
@@ -921,7 +1239,7 @@ def read(path):
 
     # what is in the file and not applied
     ignored = [TAG_NAMES[tag] for tag in IGNORED_TAGS if tag in rawifd or tag in ifd0]
-    lens, ops2 = None, []
+    lens, ops2, ops3 = None, [], []
     for tag in (51008, 51009, 51022):
         if tag not in rawifd and tag not in ifd0:
             continue
@@ -929,6 +1247,8 @@ def read(path):
         ops = _opcodes(t.raw((rawifd if tag in rawifd else ifd0)[tag]), name, path)
         if tag == 51009:
             ops2 = ops
+        if tag == 51022:
+            ops3 = ops
         if tag != 51022:
             ignored.append(name)
         for oid, body in ops:
@@ -940,8 +1260,11 @@ def read(path):
                 oname = "WarpRectilinear (tangential terms)"
             ignored.append(oname)
     orientation = int(_one(t, ifd0, 274, _one(t, rawifd, 274, 1)))
+    if not 1 <= orientation <= 8:
+        raise InvalidOptionError("Orientation", orientation, "valid values are 1 to 8")
     corrections = _site_corrections(t, rawifd, ifd0, ops2, layout, black, path)
-    return DngFrame(path, layout, span, cfa, develop, lens, orientation, ignored, corrections)
+    finish = _file_finish(t, rawifd, ifd0, ops3, layout, lens, orientation)
+    return DngFrame(path, layout, span, cfa, develop, lens, orientation, ignored, corrections, finish)
 
 
 def _warp_rectilinear(body, h, w, path):
@@ -1073,10 +1396,16 @@ def _check_frame(frame):
     return frame
 
 
-def unpack(frame, device=0, corrections=None):
+def unpack(frame, device=0, corrections=None, finish=None):
     """The cropped H x W mosaic of a DngFrame as a NumPy array of its dtype: span up, raw_unpack or raw_ljpeg, mosaic down.
     A lossless-JPEG frame one of whose streams did not decode raises ImageLoadError.  `corrections`: None, "auto" (the
-    frame's own) or a SiteCorrections, applied to the unpacked mosaic (demosaic.correct_sites)."""
+    frame's own) or a SiteCorrections, applied to the unpacked mosaic (demosaic.correct_sites).  `finish`: None, "auto" or
+    a Finish -- its VIGNETTE only, behind the corrections (demosaic.radial_gain; no lens follows here: the table is the
+    polynomial itself); crop and orientation belong to the developed frame (`develop`)."""
+    fin = resolve_finish(_check_frame(frame), finish)
+    if fin is not None and fin.vignette is not None:
+        from .demosaic import radial_gain
+        return radial_gain(unpack(frame, device, corrections), frame.cfa, fin.vignette, device=device)
     sc = resolve_corrections(_check_frame(frame), corrections)
     if sc is not None:
         from .demosaic import correct_sites
@@ -1167,28 +1496,40 @@ def _resolve(frame, develop, lens):
     return develop, lens
 
 
-def develop(frame, develop="auto", lens="auto", calibration=None, device=0, corrections=None):
+def develop(frame, develop="auto", lens="auto", calibration=None, device=0, corrections=None, finish=None):
     """A DngFrame -> H x W x 3 BGR of its dtype: unpack, then `debayer` with the frame's own Cfa.  `develop`, `lens`: "auto"
     takes frame.develop / frame.lens, None switches the step off, an object overrides it.  `calibration`: a
     demosaic.Calibration applied to the unpacked mosaic first.  `corrections`: None, "auto" or a SiteCorrections -- the
-    file's site corrections, ahead of the calibration."""
+    file's site corrections, ahead of the calibration.  `finish`: None, "auto" or a Finish -- the vignette gain behind the
+    corrections, crop and orientation last: the result is then H' x W' x 3 (`DngFrame.finished_shape`)."""
     dev, ln = _resolve(_check_frame(frame), develop, lens)
     sc = resolve_corrections(frame, corrections)
+    fin = resolve_finish(frame, finish)
+    if fin is not None:
+        try:
+            return debayer(unpack(frame, device), frame.cfa, develop=dev, device=device, calibration=calibration, lens=ln, corrections=sc,
+                           finish=fin)
+        finally:
+            if fin is frame.finish:
+                fin.close()     # (the file's own table: debayer has waited for the device)
     if sc is not None:
         return debayer(unpack(frame, device), frame.cfa, develop=dev, device=device, calibration=calibration, lens=ln, corrections=sc)
     return debayer(unpack(frame, device), frame.cfa, develop=dev, device=device, calibration=calibration, lens=ln)
 
 
-def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None, device=0, corrections=None):
+def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None, device=0, corrections=None, finish=None):
     """Read the n DNG files (equal cropped shape and dtype), upload their spans and unpack and demosaic them side by side
     into `dev_out` (device pointer, n x H x W x 3 of their dtype): exactly what pipeline.align_and_stack_device(dev_frames,
     ...) takes, as demosaic.debayer_frames_device does for mosaics.  Waits for the device.  Returns (H, W, dtype).
-    `corrections`: None, "auto" (each file's own) or a SiteCorrections, applied in place behind the unpack."""
+    `corrections`: None, "auto" (each file's own) or a SiteCorrections, applied in place behind the unpack.
+    `finish`: None, "auto" (each file's own) or a Finish: the frames in `dev_out` are then n x H' x W' x 3, the finished
+    shape, which every file must share, and (H', W', dtype) is returned."""
     if len(paths) == 0:
         raise ValueError("no files")
     _lib.require_device()
     first = None
-    stage = scratch = None
+    stage = scratch = fscratch = None
+    out_shape = None
     try:
         for i, p in enumerate(paths):
             frame = read(p)
@@ -1202,6 +1543,16 @@ def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None,
             dev, ln = _resolve(frame, develop, lens)
             if ln is not None and scratch is None:
                 scratch = _lib.DeviceBuffer(frame_bytes, device)
+            fin = resolve_finish(frame, finish)
+            if finish is not None:
+                shape = frame.shape if fin is None else fin.finished_shape(frame.shape)
+                if out_shape is None:
+                    out_shape = shape
+                elif shape != out_shape:
+                    raise InvalidOptionError("paths", p, f"a frame finished to {shape} among ones finished to {out_shape}")
+                out_bytes = out_shape[0] * out_shape[1] * 3 * frame.dtype.itemsize
+                if fin is not None and fscratch is None:
+                    fscratch = _lib.DeviceBuffer(frame_bytes, device)
             up = _Staged(frame, device)
             try:
                 up.unpack_into(frame.layout, stage.ptr, device)
@@ -1209,8 +1560,12 @@ def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None,
                 if sc is not None:
                     from .demosaic import correct_sites_device
                     correct_sites_device(stage.ptr, h, w, frame.dtype, frame.cfa, sc, device=device)
-                debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, frame.dtype, frame.cfa, device=device, develop=dev,
-                               calibration=calibration, lens=ln, lens_scratch=scratch)
+                if fin is not None:
+                    debayer_device(stage.ptr, dev_out + i * out_bytes, h, w, frame.dtype, frame.cfa, device=device, develop=dev,
+                                   calibration=calibration, lens=ln, lens_scratch=scratch, finish=fin, finish_scratch=fscratch)
+                else:
+                    debayer_device(stage.ptr, dev_out + i * frame_bytes, h, w, frame.dtype, frame.cfa, device=device, develop=dev,
+                                   calibration=calibration, lens=ln, lens_scratch=scratch)
                 # the stage and the staged span are reused / freed: the null stream's kernels must be through first
                 _lib.check(_lib.load().mi_device_synchronize(device))
                 up.check_status()
@@ -1218,9 +1573,12 @@ def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None,
                 up.buf.free()
                 if isinstance(corrections, str) and frame.corrections is not None:
                     frame.corrections.close()     # (the device was waited for above, or nothing was queued)
+                if isinstance(finish, str):
+                    frame.finish.close()
     finally:
-        if stage is not None:
-            stage.free()
-        if scratch is not None:
-            scratch.free()
+        for buf in (stage, scratch, fscratch):
+            if buf is not None:
+                buf.free()
+    if out_shape is not None:
+        return out_shape[0], out_shape[1], first.dtype
     return h, w, first.dtype

@@ -318,10 +318,12 @@ class PyramidStack(BaseStackAlgo):
             if self.raw is not None and _is_dng(img_path):
                 frame = decoded.result() if decoded is not None else self._read_file(img_path)
                 updated = metadata is None
+                fin = self.raw.finish_for(frame)
+                shape = frame.shape if fin is None else fin.finished_shape(frame.shape)   # what the stack sees
                 if updated:
-                    metadata = (frame.shape, frame.dtype)
-                elif frame.shape != metadata[0][:2]:
-                    raise ShapeError(metadata[0], frame.shape)
+                    metadata = (shape, frame.dtype)
+                elif shape != metadata[0][:2]:
+                    raise ShapeError(metadata[0], shape)
                 elif frame.dtype != metadata[1]:
                     raise BitDepthError(metadata[1], frame.dtype)
                 if updated:
@@ -352,14 +354,17 @@ class PyramidStack(BaseStackAlgo):
 
     def _push_raw(self, stack, frame):
         """one DngFrame into the stack under self.raw.  Without a lens: Stack.push_packed.  With one (the push has no lens
-        path): the frame is unpacked, demosaiced and lens-corrected on the device, then pushed from there, before it is fused."""
+        path): the frame is unpacked, demosaiced and lens-corrected on the device, then pushed from there, before it is fused.
+        A finish (dng.Finish: vignette, crop, orientation) takes the same route: unpack, debayer, [lens], finish, push -- the
+        handle was created with the finished shape."""
         raw = self.raw
         dev, ln = raw.develop_for(frame), raw.lens_for(frame)
         if dev is not None and dev is frame.develop:     # files of one camera share one Develop: one tone table on the device
             dev = self._raw_develops.setdefault(dev.matrix_q, dev)
         from .dng import resolve_corrections
         sc = resolve_corrections(frame, raw.corrections)
-        if ln is None:
+        fin = raw.finish_for(frame)
+        if ln is None and fin is None:
             if raw.corrections is not None:
                 stack.set_site_correction(sc)       # (None clears what an earlier file of the folder set)
             stack.push_packed(frame, develop=dev, calibration=raw.calibration)
@@ -371,9 +376,14 @@ class PyramidStack(BaseStackAlgo):
         up = _Staged(frame, self.device)
         mosaic, bgr, scratch = (_lib.DeviceBuffer(nb, self.device), _lib.DeviceBuffer(3 * nb, self.device),
                                 _lib.DeviceBuffer(3 * nb, self.device))
+        fscratch = None if fin is None else _lib.DeviceBuffer(3 * nb, self.device)
         try:
             up.unpack_into(frame.layout, mosaic.ptr, self.device)
-            if sc is None:
+            if fin is not None:     # (bgr then holds the finished frame: no larger than the developed one)
+                debayer_device(mosaic.ptr, bgr.ptr, h, w, frame.dtype, frame.cfa, device=self.device, develop=dev,
+                               calibration=raw.calibration, lens=ln, lens_scratch=scratch, corrections=sc, finish=fin,
+                               finish_scratch=fscratch)
+            elif sc is None:
                 debayer_device(mosaic.ptr, bgr.ptr, h, w, frame.dtype, frame.cfa, device=self.device, develop=dev,
                                calibration=raw.calibration, lens=ln, lens_scratch=scratch)
             else:
@@ -384,10 +394,12 @@ class PyramidStack(BaseStackAlgo):
             stack.push_frames_device(bgr.ptr, 1)
             stack.sync()                                                 # ... and the handle's, ahead of the buffers' release
         finally:
-            for b in (up.buf, mosaic, bgr, scratch):
+            for b in (up.buf, mosaic, bgr, scratch) + (() if fscratch is None else (fscratch,)):
                 b.free()
             if sc is not None and sc is frame.corrections:
                 sc.close()      # (the file's own tables: nothing queued reads them any more)
+            if fin is not None and fin is frame.finish:
+                fin.close()
 
     def focus_stack_arrays(self, frames, mosaic=None, develop=None, calibration=None):
         """In-memory variant (no file I/O): `frames` is a sequence of H x W x 3 uint8/uint16
