@@ -668,17 +668,44 @@ class Stack:
                 check(load().mi_stack_push_frame(self._h, a.ctypes.data, a.strides[0]))
                 return
             a = np.ascontiguousarray(a)
+        lib = load()
+        self._push_host(lambda pinned: (lib.mi_stack_push_frame_pinned if pinned else lib.mi_stack_push_frame)(self._h, a.ctypes.data, 0),
+                        a, zero_copy)
+
+    def _push_host(self, push, a, zero_copy):
+        """the tail of every host push: `push(1)` straight out of the array `a` where `zero_copy` asks for it and `a` is
+        pinned -- the array is then kept until its upload is waited for -- and else, or when the library does not see
+        pinned memory there, the copying `push(0)`"""
         if zero_copy and is_pinned(a):
-            rc = load().mi_stack_push_frame_pinned(self._h, a.ctypes.data, 0)
+            rc = push(1)
             if rc == MI_OK:
-                self._inflight = getattr(self, "_inflight", [])
                 self._inflight.append(a)
                 if len(self._inflight) > 64:
                     self.wait_uploads(32)
                 return
             if rc != MI_ERR_INVALID:     # MI_ERR_INVALID: the library does not see pinned memory there (stale record)
                 check(rc)
-        check(load().mi_stack_push_frame(self._h, a.ctypes.data, 0))
+        check(push(0))
+
+    @staticmethod
+    def _keep(kept, obj):
+        """`obj` stays alive in the list `kept`, once (by identity: the objects hold arrays and do not compare)"""
+        if not any(x is obj for x in kept):
+            kept.append(obj)
+
+    def _prepared(self, shape, cfa, develop, calibration):
+        """(cal, d, sites, n_sites): the structs and the device site list of push_mosaic / push_packed's `calibration` and
+        `develop`, None (and 0) where one is absent; the handle keeps both objects, whose device tables the queued kernels read"""
+        from .demosaic import check_calibration, check_develop
+        cal = d = sites = None
+        n_sites = 0
+        if calibration is not None:
+            cal = check_calibration(calibration).prepared(shape, self.in_dtype, cfa, self.device)
+            self._keep(self._calibrations, calibration)
+        if develop is not None:
+            d, sites, n_sites = check_develop(develop).prepared(shape, self.in_dtype, self.device)
+            self._keep(self._develops, develop)
+        return cal, d, sites, n_sites
 
     def set_site_correction(self, corrections):
         """The site corrections (a dng.SiteCorrections, or None to clear) every later push_mosaic / push_packed of this
@@ -729,46 +756,24 @@ class Stack:
             raise ValueError(f"mosaic dtype {a.dtype} != {self.in_dtype}")
         c = cfa.struct(self.in_dtype)
         self._site_for(corrections, cfa)
+        cal, d, sites, n_sites = self._prepared(a.shape, cfa, develop, calibration)
+        lib = load()
         if calibration is not None:
-            from .demosaic import check_calibration, check_develop
-            cal = check_calibration(calibration).prepared(a.shape, self.in_dtype, cfa, self.device)
-            d, sites, n_sites = (None, None, 0) if develop is None else check_develop(develop).prepared(a.shape, self.in_dtype, self.device)
-            self._calibrations = getattr(self, "_calibrations", [])
-            if not any(x is calibration for x in self._calibrations):
-                self._calibrations.append(calibration)
-            if develop is not None and not any(x is develop for x in self._develops):
-                self._develops.append(develop)
-
             def push(ptr, stride, pinned):
-                return load().mi_stack_push_mosaic_calibrated(self._h, ptr, stride, C.byref(c), C.byref(cal),
-                                                              None if d is None else C.byref(d), sites, n_sites, pinned)
+                return lib.mi_stack_push_mosaic_calibrated(self._h, ptr, stride, C.byref(c), C.byref(cal),
+                                                           None if d is None else C.byref(d), sites, n_sites, pinned)
         elif develop is None:
             def push(ptr, stride, pinned):
-                return load().mi_stack_push_mosaic(self._h, ptr, stride, C.byref(c), pinned)
+                return lib.mi_stack_push_mosaic(self._h, ptr, stride, C.byref(c), pinned)
         else:
-            from .demosaic import check_develop
-            d, sites, n_sites = check_develop(develop).prepared(a.shape, self.in_dtype, self.device)
-            self._develops = getattr(self, "_develops", [])
-            if not any(x is develop for x in self._develops):
-                self._develops.append(develop)
-
             def push(ptr, stride, pinned):
-                return load().mi_stack_push_mosaic_developed(self._h, ptr, stride, C.byref(c), C.byref(d), sites, n_sites, pinned)
+                return lib.mi_stack_push_mosaic_developed(self._h, ptr, stride, C.byref(c), C.byref(d), sites, n_sites, pinned)
         if not a.flags.c_contiguous:
             if a.strides[1] == a.itemsize and a.strides[0] > 0:
                 check(push(a.ctypes.data, a.strides[0], 0))
                 return
             a = np.ascontiguousarray(a)
-        if zero_copy and is_pinned(a):
-            rc = push(a.ctypes.data, 0, 1)
-            if rc == MI_OK:
-                self._inflight.append(a)
-                if len(self._inflight) > 64:
-                    self.wait_uploads(32)
-                return
-            if rc != MI_ERR_INVALID:     # MI_ERR_INVALID: the library does not see pinned memory there (stale record)
-                check(rc)
-        check(push(a.ctypes.data, 0, 0))
+        self._push_host(lambda pinned: push(a.ctypes.data, 0, pinned), a, zero_copy)
 
     def push_packed(self, frame, zero_copy=False, develop=None, calibration=None, corrections=None):
         """Push one host frame as the packed sample bytes of its raw file (`frame`: a dng.DngFrame whose cropped size and
@@ -795,18 +800,7 @@ class Stack:
         compressed = getattr(lay, "compression", 1) == 7
         offsets = lay.segments if compressed else lay.offsets     # (descriptors stand where the offsets do)
         entry = load().mi_stack_push_ljpeg if compressed else load().mi_stack_push_packed
-        cal = d = sites = None
-        n_sites = 0
-        if calibration is not None:
-            from .demosaic import check_calibration
-            cal = check_calibration(calibration).prepared((lay.height, lay.width), self.in_dtype, frame.cfa, self.device)
-            if not any(x is calibration for x in self._calibrations):
-                self._calibrations.append(calibration)
-        if develop is not None:
-            from .demosaic import check_develop
-            d, sites, n_sites = check_develop(develop).prepared((lay.height, lay.width), self.in_dtype, self.device)
-            if not any(x is develop for x in self._develops):
-                self._develops.append(develop)
+        cal, d, sites, n_sites = self._prepared((lay.height, lay.width), frame.cfa, develop, calibration)
         span = frame.span
         if self.float_type == MI_F64 or self.params.impl == IMPL_SIMPLE:
             from .dng import host_span
@@ -816,16 +810,7 @@ class Stack:
             return entry(self._h, span.ctypes.data, span.nbytes, offsets.ctypes.data, C.byref(L),
                          None if table is None else table.ctypes.data, C.byref(c), None if cal is None else C.byref(cal),
                          None if d is None else C.byref(d), sites, n_sites, pinned)
-        if zero_copy and is_pinned(span):
-            rc = push(1)
-            if rc == MI_OK:
-                self._inflight.append(span)
-                if len(self._inflight) > 64:
-                    self.wait_uploads(32)
-                return
-            if rc != MI_ERR_INVALID:     # MI_ERR_INVALID: the library does not see pinned memory there (stale record)
-                check(rc)
-        check(push(0))
+        self._push_host(push, span, zero_copy)
 
     def ljpeg_status(self):
         """the status flags (LJPEG_NOCODE, LJPEG_OVERRUN, ...) of every lossless-JPEG frame pushed since the last call, ORed:
@@ -838,9 +823,7 @@ class Stack:
         """block until at most `max_outstanding` of the pinned frames pushed so far are still being uploaded: a producer that
         cycles k pinned buffers calls wait_uploads(k - 1) before it overwrites the oldest"""
         check(load().mi_stack_wait_uploads(self._h, int(max_outstanding)))
-        fl = getattr(self, "_inflight", None)
-        if fl:
-            del fl[:max(0, len(fl) - int(max_outstanding))]
+        del self._inflight[:max(0, len(self._inflight) - int(max_outstanding))]
 
     def push_frames_device(self, dev_ptr, n, frame_stride_bytes=0):
         check(load().mi_stack_push_frames_device(self._h, dev_ptr, int(n),

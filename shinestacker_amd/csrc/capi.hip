@@ -1618,6 +1618,14 @@ int mi_stack_push_frame(mi_stack_t* s, const void* host_bgr, size_t row_stride_b
     return tiled_push_host(s, host_bgr, row_stride_bytes);
 }
 
+// a zero-copy push reads `p` in place: it must lie in pinned host memory (`fn`: the entry point, `what`: the noun of its message)
+static int pinned_probe(const void* p, const char* fn, const char* what) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeHost) return MI_OK;
+    (void)hipGetLastError();
+    return fail(MI_ERR_INVALID, "%s: the %s is not in pinned host memory (mi_host_alloc / mi_host_register)", fn, what);
+}
+
 int mi_stack_push_frame_pinned(mi_stack_t* s, const void* host_bgr, size_t row_stride_bytes) {
     int rc = check_handle(s);
     if (rc) return rc;
@@ -1626,11 +1634,7 @@ int mi_stack_push_frame_pinned(mi_stack_t* s, const void* host_bgr, size_t row_s
     if (s->idx_exported) return fail(MI_ERR_STATE, "the winner indices were exported (index stride > 1): reset the handle before pushing more frames");
     if (s->p.impl != MI_IMPL_TILED || s->f64) return mi_stack_push_frame(s, host_bgr, row_stride_bytes);   // synchronous paths
     MI_HIP(hipSetDevice(s->p.device));
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, host_bgr) != hipSuccess || at.type != hipMemoryTypeHost) {
-        (void)hipGetLastError();
-        return fail(MI_ERR_INVALID, "mi_stack_push_frame_pinned: the frame is not in pinned host memory (mi_host_alloc / mi_host_register)");
-    }
+    if ((rc = pinned_probe(host_bgr, "mi_stack_push_frame_pinned", "frame"))) return rc;
     if ((rc = mosaic_flush(s))) return rc;   // call order
     return tiled_push_host(s, host_bgr, row_stride_bytes, true);
 }
@@ -1674,28 +1678,50 @@ int mi_demosaic(int device, const void* host_mosaic, void* host_bgr, int height,
     return tmp.download(host_bgr, dst, nb * 3);
 }
 
-int mi_stack_push_mosaic(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa, int pinned) {
-    int rc = check_handle(s);
-    if (rc) return rc;
-    if (!host_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
-    if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
-    if ((rc = cfa_check(cfa, s->p.in_dtype))) return rc;
-    const size_t rb = (size_t)s->p.width * dtype_size(s->p.in_dtype);
-    if (row_stride_bytes == 0) row_stride_bytes = rb;
-    if (row_stride_bytes < rb) return fail(MI_ERR_INVALID, "row stride smaller than a row");
+// The raw pushes (mi_stack_push_mosaic*, mi_stack_push_packed, mi_stack_push_ljpeg) check in one order: the source, the
+// arguments below, the handle's state, the pinned source.  `need_calib`, `need_develop`: a null one is an error, not "none";
+// `sites`: the entry point takes defect sites.
+static int raw_args_check(const mi_stack_t* s, const mi_cfa_t* cfa, const mi_calib_t* calib, bool need_calib, const mi_develop_t* develop,
+                          bool need_develop, bool sites, const int32_t* dev_sites, int n_sites) {
+    int rc;
+    if ((rc = cfa_check(cfa, s->p.in_dtype)) || ((calib || need_calib) && (rc = calib_check(calib))) ||
+        ((develop || need_develop) && (rc = develop_check(develop))) || (sites && (rc = sites_check(dev_sites, n_sites, s->p.height, s->p.width))))
+        return rc;
+    return MI_OK;
+}
+// the handle takes a raw frame now; *async: it takes it on the copy stream, so a pinned source is read in place
+static int raw_state_check(const mi_stack_t* s, bool* async) {
     if (s->idx_exported) return fail(MI_ERR_STATE, "the winner indices were exported (index stride > 1): reset the handle before pushing more frames");
     if (s->finished) return fail(MI_ERR_STATE, "push after finish; call mi_stack_reset first");
     MI_HIP(hipSetDevice(s->p.device));
-    const bool async = s->p.impl == MI_IMPL_TILED && !s->f64;
+    *async = s->p.impl == MI_IMPL_TILED && !s->f64;
+    return MI_OK;
+}
+
+// the three mosaic pushes behind check_handle; `fn`: the entry point's name.  Absent arguments are null and not needed.
+static int mosaic_entry(mi_stack_t* s, const char* fn, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa,
+                        const mi_calib_t* calib, bool need_calib, const mi_develop_t* develop, bool need_develop, const int32_t* dev_sites,
+                        int n_sites, int pinned) {
+    int rc;
+    bool async;
+    if (!host_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
+    if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
+    if ((rc = raw_args_check(s, cfa, calib, need_calib, develop, need_develop, need_calib || need_develop, dev_sites, n_sites))) return rc;
+    const size_t rb = (size_t)s->p.width * dtype_size(s->p.in_dtype);
+    if (row_stride_bytes == 0) row_stride_bytes = rb;
+    if (row_stride_bytes < rb) return fail(MI_ERR_INVALID, "row stride smaller than a row");
+    if ((rc = raw_state_check(s, &async))) return rc;
     if (pinned && async) {
         if (row_stride_bytes != rb) return fail(MI_ERR_INVALID, "a pinned mosaic must have contiguous rows");
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, host_mosaic) != hipSuccess || at.type != hipMemoryTypeHost) {
-            (void)hipGetLastError();
-            return fail(MI_ERR_INVALID, "mi_stack_push_mosaic: the mosaic is not in pinned host memory (mi_host_alloc / mi_host_register)");
-        }
+        if ((rc = pinned_probe(host_mosaic, fn, "mosaic"))) return rc;
     }
-    return mosaic_push(s, host_mosaic, row_stride_bytes, *cfa, pinned && async);
+    return mosaic_push(s, MosaicFrame{host_mosaic, row_stride_bytes, nullptr, cfa, pinned && async, calib, develop, dev_sites, n_sites});
+}
+
+int mi_stack_push_mosaic(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa, int pinned) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    return mosaic_entry(s, "mi_stack_push_mosaic", host_mosaic, row_stride_bytes, cfa, nullptr, false, nullptr, false, nullptr, 0, pinned);
 }
 
 // ---------------------------------------------------------------- raw development: defect sites, colour matrix, tone curve
@@ -1756,28 +1782,8 @@ int mi_stack_push_mosaic_developed(mi_stack_t* s, const void* host_mosaic, size_
                                    const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned) {
     int rc = check_handle(s);
     if (rc) return rc;
-    if (!host_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
-    if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
-    if ((rc = cfa_check(cfa, s->p.in_dtype)) || (rc = develop_check(develop)) ||
-        (rc = sites_check(dev_sites, n_sites, s->p.height, s->p.width)))
-        return rc;
-    const size_t rb = (size_t)s->p.width * dtype_size(s->p.in_dtype);
-    if (row_stride_bytes == 0) row_stride_bytes = rb;
-    if (row_stride_bytes < rb) return fail(MI_ERR_INVALID, "row stride smaller than a row");
-    if (s->idx_exported) return fail(MI_ERR_STATE, "the winner indices were exported (index stride > 1): reset the handle before pushing more frames");
-    if (s->finished) return fail(MI_ERR_STATE, "push after finish; call mi_stack_reset first");
-    MI_HIP(hipSetDevice(s->p.device));
-    const bool async = s->p.impl == MI_IMPL_TILED && !s->f64;
-    if (pinned && async) {
-        if (row_stride_bytes != rb) return fail(MI_ERR_INVALID, "a pinned mosaic must have contiguous rows");
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, host_mosaic) != hipSuccess || at.type != hipMemoryTypeHost) {
-            (void)hipGetLastError();
-            return fail(MI_ERR_INVALID, "mi_stack_push_mosaic_developed: the mosaic is not in pinned host memory (mi_host_alloc / mi_host_register)");
-        }
-    }
-    const mi_develop_t d = *develop;
-    return mosaic_push(s, host_mosaic, row_stride_bytes, *cfa, pinned && async, &d, dev_sites, n_sites);
+    return mosaic_entry(s, "mi_stack_push_mosaic_developed", host_mosaic, row_stride_bytes, cfa, nullptr, false, develop, true, dev_sites,
+                        n_sites, pinned);
 }
 
 // ---------------------------------------------------------------- raw calibration frames (kernels_calib.hpp)
@@ -2109,30 +2115,8 @@ int mi_stack_push_mosaic_calibrated(mi_stack_t* s, const void* host_mosaic, size
                                     int pinned) {
     int rc = check_handle(s);
     if (rc) return rc;
-    if (!host_mosaic) return fail(MI_ERR_INVALID, "null mosaic");
-    if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
-    if ((rc = cfa_check(cfa, s->p.in_dtype)) || (rc = calib_check(calib)) || (develop && (rc = develop_check(develop))) ||
-        (rc = sites_check(dev_sites, n_sites, s->p.height, s->p.width)))
-        return rc;
-    const size_t rb = (size_t)s->p.width * dtype_size(s->p.in_dtype);
-    if (row_stride_bytes == 0) row_stride_bytes = rb;
-    if (row_stride_bytes < rb) return fail(MI_ERR_INVALID, "row stride smaller than a row");
-    if (s->idx_exported) return fail(MI_ERR_STATE, "the winner indices were exported (index stride > 1): reset the handle before pushing more frames");
-    if (s->finished) return fail(MI_ERR_STATE, "push after finish; call mi_stack_reset first");
-    MI_HIP(hipSetDevice(s->p.device));
-    const bool async = s->p.impl == MI_IMPL_TILED && !s->f64;
-    if (pinned && async) {
-        if (row_stride_bytes != rb) return fail(MI_ERR_INVALID, "a pinned mosaic must have contiguous rows");
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, host_mosaic) != hipSuccess || at.type != hipMemoryTypeHost) {
-            (void)hipGetLastError();
-            return fail(MI_ERR_INVALID, "mi_stack_push_mosaic_calibrated: the mosaic is not in pinned host memory (mi_host_alloc / mi_host_register)");
-        }
-    }
-    const mi_calib_t c = *calib;
-    mi_develop_t d{};
-    if (develop) d = *develop;
-    return mosaic_push(s, host_mosaic, row_stride_bytes, *cfa, pinned && async, develop ? &d : nullptr, dev_sites, n_sites, &c);
+    return mosaic_entry(s, "mi_stack_push_mosaic_calibrated", host_mosaic, row_stride_bytes, cfa, calib, true, develop, false, dev_sites,
+                        n_sites, pinned);
 }
 
 // ---------------------------------------------------------------- packed raw samples (kernels_unpack.hpp)
@@ -2291,9 +2275,21 @@ int mi_raw_ljpeg(int device, const void* host_span, size_t span_bytes, const mi_
     return tmp.download(host_out, out, nb);
 }
 
+// the part of mi_stack_push_packed and mi_stack_push_ljpeg behind the span's checks
 static int packed_push(mi_stack_t* s, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets, const mi_ljpeg_seg_t* segs,
                        const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_cfa_t* cfa, const mi_calib_t* calib,
-                       const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned);
+                       const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned) {
+    int rc;
+    bool async;
+    if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
+    if (layout->height != s->p.height || layout->width != s->p.width || layout->dtype != s->p.in_dtype)
+        return fail(MI_ERR_INVALID, "layout height, width and dtype must be the handle's (got %dx%d dtype %d for %dx%d dtype %d)", layout->width,
+                    layout->height, layout->dtype, s->p.width, s->p.height, s->p.in_dtype);
+    if ((rc = raw_args_check(s, cfa, calib, false, develop, false, true, dev_sites, n_sites)) || (rc = raw_state_check(s, &async))) return rc;
+    if (pinned && async && (rc = pinned_probe(host_span, segs ? "mi_stack_push_ljpeg" : "mi_stack_push_packed", "span"))) return rc;
+    const PackedSrc pk{host_span, span_bytes, seg_offsets, segs, unpack_nsegs(*layout), layout, host_table};
+    return mosaic_push(s, MosaicFrame{nullptr, 0, &pk, cfa, pinned && async, calib, develop, dev_sites, n_sites});
+}
 
 int mi_stack_push_packed(mi_stack_t* s, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets,
                          const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_cfa_t* cfa, const mi_calib_t* calib,
@@ -2329,39 +2325,6 @@ int mi_stack_ljpeg_status(mi_stack_t* s, uint32_t* flags) {
     MI_HIP(hipMemcpy(flags, m->ljstatus, sizeof(uint32_t), hipMemcpyDeviceToHost));
     MI_HIP(hipMemsetAsync(m->ljstatus, 0, sizeof(uint32_t), s->stream));   // (in order with the next frame's decode kernel)
     return MI_OK;
-}
-
-// the part of mi_stack_push_packed and mi_stack_push_ljpeg behind the span's checks
-static int packed_push(mi_stack_t* s, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets, const mi_ljpeg_seg_t* segs,
-                       const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_cfa_t* cfa, const mi_calib_t* calib,
-                       const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned) {
-    int rc;
-    if (s->p.height < 2 || s->p.width < 2) return fail(MI_ERR_INVALID, "height and width must be >= 2 for a mosaic");
-    if (layout->height != s->p.height || layout->width != s->p.width || layout->dtype != s->p.in_dtype)
-        return fail(MI_ERR_INVALID, "layout height, width and dtype must be the handle's (got %dx%d dtype %d for %dx%d dtype %d)", layout->width,
-                    layout->height, layout->dtype, s->p.width, s->p.height, s->p.in_dtype);
-    if ((rc = cfa_check(cfa, s->p.in_dtype)) || (calib && (rc = calib_check(calib))) || (develop && (rc = develop_check(develop))) ||
-        (rc = sites_check(dev_sites, n_sites, s->p.height, s->p.width)))
-        return rc;
-    if (s->idx_exported) return fail(MI_ERR_STATE, "the winner indices were exported (index stride > 1): reset the handle before pushing more frames");
-    if (s->finished) return fail(MI_ERR_STATE, "push after finish; call mi_stack_reset first");
-    MI_HIP(hipSetDevice(s->p.device));
-    const bool async = s->p.impl == MI_IMPL_TILED && !s->f64;
-    if (pinned && async) {
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, host_span) != hipSuccess || at.type != hipMemoryTypeHost) {
-            (void)hipGetLastError();
-            return fail(MI_ERR_INVALID, "%s: the span is not in pinned host memory (mi_host_alloc / mi_host_register)",
-                        segs ? "mi_stack_push_ljpeg" : "mi_stack_push_packed");
-        }
-    }
-    mi_calib_t c{};
-    if (calib) c = *calib;
-    mi_develop_t d{};
-    if (develop) d = *develop;
-    const mi_raw_layout_t L = *layout;
-    const PackedSrc pk{host_span, span_bytes, seg_offsets, segs, unpack_nsegs(L), &L, host_table};
-    return mosaic_push(s, nullptr, 0, *cfa, pinned && async, develop ? &d : nullptr, dev_sites, n_sites, calib && c.flags ? &c : nullptr, &pk);
 }
 
 int mi_host_alloc(void** ptr, size_t bytes) {

@@ -1,41 +1,35 @@
-// mosaic_host.hpp -- the mosaic stage of a stack handle: host frames arrive as raw Bayer mosaics (a third of the bytes of a BGR
-// frame over the host link) and become BGR frames on the device.  Included by capi.hip after tiled_host.hpp; nothing of it
-// exists until the first mi_stack_push_mosaic of a handle.
+// mosaic_host.hpp -- the mosaic stage of a stack handle: a host frame arrives raw -- as a Bayer mosaic (a third of the bytes of a
+// BGR frame over the host link) or as the packed sample bytes of a raw file (0.75 of a uint16 mosaic's bytes at 12 bits) -- and
+// becomes a BGR frame on the device.  Included by capi.hip after tiled_host.hpp; nothing of it exists until a handle's first raw
+// push or mi_stack_set_site_correction.  Every raw entry point of capi.hip describes its frame as one MosaicFrame and hands it to
+// mosaic_push, which has one path:
 //
-//   stc         the stage's copy stream (the low priority class, as the ring's copy stream and for its reason): the upload of
-//               mosaic k into device slot k % NSLOT, then evCopied[slot].  Uploads run ahead of the kernels by NSLOT mosaics.
-//   demosaic    on s->stream behind evCopied[slot], into frame `pending` of `bgr`, then evSlotFree[slot], which the copy stream
-//               waits for before it overwrites the slot.  The kernel is a twelfth of the copy's time; on the copy stream it
-//               would run in the low class behind another handle's level kernels and hold the next upload back (measured:
-//               docs/studies.md, "raw mosaics").  On s->stream it needs no stream of its own -- the handle stays inside its four
-//               hardware queues -- and is in order with the batch that reads its output.
+//   upload      on stc, the stage's copy stream (the low priority class, as the ring's copy stream and for its reason), into
+//               device slot k % NSLOT, then evCopied[slot]; uploads run ahead of the kernels by NSLOT frames.  A mosaic goes
+//               into slot[slot].  A packed span goes into pslot[slot], laid out [span | segment offsets or lossless-JPEG
+//               descriptors | table], the part behind the span out of the pinned meta[slot].  With site corrections set
+//               (mi_stack_set_site_correction: the setter copies every table into one pinned block, laid out as it will lie
+//               on the device) the block goes up into cslot[slot] ahead of both.  Pinned sources are read in place (evUp, for
+//               mi_stack_wait_uploads); pageable ones go through a ring of pinned bounce buffers (PinRing, copy_rows).
+//   kernels     frame_kernels, on s->stream behind evCopied[slot], into frame `pending` of `bgr`: raw_unpack or raw_ljpeg
+//               (packed spans; the latter ORs every segment's status flags into `ljstatus`, which mi_stack_ljpeg_status reads
+//               and clears), the bad-site kernels and mosaic_site_correct (site corrections), calibration, the defect kernel,
+//               the (developed) demosaic -- all but the last in place on slot[slot].  evSlotFree[slot] follows them, and the
+//               copy stream waits for it before it overwrites any of the slot's buffers.  The kernels are a twelfth of the
+//               copy's time; on the copy stream they would run in the low class behind another handle's level kernels and
+//               hold the next upload back (measured: docs/studies.md, "raw mosaics").  On s->stream they need no stream of
+//               their own -- the handle stays inside its four hardware queues -- and are in order with the batch that reads
+//               their output.  The caller's device tables (tone, sites, dark frame, gains) are read by those kernels.
 //   bgr         bcap BGR frames -- what the ring is for host BGR frames.  A full buffer, or a flush, hands it to dispatch_push
 //               as one batch: the level-0 interior kernel follows the demosaics on s->stream, run_batch's evInput carries them
 //               to the border stream, and tiled_push joins the side streams back into s->stream, so the next demosaic into
-//               `bgr` is ordered behind every reader of the batch -- the two-event handshake tiled_flush keeps with its ring,
-//               here evCopied / evSlotFree per slot and the stream's own order for `bgr`.
-//   develop     mi_stack_push_mosaic_developed: the defect kernel (step 0) on s->stream behind evCopied[slot], in place on the
-//               slot, then the developed demosaic; evSlotFree[slot] follows both, so the copy stream never overwrites a slot
-//               that step 0 still writes.  The caller's device tables (tone, sites) are read by those kernels.
-//   calibrate   mi_stack_push_mosaic_calibrated: the calibration kernel (kernels_calib.hpp) on s->stream behind evCopied[slot], in
-//               place on the slot, ahead of the defect kernel and the (developed) demosaic; evSlotFree[slot] follows all of them.
-//               The caller's dark frame and gain table are read by that kernel.
-//   packed      mi_stack_push_packed: the frame arrives as the packed sample bytes of a raw file (kernels_unpack.hpp), 0.75 of a
-//               uint16 mosaic's bytes at 12 bits.  The span is uploaded on stc into pslot[slot], a packed slot beside the mosaic
-//               slot laid out [span | segment offsets | table], the offsets and the table out of the pinned meta[slot]; the
-//               unpack kernel runs on s->stream behind evCopied[slot] and writes slot[slot], and calibration, defect repair
-//               and the demosaic follow as for a mosaic.  evSlotFree[slot] is behind all of them, so it guards both slots.
-//               The packed slots belong to the stage (not to s->allocs): they grow when a later span is larger, after a wait
-//               for both streams.
-//   ljpeg       mi_stack_push_ljpeg: the same route with a lossless-JPEG span (kernels_ljpeg.hpp): the packed slot holds [span |
-//               descriptors | table], raw_ljpeg takes raw_unpack's place and ORs every segment's status flags into `ljstatus`,
-//               one device word of the stage (mi_stack_ljpeg_status reads and clears it).
-//   site corr   mi_stack_set_site_correction: the file's own per-site corrections (kernels_sitecorr.hpp).  The setter copies
-//               every table into one pinned block of the stage, laid out as it will lie on the device; every later push
-//               uploads the block on stc into cslot[slot] ahead of evCopied[slot], and the bad-site kernels and
-//               mosaic_site_correct run on s->stream behind the upload (or the unpack) and ahead of calibration.  The block is
-//               replaced only after a wait for stc; the device slots grow after a wait for both streams.
-//   order       frames are fused in call order: the first mosaic after host BGR frames flushes the ring (mosaic_push), and
+//               `bgr` is ordered behind every reader of the batch.
+//   growing     pslot, meta, cslot and the span bounce ring belong to the stage (not to s->allocs) and grow when a later frame
+//               needs more (set_realloc), after a wait for whatever reads them: the device slots for both streams, the pinned
+//               blocks for stc.
+//   float-64 and MI_IMPL_SIMPLE handles
+//               one slot, no copy stream: upload, frame_kernels, dispatch_push and a wait, one frame at a time on s->stream.
+//   order       frames are fused in call order: the first raw frame after host BGR frames flushes the ring (mosaic_push), and
 //               every call that takes frames of another kind or reads state flushes this stage first (stack_flush in capi.hip).
 #pragma once
 
@@ -47,21 +41,69 @@
 
 namespace mi {
 
+// free the `n` buffers of a set and allocate them again with `bytes` each, in device memory or (`pinned`) in pinned host memory.
+// The caller has waited for whatever reads them.  A failure leaves capacity 0 and the buffer that failed null.
+inline int set_realloc(void** buf, int n, size_t* cap, size_t bytes, bool pinned) {
+    for (int i = 0; i < n; ++i) {
+        if (buf[i]) (void)(pinned ? hipHostFree(buf[i]) : hipFree(buf[i]));
+        buf[i] = nullptr;
+    }
+    *cap = 0;
+    for (int i = 0; i < n; ++i) {
+        if (pinned) MI_HIP(hipHostMalloc(&buf[i], bytes, hipHostMallocDefault));
+        else if (hipMalloc(&buf[i], bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MI_ERR_NOMEM, "out of device memory");
+        }
+    }
+    *cap = bytes;
+    return MI_OK;
+}
+
+// a ring of pinned bounce buffers for sources in pageable memory, each with the event of the upload out of it
+struct PinRing {
+    static constexpr int N = 3;
+    void* buf[N] = {};
+    hipEvent_t ev[N] = {};
+    size_t cap = 0;
+    long no = 0;
+};
+inline int pin_reserve(PinRing& r, size_t bytes) {
+    int rc = set_realloc(r.buf, PinRing::N, &r.cap, bytes, true);
+    for (int i = 0; !rc && i < PinRing::N; ++i)
+        if (!r.ev[i]) MI_HIP(hipEventCreateWithFlags(&r.ev[i], hipEventDisableTiming));
+    return rc;
+}
+inline void pin_destroy(PinRing& r) {
+    for (int i = 0; i < PinRing::N; ++i) {
+        if (r.buf[i]) (void)hipHostFree(r.buf[i]);
+        if (r.ev[i]) (void)hipEventDestroy(r.ev[i]);
+    }
+}
+// `rows` rows of `row_bytes` (a span: one row) through the ring's next buffer into `dst` on `stc`; the caller's memory is free
+// again on return
+inline int pin_upload(PinRing& r, hipStream_t stc, void* dst, const void* src, size_t src_stride, size_t row_bytes, size_t rows) {
+    const int k = (int)(r.no++ % PinRing::N);
+    MI_HIP(hipEventSynchronize(r.ev[k]));   // bounce buffer free again? (no-op when unused)
+    copy_rows(r.buf[k], src, src_stride, row_bytes, rows, copy_threads(row_bytes * rows));
+    MI_HIP(hipMemcpyAsync(dst, r.buf[k], row_bytes * rows, hipMemcpyHostToDevice, stc));
+    MI_HIP(hipEventRecord(r.ev[k], stc));
+    return MI_OK;
+}
+
 struct MosaicStage {
     static constexpr int NSLOT = 4;
-    static constexpr int NPIN = 3;
     static constexpr int NUP = MI_NUP;
     hipStream_t stc = nullptr;                // copy stream
     void* slot[NSLOT] = {};                   // H x W mosaics on the device
     hipEvent_t evCopied[NSLOT] = {};          // the upload into slot[i] finished
     hipEvent_t evSlotFree[NSLOT] = {};        // the demosaic out of slot[i] finished
     void* bgr = nullptr;                      // bcap BGR frames
-    void* pin[NPIN] = {nullptr, nullptr, nullptr};
-    hipEvent_t evPin[NPIN] = {nullptr, nullptr, nullptr};   // the upload out of pin[i] finished
+    PinRing pin;                              // bounce buffers of mosaics that are not pinned
     hipEvent_t evUp[NUP] = {};                // pinned mosaics: one event per upload, for mi_stack_wait_uploads
     size_t mosaic_bytes = 0;
     int pending = 0;                          // frames demosaiced (or being) into `bgr`, not yet handed over
-    long slot_no = 0, pin_no = 0, up_no = 0;
+    long slot_no = 0, up_no = 0;
     long frames_up_seen = 0;                  // TiledState::up_no at the most recent pinned mosaic
     long run = 0;                             // pinned mosaics since the most recent pinned BGR frame
     // packed spans (mi_stack_push_packed)
@@ -69,10 +111,7 @@ struct MosaicStage {
     size_t pslot_cap = 0;
     void* meta[NSLOT] = {};                   // pinned: the offsets and the table that go with pslot[i]
     size_t meta_cap = 0;
-    void* ppin[NPIN] = {nullptr, nullptr, nullptr};         // bounce buffers of spans that are not pinned
-    hipEvent_t evPPin[NPIN] = {nullptr, nullptr, nullptr};  // the upload out of ppin[i] finished
-    size_t ppin_cap = 0;
-    long ppin_no = 0;
+    PinRing ppin;                             // bounce buffers of spans that are not pinned
     uint32_t* ljstatus = nullptr;             // lossless-JPEG spans: every frame's status flags ORed (in s->allocs)
     // site corrections (mi_stack_set_site_correction)
     bool sc_on = false;
@@ -282,14 +321,8 @@ inline void mosaic_destroy(mi_stack* s) {
     MosaicStage* m = mstage(s);
     if (!m) return;
     if (m->stc) (void)hipStreamSynchronize(m->stc);
-    for (int i = 0; i < MosaicStage::NPIN; ++i) {
-        if (m->pin[i]) (void)hipHostFree(m->pin[i]);
-        if (m->evPin[i]) (void)hipEventDestroy(m->evPin[i]);
-    }
-    for (int i = 0; i < MosaicStage::NPIN; ++i) {
-        if (m->ppin[i]) (void)hipHostFree(m->ppin[i]);
-        if (m->evPPin[i]) (void)hipEventDestroy(m->evPPin[i]);
-    }
+    pin_destroy(m->pin);
+    pin_destroy(m->ppin);
     if (m->pslot[0]) (void)hipStreamSynchronize(s->stream);   // (the unpack kernels read the packed slots)
     for (int i = 0; i < MosaicStage::NSLOT; ++i) {
         if (m->meta[i]) (void)hipHostFree(m->meta[i]);
@@ -353,26 +386,10 @@ inline int mosaic_set_site(mi_stack* s, const mi_site_correct_t* c, const int64_
     MI_HIP(hipSetDevice(s->p.device));
     if (m->stc) MI_HIP(hipStreamSynchronize(m->stc));      // no upload reads the block that is rewritten
     else MI_HIP(hipStreamSynchronize(s->stream));          // (the synchronous route uploads on the handle's stream)
-    if (bytes > m->sc_host_cap) {
-        if (m->sc_host) (void)hipHostFree(m->sc_host);
-        m->sc_host = nullptr;
-        m->sc_host_cap = 0;
-        MI_HIP(hipHostMalloc(&m->sc_host, bytes, hipHostMallocDefault));
-        m->sc_host_cap = bytes;
-    }
+    if (bytes > m->sc_host_cap && (rc = set_realloc(&m->sc_host, 1, &m->sc_host_cap, bytes, true))) return rc;
     if (bytes > m->cslot_cap) {
         MI_HIP(hipStreamSynchronize(s->stream));           // nothing reads what is freed
-        for (int i = 0; i < nslot; ++i) {
-            if (m->cslot[i]) (void)hipFree(m->cslot[i]);
-            m->cslot[i] = nullptr;
-        }
-        m->cslot_cap = 0;
-        for (int i = 0; i < nslot; ++i)
-            if (hipMalloc(&m->cslot[i], bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(MI_ERR_NOMEM, "out of device memory");
-            }
-        m->cslot_cap = bytes;
+        if ((rc = set_realloc(m->cslot, nslot, &m->cslot_cap, bytes, false))) return rc;
     }
     if ((c->flags & MI_SITE_BAD_CONST) && !m->sc_bits && (rc = dev_alloc(s, (void**)&m->sc_bits, defects_const_scratch_bytes(H, W)))) return rc;
     memset(m->sc_host, 0, bytes);
@@ -420,23 +437,51 @@ inline int mosaic_flush(mi_stack* s) {
     return dispatch_push(s, m->bgr, n, t->frame_bytes);
 }
 
-// the kernels of one mosaic, in place on `slot` and then into `frame`: calibration, defect sites, (developed) demosaic.  Without
-// `cal`, `dev` and sites: the plain demosaic alone, exactly the launches of a handle that never heard of the others.
-inline void mosaic_kernels(hipStream_t st, void* slot, void* frame, int H, int W, int dtype, const mi_cfa_t& cfa,
-                           const mi_calib_t* cal, const mi_develop_t* dev, const int32_t* dev_sites, int n_sites) {
-    if (cal) calibrate_launch(st, slot, H, W, dtype, cfa, *cal);
-    defects_launch(st, slot, H, W, dtype, dev_sites, n_sites);   // (n_sites == 0 launches nothing)
-    if (dev) develop_launch(st, slot, frame, H, W, dtype, cfa, *dev);
-    else demosaic_launch(st, slot, frame, H, W, dtype, cfa);
-}
+// the frame one raw push brings (arguments checked by the caller, capi.hip)
+struct MosaicFrame {
+    const void* mosaic = nullptr;           // host: H rows, `row_stride` bytes apart, or ...
+    size_t row_stride = 0;
+    const PackedSrc* pk = nullptr;          // ... the packed span the mosaic is unpacked or decoded from (`mosaic` is not read)
+    const mi_cfa_t* cfa = nullptr;
+    bool pinned = false;                    // the source lies in pinned memory, contiguous: uploaded out of it
+    const mi_calib_t* cal = nullptr;        // calibration, or null
+    const mi_develop_t* dev = nullptr;      // development, or null: the plain demosaic
+    const int32_t* dev_sites = nullptr;     // device: the defect sites
+    int n_sites = 0;
+};
 
-// the kernel that turns the packed slot `ps` ([span | offsets or descriptors | table]) into the mosaic `slot`
-inline void packed_launch(hipStream_t st, const PackedSrc& pk, const char* ps, size_t seg_at, size_t table_at, void* slot, uint32_t* ljstatus) {
-    if (pk.ljseg)
-        ljpeg_launch(st, ps, pk.span_bytes, (const mi_ljpeg_seg_t*)(ps + seg_at), *pk.layout, (const uint16_t*)(ps + table_at), slot, nullptr,
-                     ljstatus);
-    else
-        unpack_launch(st, ps, pk.span_bytes, (const uint32_t*)(ps + seg_at), *pk.layout, (const uint16_t*)(ps + table_at), slot);
+// a packed span's device layout: [span | offsets or descriptors | table], each part 256-byte aligned
+struct PackedAt {
+    size_t seg_at = 0, seg_bytes = 0, table_at = 0, table_bytes = 0;
+    explicit PackedAt(const PackedSrc* pk) {
+        if (!pk) return;
+        seg_at = packed_align(pk->span_bytes);
+        seg_bytes = packed_align(packed_seg_bytes(*pk));
+        table_at = seg_at + seg_bytes;
+        table_bytes = (size_t)pk->layout->table_len * sizeof(uint16_t);
+    }
+};
+
+// the kernels of one frame on `st`: unpack or decode the packed slot `ps` into `slot`, then in place on `slot` the site
+// corrections (tables in the device block `cs`), calibration and the defect sites, then the (developed) demosaic into `frame`.
+// A plain mosaic without site corrections: the demosaic alone, exactly the launches of a handle that never heard of the others.
+inline void frame_kernels(hipStream_t st, const mi_stack* s, const MosaicFrame& f, const char* ps, const void* cs, void* slot, void* frame) {
+    const MosaicStage* m = mstage(s);
+    const int H = s->p.height, W = s->p.width, dtype = s->p.in_dtype;
+    if (f.pk) {
+        const PackedSrc& pk = *f.pk;
+        const PackedAt at(f.pk);
+        if (pk.ljseg)
+            ljpeg_launch(st, ps, pk.span_bytes, (const mi_ljpeg_seg_t*)(ps + at.seg_at), *pk.layout, (const uint16_t*)(ps + at.table_at), slot,
+                         nullptr, m->ljstatus);
+        else
+            unpack_launch(st, ps, pk.span_bytes, (const uint32_t*)(ps + at.seg_at), *pk.layout, (const uint16_t*)(ps + at.table_at), slot);
+    }
+    if (m->sc_on) site_kernels(st, slot, H, W, dtype, *f.cfa, site_at(m, (const char*)cs), m->sc_bits);
+    if (f.cal) calibrate_launch(st, slot, H, W, dtype, *f.cfa, *f.cal);
+    defects_launch(st, slot, H, W, dtype, f.dev_sites, f.n_sites);   // (n_sites == 0 launches nothing)
+    if (f.dev) develop_launch(st, slot, frame, H, W, dtype, *f.cfa, *f.dev);
+    else demosaic_launch(st, slot, frame, H, W, dtype, *f.cfa);
 }
 
 // room for a span of `span_bytes` with `meta_bytes` of offsets and table behind it, in every packed slot the handle uses.
@@ -445,89 +490,46 @@ inline int packed_reserve(mi_stack* s, size_t span_bytes, size_t meta_bytes) {
     MosaicStage* m = mstage(s);
     const int nslot = s->p.impl == MI_IMPL_TILED ? MosaicStage::NSLOT : 1;
     const size_t need = packed_align(span_bytes) + meta_bytes;
+    int rc;
     if (need <= m->pslot_cap && meta_bytes <= m->meta_cap) return MI_OK;
     if (m->stc) MI_HIP(hipStreamSynchronize(m->stc));
     MI_HIP(hipStreamSynchronize(s->stream));
-    if (need > m->pslot_cap) {
-        for (int i = 0; i < nslot; ++i) {
-            if (m->pslot[i]) (void)hipFree(m->pslot[i]);
-            m->pslot[i] = nullptr;
-        }
-        m->pslot_cap = 0;
-        for (int i = 0; i < nslot; ++i)
-            if (hipMalloc(&m->pslot[i], need) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(MI_ERR_NOMEM, "out of device memory");
-            }
-        m->pslot_cap = need;
-    }
-    if (meta_bytes > m->meta_cap) {
-        for (int i = 0; i < nslot; ++i) {
-            if (m->meta[i]) (void)hipHostFree(m->meta[i]);
-            m->meta[i] = nullptr;
-        }
-        m->meta_cap = 0;
-        for (int i = 0; i < nslot; ++i) MI_HIP(hipHostMalloc(&m->meta[i], meta_bytes, hipHostMallocDefault));
-        m->meta_cap = meta_bytes;
-    }
+    if (need > m->pslot_cap && (rc = set_realloc(m->pslot, nslot, &m->pslot_cap, need, false))) return rc;
+    if (meta_bytes > m->meta_cap && (rc = set_realloc(m->meta, nslot, &m->meta_cap, meta_bytes, true))) return rc;
     return MI_OK;
 }
 
-// One host mosaic (arguments checked by mi_stack_push_mosaic / _developed / _calibrated): stage it, start upload and
-// demosaic, return.  `dev`: development (null: the plain demosaic); with `n_sites` > 0 the defect kernel runs in place on the
-// slot, behind the upload and ahead of the demosaic; `cal`: calibration, in place on the slot ahead of both.  `pk`: the frame
-// comes as a packed span (mi_stack_push_packed) -- `host_mosaic` is not read, the span is uploaded into the packed slot and
-// the unpack kernel writes the mosaic slot ahead of everything else.
-inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t& cfa, bool pinned,
-                       const mi_develop_t* dev = nullptr, const int32_t* dev_sites = nullptr, int n_sites = 0,
-                       const mi_calib_t* cal = nullptr, const PackedSrc* pk = nullptr) {
+// One raw host frame: stage it, start its upload and its kernels, return.
+inline int mosaic_push(mi_stack* s, const MosaicFrame& f) {
     TiledState* t = tstate(s);
-    int rc = tiled_flush(s);   // call order: host BGR frames staged before this mosaic are fused first
+    int rc = tiled_flush(s);   // call order: host BGR frames staged before this frame are fused first
     if (rc) return rc;
     if (!mstage(s) && (rc = mosaic_create(s))) return rc;
     MosaicStage* m = mstage(s);
-    const int H = s->p.height, W = s->p.width;
-    const size_t rb = (size_t)W * dtype_size(s->p.in_dtype);
+    const PackedSrc* pk = f.pk;
+    const size_t rb = (size_t)s->p.width * dtype_size(s->p.in_dtype);
     const bool sc = m->sc_on;      // site corrections: the stage's tables go up with this frame
-    if (sc && (rc = site_black_check(cfa.black, m->sc_dmin, m->sc_dmax, s->p.in_dtype))) return rc;
-    // a packed span's device layout: [span | offsets | table]
-    const size_t seg_bytes = pk ? packed_align(packed_seg_bytes(*pk)) : 0;
-    const size_t table_bytes = pk ? (size_t)pk->layout->table_len * sizeof(uint16_t) : 0;
-    const size_t seg_at = pk ? packed_align(pk->span_bytes) : 0, table_at = seg_at + seg_bytes;
-    if (pk && (rc = packed_reserve(s, pk->span_bytes, seg_bytes + table_bytes))) return rc;
+    if (sc && (rc = site_black_check(f.cfa->black, m->sc_dmin, m->sc_dmax, s->p.in_dtype))) return rc;
+    const PackedAt at(pk);
+    if (pk && (rc = packed_reserve(s, pk->span_bytes, at.seg_bytes + at.table_bytes))) return rc;
     if (pk && pk->ljseg && !m->ljstatus) {
         if ((rc = dev_alloc(s, (void**)&m->ljstatus, sizeof(uint32_t)))) return rc;
         MI_HIP(hipMemsetAsync(m->ljstatus, 0, sizeof(uint32_t), s->stream));
     }
-    if (pk && s->p.impl != MI_IMPL_TILED) {
-        // the synchronous route of a packed span: upload, unpack, then as a mosaic below
+    if (s->p.impl != MI_IMPL_TILED) {
+        // float-64 and MI_IMPL_SIMPLE handles: upload, kernels, push, wait -- one frame at a time on the handle's stream
         char* ps = (char*)m->pslot[0];
-        MI_HIP(hipMemcpyAsync(ps, pk->span, pk->span_bytes, hipMemcpyHostToDevice, s->stream));
-        MI_HIP(hipMemcpyAsync(ps + seg_at, packed_seg(*pk), packed_seg_bytes(*pk), hipMemcpyHostToDevice, s->stream));
-        if (table_bytes) MI_HIP(hipMemcpyAsync(ps + table_at, pk->table, table_bytes, hipMemcpyHostToDevice, s->stream));
-        packed_launch(s->stream, *pk, ps, seg_at, table_at, m->slot[0], m->ljstatus);
-        if (sc) {
-            MI_HIP(hipMemcpyAsync(m->cslot[0], m->sc_host, m->sc_bytes, hipMemcpyHostToDevice, s->stream));
-            site_kernels(s->stream, m->slot[0], H, W, s->p.in_dtype, cfa, site_at(m, (const char*)m->cslot[0]), m->sc_bits);
-        }
-        mosaic_kernels(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
+        if (pk) {
+            MI_HIP(hipMemcpyAsync(ps, pk->span, pk->span_bytes, hipMemcpyHostToDevice, s->stream));
+            MI_HIP(hipMemcpyAsync(ps + at.seg_at, packed_seg(*pk), packed_seg_bytes(*pk), hipMemcpyHostToDevice, s->stream));
+            if (at.table_bytes) MI_HIP(hipMemcpyAsync(ps + at.table_at, pk->table, at.table_bytes, hipMemcpyHostToDevice, s->stream));
+        } else MI_HIP(hipMemcpy2DAsync(m->slot[0], rb, f.mosaic, f.row_stride, rb, s->p.height, hipMemcpyHostToDevice, s->stream));
+        if (sc) MI_HIP(hipMemcpyAsync(m->cslot[0], m->sc_host, m->sc_bytes, hipMemcpyHostToDevice, s->stream));
+        frame_kernels(s->stream, s, f, ps, m->cslot[0], m->slot[0], s->frame_dev);
         MI_HIP(hipGetLastError());
         rc = dispatch_push(s, s->frame_dev, 1, t->frame_bytes);
         MI_HIP(hipStreamSynchronize(s->stream));   // (also on failure: the copies read the caller's arrays)
         return rc;
-    }
-    if (s->p.impl != MI_IMPL_TILED) {
-        // float-64 and MI_IMPL_SIMPLE handles: upload, demosaic, push, wait -- one frame at a time on the handle's stream
-        MI_HIP(hipMemcpy2DAsync(m->slot[0], rb, host_mosaic, row_stride_bytes, rb, H, hipMemcpyHostToDevice, s->stream));
-        if (sc) {
-            MI_HIP(hipMemcpyAsync(m->cslot[0], m->sc_host, m->sc_bytes, hipMemcpyHostToDevice, s->stream));
-            site_kernels(s->stream, m->slot[0], H, W, s->p.in_dtype, cfa, site_at(m, (const char*)m->cslot[0]), m->sc_bits);
-        }
-        mosaic_kernels(s->stream, m->slot[0], s->frame_dev, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
-        MI_HIP(hipGetLastError());
-        if ((rc = dispatch_push(s, s->frame_dev, 1, t->frame_bytes))) return rc;
-        MI_HIP(hipStreamSynchronize(s->stream));
-        return MI_OK;
     }
     const int si = (int)(m->slot_no % MosaicStage::NSLOT);
     void* slot = m->slot[si];
@@ -540,74 +542,35 @@ inline int mosaic_push(mi_stack* s, const void* host_mosaic, size_t row_stride_b
         MI_HIP(hipEventSynchronize(m->evCopied[si]));   // (no-op on an event never recorded)
         char* mb = (char*)m->meta[si];
         memcpy(mb, packed_seg(*pk), packed_seg_bytes(*pk));
-        if (table_bytes) memcpy(mb + seg_bytes, pk->table, table_bytes);
-        MI_HIP(hipMemcpyAsync(ps + seg_at, mb, seg_bytes + table_bytes, hipMemcpyHostToDevice, m->stc));
+        if (at.table_bytes) memcpy(mb + at.seg_bytes, pk->table, at.table_bytes);
+        MI_HIP(hipMemcpyAsync(ps + at.seg_at, mb, at.seg_bytes + at.table_bytes, hipMemcpyHostToDevice, m->stc));
     }
-    if (pinned) {
+    // the frame itself: the span into the packed slot, or the mosaic into the mosaic slot
+    void* dst = pk ? (void*)ps : slot;
+    const void* src = pk ? pk->span : f.mosaic;
+    const size_t bytes = pk ? pk->span_bytes : m->mosaic_bytes;
+    if (f.pinned) {
         hipEvent_t& ev = m->evUp[m->up_no % MosaicStage::NUP];
         if (!ev) MI_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         else MI_HIP(hipEventSynchronize(ev));   // (only when more than NUP uploads are in flight)
-        if (pk) MI_HIP(hipMemcpyAsync(ps, pk->span, pk->span_bytes, hipMemcpyHostToDevice, m->stc));
-        else MI_HIP(hipMemcpyAsync(slot, host_mosaic, m->mosaic_bytes, hipMemcpyHostToDevice, m->stc));
+        MI_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, m->stc));
         MI_HIP(hipEventRecord(ev, m->stc));
         if (m->frames_up_seen != t->up_no) { m->frames_up_seen = t->up_no; m->run = 0; }
         m->run++;
         m->up_no++;
-    } else if (pk) {
-        if (pk->span_bytes > m->ppin_cap) {
-            MI_HIP(hipStreamSynchronize(m->stc));   // (no upload reads a bounce buffer that is freed)
-            for (int i = 0; i < MosaicStage::NPIN; ++i) {
-                if (m->ppin[i]) (void)hipHostFree(m->ppin[i]);
-                m->ppin[i] = nullptr;
-            }
-            m->ppin_cap = 0;
-            for (int i = 0; i < MosaicStage::NPIN; ++i) {
-                MI_HIP(hipHostMalloc(&m->ppin[i], pk->span_bytes, hipHostMallocDefault));
-                if (!m->evPPin[i]) MI_HIP(hipEventCreateWithFlags(&m->evPPin[i], hipEventDisableTiming));
-            }
-            m->ppin_cap = pk->span_bytes;
-        }
-        const int k = (int)(m->ppin_no++ % MosaicStage::NPIN);
-        MI_HIP(hipEventSynchronize(m->evPPin[k]));   // bounce buffer free again? (no-op when unused)
-        char* pb = (char*)m->ppin[k];
-        const size_t nb = pk->span_bytes;
-        const int nthr = nb >= ((size_t)32 << 20) ? 4 : 1;
-        const std::function<void(int)> band = [&](int j) {
-            const size_t a = nb * (size_t)j / nthr, b = nb * (size_t)(j + 1) / nthr;
-            memcpy(pb + a, (const char*)pk->span + a, b - a);
-        };
-        if (nthr == 1) band(0);
-        else CopyPool::get().run(nthr, band);
-        MI_HIP(hipMemcpyAsync(ps, pb, nb, hipMemcpyHostToDevice, m->stc));
-        MI_HIP(hipEventRecord(m->evPPin[k], m->stc));
     } else {
-        if (!m->pin[0])
-            for (int i = 0; i < MosaicStage::NPIN; ++i) {
-                MI_HIP(hipHostMalloc(&m->pin[i], m->mosaic_bytes, hipHostMallocDefault));
-                MI_HIP(hipEventCreateWithFlags(&m->evPin[i], hipEventDisableTiming));
-            }
-        const int k = (int)(m->pin_no++ % MosaicStage::NPIN);
-        MI_HIP(hipEventSynchronize(m->evPin[k]));   // bounce buffer free again? (no-op when unused)
-        char* pb = (char*)m->pin[k];
-        // row bands on the copy pool for big mosaics, as tiled_push_host copies big frames
-        const int nthr = m->mosaic_bytes >= ((size_t)32 << 20) ? 4 : 1;
-        const std::function<void(int)> band = [&](int j) {
-            const int y0 = (int)((long)H * j / nthr), y1 = (int)((long)H * (j + 1) / nthr);
-            if (row_stride_bytes == rb) memcpy(pb + (size_t)y0 * rb, (const char*)host_mosaic + (size_t)y0 * rb, rb * (size_t)(y1 - y0));
-            else
-                for (int y = y0; y < y1; ++y) memcpy(pb + (size_t)y * rb, (const char*)host_mosaic + (size_t)y * row_stride_bytes, rb);
-        };
-        if (nthr == 1) band(0);
-        else CopyPool::get().run(nthr, band);
-        MI_HIP(hipMemcpyAsync(slot, pb, m->mosaic_bytes, hipMemcpyHostToDevice, m->stc));
-        MI_HIP(hipEventRecord(m->evPin[k], m->stc));
+        PinRing& ring = pk ? m->ppin : m->pin;   // (mosaics are all of one size: their ring is allocated once)
+        if (bytes > ring.cap) {
+            if (pk) MI_HIP(hipStreamSynchronize(m->stc));   // (no upload reads a bounce buffer that is freed)
+            if ((rc = pin_reserve(ring, bytes))) return rc;
+        }
+        if (pk) rc = pin_upload(ring, m->stc, dst, src, bytes, bytes, 1);
+        else rc = pin_upload(ring, m->stc, dst, src, f.row_stride, rb, (size_t)s->p.height);
+        if (rc) return rc;
     }
     MI_HIP(hipEventRecord(m->evCopied[si], m->stc));
     MI_HIP(hipStreamWaitEvent(s->stream, m->evCopied[si], 0));
-    void* frame = (char*)m->bgr + (size_t)m->pending * t->frame_bytes;
-    if (pk) packed_launch(s->stream, *pk, ps, seg_at, table_at, slot, m->ljstatus);
-    if (sc) site_kernels(s->stream, slot, H, W, s->p.in_dtype, cfa, site_at(m, (const char*)m->cslot[si]), m->sc_bits);
-    mosaic_kernels(s->stream, slot, frame, H, W, s->p.in_dtype, cfa, cal, dev, dev_sites, n_sites);
+    frame_kernels(s->stream, s, f, ps, m->cslot[si], slot, (char*)m->bgr + (size_t)m->pending * t->frame_bytes);
     MI_HIP(hipGetLastError());
     MI_HIP(hipEventRecord(m->evSlotFree[si], s->stream));
     m->pending++;

@@ -18,6 +18,8 @@
 // on disjoint pixels; levels >= 1 and base: st2; payload passes: events per level), so stream order keeps the first-max semantics.
 #pragma once
 
+#include "host_copy.hpp"
+
 namespace mi {
 
 #ifndef MI_NUP
@@ -933,65 +935,6 @@ int tiled_flush(mi_stack* s) {
     return MI_OK;
 }
 
-// Persistent helper threads for the bounce copy of big frames (round 3 spawned three std::threads per frame): workers
-// sleep on a condition variable and take the row bands of ONE copy at a time.
-class CopyPool {
-public:
-    static CopyPool& get() {
-        static CopyPool p;
-        return p;
-    }
-    // runs fn(k) for k = 0 .. parts-1: k = 0 on the caller, the others on the workers; returns when all are done
-    void run(int parts, const std::function<void(int)>& fn) {
-        std::lock_guard<std::mutex> serial(call_mu_);   // one copy at a time (several stacks may push from several threads)
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            fn_ = &fn;
-            next_ = 1;
-            parts_ = parts;
-            pending_ = parts - 1;
-        }
-        cv_.notify_all();
-        fn(0);
-        std::unique_lock<std::mutex> lk(mu_);
-        done_.wait(lk, [&] { return pending_ == 0; });
-        fn_ = nullptr;
-    }
-
-private:
-    CopyPool() {
-        for (int i = 0; i < NW; ++i) th_[i] = std::thread([this] { loop(); });
-    }
-    ~CopyPool() {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : th_) t.join();
-    }
-    void loop() {
-        std::unique_lock<std::mutex> lk(mu_);
-        for (;;) {
-            cv_.wait(lk, [&] { return stop_ || (fn_ && next_ < parts_); });
-            if (stop_) return;
-            const int k = next_++;
-            const auto* fn = fn_;
-            lk.unlock();
-            (*fn)(k);
-            lk.lock();
-            if (--pending_ == 0) done_.notify_all();
-        }
-    }
-    static constexpr int NW = 3;
-    std::thread th_[NW];
-    std::mutex mu_, call_mu_;
-    std::condition_variable cv_, done_;
-    const std::function<void(int)>* fn_ = nullptr;
-    int next_ = 0, parts_ = 0, pending_ = 0;
-    bool stop_ = false;
-};
-
 // One host frame: copy it into a pinned bounce buffer, start the asynchronous upload into the
 // device ring and return (the caller's buffer is free again); a full ring triggers a fused batch.
 // `pinned`: the caller's buffer IS pinned memory (mi_host_alloc / mi_host_register) with contiguous rows: the upload
@@ -1049,20 +992,8 @@ int tiled_push_host(mi_stack* s, const void* host_bgr, size_t row_stride_bytes, 
             const int slot = (int)(t->pin_no % TiledState::NPIN);
             MI_HIP(hipEventSynchronize(t->evPin[slot]));  // bounce buffer free again? (no-op when unused)
             char* pb = (char*)t->pin[slot];
-            // One thread copies ~25 GB/s into pinned memory -- half of what the PCIe link then moves; big
-            // frames are copied by four threads (the caller + the pool's three), in row bands.
-            const int H = s->p.height;
-            const size_t total = rb * (size_t)H;
-            const int nthr = total >= ((size_t)32 << 20) ? 4 : 1;
-            const std::function<void(int)> band = [&](int k) {
-                const int y0 = (int)((long)H * k / nthr), y1 = (int)((long)H * (k + 1) / nthr);
-                if (row_stride_bytes == rb) memcpy(pb + (size_t)y0 * rb, (const char*)host_bgr + (size_t)y0 * rb, rb * (size_t)(y1 - y0));
-                else
-                    for (int y = y0; y < y1; ++y)
-                        memcpy(pb + (size_t)y * rb, (const char*)host_bgr + (size_t)y * row_stride_bytes, rb);
-            };
-            if (nthr == 1) band(0);
-            else CopyPool::get().run(nthr, band);
+            // big frames are copied by four threads, in row bands (host_copy.hpp)
+            copy_rows(pb, host_bgr, row_stride_bytes, rb, (size_t)s->p.height, copy_threads(rb * (size_t)s->p.height));
             MI_HIP(hipMemcpyAsync(dst, pb, t->frame_bytes, hipMemcpyHostToDevice, t->stc));
             MI_HIP(hipEventRecord(t->evPin[slot], t->stc));
             t->pin_no++;

@@ -247,7 +247,8 @@ def two_stage(args):
                 def _map(seed):
                     n = np.random.default_rng(seed).uniform(0.8, 1.6, size=(13, 17))
                     return dng.GainMap(n, spacing=(1.0 / 12, 1.0 / 16))
-                sc = dng.SiteCorrections(black_h=np.arange(W) % 3 - 1, black_v=1 - np.arange(H) % 3, gains=[_map(k) for k in range(4)])
+                # (deltas >= 0: the frames' black level is 0, so black + delta_h + delta_v has no room below)
+                sc = dng.SiteCorrections(black_h=np.arange(W) % 3, black_v=np.arange(H) % 3, gains=[_map(k) for k in range(4)])
 
                 def run_corrected():
                     for s_ in stacks:
