@@ -16,7 +16,7 @@
 //
 // **Nearness, per source pixel (y, x), all float32, each operation rounded on its own:**
 // 1. `t = depth / float32(N - 1)`. This is one correctly rounded divide. `t = 0` when N == 1.
-// 2. `t = min(max(t, 0), 1)`.
+// 2. `t = min(max(t, 0), 1)`.  A NaN depth has nearness `t = 0`, like any depth at or below the first frame.
 // 3. If `near == 'first'`: `t = 1 - t`.
 //
 // **Target:**
@@ -39,7 +39,7 @@
 // Rows are independent. This translation unit is compiled with contraction off, like `kernels_depth.hpp`.
 //
 // (Implementation notes, not part of the specification: max(t, 0) is written `t > 0 ? t : 0`, which also turns -0 into +0 --
-// the same d, and bits that order like the value -- and a NaN depth into nearness 0.)
+// the same d, and bits that order like the value -- and is what gives a NaN depth its nearness 0.)
 //
 // stereo_view_kernel: a workgroup of 256 owns MI_SV_SEG = 512 consecutive targets of one output row.
 //   1. scatter: every source column that can reach the segment or its hole-search halo -- targets [x0 - 66, x0 + 512 + 66),
@@ -48,8 +48,11 @@
 //      the workgroup, so the nearness is not staged in LDS on its own: the winner word per target is the staged state.
 //   2. resolve: a lane per target.  A word that is set gives xs = x' - d(t_win).  A hole walks the words to its left and to
 //      its right, at most MI_SV_HALO = 66 each way and never past the row's ends.  That reach is enough: consecutive
-//      sources land at most 1 + (max d - min d) <= ceil(|shift|) + 2 targets apart, and ceil(|shift|) < W keeps the landing of
-//      the row's last (first) source inside the row, so a side with no winner inside the reach has none at all.
+//      sources land at most 1 + (max d - min d) <= ceil(|shift|) + 2 targets apart, inside the row or past its ends, and the
+//      row's last (first) source lands at most 64 targets left (right) of the row's last (first) target, so a side with no
+//      winner inside the reach has none at all.  A whole row can be left without a winner: rint rounds both half-way ends of d
+//      outward, so max d - min d can be ceil(|shift|) + 1 = W (pivot 0.5, shift 3, W = 4: d = -2 and +2), and a row whose
+//      one half leaves over the left edge and whose other half over the right keeps its own pixels (`at < 0` below).
 //      The source columns go to a second LDS array (2 KB; 4.6 KB with the winner words).
 //   3. copy: the segment's 512 x 3 samples as 4-byte words (bytes at a ragged head and tail): a lane assembles a word from
 //      the 4 / sizeof(T) samples it names -- gathers at x' - d with |d| <= 64, close to coalesced -- and stores it.

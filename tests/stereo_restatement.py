@@ -2,7 +2,8 @@
 csrc/kernels_stereo.hpp): the yardstick of tests/test_stereo_host.py and tests/test_gpu_stereo.py, which hold the HIP kernel
 to it with array_equal.  Not a test module.
 
-    nearness   t = depth / float32(N - 1)  (0 when N == 1),  t = min(max(t, 0), 1),  t = 1 - t when near == 'first'
+    nearness   t = depth / float32(N - 1)  (0 when N == 1),  t = min(max(t, 0), 1), 0 for a NaN depth,  t = 1 - t when
+               near == 'first'
     target     d = int32(rint(float32(shift) * (t - float32(pivot)))),  x' = x + d,  dropped outside [0, W)
     occlusion  among the sources of a row on one target the largest t wins
     holes      the nearest filled target to the left and to the right: the smaller winning t, the left one on a tie, the one
@@ -23,7 +24,8 @@ def nearness(depth, n_frames, near="last"):
         t = np.zeros(depth.shape, np.float32)
     else:
         t = depth / np.float32(int(n_frames) - 1)
-    t = np.minimum(np.maximum(t, np.float32(0)), np.float32(1))
+    t = np.where(t > np.float32(0), t, np.float32(0))       # max(t, 0); a NaN depth has nearness 0
+    t = np.minimum(t, np.float32(1))
     if near == "first":
         t = np.float32(1) - t
     assert t.dtype == np.float32

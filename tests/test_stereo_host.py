@@ -117,6 +117,7 @@ def test_depth_outside_the_stack_is_clamped():
     for near in ("last", "first"):
         assert np.array_equal(sr.view(img, over, n, 11.0, 0.5, near), sr.view(img, z, n, 11.0, 0.5, near))
     assert sr.nearness(np.float32([-0.5, 6.5, 3.0]), n).tolist() == [0.0, 1.0, 0.5]
+    assert sr.nearness(np.float32([np.nan, np.inf, -np.inf, -0.0]), n).tobytes() == np.float32([0.0, 1.0, 0.0, 0.0]).tobytes()
 
 
 def test_half_way_products_round_to_even():
