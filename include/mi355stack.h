@@ -776,6 +776,28 @@ MI_API int mi_develop(int device, const void* host_mosaic, void* host_bgr, int h
 MI_API int mi_stack_push_mosaic_developed(mi_stack_t* s, const void* host_mosaic, size_t row_stride_bytes, const mi_cfa_t* cfa,
                                           const mi_develop_t* develop, const int32_t* dev_sites, int n_sites, int pinned);
 
+/* ---- linear raw frames in: an already demosaiced frame developed without a demosaic (kernels_linear.hpp) ----
+ * height x width x spp samples of MI_U8 / MI_U16 in file order (R, G, B; spp 1: one grey sample per pixel) become a
+ * height x width x 3 BGR frame of the same dtype in one pass.  Per sample: v' = min(white, (max(v - black[c], 0) * gain_q[c] +
+ * 2048) >> 12), c the sample's channel (0 at spp 1, where b = g = r = v'); then steps C and D of mi_develop_t on (b, g, r), as
+ * behind the demosaic.  Exact: tests/linear_restatement.py states it in NumPy and the kernel is held to it bit for bit. */
+typedef struct mi_linear {
+    int32_t black[3];     /* black level per channel (R, G, B), >= 0; spp 1 reads entry 0                      */
+    uint32_t gain_q[3];   /* round(gain * 4096) per channel, <= 65535: white balance, bit depth; spp 1: entry 0 */
+    int32_t white;        /* output clamp, 1 .. the dtype's maximum                                            */
+    int32_t spp;          /* samples per pixel: 1 or 3                                                         */
+} mi_linear_t;
+/* height, width >= 1 with height * width * 3 < 2^32.  MI_ERR_INVALID names the argument; the checks come before the first
+ * device call.  mi_linear_develop_device: `develop` may be null (step A alone); the pointers are aligned to their samples
+ * (4-byte aligned ones take the wide path); enqueued on `stream`, not waited for.  mi_linear_develop: the host form -- uploads,
+ * runs, downloads and waits; matrix_q (9 ints) or NULL, host_tone (the table in host memory) or NULL. */
+MI_API int mi_linear_develop_device(int device, void* stream, const void* dev_samples, void* dev_bgr, int height, int width, int dtype,
+                                    const mi_linear_t* linear, const mi_develop_t* develop);
+MI_API int mi_linear_develop(int device, const void* host_samples, void* host_bgr, int height, int width, int dtype,
+                             const mi_linear_t* linear, const int32_t* matrix_q, const void* host_tone);
+/* the pixels one workgroup of linear_develop takes of frames of `dtype` (for tests that aim at its edges); 0: unknown dtype */
+MI_API int mi_linear_span(int dtype);
+
 /* ---- raw calibration frames: master dark / flat, the flat's gain table, (raw - dark) * flat_gain (kernels_calib.hpp) ----
  * Integer and exact, on height x width mosaics of MI_U8 / MI_U16 (height, width >= 2, height * width < 2^31), maxv the dtype's
  * maximum, pos = 2 (y & 1) + (x & 1); nothing depends on the colour pattern.  tests/calib_restatement.py states it in NumPy.
@@ -940,6 +962,31 @@ MI_API int mi_raw_ljpeg_device(int device, void* stream, const void* dev_span, s
                                const mi_raw_layout_t* layout, const uint16_t* dev_table, void* dev_out, uint32_t* dev_status);
 MI_API int mi_raw_ljpeg(int device, const void* host_span, size_t span_bytes, const mi_ljpeg_seg_t* segs,
                         const mi_raw_layout_t* layout, const uint16_t* host_table, void* host_out, uint32_t* status_out);
+/* Three components: the tiles or strips of a LinearRaw frame, each one SOF3 stream with Nf = 3 (R, G, B interleaved along the
+ * line) and X equal to the segment's PIXEL width; `layout` counts samples (seg_width = 3 X).  The same head as mi_ljpeg_seg_t
+ * with three tables; everything stated above holds with ncomp == 3 -- placement, prediction, status bits, the
+ * MI_LJPEG_MAX_LINE rule (in samples), the alignment rules.  The host form checks, per segment: ncomp == 3, x * 3 == the
+ * segment's columns, the rest as mi_raw_ljpeg.  A descriptor in device memory that the host form would refuse sets
+ * MI_LJPEG_UNDECODED and leaves its segment unwritten. */
+typedef struct mi_ljpeg_seg3 {
+    uint32_t scan_off;
+    uint32_t scan_bytes;
+    int32_t x;              /* pixels per line: x * 3 == the segment's columns                          */
+    int32_t y;
+    uint8_t ncomp;          /* 3                                                                        */
+    uint8_t predictor;
+    uint8_t precision;
+    uint8_t reserved;
+    uint8_t counts[3][16];
+    uint8_t values[3][17];
+    uint8_t pad[9];         /* to 128 bytes                                                             */
+} mi_ljpeg_seg3_t;
+MI_API int mi_raw_ljpeg3_device(int device, void* stream, const void* dev_span, size_t span_bytes, const mi_ljpeg_seg3_t* dev_segs,
+                                const mi_raw_layout_t* layout, const uint16_t* dev_table, void* dev_out, uint32_t* dev_status);
+/* the samples of one batch of raw_ljpeg3's walker, a whole number of pixels (for tests that aim at its edges) */
+MI_API int mi_ljpeg3_batch(void);
+MI_API int mi_raw_ljpeg3(int device, const void* host_span, size_t span_bytes, const mi_ljpeg_seg3_t* segs,
+                         const mi_raw_layout_t* layout, const uint16_t* host_table, void* host_out, uint32_t* status_out);
 /* mi_stack_push_packed for a lossless-JPEG span: the packed slot holds [span | descriptors | table], raw_ljpeg takes the place
  * of raw_unpack, and everything else -- routes, the pinned rule, the kernels behind it -- is the same.  Packed, compressed,
  * mosaic and BGR pushes may mix on one handle.  The stage ORs every frame's status flags into one device word of its own:
@@ -950,6 +997,17 @@ MI_API int mi_stack_push_ljpeg(mi_stack_t* s, const void* host_span, size_t span
                                const mi_calib_t* calib, const mi_develop_t* develop, const int32_t* dev_sites, int n_sites,
                                int pinned);
 MI_API int mi_stack_ljpeg_status(mi_stack_t* s, uint32_t* flags);
+/* mi_stack_push_packed for a linear frame (mi_linear_t: an already demosaiced frame of spp = 1 or 3 samples per pixel): the
+ * span goes up exactly as a packed or compressed span does and `layout` counts SAMPLES -- height the handle's, width the handle's
+ * times linear->spp.  compressed == 0: `segs` are the uint32 segment offsets and raw_unpack runs; else they are the descriptors,
+ * mi_ljpeg_seg3_t at spp 3 and mi_ljpeg_seg_t at spp 1, and raw_ljpeg3 / raw_ljpeg runs (status: mi_stack_ljpeg_status).  The
+ * samples land in a slot of the stage that holds height x width x spp of them and mi_linear_develop_device's kernel takes them
+ * to the batch's BGR frame (`develop` may be null); nothing is corrected per site, calibrated or repaired, and a site
+ * correction set on the handle does not touch such a frame.  The checks are those of mi_raw_unpack / mi_raw_ljpeg[3], of
+ * mi_linear_t and of mi_develop_t.  Linear, packed, compressed, mosaic and BGR pushes may mix on one handle, frame by frame. */
+MI_API int mi_stack_push_linear(mi_stack_t* s, const void* host_span, size_t span_bytes, const void* segs, int compressed,
+                                const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_linear_t* linear,
+                                const mi_develop_t* develop, int pinned);
 
 /* ---- site corrections: the per-site corrections a raw file carries for its own samples (kernels_sitecorr.hpp) ----
  * DNG's BlackLevelDeltaH/V, GainMap, FixBadPixelsList and FixBadPixelsConstant, resolved on the host into integer tables.

@@ -67,6 +67,21 @@ class DevelopStruct(C.Structure):
     _fields_ = [("flags", C.c_int32), ("matrix_q", C.c_int32 * 9), ("dev_tone", C.c_void_p)]
 
 
+class LinearStruct(C.Structure):
+    """mi_linear_t: what linear_develop sees of a demosaic.Linear (demosaic.Linear.quantised)"""
+    _fields_ = [("black", C.c_int32 * 3), ("gain_q", C.c_uint32 * 3), ("white", C.c_int32), ("spp", C.c_int32)]
+
+
+def linear_span(dtype):
+    """the pixels one workgroup of linear_develop takes of frames of `dtype`: the library's own figure (mi_linear_span)"""
+    return int(load().mi_linear_span(DTYPE_CODE[np.dtype(dtype)]))
+
+
+def ljpeg3_batch():
+    """the samples of one batch of raw_ljpeg3, a whole number of pixels: the library's own figure (mi_ljpeg3_batch)"""
+    return int(load().mi_ljpeg3_batch())
+
+
 MI_CALIB_DARK, MI_CALIB_FLAT = 1, 2
 
 
@@ -123,6 +138,10 @@ class LjpegSeg(C.Structure):
 LJPEG_SEG_DTYPE = np.dtype([("scan_off", "<u4"), ("scan_bytes", "<u4"), ("x", "<i4"), ("y", "<i4"), ("ncomp", "u1"), ("predictor", "u1"),
                             ("precision", "u1"), ("reserved", "u1"), ("counts", "u1", (2, 16)), ("values", "u1", (2, 17)),
                             ("pad", "u1", (10,))])
+# mi_ljpeg_seg3_t: three components (the tiles of a LinearRaw frame), 128 bytes
+LJPEG_SEG3_DTYPE = np.dtype([("scan_off", "<u4"), ("scan_bytes", "<u4"), ("x", "<i4"), ("y", "<i4"), ("ncomp", "u1"), ("predictor", "u1"),
+                             ("precision", "u1"), ("reserved", "u1"), ("counts", "u1", (3, 16)), ("values", "u1", (3, 17)),
+                             ("pad", "u1", (9,))])
 LJPEG_NOCODE, LJPEG_OVERRUN, LJPEG_UNDECODED = 1, 2, 4
 LJPEG_MAX_LINE = 24576
 LJPEG_FLAG_NAMES = {LJPEG_NOCODE: "a 16-bit prefix matched no Huffman code", LJPEG_OVERRUN: "the data ended before the last sample",
@@ -319,6 +338,12 @@ SIGNATURES = {
                              C.c_void_p, C.c_int]),
     "mi_stack_push_mosaic_developed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CfaStruct), C.POINTER(DevelopStruct),
                                                  C.c_void_p, C.c_int, C.c_int]),
+    "mi_linear_develop_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(LinearStruct),
+                                           C.POINTER(DevelopStruct)]),
+    "mi_linear_develop": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(LinearStruct), C.c_void_p,
+                                    C.c_void_p]),
+    "mi_linear_span": (C.c_int, [C.c_int]),
+    "mi_ljpeg3_batch": (C.c_int, []),
     "mi_mosaic_master_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mi_mosaic_master": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mi_flat_gain_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct),
@@ -358,6 +383,12 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p]),
     "mi_raw_ljpeg": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p, C.c_void_p,
                                C.c_void_p]),
+    "mi_raw_ljpeg3_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "mi_raw_ljpeg3": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
+    "mi_stack_push_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(RawLayoutStruct), C.c_void_p,
+                                       C.POINTER(LinearStruct), C.POINTER(DevelopStruct), C.c_int]),
     "mi_stack_push_ljpeg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p,
                                       C.POINTER(CfaStruct), C.POINTER(CalibStruct), C.POINTER(DevelopStruct), C.c_void_p, C.c_int,
                                       C.c_int]),
@@ -783,7 +814,13 @@ class Stack:
         own Cfa exactly as push_mosaic does.  `develop`, `calibration`: as in push_mosaic (None: that step is not run).
         `zero_copy`: the frame's span must then lie in pinned memory (a file mapping is not: it takes the copying path).
         `corrections`: "auto" -- the frame's own site corrections (frame.corrections; cleared on the handle when the frame has
-        none) -- or a dng.SiteCorrections, set on the handle as push_mosaic does; None: the handle's current setting."""
+        none) -- or a dng.SiteCorrections, set on the handle as push_mosaic does; None: the handle's current setting.
+        A LinearRaw frame (frame.linear) takes the same path (mi_stack_push_linear): its span is unpacked or decoded into a slot
+        of H x W x spp samples and linear_develop stands where the demosaic does, with `develop`'s colour matrix and tone
+        curve.  What is per CFA site is refused with it (dng.check_linear_options: `calibration`, Develop.defects, a
+        SiteCorrections object), and a site correction held by the handle does not touch it.  Linear and CFA frames may mix."""
+        if getattr(frame, "linear", None) is not None:
+            return self._push_linear(frame, zero_copy, develop, calibration, corrections)
         lay = frame.layout
         if (lay.height, lay.width) != (self.height, self.width):
             raise ValueError(f"mosaic shape {(lay.height, lay.width)} != {(self.height, self.width)}")
@@ -810,6 +847,34 @@ class Stack:
             return entry(self._h, span.ctypes.data, span.nbytes, offsets.ctypes.data, C.byref(L),
                          None if table is None else table.ctypes.data, C.byref(c), None if cal is None else C.byref(cal),
                          None if d is None else C.byref(d), sites, n_sites, pinned)
+        self._push_host(push, span, zero_copy)
+
+    def _push_linear(self, frame, zero_copy, develop, calibration, corrections):
+        """push_packed for a LinearRaw frame"""
+        from .dng import check_linear_options, host_span
+        check_linear_options(frame, calibration, corrections, develop)
+        lay, lin = frame.layout, frame.linear
+        if (lay.height, lay.width) != (self.height, self.width * lay.spp) or lin.spp != lay.spp:
+            raise ValueError(f"frame shape {frame.shape} at {lin.spp} samples != {(self.height, self.width)}")
+        if lay.dtype != self.in_dtype:
+            raise ValueError(f"frame dtype {lay.dtype} != {self.in_dtype}")
+        ls = lin.struct(self.in_dtype)
+        L, table = lay.struct(), lay.table
+        compressed = lay.compression == 7
+        segs = lay.segments if compressed else lay.offsets
+        d = None
+        if develop is not None:
+            from .demosaic import check_develop
+            d, _, _ = check_develop(develop).prepared(frame.shape, self.in_dtype, self.device)
+            self._keep(self._develops, develop)
+        span = frame.span
+        if self.float_type == MI_F64 or self.params.impl == IMPL_SIMPLE:
+            span = host_span(frame)     # the synchronous route uploads straight out of the caller's memory
+        entry = load().mi_stack_push_linear
+
+        def push(pinned):
+            return entry(self._h, span.ctypes.data, span.nbytes, segs.ctypes.data, int(compressed), C.byref(L),
+                         None if table is None else table.ctypes.data, C.byref(ls), None if d is None else C.byref(d), pinned)
         self._push_host(push, span, zero_copy)
 
     def ljpeg_status(self):

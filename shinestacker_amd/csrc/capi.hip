@@ -1786,6 +1786,67 @@ int mi_stack_push_mosaic_developed(mi_stack_t* s, const void* host_mosaic, size_
                         n_sites, pinned);
 }
 
+// ---------------------------------------------------------------- linear raw frames (kernels_linear.hpp)
+// argument checks of mi_linear_develop*: no device call
+// (the levels alone: mi_stack_push_linear shares them)
+static int linear_levels_check(const mi_linear_t* lin, int dtype);
+static int linear_check(const void* samples, const void* bgr, int height, int width, int dtype, const mi_linear_t* lin) {
+    if (!samples) return fail(MI_ERR_INVALID, "null samples");
+    if (!bgr) return fail(MI_ERR_INVALID, "null bgr output");
+    if (height < 1 || width < 1) return fail(MI_ERR_INVALID, "height and width must be >= 1 for a linear frame (got %dx%d)", width, height);
+    if ((uint64_t)height * (uint64_t)width * 3ull >= (1ull << 32)) return fail(MI_ERR_INVALID, "height x width too large");
+    return linear_levels_check(lin, dtype);
+}
+static int linear_levels_check(const mi_linear_t* lin, int dtype) {
+    if (!lin) return fail(MI_ERR_INVALID, "null linear");
+    if (dtype != MI_U8 && dtype != MI_U16) return fail(MI_ERR_INVALID, "dtype must be MI_U8 or MI_U16 for a linear frame (got %d)", dtype);
+    if (lin->spp != 1 && lin->spp != 3) return fail(MI_ERR_INVALID, "linear spp must be 1 or 3 (got %d)", lin->spp);
+    const int maxv = dtype == MI_U8 ? 255 : 65535;
+    for (int k = 0; k < 3; ++k) {
+        if (lin->black[k] < 0) return fail(MI_ERR_INVALID, "linear black[%d] must be >= 0 (got %d)", k, lin->black[k]);
+        if (lin->gain_q[k] > 65535u) return fail(MI_ERR_INVALID, "linear gain_q[%d] must be <= 65535 (got %u)", k, lin->gain_q[k]);
+    }
+    if (lin->white < 1 || lin->white > maxv) return fail(MI_ERR_INVALID, "linear white must be in [1, %d] (got %d)", maxv, lin->white);
+    return MI_OK;
+}
+
+int mi_linear_span(int dtype) { return dtype == MI_U8 || dtype == MI_U16 ? linear_span(dtype) : 0; }
+
+int mi_linear_develop_device(int device, void* stream, const void* dev_samples, void* dev_bgr, int height, int width, int dtype,
+                             const mi_linear_t* linear, const mi_develop_t* develop) {
+    int rc = linear_check(dev_samples, dev_bgr, height, width, dtype, linear);
+    if (rc || (develop && (rc = develop_check(develop)))) return rc;
+    if (((uintptr_t)dev_samples | (uintptr_t)dev_bgr) & (dtype_size(dtype) - 1))
+        return fail(MI_ERR_INVALID, "dev_samples and dev_bgr must be aligned to their samples");
+    MI_HIP(hipSetDevice(device));
+    linear_develop_launch((hipStream_t)stream, dev_samples, dev_bgr, height, width, dtype, *linear, develop);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_linear_develop(int device, const void* host_samples, void* host_bgr, int height, int width, int dtype, const mi_linear_t* linear,
+                      const int32_t* matrix_q, const void* host_tone) {
+    int rc = linear_check(host_samples, host_bgr, height, width, dtype, linear);
+    if (rc || (matrix_q && (rc = matrix_check(matrix_q)))) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t isz = dtype_size(dtype), npx = (size_t)height * width;
+    mi_develop_t d{};
+    if (matrix_q) {
+        d.flags |= MI_DEVELOP_MATRIX;
+        memcpy(d.matrix_q, matrix_q, sizeof(d.matrix_q));
+    }
+    DevScratch tmp(nullptr);
+    void *src = nullptr, *dst = nullptr, *tone = nullptr;
+    if ((rc = tmp.upload(&src, host_samples, npx * linear->spp * isz)) || (rc = tmp.alloc(&dst, npx * 3 * isz))) return rc;
+    if (host_tone) {
+        if ((rc = tmp.upload(&tone, host_tone, (dtype == MI_U8 ? 256 : 65536) * isz))) return rc;
+        d.flags |= MI_DEVELOP_TONE;
+        d.dev_tone = tone;
+    }
+    if ((rc = mi_linear_develop_device(device, nullptr, src, dst, height, width, dtype, linear, &d))) return rc;
+    return tmp.download(host_bgr, dst, npx * 3 * isz);
+}
+
 // ---------------------------------------------------------------- raw calibration frames (kernels_calib.hpp)
 int mi_mosaic_master_device(int device, void* stream, const void* dev_frames, int n, int height, int width, int dtype, int reject,
                             void* dev_out) {
@@ -2198,12 +2259,19 @@ int mi_raw_unpack(int device, const void* host_span, size_t span_bytes, const ui
 }
 
 // descriptors in host memory (mi_raw_ljpeg, mi_stack_push_ljpeg): what the kernel would flag or mis-decode is refused here
-static int ljpeg_segs_check(size_t span_bytes, const mi_ljpeg_seg_t* segs, const mi_raw_layout_t* L) {
+// (SEG: mi_ljpeg_seg_t, or mi_ljpeg_seg3_t for the three-component entry points; a template has C++ linkage)
+extern "C++" {
+template <typename SEG>
+static int ljpeg_segs_check(size_t span_bytes, const SEG* segs, const mi_raw_layout_t* L) {
     const int nsx = unpack_nsx(*L), nsy = cdiv(L->image_height, L->seg_height);
     for (int k = 0; k < nsx * nsy; ++k) {
-        const mi_ljpeg_seg_t& S = segs[k];
+        const SEG& S = segs[k];
         const int rows = L->tiled ? L->seg_height : std::min(L->seg_height, L->image_height - (k / nsx) * L->seg_height);
-        if (S.ncomp != 1 && S.ncomp != 2) return fail(MI_ERR_INVALID, "segs[%d].ncomp must be 1 or 2 (got %d)", k, S.ncomp);
+        if constexpr (std::is_same<SEG, mi_ljpeg_seg3_t>::value) {
+            if (S.ncomp != 3) return fail(MI_ERR_INVALID, "segs[%d].ncomp must be 3 (got %d)", k, S.ncomp);
+        } else {
+            if (S.ncomp != 1 && S.ncomp != 2) return fail(MI_ERR_INVALID, "segs[%d].ncomp must be 1 or 2 (got %d)", k, S.ncomp);
+        }
         if (S.predictor < 1 || S.predictor > 7) return fail(MI_ERR_INVALID, "segs[%d].predictor must be in [1, 7] (got %d)", k, S.predictor);
         if (S.precision < 2 || S.precision > L->bits)
             return fail(MI_ERR_INVALID, "segs[%d].precision must be in [2, layout bits = %d] (got %d)", k, L->bits, S.precision);
@@ -2232,6 +2300,7 @@ static int ljpeg_segs_check(size_t span_bytes, const mi_ljpeg_seg_t* segs, const
     }
     return MI_OK;
 }
+}  // extern "C++"
 // raw_layout_check for the lossless-JPEG entry points: the descriptors stand where the offsets do
 static int ljpeg_layout_check(const void* span, size_t span_bytes, const mi_ljpeg_seg_t* segs, const mi_raw_layout_t* L, const uint16_t* table,
                               const void* out) {
@@ -2275,6 +2344,45 @@ int mi_raw_ljpeg(int device, const void* host_span, size_t span_bytes, const mi_
     return tmp.download(host_out, out, nb);
 }
 
+// three components (mi_ljpeg_seg3_t): the same checks, the same order
+int mi_ljpeg3_batch(void) { return ljpeg::BATCH3; }
+int mi_raw_ljpeg3_device(int device, void* stream, const void* dev_span, size_t span_bytes, const mi_ljpeg_seg3_t* dev_segs,
+                         const mi_raw_layout_t* layout, const uint16_t* dev_table, void* dev_out, uint32_t* dev_status) {
+    if (dev_span && !dev_segs) return fail(MI_ERR_INVALID, "null segs");
+    int rc = raw_layout_check(dev_span, span_bytes, (const uint32_t*)dev_segs, layout, dev_table, dev_out);
+    if (rc) return rc;
+    if ((uintptr_t)dev_span & 3) return fail(MI_ERR_INVALID, "dev_span must be 4-byte aligned");
+    if ((uintptr_t)dev_segs & 15) return fail(MI_ERR_INVALID, "dev_segs must be 16-byte aligned");
+    if ((uintptr_t)dev_out & (dtype_size(layout->dtype) - 1)) return fail(MI_ERR_INVALID, "dev_out must be aligned to its samples");
+    if ((uintptr_t)dev_status & 3) return fail(MI_ERR_INVALID, "dev_status must be 4-byte aligned");
+    MI_HIP(hipSetDevice(device));
+    ljpeg3_launch((hipStream_t)stream, dev_span, span_bytes, dev_segs, *layout, dev_table, dev_out, dev_status, nullptr);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_raw_ljpeg3(int device, const void* host_span, size_t span_bytes, const mi_ljpeg_seg3_t* segs, const mi_raw_layout_t* layout,
+                  const uint16_t* host_table, void* host_out, uint32_t* status_out) {
+    if (host_span && !segs) return fail(MI_ERR_INVALID, "null segs");
+    int rc = raw_layout_check(host_span, span_bytes, (const uint32_t*)segs, layout, host_table, host_out);
+    if (rc || (rc = ljpeg_segs_check(span_bytes, segs, layout))) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t nb = (size_t)layout->height * layout->width * dtype_size(layout->dtype);
+    const size_t nseg = (size_t)unpack_nsegs(*layout);
+    DevScratch tmp(nullptr);
+    void *span = nullptr, *out = nullptr;
+    mi_ljpeg_seg3_t* seg = nullptr;
+    uint16_t* table = nullptr;
+    uint32_t* status = nullptr;
+    if ((rc = tmp.upload(&span, host_span, span_bytes)) || (rc = tmp.upload(&seg, segs, nseg * sizeof(mi_ljpeg_seg3_t))) ||
+        (layout->table_len > 0 && (rc = tmp.upload(&table, host_table, (size_t)layout->table_len * sizeof(uint16_t)))) ||
+        (rc = tmp.alloc(&out, nb)) || (rc = tmp.alloc(&status, nseg * sizeof(uint32_t))) ||
+        (rc = mi_raw_ljpeg3_device(device, nullptr, span, span_bytes, seg, layout, table, out, status)))
+        return rc;
+    if (status_out && (rc = tmp.download(status_out, status, nseg * sizeof(uint32_t)))) return rc;
+    return tmp.download(host_out, out, nb);
+}
+
 // the part of mi_stack_push_packed and mi_stack_push_ljpeg behind the span's checks
 static int packed_push(mi_stack_t* s, const void* host_span, size_t span_bytes, const uint32_t* seg_offsets, const mi_ljpeg_seg_t* segs,
                        const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_cfa_t* cfa, const mi_calib_t* calib,
@@ -2310,6 +2418,36 @@ int mi_stack_push_ljpeg(mi_stack_t* s, const void* host_span, size_t span_bytes,
     if ((rc = ljpeg_layout_check(host_span, span_bytes, segs, layout, host_table, s)) || (rc = ljpeg_segs_check(span_bytes, segs, layout)))
         return rc;
     return packed_push(s, host_span, span_bytes, nullptr, segs, layout, host_table, cfa, calib, develop, dev_sites, n_sites, pinned);
+}
+
+// A linear frame through the one ingest path: the span goes up as a packed or compressed span does, raw_unpack / raw_ljpeg /
+// raw_ljpeg3 fill a linear slot of height x width x spp samples and linear_develop takes it to the batch's BGR frame.
+int mi_stack_push_linear(mi_stack_t* s, const void* host_span, size_t span_bytes, const void* segs, int compressed,
+                         const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_linear_t* linear, const mi_develop_t* develop,
+                         int pinned) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if (host_span && !segs) return fail(MI_ERR_INVALID, compressed ? "null segs" : "null seg_offsets");
+    if ((rc = raw_layout_check(host_span, span_bytes, (const uint32_t*)segs, layout, host_table, s)) ||
+        (rc = linear_levels_check(linear, s->p.in_dtype)))
+        return rc;
+    const bool three = compressed && linear->spp == 3;
+    if (!compressed) rc = raw_segments_check(span_bytes, (const uint32_t*)segs, layout);
+    else if (three) rc = ljpeg_segs_check(span_bytes, (const mi_ljpeg_seg3_t*)segs, layout);
+    else rc = ljpeg_segs_check(span_bytes, (const mi_ljpeg_seg_t*)segs, layout);
+    if (rc || (develop && (rc = develop_check(develop)))) return rc;
+    if (layout->height != s->p.height || (int64_t)layout->width != (int64_t)s->p.width * linear->spp || layout->dtype != s->p.in_dtype)
+        return fail(MI_ERR_INVALID, "layout height, width / spp and dtype must be the handle's (got %dx%d samples at spp %d, dtype %d for %dx%d dtype %d)",
+                    layout->width, layout->height, linear->spp, layout->dtype, s->p.width, s->p.height, s->p.in_dtype);
+    bool async;
+    if ((rc = raw_state_check(s, &async))) return rc;
+    if (pinned && async && (rc = pinned_probe(host_span, "mi_stack_push_linear", "span"))) return rc;
+    PackedSrc pk{host_span, span_bytes, compressed ? nullptr : (const uint32_t*)segs,
+                 compressed && !three ? (const mi_ljpeg_seg_t*)segs : nullptr, unpack_nsegs(*layout), layout, host_table};
+    if (three) pk.ljseg3 = (const mi_ljpeg_seg3_t*)segs;
+    MosaicFrame f{nullptr, 0, &pk, nullptr, pinned && async, nullptr, develop, nullptr, 0};
+    f.lin = linear;
+    return mosaic_push(s, f);
 }
 
 int mi_stack_ljpeg_status(mi_stack_t* s, uint32_t* flags) {

@@ -278,4 +278,182 @@ inline void ljpeg_launch(hipStream_t st, const void* span, size_t span_bytes, co
     else hipLaunchKernelGGL(raw_ljpeg<uint16_t>, grid, blk, lds, st, A);
 }
 
+// ---------------------------------------------------------------- three components: the tiles of a LinearRaw frame
+// raw_ljpeg3 is raw_ljpeg's sibling for streams of Nf = 3 (mi_ljpeg_seg3_t: R, G, B interleaved along the line; the layout
+// counts samples, seg_w = 3 X).  Everything above holds -- one segment per wavefront, the tables and the walker of
+// ljpeg_core.hpp unchanged, the same ring, top-up and guarantee, the same status bits, every loop bound from the launch -- and
+// one thing differs: the batch is ljpeg::BATCH3 = 192 samples, 64 whole pixels, one pixel per lane, so the per-component prefix
+// scan keeps its phase from batch to batch (a batch of 256 would start every third batch on another component).  A
+// descriptor the host forms refuse (ncomp other than 3, a width that is no multiple of 3, ...) sets MI_LJPEG_UNDECODED and
+// the segment is left unwritten: nothing is decoded from it.
+namespace ljpeg {
+constexpr int NC3 = 3;
+constexpr int BATCH3 = NC3 * LANES;        // one pixel per lane
+constexpr int LUT3_BYTES = NC3 * (1 << LUT_BITS) * 2;
+constexpr int LDS3_FIXED = RING + LUT3_BYTES + NC3 * HUFF_STRIDE + BATCH3 * 2;
+static_assert(LDS3_FIXED % 16 == 0, "LDS carve");
+static_assert(8 * BATCH3 + 16 < RING - CHUNK, "a batch must not outrun the ring");
+static_assert(LDS3_FIXED + 2 * MAX_LINE <= 65536, "LDS budget");
+}  // namespace ljpeg
+
+struct Ljpeg3Args : LjpegArgs {
+    const mi_ljpeg_seg3_t* segs3;   // (`segs` of the base is not read)
+};
+
+template <typename T>
+__global__ __launch_bounds__(64) void raw_ljpeg3(Ljpeg3Args A) {
+    using namespace ljpeg;
+    extern __shared__ __attribute__((aligned(16))) unsigned char ljpeg_smem[];
+    uint32_t* ring = (uint32_t*)ljpeg_smem;
+    uint16_t* lut = (uint16_t*)(ljpeg_smem + RING);
+    unsigned char* const huffs = ljpeg_smem + RING + LUT3_BYTES;                  // three Huff, HUFF_STRIDE apart
+    const auto huff = [huffs](int c) -> Huff& { return *(Huff*)(huffs + c * HUFF_STRIDE); };
+    uint16_t* d = (uint16_t*)(ljpeg_smem + RING + LUT3_BYTES + NC3 * HUFF_STRIDE);      // a batch: differences, then values
+    uint16_t* line = d + BATCH3;                                                  // the line above (seg_w <= MAX_LINE)
+    const int lane = (int)threadIdx.x, k = (int)blockIdx.x;
+    const int sy = k / A.nsx, sx = k - sy * A.nsx;
+    const int rows = A.tiled ? A.seg_h : min(A.seg_h, A.image_h - sy * A.seg_h);
+    const int W = A.seg_w;
+    const mi_ljpeg_seg3_t& S = A.segs3[k];
+    uint32_t status = 0;
+    const int pred = S.predictor, prec = S.precision;
+    if (S.ncomp != NC3 || W % NC3 || pred < 1 || pred > 7 || prec < 2 || prec > 16 || (pred != 1 && W > MAX_LINE)) {
+        if (lane == 0) {            // (the host forms refuse it; uniform over the wave: no barrier is skipped by a part of it)
+            if (A.status) A.status[k] = MI_LJPEG_UNDECODED;
+            if (A.status_or) atomicOr(A.status_or, MI_LJPEG_UNDECODED);
+        }
+        return;
+    }
+    // tables
+    if (lane < NC3) huff_build(huff(lane), S.counts[lane], S.values[lane]);
+    __syncthreads();
+    for (int j = lane; j < NC3 << LUT_BITS; j += LANES) {
+        int len;
+        const int s = huff_decode(huff(j >> LUT_BITS), (uint32_t)(j & ((1 << LUT_BITS) - 1)) << (16 - LUT_BITS), len);
+        lut[j] = s >= 0 && s <= 16 && len <= LUT_BITS ? (uint16_t)(len << 8 | s) : (uint16_t)0;
+    }
+    // the data: [scan_off, data_end) of the span
+    const uint32_t scan_off = S.scan_off;
+    const uint32_t lim = scan_off < A.span_bytes ? min(S.scan_bytes, A.span_bytes - scan_off) : 0u;
+    const uint32_t data_end = scan_off + lim;
+    uint32_t staged = scan_off & ~3u;          // the ring holds [.., staged) of the span
+    BitReader<RingBytes> rd(RingBytes{(const uint8_t*)ring, scan_off, lim});
+    const uint32_t half = 1u << (prec - 1);
+    uint32_t seed[NC3] = {half, half, half};    // what predicts a line's first pixel, per component
+    uint32_t carry[NC3] = {0, 0, 0};            // Ra at the start of a batch (the prefix sum's)
+    uint32_t ra[NC3] = {0, 0, 0}, rc[NC3] = {0, 0, 0};     // the walker's, predictors 3 to 7
+    const int nb = (W + BATCH3 - 1) / BATCH3;
+    for (int r = 0; r < rows; ++r) {
+        const bool scan = pred == 1 || r == 0, serial = !scan && pred >= 3;
+        for (int b = 0; b < nb; ++b) {
+            const int c0 = b * BATCH3, n = min(BATCH3, W - c0);      // (W % 3 == 0: n is a whole number of pixels)
+            // top the ring up
+            const uint32_t rpos = (scan_off + (uint32_t)__shfl((int)rd.pos, 0)) & ~3u;
+            for (int t = 0; t < RING / CHUNK; ++t)
+                if (staged < data_end && staged - rpos <= (uint32_t)(RING - CHUNK)) {
+                    ring[((staged >> 2) + lane) & (RING / 4 - 1)] = ljpeg_dword(A, (uint64_t)staged + 4 * lane);
+                    staged += CHUNK;
+                }
+            __syncthreads();
+            // the walk
+            if (lane == 0) {
+                if (r == 0 && b == 0) rd.template fill<8>();
+                int c = 0;
+                for (int i = 0; i < n; ++i) {
+                    rd.template fill<4>();
+                    const uint32_t e = lut[(c << LUT_BITS) + (rd.peek16() >> (16 - LUT_BITS))];
+                    uint32_t v;
+                    if (e) {
+                        rd.skip((int)(e >> 8));
+                        v = take_difference(rd, (int)(e & 0xff));
+                    } else {
+                        v = decode_difference(rd, huff(c), status);
+                    }
+                    if (serial) {
+                        const int col = c0 + i;
+                        const int Rb = line[col], Ra = (int)ra[c], Rc = (int)rc[c];
+                        int px;
+                        if (col < NC3) px = Rb;
+                        else if (pred == 3) px = Rc;
+                        else if (pred == 4) px = Ra + Rb - Rc;
+                        else if (pred == 5) px = Ra + ((Rb - Rc) >> 1);
+                        else if (pred == 6) px = Rb + ((Ra - Rc) >> 1);
+                        else px = (Ra + Rb) >> 1;
+                        v = ((uint32_t)px + v) & 0xffffu;
+                        line[col] = (uint16_t)v;
+                        ra[c] = v;
+                        rc[c] = (uint32_t)Rb;
+                    }
+                    d[i] = (uint16_t)v;
+                    c = c == NC3 - 1 ? 0 : c + 1;
+                }
+            }
+            __syncthreads();
+            // differences -> values
+            if (scan) {
+                if (b == 0) { carry[0] = seed[0]; carry[1] = seed[1]; carry[2] = seed[2]; }
+                const int i0 = lane * NC3;
+                const bool on = i0 < n;                 // this lane's pixel lies in the batch
+                uint32_t x[NC3];
+#pragma unroll
+                for (int c = 0; c < NC3; ++c) x[c] = on ? (uint32_t)d[i0 + c] : 0u;
+#pragma unroll
+                for (int o = 1; o < LANES; o <<= 1) {   // inclusive scan over the lanes, per component
+#pragma unroll
+                    for (int c = 0; c < NC3; ++c) {
+                        const uint32_t y = (uint32_t)__shfl_up((int)x[c], o);
+                        if (lane >= o) x[c] += y;
+                    }
+                }
+                if (on) {
+#pragma unroll
+                    for (int c = 0; c < NC3; ++c) {
+                        const uint32_t v = (x[c] + carry[c]) & 0xffffu;
+                        d[i0 + c] = (uint16_t)v;
+                        if (pred != 1) line[c0 + i0 + c] = (uint16_t)v;
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int c = 0; c < NC3; ++c) {
+                    carry[c] = d[n - NC3 + c];
+                    if (b == 0) seed[c] = d[c];
+                }
+            } else if (pred == 2) {
+                for (int i = lane; i < n; i += LANES) {
+                    const uint32_t v = ((uint32_t)line[c0 + i] + d[i]) & 0xffffu;
+                    d[i] = (uint16_t)v;
+                    line[c0 + i] = (uint16_t)v;
+                }
+                __syncthreads();
+            }
+            // table, shift, crop, store
+            const int ys = sy * A.seg_h + r, xs0 = sx * W + c0;
+            for (int i = lane; i < n; i += LANES) ljpeg_store<T>(A, ys, xs0 + i, d[i]);
+        }
+    }
+    if (lane == 0) {
+        if (rd.overrun()) status |= ST_OVERRUN;
+        if (A.status) A.status[k] = status;
+        if (A.status_or && status) atomicOr(A.status_or, status);
+    }
+}
+
+// arguments checked by the caller (capi.hip: raw_layout_check, ljpeg3_segs_check)
+inline void ljpeg3_launch(hipStream_t st, const void* span, size_t span_bytes, const mi_ljpeg_seg3_t* segs, const mi_raw_layout_t& L,
+                          const uint16_t* table, void* out, uint32_t* status, uint32_t* status_or) {
+    using namespace ljpeg;
+    Ljpeg3Args A{};
+    A.span = (const uint8_t*)span; A.segs = nullptr; A.segs3 = segs; A.table = L.table_len > 0 ? table : nullptr; A.out = out;
+    A.status = status; A.status_or = status_or;
+    A.span_bytes = (uint32_t)span_bytes;
+    A.h = L.height; A.w = L.width; A.crop_y = L.crop_y; A.crop_x = L.crop_x; A.image_h = L.image_height;
+    A.seg_h = L.seg_height; A.seg_w = L.seg_width; A.nsx = unpack_nsx(L); A.tiled = L.tiled;
+    A.shift = L.shift; A.table_len = L.table_len;
+    const size_t lds = LDS3_FIXED + (L.seg_width <= MAX_LINE ? 2 * (size_t)((L.seg_width + 7) & ~7) : 0);
+    const dim3 grid((unsigned)unpack_nsegs(L)), blk(LANES);
+    if (L.dtype == MI_U8) hipLaunchKernelGGL(raw_ljpeg3<uint8_t>, grid, blk, lds, st, A);
+    else hipLaunchKernelGGL(raw_ljpeg3<uint16_t>, grid, blk, lds, st, A);
+}
+
 }  // namespace mi

@@ -27,6 +27,12 @@
 //   growing     pslot, meta, cslot and the span bounce ring belong to the stage (not to s->allocs) and grow when a later frame
 //               needs more (set_realloc), after a wait for whatever reads them: the device slots for both streams, the pinned
 //               blocks for stc.
+//   linear      a linear frame (mi_stack_push_linear: MosaicFrame::lin in place of the cfa) is a packed span whose layout counts
+//               SAMPLES, spp of them per pixel.  Its span goes into pslot[slot] as any span does; raw_unpack, raw_ljpeg or
+//               raw_ljpeg3 write H x W x spp samples -- into lslot[slot], never into slot[slot], which holds H x W and is
+//               allocated once -- and linear_develop takes them to the frame in `bgr`; nothing runs per site.  lslot belongs to
+//               the stage and grows as pslot does (linear_reserve), shares the slot index and both events with the mosaic slots,
+//               and is written by kernels of s->stream only, which are in order: no further ordering is needed.
 //   float-64 and MI_IMPL_SIMPLE handles
 //               one slot, no copy stream: upload, frame_kernels, dispatch_push and a wait, one frame at a time on s->stream.
 //   order       frames are fused in call order: the first raw frame after host BGR frames flushes the ring (mosaic_push), and
@@ -35,6 +41,7 @@
 
 #include "kernels_calib.hpp"
 #include "kernels_demosaic.hpp"
+#include "kernels_linear.hpp"
 #include "kernels_ljpeg.hpp"
 #include "kernels_sitecorr.hpp"
 #include "kernels_unpack.hpp"
@@ -113,6 +120,9 @@ struct MosaicStage {
     size_t meta_cap = 0;
     PinRing ppin;                             // bounce buffers of spans that are not pinned
     uint32_t* ljstatus = nullptr;             // lossless-JPEG spans: every frame's status flags ORed (in s->allocs)
+    // linear frames (mi_stack_push_linear): the unpacked H x W x spp samples; they belong to the stage and grow as pslot does
+    void* lslot[NSLOT] = {};
+    size_t lslot_cap = 0;
     // site corrections (mi_stack_set_site_correction)
     bool sc_on = false;
     mi_site_correct_t sc = {};                // its pointers hold OFFSETS into the block
@@ -133,10 +143,15 @@ struct PackedSrc {
     int nseg;
     const mi_raw_layout_t* layout;
     const uint16_t* table;      // host, layout->table_len entries, or null
+    const mi_ljpeg_seg3_t* ljseg3 = nullptr;   // ... or its three-component descriptors (a linear frame of three samples)
 };
 inline size_t packed_align(size_t n) { return (n + 255) & ~(size_t)255; }
-inline const void* packed_seg(const PackedSrc& pk) { return pk.ljseg ? (const void*)pk.ljseg : (const void*)pk.seg; }
-inline size_t packed_seg_bytes(const PackedSrc& pk) { return (size_t)pk.nseg * (pk.ljseg ? sizeof(mi_ljpeg_seg_t) : sizeof(uint32_t)); }
+inline const void* packed_seg(const PackedSrc& pk) {
+    return pk.ljseg3 ? (const void*)pk.ljseg3 : pk.ljseg ? (const void*)pk.ljseg : (const void*)pk.seg;
+}
+inline size_t packed_seg_bytes(const PackedSrc& pk) {
+    return (size_t)pk.nseg * (pk.ljseg3 ? sizeof(mi_ljpeg_seg3_t) : pk.ljseg ? sizeof(mi_ljpeg_seg_t) : sizeof(uint32_t));
+}
 
 inline MosaicStage* mstage(const mi_stack* s) { return reinterpret_cast<MosaicStage*>(s->mosaic); }
 
@@ -323,10 +338,11 @@ inline void mosaic_destroy(mi_stack* s) {
     if (m->stc) (void)hipStreamSynchronize(m->stc);
     pin_destroy(m->pin);
     pin_destroy(m->ppin);
-    if (m->pslot[0]) (void)hipStreamSynchronize(s->stream);   // (the unpack kernels read the packed slots)
+    if (m->pslot[0]) (void)hipStreamSynchronize(s->stream);   // (the unpack kernels read the packed slots, and write the linear ones)
     for (int i = 0; i < MosaicStage::NSLOT; ++i) {
         if (m->meta[i]) (void)hipHostFree(m->meta[i]);
         if (m->pslot[i]) (void)hipFree(m->pslot[i]);
+        if (m->lslot[i]) (void)hipFree(m->lslot[i]);
     }
     for (int i = 0; i < MosaicStage::NUP; ++i)
         if (m->evUp[i]) (void)hipEventDestroy(m->evUp[i]);
@@ -448,6 +464,8 @@ struct MosaicFrame {
     const mi_develop_t* dev = nullptr;      // development, or null: the plain demosaic
     const int32_t* dev_sites = nullptr;     // device: the defect sites
     int n_sites = 0;
+    const mi_linear_t* lin = nullptr;       // a linear frame (with `pk`, in place of `cfa`): its levels; no site is corrected,
+                                            // calibrated or repaired, and linear_develop stands where the demosaic does
 };
 
 // a packed span's device layout: [span | offsets or descriptors | table], each part 256-byte aligned
@@ -471,11 +489,18 @@ inline void frame_kernels(hipStream_t st, const mi_stack* s, const MosaicFrame& 
     if (f.pk) {
         const PackedSrc& pk = *f.pk;
         const PackedAt at(f.pk);
-        if (pk.ljseg)
+        if (pk.ljseg3)
+            ljpeg3_launch(st, ps, pk.span_bytes, (const mi_ljpeg_seg3_t*)(ps + at.seg_at), *pk.layout, (const uint16_t*)(ps + at.table_at), slot,
+                          nullptr, m->ljstatus);
+        else if (pk.ljseg)
             ljpeg_launch(st, ps, pk.span_bytes, (const mi_ljpeg_seg_t*)(ps + at.seg_at), *pk.layout, (const uint16_t*)(ps + at.table_at), slot,
                          nullptr, m->ljstatus);
         else
             unpack_launch(st, ps, pk.span_bytes, (const uint32_t*)(ps + at.seg_at), *pk.layout, (const uint16_t*)(ps + at.table_at), slot);
+    }
+    if (f.lin) {        // `slot` holds H x W x spp samples (a linear slot): one pass to the BGR frame, nothing per site
+        linear_develop_launch(st, slot, frame, H, W, dtype, *f.lin, f.dev);
+        return;
     }
     if (m->sc_on) site_kernels(st, slot, H, W, dtype, *f.cfa, site_at(m, (const char*)cs), m->sc_bits);
     if (f.cal) calibrate_launch(st, slot, H, W, dtype, *f.cfa, *f.cal);
@@ -499,6 +524,18 @@ inline int packed_reserve(mi_stack* s, size_t span_bytes, size_t meta_bytes) {
     return MI_OK;
 }
 
+// room for H x W x spp samples in every linear slot the handle uses.  Growing waits for both streams first: nothing reads or
+// writes what is freed.  (The mosaic slots stay H x W samples: a linear frame never lands in one.)
+inline int linear_reserve(mi_stack* s, int spp) {
+    MosaicStage* m = mstage(s);
+    const int nslot = s->p.impl == MI_IMPL_TILED ? MosaicStage::NSLOT : 1;
+    const size_t need = m->mosaic_bytes * (size_t)spp;
+    if (need <= m->lslot_cap) return MI_OK;
+    if (m->stc) MI_HIP(hipStreamSynchronize(m->stc));
+    MI_HIP(hipStreamSynchronize(s->stream));
+    return set_realloc(m->lslot, nslot, &m->lslot_cap, need, false);
+}
+
 // One raw host frame: stage it, start its upload and its kernels, return.
 inline int mosaic_push(mi_stack* s, const MosaicFrame& f) {
     TiledState* t = tstate(s);
@@ -508,11 +545,12 @@ inline int mosaic_push(mi_stack* s, const MosaicFrame& f) {
     MosaicStage* m = mstage(s);
     const PackedSrc* pk = f.pk;
     const size_t rb = (size_t)s->p.width * dtype_size(s->p.in_dtype);
-    const bool sc = m->sc_on;      // site corrections: the stage's tables go up with this frame
+    const bool sc = m->sc_on && !f.lin;      // site corrections: the stage's tables go up with this frame (a linear one has no sites)
     if (sc && (rc = site_black_check(f.cfa->black, m->sc_dmin, m->sc_dmax, s->p.in_dtype))) return rc;
     const PackedAt at(pk);
     if (pk && (rc = packed_reserve(s, pk->span_bytes, at.seg_bytes + at.table_bytes))) return rc;
-    if (pk && pk->ljseg && !m->ljstatus) {
+    if (f.lin && (rc = linear_reserve(s, f.lin->spp))) return rc;
+    if (pk && (pk->ljseg || pk->ljseg3) && !m->ljstatus) {
         if ((rc = dev_alloc(s, (void**)&m->ljstatus, sizeof(uint32_t)))) return rc;
         MI_HIP(hipMemsetAsync(m->ljstatus, 0, sizeof(uint32_t), s->stream));
     }
@@ -525,14 +563,14 @@ inline int mosaic_push(mi_stack* s, const MosaicFrame& f) {
             if (at.table_bytes) MI_HIP(hipMemcpyAsync(ps + at.table_at, pk->table, at.table_bytes, hipMemcpyHostToDevice, s->stream));
         } else MI_HIP(hipMemcpy2DAsync(m->slot[0], rb, f.mosaic, f.row_stride, rb, s->p.height, hipMemcpyHostToDevice, s->stream));
         if (sc) MI_HIP(hipMemcpyAsync(m->cslot[0], m->sc_host, m->sc_bytes, hipMemcpyHostToDevice, s->stream));
-        frame_kernels(s->stream, s, f, ps, m->cslot[0], m->slot[0], s->frame_dev);
+        frame_kernels(s->stream, s, f, ps, m->cslot[0], f.lin ? m->lslot[0] : m->slot[0], s->frame_dev);
         MI_HIP(hipGetLastError());
         rc = dispatch_push(s, s->frame_dev, 1, t->frame_bytes);
         MI_HIP(hipStreamSynchronize(s->stream));   // (also on failure: the copies read the caller's arrays)
         return rc;
     }
     const int si = (int)(m->slot_no % MosaicStage::NSLOT);
-    void* slot = m->slot[si];
+    void* slot = f.lin ? m->lslot[si] : m->slot[si];
     if (m->slot_no >= MosaicStage::NSLOT) MI_HIP(hipStreamWaitEvent(m->stc, m->evSlotFree[si], 0));
     m->slot_no++;
     char* ps = pk ? (char*)m->pslot[si] : nullptr;

@@ -31,6 +31,13 @@ definition); pos = 2 (y & 1) + (x & 1), nothing here depends on the colour patte
     calibrate              in place on the raw samples, ahead of step 0: e = max(v - (dark or black[pos]), 0),
                            e' = (e * G_q + 8192) >> 14 with a flat, out = min(maxv, e' + black[pos])
 
+Linear raw frames, `Linear` and `develop_linear[_device]` (csrc/kernels_linear.hpp; tests/linear_restatement.py is the
+definition): an already demosaiced frame -- a DNG's LinearRaw IFD -- needs no step B.  H x W x 3 samples in R, G, B order (or
+H x W: one grey sample per pixel) become H x W x 3 BGR in one pass:
+
+    step A, per sample     v' = min(white, (max(v - black[c], 0) * gain_q[c] + 2048) >> 12), c the channel; spp 1: b = g = r = v'
+    steps C and D          `Develop`'s colour matrix and tone curve, as above; lens and finish run behind it as behind `debayer`
+
 There is no CPU path: without a GPU or the library `debayer` and its kin raise DeviceError.  `mosaic_of`, `srgb_tone`,
 `gamma_tone` and `defects_from_dark` are host NumPy.
 """
@@ -815,6 +822,191 @@ def debayer(mosaic, cfa, develop=None, device=0, calibration=None, lens=None, co
     _lib.check(_lib.load().mi_develop(device, a.ctypes.data, out.ctypes.data, a.shape[0], a.shape[1], _lib.DTYPE_CODE[a.dtype],
                                       _lib.C.byref(c), mq, None if tone is None else tone.ctypes.data,
                                       sites.ctypes.data if len(sites) else None, len(sites)))
+    return out
+
+
+# ---------------------------------------------------------------- linear raw frames: no demosaic (csrc/kernels_linear.hpp)
+class Linear:
+    """The levels of an already demosaiced raw frame (a DNG's LinearRaw IFD), applied per sample where `Cfa` applies them per
+    cell position: v' = min(white, (max(v - black[c], 0) * gain_q[c] + 2048) >> 12), c the sample's channel in file order
+    (R, G, B); at spp 1 the one grey sample becomes b = g = r (tests/linear_restatement.py is the definition).
+
+    black    black level, one non-negative int or `spp` of them
+    gains    one float or `spp` in [0, 16): white balance and bit-depth scaling; quantised once, here, as round(gain * 4096)
+    white    the output clamp; None: the dtype's maximum
+    spp      samples per pixel: 1 or 3
+    """
+
+    def __init__(self, black=0, gains=1.0, white=None, spp=3):
+        if isinstance(spp, bool) or not isinstance(spp, (int, np.integer)) or spp not in (1, 3):
+            raise InvalidOptionError("spp", spp, "a linear frame has 1 or 3 samples per pixel")
+        self.spp = int(spp)
+
+        def per_channel(name, value, kinds):
+            if isinstance(value, kinds) and not isinstance(value, bool):
+                return [value] * self.spp
+            try:
+                vals = list(value)
+            except TypeError:
+                vals = None
+            if vals is None or len(vals) not in (1, self.spp) or not all(isinstance(v, kinds) and not isinstance(v, bool) for v in vals):
+                raise InvalidOptionError(name, value, f"one number, or {self.spp} (one per sample of a pixel)")
+            return vals * self.spp if len(vals) == 1 and self.spp > 1 else vals
+        self.black = [int(b) for b in per_channel("black", black, (int, np.integer))]
+        if min(self.black) < 0 or max(self.black) > 65535:
+            raise InvalidOptionError("black", black, "black levels lie in [0, 65535]")
+        self.gains = [float(g) for g in per_channel("gains", gains, (int, float, np.integer, np.floating))]
+        if not all(math.isfinite(g) and 0.0 <= g < 16.0 for g in self.gains):
+            raise InvalidOptionError("gains", gains, "gains lie in [0, 16)")
+        self.gain_q = [int(math.floor(g * 4096.0 + 0.5)) for g in self.gains]
+        if max(self.gain_q) > 65535:
+            raise InvalidOptionError("gains", gains, "round(gain * 4096) must fit 16 bits")
+        if white is not None:
+            if isinstance(white, bool) or not isinstance(white, (int, np.integer)) or not 1 <= int(white) <= 65535:
+                raise InvalidOptionError("white", white, "the white level is an int in [1, the dtype's maximum]")
+            white = int(white)
+        self.white = white
+
+    def __repr__(self):
+        return f"Linear(black={self.black}, gains={self.gains}, white={self.white}, spp={self.spp})"
+
+    def quantised(self, dtype=np.uint16):
+        """the ints the kernel sees for frames of `dtype`: (black[spp], gain_q[spp], white, spp)"""
+        maxv = int(np.iinfo(_dtype(dtype)).max)
+        white = maxv if self.white is None else self.white
+        if white > maxv:
+            raise InvalidOptionError("white", white, f"exceeds the maximum {maxv} of {np.dtype(dtype)}")
+        return tuple(self.black), tuple(self.gain_q), white, self.spp
+
+    def struct(self, dtype):
+        """mi_linear_t for frames of `dtype` (at spp 1 the entries 1 and 2 repeat entry 0; the kernel reads entry 0)"""
+        black, gain_q, white, spp = self.quantised(dtype)
+        return _lib.LinearStruct((_lib.C.c_int32 * 3)(*(black * 3)[:3]), (_lib.C.c_uint32 * 3)(*(gain_q * 3)[:3]), white, spp)
+
+
+def _check_linear(linear):
+    if not isinstance(linear, Linear):
+        raise InvalidOptionError("linear", linear, "a shinestacker_amd.demosaic.Linear is expected")
+    return linear
+
+
+def check_samples(samples, linear, shape=None, dtype=None):
+    """the samples of a linear frame: H x W x 3 (spp 3) or H x W (spp 1; H x W x 1 is taken too) of uint8 / uint16"""
+    a = np.asarray(samples)
+    _dtype(a.dtype)
+    spp = _check_linear(linear).spp
+    if a.ndim == 3 and a.shape[2] == 1 and spp == 1:
+        a = a[:, :, 0]
+    if a.ndim != (3 if spp == 3 else 2) or a.shape[0] < 1 or a.shape[1] < 1 or (spp == 3 and a.shape[2] != 3):
+        raise InvalidOptionError("samples", a.shape, "a linear frame is H x W x 3 samples (spp 3) or H x W (spp 1)")
+    if shape is not None and a.shape[:2] != tuple(shape):
+        raise InvalidOptionError("samples", a.shape, f"expected {tuple(shape)} pixels")
+    if dtype is not None and a.dtype != np.dtype(dtype):
+        raise BitDepthError(np.dtype(dtype), a.dtype)
+    return a
+
+
+def _linear_options(develop, finish):
+    """what a linear frame does not take: defect sites and a vignette gain address the sites of a CFA mosaic"""
+    if develop is not None and check_develop(develop).defects is not None:
+        raise InvalidOptionError("develop", develop, "Develop.defects lists the sites of a CFA mosaic: a LinearRaw frame has none")
+    if finish is not None:
+        from .dng import check_finish
+        if check_finish(finish).vignette is not None:
+            raise InvalidOptionError("finish", finish, "Finish.vignette is a gain on the sites of a CFA mosaic: a LinearRaw frame has none")
+
+
+def develop_linear_device(dev_samples, dev_bgr, h, w, dtype, linear, device=0, stream=None, develop=None, lens=None, lens_scratch=None,
+                          finish=None, finish_scratch=None):
+    """develop_linear() for samples resident in HBM: `dev_samples` (h x w x linear.spp, only read) -> `dev_bgr` (h x w x 3).
+    Queued on `stream`, not waited for.  `develop`: a Develop without defect sites -- its colour matrix and tone curve ride
+    on the kernel; its device tables must outlive it.  `lens`, `lens_scratch`, `finish`, `finish_scratch`: as in
+    debayer_device -- the lens remap and then crop and orientation behind the development, each through one scratch frame of
+    h x w x 3 samples; a Finish with a vignette is refused (it is a gain on mosaic sites)."""
+    dt = _dtype(dtype)
+    _linear_options(develop, finish)
+    need = int(h) * int(w) * 3 * dt.itemsize
+    if finish is not None and finish.geometry((h, w)):
+        own = finish_scratch is None
+        if not own and getattr(finish_scratch, "nbytes", 0) < need:
+            raise InvalidOptionError("finish_scratch", getattr(finish_scratch, "nbytes", finish_scratch),
+                                     f"a DeviceBuffer of at least {need} bytes (h x w x 3 samples) is expected")
+        if own:
+            _lib.require_device()
+            finish_scratch = _lib.DeviceBuffer(need, device)
+        try:
+            develop_linear_device(dev_samples, finish_scratch.ptr, h, w, dt, linear, device=device, stream=stream, develop=develop,
+                                  lens=lens, lens_scratch=lens_scratch)
+            finish_frame_device(finish_scratch.ptr, dev_bgr, h, w, dt, finish, device=device, stream=stream)
+            if own:
+                _lib.check(_lib.load().mi_device_synchronize(device))
+        finally:
+            if own:
+                finish_scratch.free()
+        return
+    if lens is not None:
+        from .lens import check_lens, correct_device
+        lens = check_lens(lens)
+        own = lens_scratch is None
+        if not own and getattr(lens_scratch, "nbytes", 0) < need:
+            raise InvalidOptionError("lens_scratch", getattr(lens_scratch, "nbytes", lens_scratch),
+                                     f"a DeviceBuffer of at least {need} bytes (h x w x 3 samples) is expected")
+        if own:
+            _lib.require_device()
+            lens_scratch = _lib.DeviceBuffer(need, device)
+        try:
+            develop_linear_device(dev_samples, lens_scratch.ptr, h, w, dt, linear, device=device, stream=stream, develop=develop)
+            correct_device(lens_scratch.ptr, dev_bgr, h, w, dt, lens, device=device, stream=stream)
+            if own:
+                _lib.check(_lib.load().mi_device_synchronize(device))
+        finally:
+            if own:
+                lens_scratch.free()
+        return
+    L = _check_linear(linear).struct(dt)
+    if h < 1 or w < 1:
+        raise InvalidOptionError("samples", (h, w), "a linear frame is at least 1 x 1")
+    _lib.require_device()
+    d = None
+    if develop is not None:
+        d, _, _ = develop.prepared((h, w), dt, device)
+    _lib.check(_lib.load().mi_linear_develop_device(device, stream, dev_samples, dev_bgr, int(h), int(w), _lib.DTYPE_CODE[dt], _lib.C.byref(L),
+                                                    None if d is None else _lib.C.byref(d)))
+
+
+def develop_linear(samples, linear, develop=None, lens=None, finish=None, device=0):
+    """The samples of a linear raw frame (H x W x 3 in R, G, B order, or H x W at spp 1; uint8 / uint16) -> H x W x 3 BGR of
+    the same dtype: the levels of `linear` per sample, then `develop`'s colour matrix and tone curve (a Develop without defect
+    sites), one pass on the device.  `lens`: a lens.Lens behind it: equal to lens.correct(develop_linear(...), lens).
+    `finish`: a dng.Finish without a vignette: equal to finish_frame(develop_linear(...), finish); the result is H' x W' x 3."""
+    a = np.ascontiguousarray(check_samples(samples, linear))
+    L = linear.struct(a.dtype)
+    _linear_options(develop, finish)
+    h, w = a.shape[:2]
+    if lens is not None or finish is not None:
+        if lens is not None:
+            from .lens import check_lens
+            lens = check_lens(lens)
+        oh, ow = (h, w) if finish is None else finish.finished_shape((h, w))
+        _lib.require_device()
+        nb = h * w * 3 * a.itemsize
+        bufs = [_lib.DeviceBuffer(a.nbytes, device), _lib.DeviceBuffer(oh * ow * 3 * a.itemsize, device), _lib.DeviceBuffer(nb, device),
+                _lib.DeviceBuffer(nb, device)]
+        try:
+            bufs[0].upload(a)
+            develop_linear_device(bufs[0].ptr, bufs[1].ptr, h, w, a.dtype, linear, device=device, develop=develop, lens=lens,
+                                  lens_scratch=bufs[2], finish=finish, finish_scratch=bufs[3])
+            return bufs[1].download((oh, ow, 3), a.dtype)     # (a blocking copy on the null stream: behind the kernels)
+        finally:
+            for b in bufs:
+                b.free()
+    mq = tone = None
+    if develop is not None:
+        mq, tone, _ = develop.host_args((h, w), a.dtype)
+    _lib.require_device()
+    out = np.empty((h, w, 3), a.dtype)
+    _lib.check(_lib.load().mi_linear_develop(device, a.ctypes.data, out.ctypes.data, h, w, _lib.DTYPE_CODE[a.dtype], _lib.C.byref(L), mq,
+                                             None if tone is None else tone.ctypes.data))
     return out
 
 

@@ -23,8 +23,23 @@ match no code; a stack asks its handle (`Stack.ljpeg_status`).
 
 Refused, each with the tag's name and value, before any device call: deflate and lossy JPEG samples, a lossless-JPEG
 segment outside the above (each as InvalidOptionError("Compression", 7, "lossless JPEG: segment k: ...")), more than one sample
-per pixel, a CFA repeat other than 2 x 2, a CFALayout other than 1, bit depths other than 8, 10,
-12, 14 and 16, truncated segments, and a TIFF without a CFA IFD.
+per pixel in a CFA IFD, a CFA repeat other than 2 x 2, a CFALayout other than 1, bit depths other than 8, 10,
+12, 14 and 16, truncated segments, and a TIFF with neither a CFA nor a LinearRaw IFD.
+
+LinearRaw (PhotometricInterpretation 34892: an already demosaiced frame -- raw denoisers, pixel-shift composites, Foveon and
+monochrome bodies, a converter's "linear DNG" option) is read when no CFA IFD is there: SamplesPerPixel 1 or 3, chunky
+(PlanarConfiguration 1), one bit depth for every sample, BlackLevelRepeatDim (1, 1), BlackLevel and WhiteLevel single or per
+sample; the CFA tags are not read, everything else is read as for a mosaic.  `DngFrame.cfa` is then None and
+`DngFrame.linear` a demosaic.Linear, quantised as the Cfa is; `DngFrame.shape` stays in pixels and the RawLayout counts
+SAMPLES (`RawLayout.spp`): chunky rows of W pixels are rows of W spp samples, so raw_unpack decodes them unchanged, and a
+three-sample lossless-JPEG tile is one stream of Nf = 3 that raw_ljpeg3 decodes (descriptors: _lib.LJPEG_SEG3_DTYPE).
+`unpack` returns H x W x 3 RGB samples (H x W at one sample), `develop` runs demosaic.develop_linear on them (no demosaic;
+colour matrix, tone curve, lens, default crop and orientation as for a mosaic).  What is per CFA site does not apply
+(`check_linear_options`): a Calibration, Develop.defects, a SiteCorrections object and a Finish with a vignette raise
+InvalidOptionError; the file's own GainMap, bad-pixel opcodes, BlackLevelDeltaH/V and FixVignetteRadial are recorded in
+`corrections.skipped` / `finish.skipped` with the reason "LinearRaw frame" and stay in `ignored`.  Refused by name: planar
+storage, unequal bit depths, SamplesPerPixel 2 or 4, streams whose Nf is not the frame's.  Stack.push_packed takes a linear
+frame through the mosaic stage's one ingest path (mi_stack_push_linear): a slot of H x W x spp samples, linear_develop behind it.
 
 The tag numbers and the opcode layouts (WarpRectilinear, GainMap, FixBadPixelsConstant, FixBadPixelsList) are written from
 memory of the DNG specification: this reader is UNPINNED against a real DNG -- it has met only the files its own tests write
@@ -66,7 +81,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from .demosaic import PATTERNS, Cfa, Develop, debayer, debayer_device, srgb_tone
+from .demosaic import PATTERNS, Cfa, Develop, Linear, debayer, debayer_device, develop_linear, develop_linear_device, srgb_tone
 from .errors import ImageLoadError, InvalidOptionError
 
 EXTENSIONS = frozenset(["dng"])
@@ -94,6 +109,8 @@ OPCODE_NAMES = {1: "WarpRectilinear", 2: "WarpFisheye", 3: "FixVignetteRadial", 
                 12: "ScalePerRow", 13: "ScalePerColumn"}
 COMPRESSION_NAMES = {7: "lossless JPEG", 8: "deflate", 34892: "lossy JPEG"}
 CFA_PHOTOMETRIC = 32803
+LINEAR_PHOTOMETRIC = 34892                      # LinearRaw: an already demosaiced frame
+LINEAR_REASON = "LinearRaw frame"               # why a per-site correction of a LinearRaw file is skipped
 _TYPES = {1: ("B", 1), 2: ("c", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8), 6: ("b", 1), 7: ("B", 1), 8: ("h", 2), 9: ("i", 4),
           10: ("ii", 8), 11: ("f", 4), 12: ("d", 8), 13: ("I", 4)}
 
@@ -110,16 +127,22 @@ class RawLayout:
     offsets                     uint32, one per segment, row-major over the segment grid, rebased to the start of the span
     compression                 1: packed samples; 7: every segment is a lossless-JPEG stream
     segments                    compression 7: one _lib.LJPEG_SEG_DTYPE record (mi_ljpeg_seg_t) per segment, its scan_off
-                                rebased to the start of the span; else None
+                                rebased to the start of the span -- at spp 3 one _lib.LJPEG_SEG3_DTYPE record
+                                (mi_ljpeg_seg3_t: streams of three components); else None
     counts                      compression 7: the file's byte count of every segment
     crop_y, crop_x, height, width   the ActiveArea (or the whole image): what comes out
     shift                       every sample is shifted left by it
     table                       the LinearizationTable (uint16) or None
     dtype                       uint8 for 8-bit files, uint16 otherwise
+    spp                         samples per pixel (a Python attribute: mi_raw_layout_t does not carry it).  1: a mosaic or a grey
+                                frame.  3: a LinearRaw frame -- the layout then describes SAMPLES, not pixels: image_width,
+                                seg_width, crop_x and width are the pixel values times 3, which is how chunky rows lie, so
+                                raw_unpack decodes them unchanged and its H x 3W samples are the H x W x 3 RGB frame
     """
 
     def __init__(self, bits, big_endian, image_height, image_width, tiled, seg_height, seg_width, offsets, crop_y=0, crop_x=0,
-                 height=None, width=None, shift=0, table=None, compression=1, segments=None, counts=None):
+                 height=None, width=None, shift=0, table=None, compression=1, segments=None, counts=None, spp=1):
+        self.spp = int(spp)
         self.bits, self.big_endian = int(bits), bool(big_endian)
         self.image_height, self.image_width = int(image_height), int(image_width)
         self.tiled, self.seg_height, self.seg_width = bool(tiled), int(seg_height), int(seg_width)
@@ -131,7 +154,8 @@ class RawLayout:
         self.table = None if table is None else np.ascontiguousarray(table, dtype=np.uint16)
         self.dtype = np.dtype(np.uint8 if self.bits == 8 else np.uint16)
         self.compression = int(compression)
-        self.segments = None if segments is None else np.ascontiguousarray(segments, dtype=_lib.LJPEG_SEG_DTYPE)
+        seg_dtype = _lib.LJPEG_SEG3_DTYPE if self.spp == 3 else _lib.LJPEG_SEG_DTYPE     # (three tables for three components)
+        self.segments = None if segments is None else np.ascontiguousarray(segments, dtype=seg_dtype)
         self.counts = None if counts is None else np.ascontiguousarray(counts, dtype=np.int64)
 
     def __repr__(self):
@@ -173,8 +197,9 @@ class DngFrame:
     """One parsed DNG file (see the module's docstring).  `span` is a read-only view of the file's mapping: the frame keeps
     the mapping alive."""
 
-    def __init__(self, path, layout, span, cfa, develop, lens, orientation, ignored, corrections=None, finish=None):
+    def __init__(self, path, layout, span, cfa, develop, lens, orientation, ignored, corrections=None, finish=None, linear=None):
         self.path, self.layout, self.span, self.cfa = path, layout, span, cfa
+        self.linear = linear                # a demosaic.Linear for a LinearRaw frame (`cfa` is then None), else None
         self.develop, self.lens, self.orientation, self.ignored = develop, lens, orientation, tuple(ignored)
         self.corrections = corrections      # a SiteCorrections, or None when the file carries none
         self.finish = Finish(orientation=orientation) if finish is None else finish    # the file's own Finish
@@ -201,14 +226,15 @@ class DngFrame:
 
     @property
     def shape(self):
-        return self.layout.height, self.layout.width
+        """(H, W) in pixels"""
+        return self.layout.height, self.layout.width // self.layout.spp
 
     @property
     def dtype(self):
         return self.layout.dtype
 
     def __repr__(self):
-        return f"DngFrame({self.path!r}, {self.layout!r}, {self.cfa!r}, ignored={list(self.ignored)})"
+        return f"DngFrame({self.path!r}, {self.layout!r}, {self.cfa if self.linear is None else self.linear!r}, ignored={list(self.ignored)})"
 
 
 class Raw:
@@ -224,6 +250,10 @@ class Raw:
                  "auto": each file's own `DngFrame.finish`; a Finish: that one for every file.  The vignette gain follows
                  the site corrections, crop and orientation are the last stage: the stack, its depth map and everything
                  derived from them come out in the finished geometry.
+
+    LinearRaw files of a folder take the same options where they mean something (develop, lens, finish); `calibration`, a
+    `develop` with defect sites and a SiteCorrections object are per CFA site and raise InvalidOptionError at such a file
+    (`check_linear_options`), "auto" records what the file carries as skipped.
     """
 
     def __init__(self, develop="auto", lens="auto", calibration=None, corrections=None, finish=None):
@@ -624,6 +654,11 @@ def _bad_list(body, h, w):
 def _site_corrections(t, rawifd, ifd0, ops2, layout, black, path):
     """the SiteCorrections of a file, or None when it carries none: BlackLevelDeltaH/V of the raw IFD (or IFD0) and the
     GainMap, FixBadPixelsConstant and FixBadPixelsList opcodes `ops2` of OpcodeList2.  black: the four levels, unshifted."""
+    if layout.spp != 1 or black is None:
+        # a LinearRaw frame has no CFA sites: every per-site correction the file carries is recorded as skipped
+        skipped = [(TAG_NAMES[tag], LINEAR_REASON) for tag in (50715, 50716) if tag in rawifd or tag in ifd0]
+        skipped += [(OPCODE_NAMES[oid], LINEAR_REASON) for oid, _ in ops2 if oid in (9, 5, 4)]
+        return SiteCorrections(skipped=skipped, applies=()) if skipped else None
     h, w, shift = layout.height, layout.width, layout.shift
     maxv = int(np.iinfo(layout.dtype).max)
     skipped, applies, seen = [], [], False
@@ -918,9 +953,11 @@ def _fix_vignette_radial(body, h, w):
         return str(exc)
 
 
-def _file_finish(t, rawifd, ifd0, ops3, layout, lens, orientation):
-    """the Finish of a file: FixVignetteRadial of OpcodeList3 (`ops3`), DefaultCropOrigin / DefaultCropSize, Orientation"""
-    h, w = layout.height, layout.width
+def _file_finish(t, rawifd, ifd0, ops3, shape, lens, orientation, linear=False):
+    """the Finish of a file whose frame is `shape` = (H, W) pixels: FixVignetteRadial of OpcodeList3 (`ops3`), DefaultCropOrigin /
+    DefaultCropSize, Orientation.  `linear`: a LinearRaw file -- its FixVignetteRadial is skipped (the radial-gain kernel
+    addresses mosaic sites)."""
+    h, w = shape
     skipped = []
 
     def get(tag):
@@ -932,7 +969,9 @@ def _file_finish(t, rawifd, ifd0, ops3, layout, lens, orientation):
     vignette = None
     where = [i for i, (oid, _) in enumerate(ops3) if oid == 3]
     warps = [i for i, (oid, _) in enumerate(ops3) if oid == 1]
-    if where:
+    if where and linear:
+        skipped.append((OPCODE_NAMES[3], LINEAR_REASON))
+    elif where:
         name = OPCODE_NAMES[3]
         scale = get(50718)
         got = _fix_vignette_radial(ops3[where[0]][1], h, w)
@@ -1089,8 +1128,12 @@ def read(path):
     ifd0, _ = t.ifd(t.first)
     cands = [ifd0] + [t.ifd(off)[0] for off in (t.values(ifd0[330]) if 330 in ifd0 else ())]
     rawifd = next((c for c in cands if _one(t, c, 262, None) == CFA_PHOTOMETRIC and _one(t, c, 254, 0) == 0), None)
+    linear = rawifd is None
+    if linear:      # no mosaic: an already demosaiced frame?
+        rawifd = next((c for c in cands if _one(t, c, 262, None) == LINEAR_PHOTOMETRIC and _one(t, c, 254, 0) == 0), None)
     if rawifd is None:
         raise ImageLoadError(path, "no CFA IFD: no IFD with PhotometricInterpretation 32803 and NewSubFileType 0")
+    ifd_name = "LinearRaw" if linear else "CFA"
 
     def get(tag, default=None):
         for c in (rawifd, ifd0):
@@ -1104,31 +1147,43 @@ def read(path):
         raise InvalidOptionError("Compression", comp, ("compressed samples are not read" if kind is None else
                                                        f"{kind} compressed samples are not read") + ": only uncompressed DNGs")
     spp = _one(t, rawifd, 277, 1)
-    if spp != 1:
+    if linear and spp not in (1, 3):
+        raise InvalidOptionError("SamplesPerPixel", spp, "a LinearRaw frame of 1 or 3 samples per pixel is read")
+    if not linear and spp != 1:
         raise InvalidOptionError("SamplesPerPixel", spp, "a CFA mosaic has one sample per pixel")
     bits = _one(t, rawifd, 258, 1)
+    if linear:
+        every = tuple(t.values(rawifd[258])) if 258 in rawifd else (1,)
+        if len(every) not in (1, spp) or any(b != every[0] for b in every):
+            raise InvalidOptionError("BitsPerSample", every, f"one bit depth, or {spp} equal ones, is read")
+        planar = _one(t, rawifd, 284, 1)
+        if planar != 1:
+            raise InvalidOptionError("PlanarConfiguration", planar, "only chunky storage (1) is read: the samples of a pixel lie together")
     if bits not in BITS:
         raise InvalidOptionError("BitsPerSample", bits, "valid values are " + ", ".join(map(str, BITS)))
-    rep = tuple(t.values(rawifd[33421])) if 33421 in rawifd else (2, 2)
-    if rep != (2, 2):
-        raise InvalidOptionError("CFARepeatPatternDim", rep, "only 2 x 2 Bayer patterns are read")
-    lay = _one(t, rawifd, 50711, 1)
-    if lay != 1:
-        raise InvalidOptionError("CFALayout", lay, "only the rectangular layout 1 is read")
-    planes = tuple(get(50710, (0, 1, 2)))
-    if planes != (0, 1, 2):
-        raise InvalidOptionError("CFAPlaneColor", planes, "only red, green, blue (0, 1, 2) is read")
-    if 33422 not in rawifd:
-        raise ImageLoadError(path, "the CFA IFD has no CFAPattern")
-    pat = tuple(t.values(rawifd[33422]))
-    pattern = "".join("RGB"[v] if 0 <= v <= 2 else "?" for v in pat)
-    if pattern not in PATTERNS:
-        raise InvalidOptionError("CFAPattern", pat, "valid patterns are " + ", ".join(PATTERNS) + " with 0 = R, 1 = G, 2 = B")
+    if not linear:
+        rep = tuple(t.values(rawifd[33421])) if 33421 in rawifd else (2, 2)
+        if rep != (2, 2):
+            raise InvalidOptionError("CFARepeatPatternDim", rep, "only 2 x 2 Bayer patterns are read")
+        lay = _one(t, rawifd, 50711, 1)
+        if lay != 1:
+            raise InvalidOptionError("CFALayout", lay, "only the rectangular layout 1 is read")
+        planes = tuple(get(50710, (0, 1, 2)))
+        if planes != (0, 1, 2):
+            raise InvalidOptionError("CFAPlaneColor", planes, "only red, green, blue (0, 1, 2) is read")
+        if 33422 not in rawifd:
+            raise ImageLoadError(path, "the CFA IFD has no CFAPattern")
+        pat = tuple(t.values(rawifd[33422]))
+        pattern = "".join("RGB"[v] if 0 <= v <= 2 else "?" for v in pat)
+        if pattern not in PATTERNS:
+            raise InvalidOptionError("CFAPattern", pat, "valid patterns are " + ", ".join(PATTERNS) + " with 0 = R, 1 = G, 2 = B")
     if 256 not in rawifd or 257 not in rawifd:
-        raise ImageLoadError(path, "the CFA IFD has no ImageWidth / ImageLength")
+        raise ImageLoadError(path, f"the {ifd_name} IFD has no ImageWidth / ImageLength")
     iw, ih = _one(t, rawifd, 256, 0), _one(t, rawifd, 257, 0)
     if iw < 1 or ih < 1:
         raise InvalidOptionError("ImageWidth", (iw, ih), "the stored image is empty")
+    pw = iw                 # the stored width in pixels; from here iw, sw and the crop count SAMPLES (RawLayout.spp)
+    iw *= spp
     dt = np.dtype(np.uint8 if bits == 8 else np.uint16)
     maxv = int(np.iinfo(dt).max)
 
@@ -1138,19 +1193,20 @@ def read(path):
         sw, sh = _one(t, rawifd, 322, 0), _one(t, rawifd, 323, 0)
         if sw < 1 or sh < 1:
             raise InvalidOptionError("TileWidth", (sw, sh), "TileOffsets without a tile size")
+        sw *= spp
         off_tag, cnt_tag = 324, 325
     else:
         if 273 not in rawifd:
-            raise ImageLoadError(path, "the CFA IFD has neither StripOffsets nor TileOffsets")
+            raise ImageLoadError(path, f"the {ifd_name} IFD has neither StripOffsets nor TileOffsets")
         sw, sh = iw, min(_one(t, rawifd, 278, ih), ih)
         if sh < 1:
             raise InvalidOptionError("RowsPerStrip", sh, "a strip has at least one row")
         off_tag, cnt_tag = 273, 279
     offs = np.array(t.values(rawifd[off_tag]), np.int64)
-    layout = RawLayout(bits, t.e == ">", ih, iw, tiled, sh, sw, np.zeros(0, np.uint32), compression=comp)
+    layout = RawLayout(bits, t.e == ">", ih, iw, tiled, sh, sw, np.zeros(0, np.uint32), compression=comp, spp=spp)
     nseg = layout.grid[0] * layout.grid[1]
     if len(offs) != nseg:
-        raise InvalidOptionError(TAG_NAMES[off_tag], len(offs), f"{nseg} segments are expected for a {ih} x {iw} image")
+        raise InvalidOptionError(TAG_NAMES[off_tag], len(offs), f"{nseg} segments are expected for a {ih} x {pw} image")
     if comp == 7:
         if cnt_tag not in rawifd:
             raise InvalidOptionError("Compression", 7, f"lossless JPEG: {TAG_NAMES[cnt_tag]} is missing: the length of a compressed "
@@ -1182,19 +1238,27 @@ def read(path):
     layout.offsets = (offs - lo).astype(np.uint32)
     span = data[lo:hi]
     if comp == 7:
-        layout.segments = np.zeros(nseg, _lib.LJPEG_SEG_DTYPE)
+        # (three samples per pixel: streams of Nf = 3, descriptors with three tables; anything else in the two-table form)
+        layout.segments = np.zeros(nseg, _lib.LJPEG_SEG3_DTYPE if spp == 3 else _lib.LJPEG_SEG_DTYPE)
         for k in range(nseg):
-            _ljpeg_segment(layout.segments[k:k + 1], k, span, int(layout.offsets[k]), int(need[k]), bits, layout.segment_rows(k), sw)
+            _ljpeg_segment(layout.segments[k:k + 1], k, span, int(layout.offsets[k]), int(need[k]), bits, layout.segment_rows(k), sw,
+                           (3,) if spp == 3 else (1, 2))
 
     # crop
     if 50829 in rawifd:
         top, left, bottom, right = (int(v) for v in t.values(rawifd[50829]))
-        if not (0 <= top < bottom <= ih and 0 <= left < right <= iw):
-            raise InvalidOptionError("ActiveArea", (top, left, bottom, right), f"it lies outside the {ih} x {iw} image")
-        layout.crop_y, layout.crop_x, layout.height, layout.width = top, left, bottom - top, right - left
+        if not (0 <= top < bottom <= ih and 0 <= left < right <= pw):
+            raise InvalidOptionError("ActiveArea", (top, left, bottom, right), f"it lies outside the {ih} x {pw} image")
+        layout.crop_y, layout.crop_x, layout.height, layout.width = top, left * spp, bottom - top, (right - left) * spp
 
     # levels
-    white = int(round(get(50717, ((1 << bits) - 1,))[0]))
+    whites = [int(round(v)) for v in get(50717, ((1 << bits) - 1,))]
+    if linear and len(whites) not in (1, spp):
+        raise InvalidOptionError("WhiteLevel", tuple(whites), f"one value, or one per sample ({spp}), is expected")
+    whites = whites * spp if linear and len(whites) == 1 else whites
+    if linear and not all(1 <= v <= maxv for v in whites):
+        raise InvalidOptionError("WhiteLevel", tuple(whites), f"it lies outside [1, {maxv}]")
+    white = max(whites) if linear else whites[0]      # (a mosaic reads the first value; the shift follows the largest)
     if not 1 <= white <= maxv:
         raise InvalidOptionError("WhiteLevel", white, f"it lies outside [1, {maxv}]")
     shift = max(0, 8 * dt.itemsize - white.bit_length())
@@ -1207,25 +1271,45 @@ def read(path):
             raise InvalidOptionError("LinearizationTable", len(table), f"1 to {MAX_TABLE} entries of 16 bits are expected")
         layout.table = table.astype(np.uint16)
     brep = tuple(get(50713, (1, 1)))
+    if linear and brep != (1, 1):
+        raise InvalidOptionError("BlackLevelRepeatDim", brep, "only 1 x 1 is read for a LinearRaw frame")
     if brep not in ((1, 1), (2, 2)):
         raise InvalidOptionError("BlackLevelRepeatDim", brep, "1 x 1 or 2 x 2 is read")
-    bl = [int(np.floor(float(v) + 0.5)) for v in get(50714, (0,) * (brep[0] * brep[1]))]
-    if len(bl) != brep[0] * brep[1]:
-        raise InvalidOptionError("BlackLevel", bl, f"{brep[0] * brep[1]} values are expected")
-    black = bl * 4 if len(bl) == 1 else bl       # (its origin is the ActiveArea's: already in the crop's coordinates)
-    if min(black) < 0 or max(black) >= white:
-        raise InvalidOptionError("BlackLevel", black, f"it lies outside [0, WhiteLevel = {white})")
-
-    # colour
-    pattern = permute_pattern(pattern, layout.crop_y, layout.crop_x)
     neutral = get(50728)
-    if neutral is not None and (len(neutral) != 3 or min(neutral) <= 0):
-        raise InvalidOptionError("AsShotNeutral", tuple(neutral), "three positive values are expected")
-    gains = []
-    for pos in range(4):
-        wb = 1.0 if neutral is None else float(neutral[1]) / float(neutral["RGB".index(pattern[pos])])
-        gains.append(wb * maxv / float((white - black[pos]) << shift))
-    cfa = Cfa(pattern, black=[b << shift for b in black], gains=gains, white=None)
+
+    def check_neutral():
+        if neutral is not None and (len(neutral) != 3 or min(neutral) <= 0):
+            raise InvalidOptionError("AsShotNeutral", tuple(neutral), "three positive values are expected")
+    cfa = lin = black = None
+    if linear:
+        check_neutral()
+        bl = [int(np.floor(float(v) + 0.5)) for v in get(50714, (0,))]
+        if len(bl) not in (1, spp):
+            raise InvalidOptionError("BlackLevel", bl, f"one value, or one per sample ({spp}), is expected")
+        bl = bl * spp if len(bl) == 1 else bl
+        if min(bl) < 0 or any(b >= w for b, w in zip(bl, whites)):
+            raise InvalidOptionError("BlackLevel", bl, f"it lies outside [0, WhiteLevel = {tuple(whites)})")
+        gains = []
+        for c in range(spp):
+            wb = 1.0 if neutral is None or spp == 1 else float(neutral[1]) / float(neutral[c])
+            gains.append(wb * maxv / float((whites[c] - bl[c]) << shift))
+        lin = Linear(black=[b << shift for b in bl], gains=gains, white=None, spp=spp)
+    else:
+        bl = [int(np.floor(float(v) + 0.5)) for v in get(50714, (0,) * (brep[0] * brep[1]))]
+        if len(bl) != brep[0] * brep[1]:
+            raise InvalidOptionError("BlackLevel", bl, f"{brep[0] * brep[1]} values are expected")
+        black = bl * 4 if len(bl) == 1 else bl       # (its origin is the ActiveArea's: already in the crop's coordinates)
+        if min(black) < 0 or max(black) >= white:
+            raise InvalidOptionError("BlackLevel", black, f"it lies outside [0, WhiteLevel = {white})")
+
+        # colour
+        pattern = permute_pattern(pattern, layout.crop_y, layout.crop_x)
+        check_neutral()
+        gains = []
+        for pos in range(4):
+            wb = 1.0 if neutral is None else float(neutral[1]) / float(neutral["RGB".index(pattern[pos])])
+            gains.append(wb * maxv / float((white - black[pos]) << shift))
+        cfa = Cfa(pattern, black=[b << shift for b in black], gains=gains, white=None)
     mats = {k: get(tag) for k, tag in ((1, 50721), (2, 50722))}
     ill = {1: _one(t, ifd0, 50778, _one(t, rawifd, 50778, None)), 2: _one(t, ifd0, 50779, _one(t, rawifd, 50779, None))}
     pick = next((k for k in (1, 2) if mats[k] is not None and ill[k] == D65), None)
@@ -1254,7 +1338,7 @@ def read(path):
         for oid, body in ops:
             oname = OPCODE_NAMES.get(oid, f"Opcode{oid}")
             if tag == 51022 and oid == 1 and lens is None:
-                lens = _warp_rectilinear(body, layout.height, layout.width, path)
+                lens = _warp_rectilinear(body, layout.height, layout.width // spp, path)
                 if lens is not None:
                     continue
                 oname = "WarpRectilinear (tangential terms)"
@@ -1263,8 +1347,8 @@ def read(path):
     if not 1 <= orientation <= 8:
         raise InvalidOptionError("Orientation", orientation, "valid values are 1 to 8")
     corrections = _site_corrections(t, rawifd, ifd0, ops2, layout, black, path)
-    finish = _file_finish(t, rawifd, ifd0, ops3, layout, lens, orientation)
-    return DngFrame(path, layout, span, cfa, develop, lens, orientation, ignored, corrections, finish)
+    finish = _file_finish(t, rawifd, ifd0, ops3, (layout.height, layout.width // spp), lens, orientation, linear=linear)
+    return DngFrame(path, layout, span, cfa, develop, lens, orientation, ignored, corrections, finish, linear=lin)
 
 
 def _warp_rectilinear(body, h, w, path):
@@ -1292,7 +1376,7 @@ SOF_NAMES = {0xC0: "SOF0 baseline DCT", 0xC1: "SOF1 extended sequential DCT", 0x
 LJPEG_HEADER_MAX = 65536           # (markers are looked for this far into a segment: headers are a few hundred bytes)
 
 
-def _ljpeg_segment(rec, k, span, off, count, bits, rows, seg_w):
+def _ljpeg_segment(rec, k, span, off, count, bits, rows, seg_w, nfs=(1, 2)):
     """Fill the descriptor `rec` (a one-element LJPEG_SEG_DTYPE view) of segment k, the `count` bytes of `span` from `off`,
     from the stream's markers: SOI, DHT / DRI / anything with a length, SOF3, SOS.  Only the markers are read out of the
     mapping, four bytes and then the marker's own length at a time: the sample data is not touched.  The entropy-coded data
@@ -1354,8 +1438,9 @@ def _ljpeg_segment(rec, k, span, off, count, bits, rows, seg_w):
     if frame is None:
         refuse("SOS without a frame (SOF3) in front of it")
     prec, lines, x, nf, ids = frame
-    if nf not in (1, 2):
-        refuse(f"Nf = {nf} components (1 or 2 are read)")
+    if nf not in nfs:
+        refuse(f"Nf = {nf} components (1 or 2 are read)" if nfs == (1, 2) else
+               f"Nf = {nf} components (a LinearRaw frame of 3 samples per pixel is read from streams of Nf = 3)")
     if x * nf != seg_w or lines != rows:
         refuse(f"a frame of {lines} lines of {x} x {nf} samples does not match its segment of {rows} x {seg_w}")
     if not 2 <= prec <= bits:
@@ -1396,12 +1481,34 @@ def _check_frame(frame):
     return frame
 
 
+def check_linear_options(frame, calibration=None, corrections=None, develop=None, finish=None):
+    """What a LinearRaw `frame` does not take, refused by name: a Calibration, Develop.defects, a SiteCorrections object that
+    holds anything and a Finish with a vignette are all per CFA site.  ("auto" is fine: the file's own per-site corrections
+    are then recorded as skipped, `corrections.skipped` / `finish.skipped`, with the reason "LinearRaw frame".)"""
+    if calibration is not None:
+        raise InvalidOptionError("calibration", calibration, f"{frame.path}: calibration frames are per CFA site: a LinearRaw frame has none")
+    if corrections is not None and not isinstance(corrections, str) and not check_corrections(corrections).empty:
+        raise InvalidOptionError("corrections", corrections, f"{frame.path}: site corrections are per CFA site: a LinearRaw frame has none")
+    if develop is not None and not isinstance(develop, str) and develop.defects is not None:
+        raise InvalidOptionError("develop", develop, f"{frame.path}: Develop.defects lists the sites of a CFA mosaic: a LinearRaw frame has none")
+    fin = resolve_finish(frame, finish)
+    if fin is not None and fin.vignette is not None:
+        raise InvalidOptionError("finish", fin, f"{frame.path}: Finish.vignette is a gain on the sites of a CFA mosaic: a LinearRaw frame has none")
+    return fin
+
+
 def unpack(frame, device=0, corrections=None, finish=None):
     """The cropped H x W mosaic of a DngFrame as a NumPy array of its dtype: span up, raw_unpack or raw_ljpeg, mosaic down.
     A lossless-JPEG frame one of whose streams did not decode raises ImageLoadError.  `corrections`: None, "auto" (the
     frame's own) or a SiteCorrections, applied to the unpacked mosaic (demosaic.correct_sites).  `finish`: None, "auto" or
     a Finish -- its VIGNETTE only, behind the corrections (demosaic.radial_gain; no lens follows here: the table is the
-    polynomial itself); crop and orientation belong to the developed frame (`develop`)."""
+    polynomial itself); crop and orientation belong to the developed frame (`develop`).
+    A LinearRaw frame: its H x W x 3 samples in file order (R, G, B), or H x W at one sample per pixel -- the layout counts
+    samples, so the same kernel decodes them; a SiteCorrections object or a vignette is refused (check_linear_options)."""
+    if _check_frame(frame).linear is not None:
+        check_linear_options(frame, corrections=corrections, finish=finish)
+        h, w = frame.shape
+        return _unpack_plane(frame, device).reshape((h, w, 3) if frame.layout.spp == 3 else (h, w))
     fin = resolve_finish(_check_frame(frame), finish)
     if fin is not None and fin.vignette is not None:
         from .demosaic import radial_gain
@@ -1410,6 +1517,11 @@ def unpack(frame, device=0, corrections=None, finish=None):
     if sc is not None:
         from .demosaic import correct_sites
         return correct_sites(unpack(frame, device), frame.cfa, sc, device=device)
+    return _unpack_plane(frame, device)
+
+
+def _unpack_plane(frame, device):
+    """layout.height x layout.width samples of the frame's span (a mosaic; of a LinearRaw frame the H x (W spp) samples)"""
     lay = _check_frame(frame).layout
     _lib.require_device()
     out = np.empty((lay.height, lay.width), lay.dtype)
@@ -1417,7 +1529,8 @@ def unpack(frame, device=0, corrections=None, finish=None):
     span = host_span(frame)
     if lay.compression == 7:
         status = np.zeros(len(lay.segments), np.uint32)
-        _lib.check(_lib.load().mi_raw_ljpeg(device, span.ctypes.data, span.nbytes, lay.segments.ctypes.data, _lib.C.byref(L),
+        entry = _lib.load().mi_raw_ljpeg3 if lay.spp == 3 else _lib.load().mi_raw_ljpeg
+        _lib.check(entry(device, span.ctypes.data, span.nbytes, lay.segments.ctypes.data, _lib.C.byref(L),
                                             None if lay.table is None else lay.table.ctypes.data, out.ctypes.data, status.ctypes.data))
         check_ljpeg_status(frame.path, status)
         return out
@@ -1443,9 +1556,9 @@ def unpack_device(layout, dev_span, span_bytes, dev_offsets, dev_table, dev_out,
     leaves one status word per segment at `dev_status` (or None)."""
     _lib.require_device()
     L = layout.struct()
-    if layout.compression == 7:
-        _lib.check(_lib.load().mi_raw_ljpeg_device(device, stream, dev_span, int(span_bytes), dev_offsets, _lib.C.byref(L), dev_table, dev_out,
-                                                   dev_status))
+    if layout.compression == 7:     # (three samples per pixel: mi_ljpeg_seg3_t descriptors and raw_ljpeg3)
+        entry = _lib.load().mi_raw_ljpeg3_device if layout.spp == 3 else _lib.load().mi_raw_ljpeg_device
+        _lib.check(entry(device, stream, dev_span, int(span_bytes), dev_offsets, _lib.C.byref(L), dev_table, dev_out, dev_status))
         return
     _lib.check(_lib.load().mi_raw_unpack_device(device, stream, dev_span, int(span_bytes), dev_offsets, _lib.C.byref(L), dev_table, dev_out))
 
@@ -1503,6 +1616,9 @@ def develop(frame, develop="auto", lens="auto", calibration=None, device=0, corr
     file's site corrections, ahead of the calibration.  `finish`: None, "auto" or a Finish -- the vignette gain behind the
     corrections, crop and orientation last: the result is then H' x W' x 3 (`DngFrame.finished_shape`)."""
     dev, ln = _resolve(_check_frame(frame), develop, lens)
+    if frame.linear is not None:    # no mosaic: the samples straight into linear_develop; crop and orientation apply
+        fin = check_linear_options(frame, calibration, corrections, dev, finish)
+        return develop_linear(unpack(frame, device), frame.linear, develop=dev, lens=ln, finish=fin, device=device)
     sc = resolve_corrections(frame, corrections)
     fin = resolve_finish(frame, finish)
     if fin is not None:
@@ -1537,10 +1653,16 @@ def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None,
                 first = frame
                 h, w = frame.shape
                 frame_bytes = h * w * 3 * frame.dtype.itemsize
-                stage = _lib.DeviceBuffer(h * w * frame.dtype.itemsize, device)
             elif frame.shape != first.shape or frame.dtype != first.dtype:
                 raise InvalidOptionError("paths", p, f"a {frame.shape} {frame.dtype} frame among {first.shape} {first.dtype} ones")
+            stage_bytes = h * w * frame.layout.spp * frame.dtype.itemsize      # (a LinearRaw frame: spp samples per pixel)
+            if stage is None or stage.nbytes < stage_bytes:
+                if stage is not None:
+                    stage.free()        # (the device was waited for behind the frame before)
+                stage = _lib.DeviceBuffer(stage_bytes, device)
             dev, ln = _resolve(frame, develop, lens)
+            if frame.linear is not None:
+                check_linear_options(frame, calibration, corrections, dev, finish)
             if ln is not None and scratch is None:
                 scratch = _lib.DeviceBuffer(frame_bytes, device)
             fin = resolve_finish(frame, finish)
@@ -1556,11 +1678,15 @@ def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None,
             up = _Staged(frame, device)
             try:
                 up.unpack_into(frame.layout, stage.ptr, device)
-                sc = resolve_corrections(frame, corrections)
+                sc = None if frame.linear is not None else resolve_corrections(frame, corrections)
                 if sc is not None:
                     from .demosaic import correct_sites_device
                     correct_sites_device(stage.ptr, h, w, frame.dtype, frame.cfa, sc, device=device)
-                if fin is not None:
+                if frame.linear is not None:
+                    develop_linear_device(stage.ptr, dev_out + i * (frame_bytes if fin is None else out_bytes), h, w, frame.dtype,
+                                          frame.linear, device=device, develop=dev, lens=ln, lens_scratch=scratch, finish=fin,
+                                          finish_scratch=fscratch)
+                elif fin is not None:
                     debayer_device(stage.ptr, dev_out + i * out_bytes, h, w, frame.dtype, frame.cfa, device=device, develop=dev,
                                    calibration=calibration, lens=ln, lens_scratch=scratch, finish=fin, finish_scratch=fscratch)
                 else:

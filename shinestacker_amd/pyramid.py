@@ -361,6 +361,9 @@ class PyramidStack(BaseStackAlgo):
         dev, ln = raw.develop_for(frame), raw.lens_for(frame)
         if dev is not None and dev is frame.develop:     # files of one camera share one Develop: one tone table on the device
             dev = self._raw_develops.setdefault(dev.matrix_q, dev)
+        if frame.linear is not None:
+            self._push_linear(stack, frame, dev, ln)
+            return
         from .dng import resolve_corrections
         sc = resolve_corrections(frame, raw.corrections)
         fin = raw.finish_for(frame)
@@ -400,6 +403,37 @@ class PyramidStack(BaseStackAlgo):
                 sc.close()      # (the file's own tables: nothing queued reads them any more)
             if fin is not None and fin is frame.finish:
                 fin.close()
+
+    def _push_linear(self, stack, frame, dev, ln):
+        """one LinearRaw DngFrame into the stack.  Without a lens and a finish: Stack.push_packed, the one ingest path, as for a
+        CFA frame.  With one (the push has neither): its samples are unpacked and developed on the device (no demosaic:
+        demosaic.develop_linear_device), lens-corrected and finished as self.raw asks, and pushed from there.  What a linear
+        frame does not take (a calibration, defect sites, a SiteCorrections object, a vignette) is refused by name."""
+        from .demosaic import develop_linear_device
+        from .dng import _Staged, check_linear_options
+        raw = self.raw
+        fin = check_linear_options(frame, raw.calibration, raw.corrections, dev, raw.finish)
+        if ln is None and fin is None:
+            stack.push_packed(frame, develop=dev, calibration=raw.calibration, corrections=raw.corrections)
+            return
+        h, w = frame.shape
+        nb = h * w * frame.dtype.itemsize
+        up, bufs = None, []
+        try:
+            up = _Staged(frame, self.device)
+            bufs += [_lib.DeviceBuffer(frame.layout.spp * nb, self.device), _lib.DeviceBuffer(3 * nb, self.device)]
+            bufs += [_lib.DeviceBuffer(3 * nb, self.device) for opt in (ln, fin) if opt is not None]
+            up.unpack_into(frame.layout, bufs[0].ptr, self.device)
+            develop_linear_device(bufs[0].ptr, bufs[1].ptr, h, w, frame.dtype, frame.linear, device=self.device, develop=dev, lens=ln,
+                                  lens_scratch=None if ln is None else bufs[2], finish=fin,
+                                  finish_scratch=None if fin is None else bufs[-1])
+            _lib.check(_lib.load().mi_device_synchronize(self.device))   # the null stream's kernels, ahead of the handle's
+            up.check_status()
+            stack.push_frames_device(bufs[1].ptr, 1)
+            stack.sync()                                                 # ... and the handle's, ahead of the buffers' release
+        finally:
+            for b in ([] if up is None else [up.buf]) + bufs:
+                b.free()
 
     def focus_stack_arrays(self, frames, mosaic=None, develop=None, calibration=None):
         """In-memory variant (no file I/O): `frames` is a sequence of H x W x 3 uint8/uint16

@@ -109,7 +109,7 @@ def encode_frame(mosaic, bits, seg_h, seg_w, tiled, ncomp=2, threads=16):
         return encode_segment(block, ncomp, bits)
     with ThreadPoolExecutor(threads) as pool:
         done = list(pool.map(one, range(nsy * nsx)))
-    segs = np.zeros(len(done), _lib.LJPEG_SEG_DTYPE)
+    segs = np.zeros(len(done), _lib.LJPEG_SEG3_DTYPE if ncomp == 3 else _lib.LJPEG_SEG_DTYPE)     # (mi_ljpeg_seg3_t: three tables)
     parts, at = [], 0
     for k, (stream, scan, tables) in enumerate(done):
         rows = seg_h if tiled else min(seg_h, h - (k // nsx) * seg_h)
