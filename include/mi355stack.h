@@ -1107,6 +1107,54 @@ MI_API int mi_frame_finish_device(int device, void* stream, const void* dev_src,
 MI_API int mi_frame_finish(int device, const void* host_src, void* host_dst, int height, int width, int dtype, int crop_y,
                            int crop_x, int crop_h, int crop_w, int orientation);
 
+/* ---- the feature estimator: FAST-9 corners, rotated box-sum descriptors, Hamming matching, RANSAC (kernels_features.hpp) ----
+ * An algorithm of the ORB family of this library's own, pinned against nothing but tests/features_restatement.py, which states
+ * every stage in NumPy.  All stages up to the matcher are integer and exact; RANSAC is double with one rounding per operation.
+ *   gray     frame (height x width x channels, channels 1 or 3 in B, G, R order, MI_U8 / MI_U16) -> height x width bytes:
+ *            16-bit samples lose their low byte, then (1868 B + 9617 G + 4899 R + 8192) >> 14.
+ *   score    grey plane -> the FAST-9 score (16-pixel circle of radius 3, arcs of 9) of every pixel that exceeds `threshold`,
+ *            lies at least 16 pixels from every border and survives the 3 x 3 suppression (greater than the four neighbours
+ *            before it in raster order, not less than the four after it), 0 elsewhere; and the 256-bin histogram of those
+ *            scores (bin 0 stays empty).
+ *   extract  frame -> keypoints and descriptors of `levels` pyramid levels (level l + 1 = the rounded 2 x 2 mean of level l).
+ *            Level l keeps the first n_features >> l of {score >= cut} by score descending, then y, then x, where cut is the
+ *            smallest c > threshold with count(score >= c) <= max(4 (n_features >> l), 4096).  A keypoint is 5 int32
+ *            (x, y, level, score, bin): level coordinates, bin = argmax_k (m10 C[k] + m01 S[k]) over the moments of the disc
+ *            of radius 15.  A descriptor is 32 bytes: bit j = box5(p + a_j) < box5(p + b_j) for test j of the bin's pattern
+ *            (`host_pattern`: 32 x 256 x 4 int8 (xa, ya, xb, yb), every offset within 13), least significant bit first.
+ *            Levels follow each other in the output; *n_kp receives the total.  Zero keypoints is not an error.
+ *   match    32-byte descriptors: per query 3 int32 -- the train descriptor with the smallest Hamming distance (lowest index
+ *            on ties), that distance, and the smallest distance among all other train descriptors (0xFFFF when nt == 1).
+ *   ransac   src, dst: n x 2 doubles; samples: k x 2 (MI_FEAT_SIMILARITY) or k x 4 (MI_FEAT_HOMOGRAPHY) match indices.  Per
+ *            hypothesis the model (9 doubles, a 3 x 3 matrix row by row) and the number of matches with
+ *            ex*ex + ey*ey <= thr*thr; -1 and a zero model for coincident sample points, a pivot below 1e-12 in magnitude
+ *            or a sample index outside [0, n).
+ * Every entry point returns MI_ERR_INVALID naming the argument before any device call.  The device forms of gray, score, match
+ * and ransac enqueue on `stream` and do not wait; mi_feat_score_device clears dev_hist (256 uint32) itself.  Both extract forms
+ * wait for their work: the cut and the sort of each level happen on the host. */
+enum { MI_FEAT_SIMILARITY = 0, MI_FEAT_HOMOGRAPHY = 1 };
+MI_API int mi_feat_gray_device(int device, void* stream, const void* dev_frame, int height, int width, int channels, int dtype,
+                               void* dev_gray);
+MI_API int mi_feat_gray(int device, const void* host_frame, int height, int width, int channels, int dtype, void* host_gray);
+MI_API int mi_feat_score_device(int device, void* stream, const void* dev_gray, int height, int width, int threshold,
+                                void* dev_score, void* dev_hist);
+MI_API int mi_feat_score(int device, const void* host_gray, int height, int width, int threshold, void* host_score,
+                         uint32_t* host_hist);
+MI_API int mi_feat_extract_device(int device, void* stream, const void* dev_frame, int height, int width, int channels, int dtype,
+                                  int levels, int n_features, int threshold, const int8_t* host_pattern, int max_kp,
+                                  int32_t* host_kp, uint8_t* host_desc, int* n_kp);
+MI_API int mi_feat_extract(int device, const void* host_frame, int height, int width, int channels, int dtype, int levels,
+                           int n_features, int threshold, const int8_t* host_pattern, int max_kp, int32_t* host_kp,
+                           uint8_t* host_desc, int* n_kp);
+MI_API int mi_feat_match_device(int device, void* stream, const void* dev_query, int nq, const void* dev_train, int nt,
+                                void* dev_out);
+MI_API int mi_feat_match(int device, const void* host_query, int nq, const void* host_train, int nt, int32_t* host_out);
+MI_API int mi_feat_ransac_device(int device, void* stream, const double* dev_src, const double* dev_dst, int n,
+                                 const int32_t* dev_samples, int k, int model, double thr, int32_t* dev_counts,
+                                 double* dev_models);
+MI_API int mi_feat_ransac(int device, const double* host_src, const double* host_dst, int n, const int32_t* host_samples, int k,
+                          int model, double thr, int32_t* host_counts, double* host_models);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

@@ -216,9 +216,12 @@ def resolve_estimator(estimator, device=0):
         return opencv_estimator
     if estimator == "ecc":
         return ecc_estimator(device=device)
+    if estimator == "features":
+        from .features import feature_estimator
+        return feature_estimator(device=device)
     if callable(estimator):
         return estimator
-    raise InvalidOptionError("estimator", estimator, ". Valid options are: 'auto', 'opencv', 'ecc' or a callable")
+    raise InvalidOptionError("estimator", estimator, ". Valid options are: 'auto', 'opencv', 'ecc', 'features' or a callable")
 
 
 def ecc_estimator(min_correlation=0.5, max_iters=60, device=0, phase_init=False):

@@ -4079,3 +4079,6 @@ int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int
 
 // DepthMapStack handle (mi_dmap_*)
 #include "depthmap_host.hpp"
+
+// the feature estimator (mi_feat_*)
+#include "features_host.hpp"
