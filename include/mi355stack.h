@@ -1155,6 +1155,60 @@ MI_API int mi_feat_ransac_device(int device, void* stream, const double* dev_src
 MI_API int mi_feat_ransac(int device, const double* host_src, const double* host_dst, int n, const int32_t* host_samples, int k,
                           int model, double thr, int32_t* host_counts, double* host_models);
 
+/* ---- the feature estimator on resident frames: one handle, buffers kept, the cut and the sort on the device ----
+ * The stages above for a batch of frames that lie in device memory, against a reference frame whose keypoints and descriptors
+ * are extracted once.  Every device buffer for max_batch moving frames and the reference is allocated in create; estimate_batch
+ * allocates nothing.  A frame is first sub-sampled by `subsample`: `fast` takes the pixels of img[::s, ::s]; otherwise each
+ * channel is the rounded mean (a + b + c + d + 2) >> 2 of a 2 x 2 block, which is built for subsample == 2 on even sides only
+ * (anything else without `fast` is MI_ERR_INVALID; subsample == 1 ignores `fast`).
+ *   create          n_features <= 4096 here: the selection sorts a level's candidates, at most max(4 (n_features >> l), 4096) of
+ *                   them, as 64-bit keys in one workgroup's LDS, and 16384 keys are 128 KiB of the 160 KiB a workgroup may use.
+ *                   max_batch in [1, 128].  `host_pattern` as for mi_feat_extract.
+ *   set_reference   extracts the reference frame's keypoints and descriptors and keeps them; waits once.
+ *   estimate_batch  n <= max_batch frames: grey, pyramid, score, cut, selection, descriptors, matches per level (forwards, and
+ *                   backwards for MI_FEAT_MATCH_HAMMING), the good matches -- cross-check sorted by distance then query, or the
+ *                   ratio test distance < ratio * second distance in double in query order --, RANSAC over max_iters
+ *                   hypotheses (<= 4096) and the winner: the largest count, the lowest index on ties, -1 when the count is below
+ *                   the sample size or the frame has fewer than 3 (similarity) / 4 (homography) good matches.  The frame index
+ *                   rides in every launch's grid: the number of launches does not depend on n.  The host waits twice: for the
+ *                   good-match counts, from which it draws every pair's sample table (splitmix64(seed) % n_good, a repeat
+ *                   within a row drawn again; the same seed for every pair) and uploads them; and for the results.  Per frame f:
+ *                   n_good[f]; winner[f]; models[9 f ..] (zeros without a winner); inliers[f] = the winner's count;
+ *                   mask[f max_matches ..] one byte per good match; src / dst[2 f max_matches ..] the matched level-0
+ *                   positions in the moving frame / the reference, in the sub-sampled frame's pixels.  max_matches must be at
+ *                   least the sum of n_features >> level.  MI_ERR_STATE before set_reference.
+ *   tap             one stage's result for one frame of the last batch (frame_slot in [0, n); -1 = the reference, which has the
+ *                   stages up to DESC), downloaded to host_out, *n_out = the number of rows:  GRAY the grey plane of pyramid
+ *                   level `level` (rows of its width);  CUT per level 4 int32 (cut, count(score >= cut), keypoints kept, 0),
+ *                   zeros for a level that is not scored;  KP 5 int32 per keypoint;  DESC 32 bytes per keypoint;  GOOD 3 int32
+ *                   per good match (index into KP of the frame, of the reference, distance);  SAMPLES 2 or 4 int32 per
+ *                   hypothesis;  COUNTS one int32 per hypothesis.  `capacity` = the bytes host_out holds: too few is
+ *                   MI_ERR_INVALID.  `level` is read by GRAY only.
+ *   stats           running totals since create: host waits and kernel launches this handle made (taps included). */
+enum { MI_FEAT_MATCH_KNN = 0, MI_FEAT_MATCH_HAMMING = 1 };
+enum {
+    MI_FEAT_TAP_GRAY = 0,
+    MI_FEAT_TAP_CUT = 1,
+    MI_FEAT_TAP_KP = 2,
+    MI_FEAT_TAP_DESC = 3,
+    MI_FEAT_TAP_GOOD = 4,
+    MI_FEAT_TAP_SAMPLES = 5,
+    MI_FEAT_TAP_COUNTS = 6
+};
+typedef struct mi_feat_aligner* mi_feat_aligner_t;
+MI_API int mi_feat_aligner_create(mi_feat_aligner_t* out, int device, int height, int width, int dtype, int channels,
+                                  int subsample, int fast, int levels, int n_features, int threshold, const int8_t* host_pattern,
+                                  int max_batch);
+MI_API int mi_feat_aligner_set_reference(mi_feat_aligner_t fa, const void* dev_ref);
+MI_API int mi_feat_aligner_estimate_batch(mi_feat_aligner_t fa, const void* const* dev_movs, int n, int match_method, double ratio,
+                                          int kind, double rans_threshold, int max_iters, uint64_t seed, int max_matches,
+                                          int32_t* n_good, int32_t* winner, double* models, int32_t* inliers, uint8_t* mask,
+                                          double* src, double* dst);
+MI_API int mi_feat_aligner_tap(mi_feat_aligner_t fa, int frame_slot, int what, int level, void* host_out, size_t capacity,
+                               int* n_out);
+MI_API int mi_feat_aligner_stats(mi_feat_aligner_t fa, uint64_t* waits, uint64_t* launches);
+MI_API int mi_feat_aligner_destroy(mi_feat_aligner_t fa);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

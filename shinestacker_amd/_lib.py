@@ -407,6 +407,15 @@ SIGNATURES = {
                                         C.c_double, C.c_void_p, C.c_void_p]),
     "mi_feat_ransac": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p,
                                  C.c_void_p]),
+    "mi_feat_aligner_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "mi_feat_aligner_set_reference": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_feat_aligner_estimate_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
+                                                 C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_feat_aligner_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
+    "mi_feat_aligner_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mi_feat_aligner_destroy": (C.c_int, [C.c_void_p]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }
@@ -1269,6 +1278,104 @@ class Aligner:
     def close(self):
         if self._h:
             load().mi_aligner_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+FEAT_MATCH_KNN, FEAT_MATCH_HAMMING = 0, 1
+(FEAT_TAP_GRAY, FEAT_TAP_CUT, FEAT_TAP_KP, FEAT_TAP_DESC, FEAT_TAP_GOOD, FEAT_TAP_SAMPLES, FEAT_TAP_COUNTS) = range(7)
+
+
+class FeatureAligner:
+    """Device-resident feature estimator (mi_feat_aligner_t): frames stay in HBM, every buffer for `max_batch` moving frames
+    and the reference is allocated once, the cut and the sort of every level happen on the device.  `pattern`: the
+    32 x 256 x 4 int8 test table (features.pattern())."""
+
+    MAX_BATCH = 128
+    MAX_FEATURES = 4096      # a level's candidates are sorted in one workgroup's LDS
+    MAX_ITERS = 4096         # the hypothesis buffers are allocated with the handle
+
+    def __init__(self, height, width, dtype, pattern, channels=3, subsample=1, fast=True, levels=3, n_features=2000, threshold=20,
+                 max_batch=16, device=0):
+        self._h = C.c_void_p()
+        self.device = device
+        table = np.ascontiguousarray(pattern, np.int8)
+        if table.size != 32 * 256 * 4:
+            raise ValueError("a 32 x 256 x 4 int8 pattern is expected")
+        self.levels, self.max_batch = int(levels), int(max_batch)
+        self.max_matches = sum(int(n_features) >> lv for lv in range(self.levels))
+        self.shape, self._last_ns = None, 2
+        check(load().mi_feat_aligner_create(C.byref(self._h), device, int(height), int(width), DTYPE_CODE[np.dtype(dtype)],
+                                            int(channels), int(subsample), int(bool(fast)), self.levels, int(n_features),
+                                            int(threshold), table.ctypes.data, self.max_batch))
+        s = int(subsample)
+        self.shape = (-(-int(height) // s), -(-int(width) // s)) if fast or s == 1 else (int(height) // 2, int(width) // 2)
+
+    def set_reference(self, dev_ptr):
+        check(load().mi_feat_aligner_set_reference(self._h, dev_ptr))
+
+    def estimate_batch(self, dev_ptrs, match_method=FEAT_MATCH_KNN, ratio=0.75, kind=0, rans_threshold=3.0, max_iters=2000, seed=0):
+        """Up to max_batch moving frames (mi_feat_aligner_estimate_batch).  -> per frame a dict: n_good; winner (-1: no model);
+        model (9 float64); inliers (the winner's count); mask (n_good uint8); src, dst (n_good x 2 float64, level-0 positions of
+        the matches in the sub-sampled moving frame / reference)"""
+        n = len(dev_ptrs)
+        ptrs = (C.c_void_p * max(n, 1))(*dev_ptrs)
+        cap = self.max_matches
+        self._last_ns = 4 if int(kind) == 1 else 2
+        n_good, winner, inliers = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        models = np.zeros((n, 9), np.float64)
+        mask = np.zeros((n, cap), np.uint8)
+        src, dst = np.zeros((n, cap, 2), np.float64), np.zeros((n, cap, 2), np.float64)
+        check(load().mi_feat_aligner_estimate_batch(self._h, ptrs, n, int(match_method), float(ratio), int(kind), float(rans_threshold),
+                                                    int(max_iters), int(seed) & ((1 << 64) - 1), cap, n_good.ctypes.data,
+                                                    winner.ctypes.data, models.ctypes.data, inliers.ctypes.data, mask.ctypes.data,
+                                                    src.ctypes.data, dst.ctypes.data))
+        return [dict(n_good=int(g), winner=int(winner[f]), model=models[f].copy(), inliers=int(inliers[f]), mask=mask[f, :g].copy(),
+                     src=src[f, :g].copy(), dst=dst[f, :g].copy()) for f, g in enumerate(n_good.tolist())]
+
+    def tap(self, frame_slot, what, level=0):
+        """one stage's result of the last batch for one frame (-1: the reference) (mi_feat_aligner_tap): GRAY the uint8 plane of
+        pyramid level `level`; CUT levels x 4 int32 (cut, count(score >= cut), keypoints kept, 0); KP N x 5 int32; DESC N x 32
+        uint8; GOOD M x 3 int32; SAMPLES K x 2 or 4 int32; COUNTS K int32"""
+        h, w = self.shape if self.shape else (0, 0)
+        cap = {FEAT_TAP_GRAY: max(h * w, 1), FEAT_TAP_CUT: 16 * self.levels, FEAT_TAP_KP: 20 * self.max_matches,
+               FEAT_TAP_DESC: 32 * self.max_matches, FEAT_TAP_GOOD: 12 * self.max_matches, FEAT_TAP_SAMPLES: 16 * self.MAX_ITERS,
+               FEAT_TAP_COUNTS: 4 * self.MAX_ITERS}.get(what, 16)
+        buf = np.zeros(cap, np.uint8)
+        n = C.c_int(0)
+        check(load().mi_feat_aligner_tap(self._h, int(frame_slot), int(what), int(level), buf.ctypes.data, cap, C.byref(n)))
+        n = n.value
+        if what == FEAT_TAP_GRAY:
+            lh, lw = h, w
+            for _ in range(int(level)):
+                lh, lw = lh // 2, lw // 2
+            return buf[:lh * lw].reshape(lh, lw).copy()
+        if what == FEAT_TAP_CUT:
+            return buf.view(np.int32).reshape(self.levels, 4).copy()
+        if what == FEAT_TAP_KP:
+            return buf[:20 * n].view(np.int32).reshape(n, 5).copy()
+        if what == FEAT_TAP_DESC:
+            return buf[:32 * n].reshape(n, 32).copy()
+        if what == FEAT_TAP_GOOD:
+            return buf[:12 * n].view(np.int32).reshape(n, 3).copy()
+        if what == FEAT_TAP_COUNTS:
+            return buf[:4 * n].view(np.int32).copy()
+        return buf[:4 * self._last_ns * n].view(np.int32).reshape(n, self._last_ns).copy()      # SAMPLES
+
+    def stats(self):
+        """(host waits, kernel launches) this handle has made since it was created"""
+        w, k = C.c_uint64(0), C.c_uint64(0)
+        check(load().mi_feat_aligner_stats(self._h, C.byref(w), C.byref(k)))
+        return w.value, k.value
+
+    def close(self):
+        if self._h:
+            load().mi_feat_aligner_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -99,8 +99,8 @@ __device__ __forceinline__ int fast9_score(const uint8_t* g) {
 }
 
 // grid: (ceil(w / TILE_W), ceil(h / TILE_H)); block NT.  `hist` (256 counters) is zeroed by the caller.
-__global__ void __launch_bounds__(feat::NT) feat_score(const uint8_t* __restrict__ gray, uint8_t* __restrict__ score,
-                                                        uint32_t* __restrict__ hist, int h, int w, int threshold) {
+__device__ __forceinline__ void feat_score_tile(const uint8_t* __restrict__ gray, uint8_t* __restrict__ score,
+                                                uint32_t* __restrict__ hist, int h, int w, int threshold) {
     using namespace feat;
     __shared__ uint8_t G[GH * GW];
     __shared__ uint8_t S[SH * SW];
@@ -138,6 +138,11 @@ __global__ void __launch_bounds__(feat::NT) feat_score(const uint8_t* __restrict
     if (Hs[t]) atomicAdd(&hist[t], Hs[t]);
 }
 
+__global__ void __launch_bounds__(feat::NT) feat_score(const uint8_t* __restrict__ gray, uint8_t* __restrict__ score,
+                                                        uint32_t* __restrict__ hist, int h, int w, int threshold) {
+    feat_score_tile(gray, score, hist, h, w, threshold);
+}
+
 // `counter` is zeroed by the caller; at most `capacity` keys are written
 __global__ void __launch_bounds__(256) feat_compact(const uint8_t* __restrict__ score, int h, int w, int cut,
                                                      unsigned long long* __restrict__ keys, uint32_t* __restrict__ counter,
@@ -159,10 +164,10 @@ struct FeatTrig {
 // grid: ceil(n / 4); block 256 = 4 waves, one keypoint each.  keys: the level's sorted keys; every keypoint lies at least
 // EDGE from the border, so the 31 x 31 patch is inside the level.  kp: 5 ints per keypoint (x, y, level, score, bin),
 // desc: 8 words per keypoint; both already offset to the level's first keypoint.
-__global__ void __launch_bounds__(256) feat_describe(const uint8_t* __restrict__ gray, int h, int w, int level,
-                                                      const unsigned long long* __restrict__ keys, int n,
-                                                      const int8_t* __restrict__ pattern, FeatTrig trig,
-                                                      int32_t* __restrict__ kp, uint32_t* __restrict__ desc) {
+__device__ __forceinline__ void feat_describe_four(const uint8_t* __restrict__ gray, int h, int w, int level,
+                                                   const unsigned long long* __restrict__ keys, int n,
+                                                   const int8_t* __restrict__ pattern, const FeatTrig& trig,
+                                                   int32_t* __restrict__ kp, uint32_t* __restrict__ desc) {
     using namespace feat;
     __shared__ uint8_t P[4][PATCH * PATCH + 3];
     __shared__ uint16_t B[4][BOX * BOX + 1];
@@ -233,10 +238,17 @@ __global__ void __launch_bounds__(256) feat_describe(const uint8_t* __restrict__
     }
 }
 
+__global__ void __launch_bounds__(256) feat_describe(const uint8_t* __restrict__ gray, int h, int w, int level,
+                                                      const unsigned long long* __restrict__ keys, int n,
+                                                      const int8_t* __restrict__ pattern, FeatTrig trig,
+                                                      int32_t* __restrict__ kp, uint32_t* __restrict__ desc) {
+    feat_describe_four(gray, h, w, level, keys, n, pattern, trig, kp, desc);
+}
+
 // grid: ceil(nq / MATCH_NT); out: 3 ints per query (train index, distance, second distance)
-__global__ void __launch_bounds__(feat::MATCH_NT) feat_match(const unsigned long long* __restrict__ query, int nq,
-                                                              const unsigned long long* __restrict__ train, int nt,
-                                                              int32_t* __restrict__ out) {
+__device__ __forceinline__ void feat_match_block(const unsigned long long* __restrict__ query, int nq,
+                                                 const unsigned long long* __restrict__ train, int nt,
+                                                 int32_t* __restrict__ out) {
     using namespace feat;
     __shared__ unsigned long long T[MATCH_CHUNK * 4];
     const int q = blockIdx.x * MATCH_NT + threadIdx.x;
@@ -261,6 +273,12 @@ __global__ void __launch_bounds__(feat::MATCH_NT) feat_match(const unsigned long
     if (live) {
         out[(size_t)q * 3] = idx; out[(size_t)q * 3 + 1] = d1; out[(size_t)q * 3 + 2] = d2;
     }
+}
+
+__global__ void __launch_bounds__(feat::MATCH_NT) feat_match(const unsigned long long* __restrict__ query, int nq,
+                                                              const unsigned long long* __restrict__ train, int nt,
+                                                              int32_t* __restrict__ out) {
+    feat_match_block(query, nq, train, nt, out);
 }
 
 // The 8 x 9 augmented system at `a` solved in place by Gaussian elimination with partial pivoting (largest magnitude,
@@ -299,10 +317,9 @@ __device__ inline bool feat_solve8(double* a, double* h) {
 
 // grid: ceil(k / 4); block 256 = 4 waves, one hypothesis each.  src, dst: n x 2 doubles; samples: k x (2 or 4) indices;
 // counts: k ints; models: k x 9 doubles (a 3 x 3 matrix, row major; all zeros for an invalid hypothesis).
-__global__ void __launch_bounds__(feat::RANSAC_NT) feat_ransac(const double* __restrict__ src, const double* __restrict__ dst,
-                                                                int n, const int32_t* __restrict__ samples, int k, int model,
-                                                                double thr, int32_t* __restrict__ counts,
-                                                                double* __restrict__ models) {
+__device__ __forceinline__ void feat_ransac_four(const double* __restrict__ src, const double* __restrict__ dst, int n,
+                                                 const int32_t* __restrict__ samples, int k, int model, double thr,
+                                                 int32_t* __restrict__ counts, double* __restrict__ models) {
 #pragma clang fp contract(off)
     __shared__ double A[4][72];
     __shared__ double M[4][9];
@@ -381,6 +398,377 @@ __global__ void __launch_bounds__(feat::RANSAC_NT) feat_ransac(const double* __r
     if (lane == 0) {
         counts[hyp] = valid ? cnt : -1;
         for (int i = 0; i < 9; ++i) models[(size_t)hyp * 9 + i] = M[wave][i];
+    }
+}
+
+__global__ void __launch_bounds__(feat::RANSAC_NT) feat_ransac(const double* __restrict__ src, const double* __restrict__ dst,
+                                                                int n, const int32_t* __restrict__ samples, int k, int model,
+                                                                double thr, int32_t* __restrict__ counts,
+                                                                double* __restrict__ models) {
+    feat_ransac_four(src, dst, n, samples, k, model, thr, counts, models);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The batch forms of mi_feat_aligner_t (features_host.hpp).  Every buffer is an array over frame slots -- slot f's part lies at
+// base + f * stride -- and the frame index rides in the grid, so a stage is one launch whatever the batch holds.  What the
+// host decided between the stages of the single-frame form is decided here: feat_cut the cut, feat_select the sort,
+// feat_good the match filter and its order, feat_pick the winner.  Counts never leave the device: a stage reads the count
+// its predecessor left and workgroups beyond it return.
+//
+//   feat_gray_sub  the frame sub-sampled by s and turned grey in one pass: the pixels of img[::s, ::s] (AREA false), or for
+//                  s == 2 on even sides each channel's (a + b + c + d + 2) >> 2 of the 2 x 2 block (AREA true), then the
+//                  grey formula of feat_gray (16-bit samples lose their low byte after the mean, as a mean of the frame does).
+//   feat_cut       one wave per frame: lane k owns the bins 255 - 4k .. 252 - 4k; an inclusive scan over the lanes gives the
+//                  tail count above each lane's bins, and the smallest c > threshold whose tail is at most the capacity is a
+//                  minimum over the lanes.  Leaves (cut, count(score >= cut)); cut = 256 when nothing fits.
+//   feat_select    one workgroup of 1024 per frame: the score plane is read 16 bytes at a time, a pixel with score >= cut
+//                  takes a slot of the LDS key array from an LDS counter, the keys are sorted there by a bitonic network over
+//                  the next power of two (padded with all-ones keys; keys are unique, so any correct sort gives the one
+//                  answer, and this one has no data-dependent control flow), and the first min(count, n_level) leave in order.
+//                  The capacity max(4 n_level, 4096) <= SORT_MAX = 16384 keys = 128 KiB of LDS is what bounds n_features.
+//   feat_good      one workgroup per pair: the matches that pass the cross-check or the ratio test take LDS slots as keys --
+//                  (distance, query, train) for NORM_HAMMING, (query, train, distance) for KNN -- and the same sort puts
+//                  them into the order features.match gives.  Indices leave as positions in the frame's level-ordered list
+//                  (the sum of the lower levels' counts + the position within the level) beside the level-0 positions.
+//   feat_pick      one workgroup per pair: the largest count, the lowest index on ties, -1 below the sample size; then the
+//                  inlier mask of that model in residuals2's order of operations.
+namespace feat {
+constexpr int SORT_MAX = 16384, SORT_NT = 1024;
+constexpr int GOOD_MAX = 8192;                // sum of n_features >> level < 2 n_features <= 8192
+constexpr int MAX_BATCH = 128;
+constexpr int CC = 4;                         // ints per (slot, level): cut, count(score >= cut), keypoints kept, spare
+}  // namespace feat
+
+struct FeatFrames {
+    const void* p[feat::MAX_BATCH];
+};
+
+struct FeatLevels {
+    int n;                                    // levels of the handle
+    int koff[8];                              // where a level's keypoints start within a slot
+};
+
+// grid: (ceil(gh * gw / 256), frames).  The frame is H x W x channels; the grey plane gh x gw.
+template <typename T, bool AREA>
+__global__ void __launch_bounds__(256) feat_gray_sub(FeatFrames frames, uint8_t* __restrict__ dst, size_t dst_stride, int W,
+                                                      int channels, int s, int gh, int gw) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)gh * gw) return;
+    const int y = (int)(i / gw), x = (int)(i % gw);
+    const T* src = (const T*)frames.p[blockIdx.y];
+    constexpr int SH = sizeof(T) == 2 ? 8 : 0;
+    uint32_t v[3] = {0, 0, 0};
+    for (int c = 0; c < channels; ++c) {
+        if constexpr (AREA) {
+            const T* p = src + ((size_t)(2 * y) * W + 2 * x) * channels + c;
+            v[c] = (((uint32_t)p[0] + p[channels] + p[(size_t)W * channels] + p[(size_t)W * channels + channels] + 2u) >> 2) >> SH;
+        } else {
+            v[c] = (uint32_t)src[((size_t)(y * s) * W + (size_t)x * s) * channels + c] >> SH;
+        }
+    }
+    uint8_t* out = dst + blockIdx.y * dst_stride;
+    out[i] = channels == 1 ? (uint8_t)v[0] : (uint8_t)((v[0] * 1868u + v[1] * 9617u + v[2] * 4899u + (1u << 13)) >> 14);
+}
+
+// grid: (ceil((h / 2) * (w / 2) / 256), frames); src and dst are levels of the same slot
+__global__ void __launch_bounds__(256) feat_halve_batch(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t stride,
+                                                         int h, int w) {
+    const int h2 = h >> 1, w2 = w >> 1;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)h2 * w2) return;
+    const int y = (int)(i / w2), x = (int)(i % w2);
+    const uint8_t* p = src + blockIdx.y * stride + (size_t)(2 * y) * w + 2 * x;
+    dst[blockIdx.y * stride + i] = (uint8_t)(((uint32_t)p[0] + p[1] + p[w] + p[w + 1] + 2u) >> 2);
+}
+
+// grid: (ceil(w / TILE_W), ceil(h / TILE_H), frames)
+__global__ void __launch_bounds__(feat::NT) feat_score_batch(const uint8_t* __restrict__ gray, size_t gray_stride,
+                                                              uint8_t* __restrict__ score, size_t score_stride,
+                                                              uint32_t* __restrict__ hist, size_t hist_stride, int h, int w,
+                                                              int threshold) {
+    const size_t f = blockIdx.z;
+    feat_score_tile(gray + f * gray_stride, score + f * score_stride, hist + f * hist_stride, h, w, threshold);
+}
+
+// grid: frames; block 64.  hist, cc: already at the level.
+__global__ void __launch_bounds__(64) feat_cut(const uint32_t* __restrict__ hist, size_t hist_stride, int32_t* __restrict__ cc,
+                                                size_t cc_stride, int threshold, uint32_t cap) {
+    const uint32_t* h = hist + blockIdx.x * hist_stride;
+    const int lane = threadIdx.x;
+    uint32_t v[4], sum = 0;
+    for (int j = 0; j < 4; ++j) {
+        v[j] = h[255 - 4 * lane - j];
+        sum += v[j];
+    }
+    uint32_t inc = sum;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    uint32_t tail = inc - sum;                // count(score > this lane's highest bin)
+    uint32_t best_c = 256, best_n = 0;
+    for (int j = 0; j < 4; ++j) {             // downwards: a later fit is a smaller cut
+        const int c = 255 - 4 * lane - j;
+        tail += v[j];
+        if (c > threshold && tail <= cap) { best_c = (uint32_t)c; best_n = tail; }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t oc = __shfl_xor(best_c, o), on = __shfl_xor(best_n, o);
+        if (oc < best_c) { best_c = oc; best_n = on; }
+    }
+    if (lane == 0) {
+        int32_t* o = cc + blockIdx.x * cc_stride;
+        o[0] = (int32_t)best_c;
+        o[1] = (int32_t)best_n;
+    }
+}
+
+// K[0 .. n) ascending, by every thread of the workgroup (nt of them); n <= the array's power-of-two size
+__device__ __forceinline__ void feat_sort_lds(unsigned long long* K, int n, int nt) {
+    int p = 1;
+    while (p < n) p <<= 1;
+    const int t = threadIdx.x;
+    for (int i = n + t; i < p; i += nt) K[i] = ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= p; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = t; i < p; i += nt) {
+                const int o = i ^ j;
+                if (o > i) {
+                    const unsigned long long a = K[i], b = K[o];
+                    if ((a > b) == ((i & k) == 0)) { K[i] = b; K[o] = a; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// grid: frames; block SORT_NT.  score: the level's plane of slot 0; cc, keys: already at the level.
+__global__ void __launch_bounds__(feat::SORT_NT) feat_select(const uint8_t* __restrict__ score, size_t score_stride, int h, int w,
+                                                              int32_t* __restrict__ cc, size_t cc_stride,
+                                                              unsigned long long* __restrict__ keys, size_t keys_stride,
+                                                              int n_level, uint32_t cap) {
+    using namespace feat;
+    __shared__ unsigned long long K[SORT_MAX];
+    __shared__ uint32_t cnt;
+    const int t = threadIdx.x;
+    int32_t* c = cc + blockIdx.x * cc_stride;
+    const int cut = c[0];
+    if (cap > (uint32_t)SORT_MAX) cap = SORT_MAX;
+    if (t == 0) cnt = 0;
+    __syncthreads();
+    if (cut < 256) {
+        const uint8_t* p = score + blockIdx.x * score_stride;       // 16-byte aligned: the strides are multiples of 256
+        const size_t npx = (size_t)h * w, nvec = npx / 16;
+        auto take = [&](size_t i, uint32_t s) {
+            if (s < (uint32_t)cut || s == 0) return;
+            const uint32_t slot = atomicAdd(&cnt, 1u);
+            if (slot >= cap) return;
+            K[slot] = ((unsigned long long)(255 - s) << 32) | ((unsigned long long)(i / w) << 16) | (unsigned long long)(i % w);
+        };
+        for (size_t i = t; i < nvec; i += SORT_NT) {
+            const uint4 q = ((const uint4*)p)[i];
+            if ((q.x | q.y | q.z | q.w) == 0) continue;
+            const uint32_t word[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int b = 0; b < 16; ++b) take(i * 16 + b, (word[b >> 2] >> (8 * (b & 3))) & 0xFFu);
+        }
+        for (size_t i = nvec * 16 + t; i < npx; i += SORT_NT) take(i, p[i]);
+    }
+    __syncthreads();
+    const int n = (int)min(cnt, cap);
+    feat_sort_lds(K, n, SORT_NT);
+    const int kept = min(n, n_level);
+    unsigned long long* out = keys + blockIdx.x * keys_stride;
+    for (int i = t; i < kept; i += SORT_NT) out[i] = K[i];
+    if (t == 0) c[2] = kept;
+}
+
+// grid: (ceil(n_level / 4), frames); cc, keys, kp, desc: already at the level; kp_stride in keypoints
+__global__ void __launch_bounds__(256) feat_describe_batch(const uint8_t* __restrict__ gray, size_t gray_stride, int h, int w,
+                                                            int level, const unsigned long long* __restrict__ keys,
+                                                            const int32_t* __restrict__ cc, size_t cc_stride,
+                                                            const int8_t* __restrict__ pattern, FeatTrig trig,
+                                                            int32_t* __restrict__ kp, uint32_t* __restrict__ desc, size_t kp_stride) {
+    const size_t f = blockIdx.y;
+    const int n = cc[f * cc_stride + 2];
+    if ((int)blockIdx.x * 4 >= n) return;
+    feat_describe_four(gray + f * gray_stride, h, w, level, keys + f * kp_stride, n, pattern, trig, kp + f * kp_stride * 5,
+                       desc + f * kp_stride * 8);
+}
+
+// grid: (ceil(n_level / MATCH_NT), frames).  Either side may be the reference (stride 0).  q_stride, t_stride in 64-bit
+// words, out_stride in ints, the cc strides in ints; all pointers already at the level.
+__global__ void __launch_bounds__(feat::MATCH_NT) feat_match_batch(const unsigned long long* __restrict__ query, size_t q_stride,
+                                                                    const int32_t* __restrict__ q_cc, size_t q_cc_stride,
+                                                                    const unsigned long long* __restrict__ train, size_t t_stride,
+                                                                    const int32_t* __restrict__ t_cc, size_t t_cc_stride,
+                                                                    int32_t* __restrict__ out, size_t out_stride) {
+    const size_t f = blockIdx.y;
+    const int nq = q_cc[f * q_cc_stride + 2], nt = t_cc[f * t_cc_stride + 2];
+    if ((int)blockIdx.x * feat::MATCH_NT >= nq || nt < 1) return;
+    feat_match_block(query + f * q_stride, nq, train + f * t_stride, nt, out + f * out_stride);
+}
+
+// grid: frames; block SORT_NT.  cc: slot 0's level 0, ref_cc: the reference's; fwd, back, good: 3 ints per keypoint slot,
+// kp 5; kp_stride in keypoints.  method: MI_FEAT_MATCH_KNN / MI_FEAT_MATCH_HAMMING.
+__global__ void __launch_bounds__(feat::SORT_NT) feat_good(FeatLevels lv, const int32_t* __restrict__ cc, size_t cc_stride,
+                                                            const int32_t* __restrict__ ref_cc, const int32_t* __restrict__ fwd,
+                                                            const int32_t* __restrict__ back, const int32_t* __restrict__ kp,
+                                                            const int32_t* __restrict__ ref_kp, size_t kp_stride, int method,
+                                                            double ratio, int32_t* __restrict__ good, int32_t* __restrict__ n_good,
+                                                            double* __restrict__ src, double* __restrict__ dst) {
+#pragma clang fp contract(off)
+    using namespace feat;
+    __shared__ unsigned long long K[GOOD_MAX];
+    __shared__ uint32_t cnt;
+    __shared__ int P0[8], P1[8];              // keypoints of the lower levels: the moving frame's, the reference's
+    const int t = threadIdx.x;
+    const size_t f = blockIdx.x;
+    const int32_t* c = cc + f * cc_stride;
+    fwd += f * kp_stride * 3;
+    back += f * kp_stride * 3;
+    kp += f * kp_stride * 5;
+    if (t == 0) {
+        cnt = 0;
+        int a = 0, b = 0;
+        for (int l = 0; l < lv.n; ++l) {
+            P0[l] = a;
+            P1[l] = b;
+            a += c[CC * l + 2];
+            b += ref_cc[CC * l + 2];
+        }
+    }
+    __syncthreads();
+    for (int l = 0; l < lv.n; ++l) {
+        const int nq = c[CC * l + 2], nt = ref_cc[CC * l + 2];
+        if (nq < 1 || nt < 1) continue;
+        for (int q = t; q < nq; q += SORT_NT) {
+            const int32_t* e = fwd + (size_t)(lv.koff[l] + q) * 3;
+            const int idx = e[0], d1 = e[1], d2 = e[2];
+            if (idx < 0 || idx >= nt) continue;
+            const bool ok = method == MI_FEAT_MATCH_HAMMING ? back[(size_t)(lv.koff[l] + idx) * 3] == q
+                                                            : (double)d1 < ratio * (double)d2;
+            if (!ok) continue;
+            const uint32_t slot = atomicAdd(&cnt, 1u);
+            if (slot >= (uint32_t)GOOD_MAX) continue;
+            const unsigned long long r0 = (unsigned long long)(lv.koff[l] + q), r1 = (unsigned long long)(lv.koff[l] + idx);
+            K[slot] = method == MI_FEAT_MATCH_HAMMING ? ((unsigned long long)d1 << 40) | (r0 << 20) | r1
+                                                      : (r0 << 40) | (r1 << 20) | (unsigned long long)d1;
+        }
+    }
+    __syncthreads();
+    const int n = (int)min(cnt, (uint32_t)GOOD_MAX);
+    feat_sort_lds(K, n, SORT_NT);
+    good += f * kp_stride * 3;
+    src += f * kp_stride * 2;
+    dst += f * kp_stride * 2;
+    for (int i = t; i < n; i += SORT_NT) {
+        const unsigned long long key = K[i];
+        int r0, r1, d;
+        if (method == MI_FEAT_MATCH_HAMMING) {
+            d = (int)(key >> 40); r0 = (int)((key >> 20) & 0xFFFFF); r1 = (int)(key & 0xFFFFF);
+        } else {
+            r0 = (int)(key >> 40); r1 = (int)((key >> 20) & 0xFFFFF); d = (int)(key & 0xFFFFF);
+        }
+        const int32_t* a = kp + (size_t)r0 * 5;
+        const int32_t* b = ref_kp + (size_t)r1 * 5;
+        const int l = a[2] & 7;               // a match stays within its level
+        good[(size_t)i * 3] = r0 - lv.koff[l] + P0[l];
+        good[(size_t)i * 3 + 1] = r1 - lv.koff[l] + P1[l];
+        good[(size_t)i * 3 + 2] = d;
+        const double s = (double)(1 << l), h = (s - 1.0) / 2.0;     // level-0 position: x 2^l + (2^l - 1) / 2, exact
+        src[(size_t)i * 2] = (double)a[0] * s + h;
+        src[(size_t)i * 2 + 1] = (double)a[1] * s + h;
+        dst[(size_t)i * 2] = (double)b[0] * s + h;
+        dst[(size_t)i * 2 + 1] = (double)b[1] * s + h;
+    }
+    if (t == 0) n_good[f] = n;
+}
+
+// grid: (ceil(k / 4), frames); pt_stride in points.  A pair with fewer good matches than `need` is left alone.
+__global__ void __launch_bounds__(feat::RANSAC_NT) feat_ransac_batch(const double* __restrict__ src, const double* __restrict__ dst,
+                                                                      size_t pt_stride, const int32_t* __restrict__ n_good, int need,
+                                                                      const int32_t* __restrict__ samples, int k, int model,
+                                                                      double thr, int32_t* __restrict__ counts,
+                                                                      double* __restrict__ models) {
+    const size_t f = blockIdx.y;
+    const int n = n_good[f];
+    if (n < need) return;
+    const int ns = model == MI_FEAT_HOMOGRAPHY ? 4 : 2;
+    feat_ransac_four(src + f * pt_stride * 2, dst + f * pt_stride * 2, n, samples + f * (size_t)k * ns, k, model, thr,
+                     counts + f * (size_t)k, models + f * (size_t)k * 9);
+}
+
+// grid: frames; block 256.  head: 4 ints per frame (winner, its count, spare, spare); model: 9 doubles; mask: one byte per
+// good match.
+__global__ void __launch_bounds__(256) feat_pick(const int32_t* __restrict__ n_good, int need, const int32_t* __restrict__ counts,
+                                                  const double* __restrict__ models, int k, int model, double thr,
+                                                  const double* __restrict__ src, const double* __restrict__ dst, size_t pt_stride,
+                                                  int32_t* __restrict__ head, double* __restrict__ out_model,
+                                                  uint8_t* __restrict__ mask, size_t mask_stride) {
+#pragma clang fp contract(off)
+    __shared__ long long W[4];
+    __shared__ double M[9];
+    const int t = threadIdx.x;
+    const size_t f = blockIdx.x;
+    const int n = n_good[f];
+    const int ns = model == MI_FEAT_HOMOGRAPHY ? 4 : 2;
+    head += f * 4;
+    out_model += f * 9;
+    mask += f * mask_stride;
+    if (n < need) {                           // nothing was evaluated for this pair
+        if (t == 0) { head[0] = -1; head[1] = 0; }
+        if (t < 9) out_model[t] = 0.0;
+        for (int i = t; i < n; i += 256) mask[i] = 0;
+        return;
+    }
+    counts += f * (size_t)k;
+    // the largest count, then the lowest index: the maximum of (count + 1) << 32 | (2^31 - 1 - index)
+    long long best = -1;
+    for (int i = t; i < k; i += 256) {
+        const long long v = ((long long)(counts[i] + 1) << 32) | (long long)(0x7FFFFFFF - i);
+        best = v > best ? v : best;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const int hi = __shfl_xor((int)(best >> 32), o);
+        const int lo = __shfl_xor((int)(best & 0xFFFFFFFFll), o);
+        const long long v = ((long long)hi << 32) | (long long)(uint32_t)lo;
+        best = v > best ? v : best;
+    }
+    if ((t & 63) == 0) W[t >> 6] = best;
+    __syncthreads();
+    best = W[0];
+    for (int i = 1; i < 4; ++i) best = W[i] > best ? W[i] : best;
+    const int count = (int)(best >> 32) - 1;
+    const int win = count >= ns ? 0x7FFFFFFF - (int)(best & 0xFFFFFFFFll) : -1;
+    if (t < 9) {
+        const double v = win >= 0 ? models[(f * (size_t)k + win) * 9 + t] : 0.0;
+        M[t] = v;
+        out_model[t] = v;
+    }
+    if (t == 0) { head[0] = win; head[1] = win >= 0 ? count : 0; }
+    __syncthreads();
+    src += f * pt_stride * 2;
+    dst += f * pt_stride * 2;
+    const double t2 = thr * thr;
+    for (int i = t; i < n; i += 256) {
+        bool in = false;
+        if (win >= 0) {
+            const double x = src[2 * (size_t)i], y = src[2 * (size_t)i + 1], u = dst[2 * (size_t)i], v = dst[2 * (size_t)i + 1];
+            double px = (M[0] * x + M[1] * y) + M[2];
+            double py = (M[3] * x + M[4] * y) + M[5];
+            bool good = true;
+            if (model == MI_FEAT_HOMOGRAPHY) {
+                const double wd = (M[6] * x + M[7] * y) + 1.0;
+                good = !(fabs(wd) < 1e-12);
+                px = px / wd;
+                py = py / wd;
+            }
+            const double ex = px - u, ey = py - v;
+            in = good && ex * ex + ey * ey <= t2;
+        }
+        mask[i] = in ? 1 : 0;
     }
 }
 

@@ -11,6 +11,9 @@ family -- it is NOT OpenCV's ORB and is pinned against nothing but tests/feature
 Everything up to the matcher is integer and exact; RANSAC is float64 with one rounding per operation on the device, the
 refit float64 NumPy on the host.  There is no CPU path for the device stages: without a GPU they raise DeviceError.
 `FeatureParams`, `pattern`, `positions`, `sample_table` and the refit are host NumPy.
+
+`feature_estimator` works on a pair of host frames.  `FeatureAligner` is the same estimator on frames resident in device memory:
+one handle, the reference frame's features extracted once, a batch of moving frames per call (mi_feat_aligner_t).
 """
 import logging
 from collections import namedtuple
@@ -302,7 +305,11 @@ def find_transform(src_pts, dst_pts, transform=constants.DEFAULT_TRANSFORM, rans
     if counts[win] < m:
         return None, None
     t2 = np.float64(rans_threshold) * np.float64(rans_threshold)
-    inl = residuals2(models[win], src, dst, kind) <= t2
+    return _refit(src, dst, residuals2(models[win], src, dst, kind) <= t2, kind, t2)
+
+
+def _refit(src, dst, inl, kind, t2):
+    """the least-squares fit over the winning hypothesis' inliers `inl`: (M, mask) as find_transform returns them"""
     if kind == SIMILARITY:
         return fit_similarity(src[inl], dst[inl]), inl.astype(np.uint8).reshape(-1, 1)
     h = fit_homography(src[inl], dst[inl])
@@ -347,3 +354,105 @@ def feature_estimator(params=None, device=0, seed=0):
                               alignment_config.get('rans_threshold', 3.0), alignment_config.get('max_iters', 2000), seed, device)
         return len(good), m
     return estimate
+
+
+def check_subsampling(height, width, subsample, fast):
+    """The handle sub-samples on the device: `fast` for any factor, the area mean for a factor of 2 on even sides.  Every
+    other area case goes through float32 arithmetic that is pinned against nothing, and is refused."""
+    s = int(subsample)
+    if s < 1:
+        raise InvalidOptionError("subsample", subsample, "an integer >= 1 is expected")
+    if not fast and s > 1 and (s != 2 or height % 2 or width % 2):
+        raise InvalidOptionError("subsample", subsample,
+                                 f": the resident feature estimator sub-samples by area for subsample=2 on frames of even "
+                                 f"height and width only (got subsample={s} on {height} x {width}); set fast_subsampling=True "
+                                 "to run this case")
+    return s
+
+
+class FeatureAligner:
+    """`feature_estimator` for frames that are resident in device memory (mi_feat_aligner_t, csrc/features_host.hpp): one
+    handle holds every buffer for `max_batch` moving frames and the reference frame, whose keypoints and descriptors are
+    extracted once (`set_reference`).  `estimate_batch` runs every stage for the whole batch with the frame index in the
+    grid -- the cut and the sort of each level on the device -- and the host waits twice per call: for the good-match counts,
+    from which the library draws the sample tables, and for the results.  The refit is `find_transform`'s, in NumPy.
+
+    `n_features` is at most 4096 here (the selection sorts a level's candidates in one workgroup's LDS) and `max_iters` at
+    most 4096 (the hypothesis buffers are allocated with the handle); `feature_estimator` has neither limit."""
+
+    def __init__(self, height, width, dtype, params=None, subsample=1, fast=True, max_batch=16, device=0, seed=0, channels=3):
+        self.params = params or FeatureParams()
+        self.height, self.width, self.subsample = int(height), int(width), check_subsampling(height, width, subsample, fast)
+        self.fast = bool(fast) or self.subsample == 1
+        if self.params.n_features > _lib.FeatureAligner.MAX_FEATURES:
+            raise InvalidOptionError("n_features", self.params.n_features,
+                                     f": the resident feature estimator keeps at most {_lib.FeatureAligner.MAX_FEATURES} keypoints "
+                                     "on level 0 (a level's candidates are sorted in one workgroup's LDS)")
+        if isinstance(max_batch, bool) or not isinstance(max_batch, (int, np.integer)) or not 1 <= max_batch <= _lib.FeatureAligner.MAX_BATCH:
+            raise InvalidOptionError("max_batch", max_batch, f"an integer in [1, {_lib.FeatureAligner.MAX_BATCH}] is expected")
+        self.seed, self.device, self.max_batch = seed, device, int(max_batch)
+        self._al = None
+        _lib.require_device()
+        self._al = _lib.FeatureAligner(height, width, dtype, pattern(), channels=channels, subsample=self.subsample, fast=self.fast,
+                                       levels=self.params.levels, n_features=self.params.n_features,
+                                       threshold=self.params.threshold, max_batch=self.max_batch, device=device)
+        self.shape_sub = self._al.shape
+
+    @staticmethod
+    def options(matching_config, alignment_config):
+        """(match method code, ratio, kind, transform, rans_threshold, max_iters) of the configuration dictionaries, refused as
+        `feature_estimator` refuses them"""
+        matching_config, alignment_config = matching_config or {}, alignment_config or {}
+        method = alignment_config.get('align_method', constants.ALIGN_RANSAC)
+        if method != constants.ALIGN_RANSAC:
+            raise InvalidOptionError('align_method', method, ": the feature estimator (estimator='features') fits with RANSAC only")
+        transform = alignment_config.get('transform', constants.DEFAULT_TRANSFORM)
+        kind = _kind(transform)
+        match_method = matching_config.get('match_method', constants.MATCHING_KNN)
+        if match_method not in (constants.MATCHING_KNN, constants.MATCHING_NORM_HAMMING):
+            raise InvalidOptionError('match_method', match_method,
+                                     f". Valid options are: {constants.MATCHING_KNN}, {constants.MATCHING_NORM_HAMMING}")
+        max_iters = alignment_config.get('max_iters', 2000)
+        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or not 1 <= max_iters <= _lib.FeatureAligner.MAX_ITERS:
+            raise InvalidOptionError("max_iters", max_iters, f"an integer in [1, {_lib.FeatureAligner.MAX_ITERS}] is expected by the "
+                                     "resident feature estimator")
+        code = _lib.FEAT_MATCH_KNN if match_method == constants.MATCHING_KNN else _lib.FEAT_MATCH_HAMMING
+        return (code, float(matching_config.get('threshold', 0.75)), kind, transform,
+                float(alignment_config.get('rans_threshold', 3.0)), int(max_iters))
+
+    def set_reference(self, dev_ptr):
+        self._al.set_reference(dev_ptr)
+
+    def estimate_raw(self, dev_ptrs, matching_config=None, alignment_config=None):
+        """the library's per-frame results (`_lib.FeatureAligner.estimate_batch`) for the configuration dictionaries"""
+        code, ratio, kind, _, thr, max_iters = self.options(matching_config, alignment_config)
+        return self._al.estimate_batch(list(dev_ptrs), code, ratio, kind, thr, max_iters, self.seed)
+
+    def estimate_batch(self, dev_ptrs, matching_config=None, alignment_config=None):
+        """-> per frame (n_good, M, inlier_fraction): M maps the moving frame onto the reference in full-resolution pixels
+        (`align.rescale_transform`), 2 x 3 or 3 x 3, or None with fewer than 3 / 4 good matches or without a model;
+        inlier_fraction = the refit's inliers / n_good (0.0 without a model)"""
+        from .align import rescale_transform
+        _, _, kind, transform, thr, _ = self.options(matching_config, alignment_config)
+        t2 = np.float64(thr) * np.float64(thr)
+        out = []
+        for r in self.estimate_raw(dev_ptrs, matching_config, alignment_config):
+            if r["n_good"] < (4 if kind == HOMOGRAPHY else 3) or r["winner"] < 0:
+                out.append((r["n_good"], None, 0.0))
+                continue
+            m, mask = _refit(r["src"], r["dst"], r["mask"].astype(bool), kind, t2)
+            if self.subsample > 1:
+                m = rescale_transform(m, transform, self.subsample, (self.height, self.width), self.shape_sub)
+            out.append((r["n_good"], m, float(mask.sum()) / r["n_good"]))
+        return out
+
+    def tap(self, frame_slot, what, level=0):
+        return self._al.tap(frame_slot, what, level)
+
+    def stats(self):
+        return self._al.stats()
+
+    def close(self):
+        if self._al is not None:
+            self._al.close()
+            self._al = None

@@ -814,7 +814,8 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                            balance=None, ecc_batch=16, step_process=False, native_loop=True, handles=None,
                            keep_handles=False, info=None, chain_refine=True, chain_serial=False, mask_noise=None,
                            vignetting=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None,
-                           depth_composite=None, lens=None, **stack_kwargs):
+                           depth_composite=None, lens=None, estimator=None, matching_config=None, feature_params=None,
+                           **stack_kwargs):
     """BASELINE config 4 with every frame resident in HBM: `dev_frames` is the device address of
     `n_frames` contiguous H x W x 3 frames.  Each frame is registered against frames[ref_idx] by
     the device ECC estimator (mi_aligner_*), warped with the blurred replicate border of
@@ -891,6 +892,19 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     the whole job in one push (`batch_frames` >= `n_frames`, InvalidOptionError otherwise).  None (default): nothing is built,
     loaded or called.
 
+    `estimator`: None / "ecc" (default) is the ECC estimator described above.  "features": every frame is registered by the
+    feature estimator instead (features.py: FAST-9 corners, rotated box-sum descriptors, Hamming matches, RANSAC), which has no
+    capture range, on one `features.FeatureAligner` handle -- `ecc_batch` frames per call, two host waits per call -- in the
+    Python frame loop.  `matching_config` (match_method, threshold) and `alignment_config` (transform, rans_threshold, max_iters,
+    subsample, fast_subsampling, min_good_matches) are read as `align_images` reads them; `feature_params`: a
+    `features.FeatureParams`.  The third return value then holds every frame's inlier fraction (1.0 at ref_idx);
+    `min_correlation` and `max_iters` (ECC's) are not used.  A frame without a model raises AlignmentError.  A frame with no
+    more than `min_good_matches` good matches while `subsample` > 1 is estimated again at subsample 1, on a second handle
+    created on first need (the reference's `align_images` retries the same way): `info["feature_retries"]` lists those frames,
+    `info["good_matches"]` receives every frame's count.  Refused with InvalidOptionError before anything is allocated:
+    `step_process=True`, `handles=` / `keep_handles=`, `align_method='LMEDS'`, area sub-sampling other than by 2 on even sides
+    (`fast_subsampling=True` runs those), more than 4096 features or RANSAC iterations.
+
     Brush retouching (`align_and_stack`'s `retouch=`) is not offered here: the frames live in the caller's buffer and the handles
     are reused between calls, so the caller paints the result itself with `retouch.apply_device`.
 
@@ -908,6 +922,25 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
         raise InvalidOptionError("vignetting", f"{height} x {width} {np.dtype(dtype).name}",
                                  "with vignetting= the byte size of a resident frame must be a multiple of 16 (the frames are "
                                  "contiguous and the apply pass needs each 16-byte aligned); use Vignetting.run_frame on host frames")
+    # estimator='features': what it does not offer is refused before a device is looked for
+    if estimator not in (None, "ecc", "features"):
+        raise InvalidOptionError("estimator", estimator, ". Valid options are: None, 'ecc', 'features' (the resident frames are "
+                                 "registered on the device)")
+    use_features = estimator == "features"
+    if use_features:
+        from . import features as _features
+        if step_process:
+            raise InvalidOptionError("estimator", estimator, ": step_process=True is not implemented with estimator='features'")
+        if handles is not None or keep_handles:
+            raise InvalidOptionError("estimator", estimator, ": handle reuse (handles= / keep_handles=) is not implemented with "
+                                     "estimator='features'")
+        fcfg = {**_DEFAULT_ALIGNMENT_CONFIG, **(alignment_config or {})}
+        _features.FeatureAligner.options(matching_config, fcfg)
+        _features.check_subsampling(height, width, max(1, int(fcfg['subsample'])), bool(fcfg['fast_subsampling']))
+        if feature_params is not None and feature_params.n_features > _lib.FeatureAligner.MAX_FEATURES:
+            raise InvalidOptionError("n_features", feature_params.n_features,
+                                     f": the resident feature estimator keeps at most {_lib.FeatureAligner.MAX_FEATURES} keypoints on level 0")
+        native_loop = False
     _lib.require_device()
     if n_frames < 1:
         raise ValueError("no frames")
@@ -1022,8 +1055,16 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     else:
         stack = _lib.Stack(height, width, in_dtype=dt, out_dtype=dt, device=device, batch_frames=batch_frames,
                            **stack_kwargs)
-        aligner = _lib.Aligner(height, width, dt, subsample=max(1, int(cfg['subsample'])), device=device,
-                               fast=bool(cfg['fast_subsampling']))
+        try:
+            if use_features:
+                aligner = _features.FeatureAligner(height, width, dt, feature_params, subsample=max(1, int(cfg['subsample'])),
+                                                   fast=bool(cfg['fast_subsampling']), max_batch=ecc_batch, device=device)
+            else:
+                aligner = _lib.Aligner(height, width, dt, subsample=max(1, int(cfg['subsample'])), device=device,
+                                       fast=bool(cfg['fast_subsampling']))
+        except BaseException:
+            stack.close()
+            raise
         created = [stack, aligner]     # released here whenever an exception leaves this call
     if native:
         # the whole loop below in ONE library call (mi_align_stack_device): same kernels in the same order on the same
@@ -1099,10 +1140,26 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     st = stack.stream   # warps, balance and the reference-frame copy run on the stacker's own stream
     aligner.set_reference(dev_frames + ref_idx * fb)
     estimates = {}
+    retry = []                              # estimator='features': the handle at subsample 1, created on first need
+    good_matches, feature_retries = [0] * n_frames, []
+    if use_features and info is not None:
+        info["good_matches"], info["feature_retries"] = good_matches, feature_retries
 
     def estimate_from(i):
         """transforms of the next `ecc_batch` moving frames starting at frame i"""
         idx = [k for k in range(i, n_frames) if k != ref_idx][:ecc_batch]
+        if use_features:
+            for k, (ng, m, frac) in zip(idx, aligner.estimate_batch([dev_frames + k * fb for k in idx], matching_config, cfg)):
+                if ng <= cfg['min_good_matches'] and aligner.subsample > 1:     # align_images' retry without sub-sampling
+                    if not retry:
+                        retry.append(_features.FeatureAligner(height, width, dt, feature_params, subsample=1, max_batch=1,
+                                                              device=device))
+                        retry[0].set_reference(dev_frames + ref_idx * fb)
+                    ng, m, frac = retry[0].estimate_batch([dev_frames + k * fb], matching_config, cfg)[0]
+                    feature_retries.append(k)
+                good_matches[k] = ng
+                estimates[k] = (m, frac)
+            return
         fit = aligner.estimate_homography_batch if homography else aligner.estimate_batch
         ms, cs, _ = fit([dev_frames + k * fb for k in idx], max_iters=max_iters)
         for k, m, c in zip(idx, ms, cs):
@@ -1138,9 +1195,14 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                 if i not in estimates:
                     estimate_from(i)
                 m, cc = estimates.pop(i)
-                if not cc >= min_correlation:
-                    raise AlignmentError(i, f"correlation {cc:.3f} < {min_correlation}")
-                mm = (C.c_double * m.size)(*m.reshape(-1))
+                if use_features:
+                    if m is None:
+                        raise AlignmentError(i, f"no transform found from {good_matches[i]} good matches")
+                    mm = (C.c_double * m.size)(*np.asarray(m, dtype=np.float64).reshape(-1))
+                else:
+                    if not cc >= min_correlation:
+                        raise AlignmentError(i, f"correlation {cc:.3f} < {min_correlation}")
+                    mm = (C.c_double * m.size)(*m.reshape(-1))
                 warp = lib.mi_warp_perspective_device if homography else lib.mi_warp_affine_device
                 _lib.check(warp(device, st, src, dst, tmp.ptr, mask.ptr, height, width, _lib.DTYPE_CODE[dt], mm, mode, bv, 21,
                                 float(cfg['border_blur'])))
@@ -1162,6 +1224,8 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
             info["corrections"] = corr.fetch_corrections()
     finally:
         aligner.close()
+        for extra in retry:
+            extra.close()
         stack.close()
         for b in [tmp, mask] + batches:
             b.free()

@@ -61,7 +61,10 @@ def main():
     ap.add_argument("--reuse-handles", action="store_true", help="time a second stack on the handles of a first one (no allocation in the timed region)")
     ap.add_argument("--vignetting", action="store_true", help="resident mode: correct the vignetting of every frame first (Vignetting's defaults; uses the Python loop)")
     ap.add_argument("--python-loop", action="store_true", help="the call-by-call Python loop instead of mi_align_stack_device")
+    ap.add_argument("--estimator", default="ecc", choices=["ecc", "features"], help="resident mode: the ECC estimator, or the feature estimator on one FeatureAligner handle (Python loop)")
+    ap.add_argument("--scene", default=None, choices=["fields", "rectangles"], help="fields (the default with ECC): smooth random fields plus pixel noise, which have no corners; rectangles (the default with --estimator features): random rectangles drawn over them")
     args = ap.parse_args()
+    args.scene = args.scene or ("rectangles" if args.estimator == "features" else "fields")
     from shinestacker_amd import _lib as L
     from shinestacker_amd.align import ecc_estimator
     from shinestacker_amd.pipeline import align_and_stack
@@ -83,6 +86,11 @@ def main():
     scene = np.empty((H, W, 3), np.uint8)
     for c in range(3):
         scene[..., c] = np.clip(30 + 190 * field + rng.integers(-6, 7, (H, W)) + 5 * c, 0, 255).astype(np.uint8)
+    if args.scene == "rectangles":   # corners for the feature estimator: the fields alone score nowhere above FAST's threshold
+        for _ in range(H * W // 2000):
+            rh, rw = rng.integers(8, 56, 2)
+            y, x = rng.integers(0, H - 8), rng.integers(0, W - 8)
+            scene[y:y + rh, x:x + rw] = rng.integers(20, 236, 3)
     for f in range(N):
         d = f - ref
         t = np.deg2rad(0.02 * d)
@@ -103,6 +111,10 @@ def main():
         pre = {'vignetting': {}} if args.vignetting else {}
         if pre and args.reuse_handles:
             raise SystemExit("--vignetting cannot be combined with --reuse-handles")
+        if args.estimator == "features":
+            if args.reuse_handles or args.step_process:
+                raise SystemExit("--estimator features cannot be combined with --reuse-handles / --step-process")
+            pre["estimator"] = "features"
         align_and_stack_device(buf.ptr, min(N, 4), H, W, np.uint8, out_dev=out.ptr, balance=bal, arith=args.arith, step_process=args.step_process, chain_refine=not args.no_chain_refine, chain_serial=args.chain_serial, batch_frames=(args.batch or None), alignment_config=acfg, native_loop=not args.python_loop, **pre, **({'ecc_batch': args.ecc_batch} if args.ecc_batch else {}))   # warm-up
         if args.reuse_handles:   # what a job of many stacks pays per stack: the handles exist already
             if args.python_loop or (args.step_process and (args.chain_serial or args.homography)):
@@ -128,7 +140,7 @@ def main():
         recovered = {k: m.copy() for k, m in enumerate(t for t in tr if t is not None)}
         for m in recovered.values():
             m[:, 2] /= 2    # compare at the sub-sampled scale like the host path below
-        report(N, H, W, dt, recovered, truth, ref, cx, cy, ("resident, step_process (chained" + (", serial" if args.chain_serial else ", neighbour pairs + composition") + (", plain" if args.no_chain_refine else ", refined against the global reference") + ")" if args.step_process else "resident") + (" + balance" if args.balance else "") + (" + vignetting" if args.vignetting else ""), list(out.download((H, W, 3), np.uint8).shape))
+        report(N, H, W, dt, recovered, truth, ref, cx, cy, ("resident, step_process (chained" + (", serial" if args.chain_serial else ", neighbour pairs + composition") + (", plain" if args.no_chain_refine else ", refined against the global reference") + ")" if args.step_process else "resident") + (", feature estimator in place of ECC" if args.estimator == "features" else "") + (", scene of rectangles" if args.scene == "rectangles" else "") + (" + balance" if args.balance else "") + (" + vignetting" if args.vignetting else ""), list(out.download((H, W, 3), np.uint8).shape))
         return
     est = ecc_estimator()
     recovered = {}

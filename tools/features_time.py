@@ -5,6 +5,10 @@ the frame, and `ecc_estimator` on the same pair.  It reports times only; it is n
    match          mi_feat_match_device, 2000 x 2000 descriptors
    ransac         mi_feat_ransac_device, 2000 hypotheses x 1000 matches, both models
    estimate       feature_estimator on one 6 MP pair from host memory (uploads included), and ecc_estimator on the same pair
+   resident       both frames in HBM.  The per-pair entry points: mi_feat_extract_device on the moving frame (and on both
+                  frames), features.match and features.find_transform on what it returns.  The handle: FeatureAligner's
+                  estimate_batch (refit included) per frame at batch 1 and at batch 16, with the host waits and kernel launches
+                  per call from its stats
 Each figure is the median over `--rounds` rounds of `--reps` back-to-back calls that end in a device synchronise.
    python tools/features_time.py [--reps 10] [--rounds 5] [--json]"""
 import argparse
@@ -116,11 +120,60 @@ def run(name, est):
 res["estimate, features (host frames)"] = median_us(lambda: run("features", feat), reps=max(1, a.reps // 5))
 res["estimate, ECC (host frames)"] = median_us(lambda: run("ecc", ecc), reps=max(1, a.reps // 5))
 
+# ---- both frames resident: the per-pair entry points against the handle
+BATCH = 16
+pair = L.DeviceBuffer((BATCH + 1) * fb)
+handle = None
+calls = {}
+try:
+    pair.upload(ref)
+    for i in range(BATCH):
+        pair.upload(mov, (i + 1) * fb)
+    movs = [pair.ptr + (i + 1) * fb for i in range(BATCH)]
+
+    def extract(ptr):
+        L.check(lib.mi_feat_extract_device(0, None, ptr, H, W, 3, L.MI_U8, p.levels, p.n_features, p.threshold, table.ctypes.data, cap,
+                                           kp.ctypes.data, desc.ctypes.data, C.byref(n)))
+        return ft.Features(kp[:n.value].copy(), desc[:n.value].copy())
+
+    f_ref = extract(pair.ptr)
+
+    def per_pair(both):
+        f1 = extract(pair.ptr) if both else f_ref
+        f0 = extract(movs[0])
+        good = ft.match(f0, f1, cfg[1]["match_method"], cfg[1]["threshold"])
+        got["per pair, resident"] = (len(good), ft.find_transform(ft.positions(f0.kp)[good[:, 0]], ft.positions(f1.kp)[good[:, 1]],
+                                                                  "ALIGN_RIGID", 3.0, 2000)[0])
+
+    few = max(1, a.reps // 5)
+    res["resident pair: extract x 2 + match + RANSAC"] = median_us(lambda: per_pair(True), reps=few)
+    res["resident pair: extract x 1 + match + RANSAC"] = median_us(lambda: per_pair(False), reps=few)
+    handle = ft.FeatureAligner(H, W, np.uint8, p, max_batch=BATCH)
+    handle.set_reference(pair.ptr)
+
+    def batch(k):
+        got[f"handle, batch {k}"] = handle.estimate_batch(movs[:k], cfg[1], cfg[2])[0][:2]
+
+    for k in (1, BATCH):
+        w0, l0 = handle.stats()
+        batch(k)
+        w1, l1 = handle.stats()
+        calls[k] = (w1 - w0, l1 - l0)
+        med, lo, hi = median_us(lambda: batch(k), reps=few)
+        res[f"handle: estimate_batch of {k}, per frame"] = (med / k, lo / k, hi / k)
+finally:
+    if handle is not None:
+        handle.close()
+    pair.free()
+
 print(f"uint8 {H} x {W} x 3 ({H * W / 1e6:.1f} MP), {n_kp} keypoints; {a.rounds} rounds of {a.reps} calls: median (min .. max) us")
 for name, (med, lo, hi) in res.items():
     print(f"  {name:36s} {med:10.1f} ({lo:10.1f} .. {hi:10.1f})   x copy {med / res['copy of the frame'][0]:8.2f}")
 for name, (ng, m) in got.items():
     print(f"  {name}: n_good {ng}, M = {np.round(np.asarray(m), 4).tolist()}   (the scene's shift is (-7, 5))")
+for k, (waits, launches) in calls.items():
+    print(f"  handle, one estimate_batch of {k}: {waits} host waits, {launches} kernel launches")
 if a.json:
     print(json.dumps({"height": H, "width": W, "keypoints": n_kp, "reps": a.reps, "rounds": a.rounds,
-                      "median_us": {k: round(v[0], 1) for k, v in res.items()}}))
+                      "median_us": {k: round(v[0], 1) for k, v in res.items()},
+                      "handle_calls": {str(k): {"waits": v[0], "launches": v[1]} for k, v in calls.items()}}))
