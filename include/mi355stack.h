@@ -237,6 +237,33 @@ MI_API int mi_stack_depth_map_device(mi_stack_t* s, double sigma, void* dev_out)
 MI_API int mi_weighted_smooth(int device, const void* host_value, const void* host_weight, int height, int width, int value_is_int32,
                        int float_type, double sigma, void* host_out);
 
+/* ---- edge-aware refinement of the depth map (kernels_guided.hpp; no reference counterpart) ----
+ * The confidence-weighted guided filter: out = mean over the windows holding a pixel of (a I + b), where depth ~ a I + b is
+ * the weighted least-squares fit of the window, I the grey of `guide` (height x width x 3 BGR, MI_U8 / MI_U16:
+ * (1868 B + 9617 G + 4899 R + 8192) >> 14 over 255 or 65535), windows of (2 radius + 1)^2 clipped to the frame, clamped to
+ * [lo, hi].  All in float64 in a fixed evaluation order (the header of kernels_guided.hpp states it;
+ * tests/guided_restatement.py is held to it bit for bit).  value, out: height x width float32; weight: height x width of
+ * weight_float_type (MI_F32 / MI_F64), finite and >= 0.
+ * MI_ERR_INVALID, with the argument's name in the message and before any device call: null pointers, height / width < 1,
+ * radius outside [1, 32], eps outside [1e-9, 1e3] or not finite, lo / hi not finite or lo > hi, another guide_dtype or
+ * weight_float_type, and for the device form planes off their types' alignment.
+ * mi_depth_guided_device: device pointers; `dev_scratch` is MI_GUIDED_SCRATCH_PLANES * height * width doubles on a 16-byte
+ * boundary; four launches are queued on `stream` and not waited for. */
+enum { MI_GUIDED_SCRATCH_PLANES = 7, MI_GUIDED_MAX_RADIUS = 32 };
+MI_API int mi_depth_guided(int device, const void* host_value, const void* host_weight, int weight_float_type, const void* host_guide,
+                    int guide_dtype, int height, int width, int radius, double eps, double lo, double hi, void* host_out);
+MI_API int mi_depth_guided_device(int device, void* stream, const void* dev_value, const void* dev_weight, int weight_float_type,
+                           const void* dev_guide, int guide_dtype, int height, int width, int radius, double eps, double lo, double hi,
+                           void* dev_scratch, void* dev_out);
+/* mi_stack_depth_map(sigma) refined against `guide` (the fused frame, height x width x 3 of guide_dtype): the weight is the
+ * running level-0 energy, lo / hi the handle's frame numbers first and first + (n - 1) * stride.  Reads the state only;
+ * every status of mi_stack_depth_map, and MI_ERR_INVALID as above.  One device allocation per call, freed on every way out.
+ * The _device form takes `dev_guide` and `dev_out` in device memory; both wait for the handle's stream. */
+MI_API int mi_stack_depth_map_refined(mi_stack_t* s, double sigma, const void* host_guide, int guide_dtype, int radius, double eps,
+                               void* host_out);
+MI_API int mi_stack_depth_map_refined_device(mi_stack_t* s, double sigma, const void* dev_guide, int guide_dtype, int radius, double eps,
+                                      void* dev_out);
+
 /* ---- per-kernel timing (hipEvent pairs on the handle's stream) ---- */
 enum {
     MI_PROF_LEVEL = 0,    /* fused level launches of levels >= 1 (simple impl: whole frames) */
@@ -709,6 +736,12 @@ MI_API int mi_dmap_tap(mi_dmap_t* d, int what, int frame, void* host_out);
  * MI_ERR_STATE before finish.  mi_dmap_depth_map_device: `dev_out` in device memory; waits for the handle's stream. */
 MI_API int mi_dmap_depth_map(mi_dmap_t* d, double sigma, void* host_out);
 MI_API int mi_dmap_depth_map_device(mi_dmap_t* d, double sigma, void* dev_out);
+/* mi_dmap_depth_map(sigma) refined as mi_stack_depth_map_refined does: w = total for the AVERAGE map and 1 for the MAX map,
+ * lo = 0, hi = N - 1.  MI_ERR_STATE before finish. */
+MI_API int mi_dmap_depth_map_refined(mi_dmap_t* d, double sigma, const void* host_guide, int guide_dtype, int radius, double eps,
+                              void* host_out);
+MI_API int mi_dmap_depth_map_refined_device(mi_dmap_t* d, double sigma, const void* dev_guide, int guide_dtype, int radius, double eps,
+                                     void* dev_out);
 
 /* ---- raw Bayer mosaics in (kernels_demosaic.hpp; no reference counterpart: the reference reads developed frames) ----
  * A height x width mosaic of MI_U8 / MI_U16, one colour sample per site, becomes a height x width x 3 BGR frame of the same

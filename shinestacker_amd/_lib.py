@@ -211,6 +211,12 @@ SIGNATURES = {
     "mi_stack_depth_map": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "mi_stack_depth_map_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "mi_weighted_smooth": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "mi_depth_guided": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                  C.c_double, C.c_double, C.c_void_p]),
+    "mi_depth_guided_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "mi_stack_depth_map_refined": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "mi_stack_depth_map_refined_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "mi_stack_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "mi_stack_profile_get": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -328,6 +334,8 @@ SIGNATURES = {
     "mi_dmap_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mi_dmap_depth_map": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "mi_dmap_depth_map_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "mi_dmap_depth_map_refined": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "mi_dmap_depth_map_refined_device": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "mi_demosaic_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct)]),
     "mi_demosaic": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CfaStruct)]),
     "mi_stack_push_mosaic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(CfaStruct), C.c_int]),
@@ -977,9 +985,14 @@ class Stack:
         check(load().mi_stack_stream(self._h, C.byref(s)))
         return s.value
 
-    def depth_map(self, sigma=0.0, dev_ptr=None):
+    def depth_map(self, sigma=0.0, dev_ptr=None, refine=None, guide=None):
         """mi_stack_depth_map: the level-0 winner index, smoothed with the running energy as the weight (sigma > 0), as an
-        H x W float32 array -- or written to `dev_ptr` (H x W float32 of device memory), in which case nothing is returned"""
+        H x W float32 array -- or written to `dev_ptr` (H x W float32 of device memory), in which case nothing is returned.
+        With `refine` ({"radius", "eps"}, depth_out.check_refine) the map is refined against `guide`, the fused frame
+        (mi_stack_depth_map_refined): an H x W x 3 uint8 / uint16 array, or with `dev_ptr` a (device address, dtype) pair."""
+        if refine is not None:
+            return _refined_depth_map(load().mi_stack_depth_map_refined, load().mi_stack_depth_map_refined_device, self, sigma,
+                                      dev_ptr, refine, guide)
         if dev_ptr is not None:
             check(load().mi_stack_depth_map_device(self._h, float(sigma), dev_ptr))
             return None
@@ -995,6 +1008,30 @@ class Stack:
         ms, n, b = C.c_double(), C.c_int64(), C.c_double()
         check(load().mi_stack_profile_get(self._h, kind, C.byref(ms), C.byref(n), C.byref(b)))
         return ms.value, n.value, b.value
+
+
+def _refined_depth_map(host_fn, device_fn, handle, sigma, dev_ptr, refine, guide):
+    """the refined depth map of a Stack or DepthMap handle: to the host from a host guide, or to `dev_ptr` from a device one"""
+    from .depth_out import check_refine
+    o = check_refine(refine, (handle.height, handle.width))
+    if guide is None:
+        raise InvalidOptionError("guide", None, "a refined depth map needs the fused frame as its guide")
+    if dev_ptr is not None:
+        if not (isinstance(guide, tuple) and len(guide) == 2):
+            raise InvalidOptionError("guide", type(guide).__name__, "with dev_ptr the guide is a (device address, dtype) pair")
+        dt = np.dtype(guide[1])
+        if dt not in (np.uint8, np.uint16):
+            raise InvalidOptionError("guide", dt, "the guide is a uint8 or uint16 BGR frame")
+        check(device_fn(handle._h, float(sigma), guide[0], DTYPE_CODE[dt], o["radius"], o["eps"], dev_ptr))
+        return None
+    g = np.asarray(guide)
+    if g.dtype not in (np.uint8, np.uint16) or g.shape != (handle.height, handle.width, 3):
+        raise InvalidOptionError("guide", (g.shape, g.dtype), f"the guide is a uint8 or uint16 BGR frame of "
+                                 f"{(handle.height, handle.width, 3)}")
+    g = np.ascontiguousarray(g)
+    out = np.empty((handle.height, handle.width), np.float32)
+    check(host_fn(handle._h, float(sigma), g.ctypes.data, DTYPE_CODE[g.dtype], o["radius"], o["eps"], out.ctypes.data))
+    return out
 
 
 class DepthMap:
@@ -1084,8 +1121,12 @@ class DepthMap:
         check(load().mi_dmap_tap(self._h, int(what), int(frame), out.ctypes.data))
         return out
 
-    def depth_map(self, sigma=0.0, dev_ptr=None):
-        """mi_dmap_depth_map: the weighted mean frame index of a finished stack, H x W float32 (or written to `dev_ptr`)"""
+    def depth_map(self, sigma=0.0, dev_ptr=None, refine=None, guide=None):
+        """mi_dmap_depth_map: the weighted mean frame index of a finished stack, H x W float32 (or written to `dev_ptr`);
+        `refine` / `guide` as Stack.depth_map takes them (mi_dmap_depth_map_refined)"""
+        if refine is not None:
+            return _refined_depth_map(load().mi_dmap_depth_map_refined, load().mi_dmap_depth_map_refined_device, self, sigma,
+                                      dev_ptr, refine, guide)
         if dev_ptr is not None:
             check(load().mi_dmap_depth_map_device(self._h, float(sigma), dev_ptr))
             return None

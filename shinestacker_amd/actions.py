@@ -357,8 +357,24 @@ class _FocusStackCommon(FrameDirectory):
             self.retouch = check_strokes(self.retouch)
             if self.depth_composite_path is None and any(s.source == "depth_composite" for s in self.retouch):
                 raise InvalidOptionError("source", "depth_composite", "a stroke paints from the composite only with depth_composite_path set")
+        # depth_refine (extension; None: off): a dict of radius and eps (depth_out.check_refine) -- every depth map this action
+        # makes (the PNG's, the stereo pair's, the composite's and so a "depth_composite" stroke's) is refined against the fused
+        # frame as the stacker returned it, before the strokes and the denoise.  It works best on the unsmoothed map
+        # (depth_map_sigma=0.0): a Gaussian has already spread the subject's depth over the edge the filter would follow.
+        self.depth_refine = kwargs.pop('depth_refine', None)
+        if self.depth_refine is not None:
+            from .depth_out import check_refine
+            self.depth_refine = check_refine(self.depth_refine)
+            if self.depth_map_path is None and self.stereo_path is None and self.depth_composite_path is None:
+                raise InvalidOptionError("depth_refine", self.depth_refine, "nothing asks for a depth map: it goes with depth_map_path, "
+                                         "stereo_path or depth_composite_path")
         self.stack_algo.process = self
         self.frame_count = -1
+
+    def _depth_map(self):
+        """the stacker's depth map under depth_map_sigma (None: the stacker's default) and depth_refine"""
+        kw = {} if self.depth_refine is None else {"refine": self.depth_refine}
+        return self.stack_algo.depth_map(**kw) if self.depth_map_sigma is None else self.stack_algo.depth_map(self.depth_map_sigma, **kw)
 
     def _depth_composite(self, img_files):
         """the composite of the input files by the stacker's depth map; the files are read one chunk frame at a time"""
@@ -370,7 +386,7 @@ class _FocusStackCommon(FrameDirectory):
                 if img is None:
                     raise RuntimeError(f"Invalid file: {path}")
                 yield img
-        depth = self.stack_algo.depth_map() if self.depth_map_sigma is None else self.stack_algo.depth_map(self.depth_map_sigma)
+        depth = self._depth_map()
         return depth_render.composite(frames(), depth, self.depth_composite_interp, device=getattr(self.stack_algo, "device", 0))
 
     def _retouch_sources(self, filenames, img_files, stacked, composite=None):
@@ -424,7 +440,7 @@ class _FocusStackCommon(FrameDirectory):
         if self.depth_map_path is not None:
             from . import depth_out
             self.sub_message_r(': depth map')
-            depth = self.stack_algo.depth_map() if self.depth_map_sigma is None else self.stack_algo.depth_map(self.depth_map_sigma)
+            depth = self._depth_map()
             depth_out.save(_join(self.working_path, self.depth_map_path), f"{self.prefix}{parts[0]}", depth, len(filenames))
         if composite is not None:
             composite_dir = _join(self.working_path, self.depth_composite_path)
@@ -433,7 +449,7 @@ class _FocusStackCommon(FrameDirectory):
         if self.stereo_path is not None:
             from . import stereo
             self.sub_message_r(': stereo view')
-            depth = self.stack_algo.depth_map() if self.depth_map_sigma is None else self.stack_algo.depth_map(self.depth_map_sigma)
+            depth = self._depth_map()
             stereo_dir = _join(self.working_path, self.stereo_path)
             os.makedirs(stereo_dir, exist_ok=True)
             write_img(f"{stereo_dir}/{self.prefix}{parts[0]}." + '.'.join(parts[1:]),

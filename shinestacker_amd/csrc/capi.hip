@@ -27,6 +27,7 @@
 #include "kernels_denoise.hpp"
 #include "kernels_unsharp.hpp"
 #include "kernels_depth.hpp"
+#include "kernels_guided.hpp"
 #include "kernels_stereo.hpp"
 #include "kernels_brush.hpp"
 #include "kernels_composite.hpp"
@@ -3786,6 +3787,146 @@ int mi_weighted_smooth(int device, const void* host_value, const void* host_weig
     const int ft = f64 ? WS_F64 : WS_F32;
     if ((rc = tmp.upload(&v, host_value, np * vb)) || (rc = tmp.upload(&w, host_weight, np * fb)) || (rc = tmp.alloc(&out, np * 4)) ||
         (rc = ws_run(nullptr, value_is_int32 ? WS_I32 : ft, v, ft, w, f64, height, width, sigma, 0, 1, out)))
+        return rc;
+    return tmp.download(host_out, out, np * 4);
+}
+
+// ---------------------------------------------------------------- depth refinement (kernels_guided.hpp)
+static_assert(MI_GUIDED_SCRATCH_PLANES == MI_GF_PLANES, "the header's scratch size is the kernels'");
+static_assert(MI_GUIDED_MAX_RADIUS == MI_GF_MAX_RADIUS, "the header's radius limit is the kernels'");
+
+// the options every entry point of the family takes, by name
+static int gf_check_options(const void* guide, int guide_dtype, int radius, double eps, const void* out) {
+    if (!guide) return fail(MI_ERR_INVALID, "guide is null");
+    if (!out) return fail(MI_ERR_INVALID, "out is null");
+    if (guide_dtype != MI_U8 && guide_dtype != MI_U16) return fail(MI_ERR_INVALID, "guide_dtype must be MI_U8 or MI_U16 (got %d)", guide_dtype);
+    if (radius < 1 || radius > MI_GF_MAX_RADIUS)
+        return fail(MI_ERR_INVALID, "radius must be in [1, %d] (got %d)", MI_GF_MAX_RADIUS, radius);
+    if (!std::isfinite(eps) || eps < 1e-9 || eps > 1e3) return fail(MI_ERR_INVALID, "eps must be in [1e-9, 1e3] (got %g)", eps);
+    return MI_OK;
+}
+
+static int gf_check(const void* value, const void* weight, int weight_float_type, const void* guide, int guide_dtype, int height,
+                    int width, int radius, double eps, double lo, double hi, const void* out) {
+    if (!value) return fail(MI_ERR_INVALID, "value is null");
+    if (!weight) return fail(MI_ERR_INVALID, "weight is null");
+    int rc = gf_check_options(guide, guide_dtype, radius, eps, out);
+    if (rc) return rc;
+    if (weight_float_type != MI_F32 && weight_float_type != MI_F64)
+        return fail(MI_ERR_INVALID, "weight_float_type must be MI_F32 or MI_F64 (got %d)", weight_float_type);
+    if (height < 1) return fail(MI_ERR_INVALID, "height must be at least 1 (got %d)", height);
+    if (width < 1) return fail(MI_ERR_INVALID, "width must be at least 1 (got %d)", width);
+    if ((size_t)height * (size_t)width * 3 > (size_t)INT32_MAX) return fail(MI_ERR_INVALID, "height x width is too large a plane");
+    if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(MI_ERR_INVALID, "lo and hi must be finite (got %g, %g)", lo, hi);
+    if (lo > hi) return fail(MI_ERR_INVALID, "lo must not exceed hi (got %g > %g)", lo, hi);
+    return MI_OK;
+}
+
+// the four launches on `st`, for device planes: p float32, w of `wtype` (WS_F32 / WS_F64) or nullptr for unit weights,
+// scratch MI_GF_PLANES planes of doubles.  Only enqueues.
+static void gf_run(hipStream_t st, const float* p, int wtype, const void* w, const void* guide, int guide_dtype, int h, int width,
+                   int radius, double eps, double lo, double hi, double* scratch, float* out) {
+    const bool w64 = w && wtype == WS_F64, g8 = guide_dtype == MI_U8;
+    if (g8 && w64)
+        gf_launch<uint8_t, double>(st, p, (const double*)w, (const uint8_t*)guide, h, width, radius, eps, lo, hi, scratch, out);
+    else if (g8)
+        gf_launch<uint8_t, float>(st, p, (const float*)w, (const uint8_t*)guide, h, width, radius, eps, lo, hi, scratch, out);
+    else if (w64)
+        gf_launch<uint16_t, double>(st, p, (const double*)w, (const uint16_t*)guide, h, width, radius, eps, lo, hi, scratch, out);
+    else
+        gf_launch<uint16_t, float>(st, p, (const float*)w, (const uint16_t*)guide, h, width, radius, eps, lo, hi, scratch, out);
+}
+
+static inline size_t gf_round16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// The refined map of a handle: `unrefined` writes the handle's own depth map into a plane (and waits for it), the filter runs
+// on `st` with the handle's weight plane and frame numbers, and the call waits for it.  One allocation holds the scratch
+// planes, the unrefined map and, for host pointers, the guide and the result; DevScratch frees it on every way out.
+extern "C++" {
+template <typename Unrefined, typename Range>
+static int gf_refine_handle(hipStream_t st, int h, int width, Unrefined unrefined, int wtype, const void* dev_w, Range range,
+                            const void* guide, int guide_dtype, int radius, double eps, void* out, bool host) {
+    const size_t np = (size_t)h * (size_t)width, gb = np * 3 * dtype_size(guide_dtype);
+    const size_t off_p = MI_GF_PLANES * np * sizeof(double), off_out = off_p + gf_round16(np * 4);
+    const size_t off_guide = off_out + (host ? gf_round16(np * 4) : 0), total = off_guide + (host ? gb : 0);
+    DevScratch tmp(st);
+    uint8_t* buf = nullptr;
+    int rc = tmp.alloc(&buf, total);
+    if (rc) return rc;
+    float* p = (float*)(buf + off_p);
+    if ((rc = unrefined(p))) return rc;
+    const void* dev_guide = guide;
+    if (host) {
+        MI_HIP(hipMemcpyAsync(buf + off_guide, guide, gb, hipMemcpyHostToDevice, st));
+        dev_guide = buf + off_guide;
+    }
+    double lo = 0.0, hi = 0.0;
+    range(&lo, &hi);
+    float* dev_out = host ? (float*)(buf + off_out) : (float*)out;
+    gf_run(st, p, wtype, dev_w, dev_guide, guide_dtype, h, width, radius, eps, lo, hi, (double*)buf, dev_out);
+    MI_HIP(hipGetLastError());
+    if (host) return tmp.download(out, dev_out, np * 4);
+    MI_HIP(hipStreamSynchronize(st));
+    return MI_OK;
+}
+}  // extern "C++"
+
+static int stack_depth_map_refined(mi_stack_t* s, double sigma, const void* guide, int guide_dtype, int radius, double eps, void* out,
+                                   bool host) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    if ((rc = gf_check_options(guide, guide_dtype, radius, eps, out))) return rc;
+    if (!host && guide_dtype == MI_U16 && ((uintptr_t)guide & 1)) return fail(MI_ERR_INVALID, "guide is not aligned to its samples");
+    MI_HIP(hipSetDevice(s->p.device));
+    return gf_refine_handle(
+        s->stream, s->p.height, s->p.width, [&](float* p) { return mi_stack_depth_map_device(s, sigma, p); }, WS_F32, s->bestE[0],
+        [&](double* lo, double* hi) {      // the handle's frame numbers: first, first + (n - 1) * stride
+            *lo = (double)s->first_index;
+            *hi = (double)(s->first_index + (s->n_pushed - 1) * s->index_stride);
+        },
+        guide, guide_dtype, radius, eps, out, host);
+}
+
+int mi_stack_depth_map_refined_device(mi_stack_t* s, double sigma, const void* dev_guide, int guide_dtype, int radius, double eps,
+                                      void* dev_out) {
+    return stack_depth_map_refined(s, sigma, dev_guide, guide_dtype, radius, eps, dev_out, false);
+}
+
+int mi_stack_depth_map_refined(mi_stack_t* s, double sigma, const void* host_guide, int guide_dtype, int radius, double eps,
+                               void* host_out) {
+    return stack_depth_map_refined(s, sigma, host_guide, guide_dtype, radius, eps, host_out, true);
+}
+
+int mi_depth_guided_device(int device, void* stream, const void* dev_value, const void* dev_weight, int weight_float_type,
+                           const void* dev_guide, int guide_dtype, int height, int width, int radius, double eps, double lo, double hi,
+                           void* dev_scratch, void* dev_out) {
+    int rc = gf_check(dev_value, dev_weight, weight_float_type, dev_guide, guide_dtype, height, width, radius, eps, lo, hi, dev_out);
+    if (rc) return rc;
+    if (!dev_scratch) return fail(MI_ERR_INVALID, "scratch is null");
+    if ((uintptr_t)dev_scratch & 15) return fail(MI_ERR_INVALID, "scratch is not aligned to 16 bytes");
+    if (((uintptr_t)dev_value & 3) || ((uintptr_t)dev_out & 3)) return fail(MI_ERR_INVALID, "value and out are float32 planes: not aligned");
+    if ((uintptr_t)dev_weight & (weight_float_type == MI_F64 ? 7 : 3)) return fail(MI_ERR_INVALID, "weight is not aligned to its type");
+    if (guide_dtype == MI_U16 && ((uintptr_t)dev_guide & 1)) return fail(MI_ERR_INVALID, "guide is not aligned to its samples");
+    MI_HIP(hipSetDevice(device));
+    gf_run((hipStream_t)stream, (const float*)dev_value, weight_float_type == MI_F64 ? WS_F64 : WS_F32, dev_weight, dev_guide, guide_dtype,
+           height, width, radius, eps, lo, hi, (double*)dev_scratch, (float*)dev_out);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_depth_guided(int device, const void* host_value, const void* host_weight, int weight_float_type, const void* host_guide,
+                    int guide_dtype, int height, int width, int radius, double eps, double lo, double hi, void* host_out) {
+    int rc = gf_check(host_value, host_weight, weight_float_type, host_guide, guide_dtype, height, width, radius, eps, lo, hi, host_out);
+    if (rc) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t np = (size_t)height * width, wb = weight_float_type == MI_F64 ? 8 : 4;
+    DevScratch tmp(nullptr);
+    void *v = nullptr, *w = nullptr, *g = nullptr, *scratch = nullptr, *out = nullptr;
+    if ((rc = tmp.upload(&v, host_value, np * 4)) || (rc = tmp.upload(&w, host_weight, np * wb)) ||
+        (rc = tmp.upload(&g, host_guide, np * 3 * dtype_size(guide_dtype))) ||
+        (rc = tmp.alloc(&scratch, MI_GF_PLANES * np * sizeof(double))) || (rc = tmp.alloc(&out, np * 4)) ||
+        (rc = mi_depth_guided_device(device, nullptr, v, w, weight_float_type, g, guide_dtype, height, width, radius, eps, lo, hi, scratch,
+                                     out)))
         return rc;
     return tmp.download(host_out, out, np * 4);
 }

@@ -701,6 +701,37 @@ int mi_dmap_depth_map(mi_dmap_t* d, double sigma, void* host_out) {
     return tmp.download(host_out, out, nb);
 }
 
+// the refined map (kernels_guided.hpp): the map above into a scratch plane, then the filter with w = total (AVERAGE) or 1 (MAX)
+// and the frame numbers 0 .. N - 1
+static int dmap_depth_map_refined(mi_dmap_t* d, double sigma, const void* guide, int guide_dtype, int radius, double eps, void* out,
+                                  bool host) {
+    if (!d) return fail(MI_ERR_INVALID, "null handle");
+    int rc = gf_check_options(guide, guide_dtype, radius, eps, out);
+    if (rc) return rc;
+    if (!host && guide_dtype == MI_U16 && ((uintptr_t)guide & 1)) return fail(MI_ERR_INVALID, "guide is not aligned to its samples");
+    if (!d->finished) return fail(MI_ERR_STATE, "the depth map exists after finish");
+    MI_HIP(hipSetDevice(d->p.device));
+    const bool w64 = d->f64 && d->p.smooth_size <= 0;   // W (dmap_finish_t)
+    return gf_refine_handle(
+        d->stream, d->p.height, d->p.width, [&](float* p) { return mi_dmap_depth_map_device(d, sigma, p); }, w64 ? WS_F64 : WS_F32,
+        d->p.map_type == MI_DM_MAP_AVERAGE ? d->tot : nullptr,
+        [&](double* lo, double* hi) {
+            *lo = 0.0;
+            *hi = (double)(d->n - 1);
+        },
+        guide, guide_dtype, radius, eps, out, host);
+}
+
+int mi_dmap_depth_map_refined_device(mi_dmap_t* d, double sigma, const void* dev_guide, int guide_dtype, int radius, double eps,
+                                     void* dev_out) {
+    return dmap_depth_map_refined(d, sigma, dev_guide, guide_dtype, radius, eps, dev_out, false);
+}
+
+int mi_dmap_depth_map_refined(mi_dmap_t* d, double sigma, const void* host_guide, int guide_dtype, int radius, double eps,
+                              void* host_out) {
+    return dmap_depth_map_refined(d, sigma, host_guide, guide_dtype, radius, eps, host_out, true);
+}
+
 int mi_dmap_finish(mi_dmap_t* d, void* host_out, size_t row_stride_bytes) {
     if (!host_out) return fail(MI_ERR_INVALID, "null output buffer");
     int rc = mi_dmap_finish_device(d, nullptr);

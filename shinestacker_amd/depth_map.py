@@ -50,11 +50,13 @@ class DepthMapStack(BaseStackAlgo):
         self.decode_threads = decode_threads
         self._dmap = None
         self._key = None
+        self._fused = None          # the frame the last stack returned: the guide of a refined depth map
 
     # ------------------------------------------------------------------ device handle
     def _handle(self, shape, dtype):
         key = (tuple(shape[:2]), np.dtype(dtype), self.map_type, self.energy, self.kernel_size, self.blur_size,
                self.smooth_size, self.temperature, self.levels, self.float_type)
+        self._fused = None
         if self._dmap is not None and self._key == key:
             self._dmap.reset()
             return self._dmap
@@ -75,15 +77,24 @@ class DepthMapStack(BaseStackAlgo):
             self._dmap.close()
             self._dmap = None
 
-    def depth_map(self, sigma=depth_out.DEPTH_MAP_SIGMA, dev_ptr=None):
+    def depth_map(self, sigma=depth_out.DEPTH_MAP_SIGMA, dev_ptr=None, refine=None):
         """The depth map this stacker is named after, of the last focus_stack / focus_stack_arrays: the mean frame index under
         the focus map's weights, H x W float32 in frame numbers [0, N - 1]; sigma > 0 smooths it (weight: the total energy
         for the AVERAGE map, 1 for the MAX map).  With `dev_ptr` (H x W float32 of device memory) the map is written there
-        and nothing is returned.  Reads the stack's state only; RuntimeError before any stack."""
+        and nothing is returned.  Reads the stack's state only; RuntimeError before any stack.
+
+        refine: None, or {"radius", "eps"} (depth_out.check_refine): the map refined against the fused frame this stacker
+        returned, as PyramidStack.depth_map does it, with the smoothing's weight and the frame numbers 0 .. N - 1.  Best on the
+        unsmoothed map (sigma 0.0, the default here).  RuntimeError before a fused frame exists."""
+        refine = depth_out.check_refine(refine)
         if self._dmap is None:
             raise RuntimeError("depth_map: no stack has been run yet")
         sigma = depth_out.check_sigma(sigma, (self._dmap.height, self._dmap.width))
-        return self._dmap.depth_map(sigma, dev_ptr)
+        if refine is None:
+            return self._dmap.depth_map(sigma, dev_ptr)
+        if self._fused is None:
+            raise RuntimeError("depth_map: refine needs the fused frame, and no stack has finished yet")
+        return depth_out.refined_from_host_guide(self._dmap, sigma, dev_ptr, refine, self._fused, self.device)
 
     def _step(self, i):
         self.process.callback('after_step', self.process.id, self.process.name, i)
@@ -166,7 +177,8 @@ class DepthMapStack(BaseStackAlgo):
             self.print_message(f": reading file (2/2) {img_path.split('/')[-1]}")
             self._step(i + n)
         self.print_message(': blend levels')
-        return dmap.finish()
+        self._fused = dmap.finish()
+        return self._fused
 
     def focus_stack_arrays(self, frames):
         """In-memory variant (no file I/O): `frames` is a sequence of H x W x 3 uint8 / uint16 BGR arrays."""
@@ -187,4 +199,5 @@ class DepthMapStack(BaseStackAlgo):
         if self.process is not None:
             for i in range(n):
                 self._step(i + n)
-        return dmap.finish()
+        self._fused = dmap.finish()
+        return self._fused

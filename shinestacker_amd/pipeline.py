@@ -111,6 +111,79 @@ def _depth_map_info(stack, sigma, info, on_device, height, width, device):
     info["depth_map"] = buf
 
 
+def _check_depth_refine(depth_refine, shape, *consumers):
+    """`depth_refine=`: None (off) or a dict of `radius` and `eps` (depth_out.check_refine) -> the options with both filled in,
+    or None when off.  Refused before anything is allocated: an unknown key, a value out of range, and the option without any
+    consumer of a depth map (`consumers`: the checked depth_map=, stereo=, depth_composite= options)."""
+    if depth_refine is None:
+        return None
+    from . import depth_out
+    opts = depth_out.check_refine(depth_refine, shape)
+    if all(c is None for c in consumers):
+        raise InvalidOptionError("depth_refine", depth_refine, "nothing asks for a depth map: it goes with depth_map=, stereo= or "
+                                 "depth_composite=")
+    return opts
+
+
+class _RefinedStack:
+    """A stacker handle whose every depth map is refined (`depth_refine=`): it stands where the handle stands in `_finish`,
+    `_stereo_render`, `_composite_render` and `_depth_map_info`.  The guide is the fused frame as the stacker returned it:
+    `finish` / `finish_device` keep a device copy before any post-stack filter or stroke sees the frame, and `depth_map` refines
+    against that copy (Stack.depth_map's refine=).  `release` frees the copy; the handle itself is the caller's."""
+
+    def __init__(self, stack, opts, height, width, dtype, device):
+        self._stack, self._opts, self._dt, self._device = stack, opts, np.dtype(dtype), device
+        self._shape = (height, width)
+        self._guide = None
+
+    def __getattr__(self, name):
+        return getattr(self._stack, name)
+
+    def _keep(self):
+        if self._guide is None:
+            self._guide = _lib.DeviceBuffer(self._shape[0] * self._shape[1] * 3 * self._dt.itemsize, self._device)
+        return self._guide
+
+    def finish(self):
+        out = self._stack.finish()
+        self._keep().upload(out)
+        return out
+
+    def finish_device(self, dev_ptr):
+        self._stack.finish_device(dev_ptr)
+        self._stack.sync()
+        g = self._keep()
+        _lib.check(_lib.load().mi_memcpy_d2d(self._device, g.ptr, dev_ptr, g.nbytes))
+
+    def depth_map(self, sigma=0.0, dev_ptr=None):
+        if self._guide is None:
+            raise RuntimeError("depth_map: refine needs the fused frame, and the stack has not finished yet")
+        guide = (self._guide.ptr, self._dt)
+        if dev_ptr is not None:
+            return self._stack.depth_map(sigma, dev_ptr, self._opts, guide)
+        buf = _lib.DeviceBuffer(self._shape[0] * self._shape[1] * 4, self._device)
+        try:
+            self._stack.depth_map(sigma, buf.ptr, self._opts, guide)
+            return buf.download(self._shape, np.float32)
+        finally:
+            buf.free()
+
+    def release(self):
+        if self._guide is not None:
+            self._guide.free()
+            self._guide = None
+
+
+def _refined(stack, opts, height, width, dtype, device):
+    """the handle the depth consumers read: `stack` itself with depth_refine off (nothing is built or copied)"""
+    return stack if opts is None else _RefinedStack(stack, opts, height, width, dtype, device)
+
+
+def _release(dstack):
+    if isinstance(dstack, _RefinedStack):
+        dstack.release()
+
+
 def _check_stereo(stereo, info, shape, dm_sigma):
     """`stereo=`: None (off) or a dict of stereo.pair's options -- layout (default 'anaglyph'), separation, pivot, near -- and
     `sigma`, the smoothing of the depth map the views are rendered from (default: the `depth_map=` sigma when that is given,
@@ -342,7 +415,7 @@ def _finish(stack, out_dev, denoise_amount, height, width, dtype, device, white_
 def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, feature_config=None,
                     matching_config=None, device=0, batch_frames=16, check_running=None, mask_noise=None, vignetting=None,
                     info=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None, retouch=None,
-                    depth_composite=None, lens=None, **stack_kwargs):
+                    depth_composite=None, lens=None, depth_refine=None, **stack_kwargs):
     """Align every frame to frames[ref_idx] (fixed reference, `step_process=False` order,
     stack_framework.py:191-232) and fuse them.  `frames`: sequence of H x W x 3 uint8/uint16 BGR
     arrays.  Returns (fused image, list of n_good_matches).
@@ -383,13 +456,22 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
     stacker.  A device copy of EVERY frame is kept as it passes (InvalidOptionError, before anything is allocated, when the free
     device memory does not hold them), and the composite is rendered in HBM from the depth plane, which is not downloaded.  A
     stroke of `retouch=` whose `source` is the string "depth_composite" paints from it.  None (default): nothing is built, loaded,
-    copied or called; the return values are the same either way."""
+    copied or called; the return values are the same either way.
+
+    `depth_refine`: a dict of `radius` (1 .. 32, default 6) and `eps` (1e-9 .. 1e3, default 1e-4) -- EVERY depth map this call
+    makes is then refined against the fused frame (depth_out.py, the edge-aware guided filter): the map `depth_map=` returns,
+    the map under the `stereo=` render and the map under the `depth_composite=` render, and so a stroke that paints from the
+    composite.  The guide is the fused frame as the stacker returned it, before the strokes and the post-stack filters, so the
+    map does not depend on them.  Refinement works best on the unsmoothed index, `depth_map=0.0`: a Gaussian has already spread
+    the subject's depth across the edge, and the filter cannot tell that bleed from the truth.  Without any of the three
+    consumers the option is refused.  None (default): nothing is built, copied or called."""
     _check_denoise_amount(denoise_amount)
     dm_sigma = _check_depth_map(depth_map, info, np.asarray(frames[0]).shape if len(frames) else None)
     dc_opts = _check_depth_composite(depth_composite, info, np.asarray(frames[0]).shape if len(frames) else None, dm_sigma) \
         if depth_composite is not None else None
     strokes = _check_brush(retouch, len(frames), dc_opts)
     sv_opts = _check_stereo(stereo, info, np.asarray(frames[0]).shape if len(frames) else None, dm_sigma) if stereo is not None else None
+    rf_opts = _check_depth_refine(depth_refine, np.asarray(frames[0]).shape if len(frames) else None, dm_sigma, sv_opts, dc_opts)
     if white_balance is not None or unsharp is not None:
         _check_retouch(white_balance, unsharp, np.asarray(frames[0]).dtype if len(frames) else np.uint8)
     _lib.require_device()
@@ -488,16 +570,21 @@ def align_and_stack(frames, ref_idx=-1, estimator=None, alignment_config=None, f
             from .errors import RunStopException
             raise RunStopException("align_and_stack")
     flush()
+    dstack = _refined(stack, rf_opts, h, w, dt, device)
     try:
-        out = _finish(stack, None, denoise_amount, h, w, dt, device, white_balance, unsharp,
-                      _stereo_render(stack, sv_opts, info, n, h, w, dt, device),
-                      _brush_paint(strokes, kept, h, w, dt, device,
-                                   _composite_render(stack, dc_opts, info, lambda: [kept[i].ptr for i in range(n)], h, w, dt, device, False)))
+        try:
+            out = _finish(dstack, None, denoise_amount, h, w, dt, device, white_balance, unsharp,
+                          _stereo_render(dstack, sv_opts, info, n, h, w, dt, device),
+                          _brush_paint(strokes, kept, h, w, dt, device,
+                                       _composite_render(dstack, dc_opts, info, lambda: [kept[i].ptr for i in range(n)], h, w, dt, device,
+                                                         False)))
+        finally:
+            for b in kept.values():
+                if b is not None:
+                    b.free()
+        _depth_map_info(dstack, dm_sigma, info, False, h, w, device)
     finally:
-        for b in kept.values():
-            if b is not None:
-                b.free()
-    _depth_map_info(stack, dm_sigma, info, False, h, w, device)
+        _release(dstack)
     stack.close()
     return out, matches
 
@@ -815,6 +902,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                            keep_handles=False, info=None, chain_refine=True, chain_serial=False, mask_noise=None,
                            vignetting=None, denoise_amount=0, white_balance=None, unsharp=None, depth_map=None, stereo=None,
                            depth_composite=None, lens=None, estimator=None, matching_config=None, feature_params=None,
+                           depth_refine=None,
                            **stack_kwargs):
     """BASELINE config 4 with every frame resident in HBM: `dev_frames` is the device address of
     `n_frames` contiguous H x W x 3 frames.  Each frame is registered against frames[ref_idx] by
@@ -905,6 +993,11 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     `step_process=True`, `handles=` / `keep_handles=`, `align_method='LMEDS'`, area sub-sampling other than by 2 on even sides
     (`fast_subsampling=True` runs those), more than 4096 features or RANSAC iterations.
 
+    `depth_refine`: a dict of `radius` and `eps`, as `align_and_stack` takes it -- every depth map this call makes (`depth_map=`,
+    the `stereo=` render, the `depth_composite=` render) is refined against the fused frame as the stacker returned it, kept in a
+    device copy until the call ends; best with the unsmoothed index, `depth_map=0.0`.  Refused without any of the three
+    consumers.  None (default): nothing is built, copied or called.
+
     Brush retouching (`align_and_stack`'s `retouch=`) is not offered here: the frames live in the caller's buffer and the handles
     are reused between calls, so the caller paints the result itself with `retouch.apply_device`.
 
@@ -916,6 +1009,7 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
     dm_sigma = _check_depth_map(depth_map, info, (height, width))
     sv_opts = _check_stereo(stereo, info, (height, width), dm_sigma) if stereo is not None else None
     dc_opts = _check_depth_composite(depth_composite, info, (height, width), dm_sigma) if depth_composite is not None else None
+    rf_opts = _check_depth_refine(depth_refine, (height, width), dm_sigma, sv_opts, dc_opts)
     stack_kwargs["arith"] = resolve_arith(stack_kwargs.get("arith"), stack_kwargs.get("float_type"))   # one default for every entry point
     if vignetting is not None and (height * width * 3 * np.dtype(dtype).itemsize) % 16:
         # mi_vignette_apply_device works on 16-byte accesses: every frame of the contiguous stack must start on one
@@ -1011,12 +1105,16 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
                 stack = _lib.Stack(height, width, in_dtype=dt, out_dtype=dt, device=device, **stack_kwargs)
                 created.append(stack.close)
             stack.push_frames_device(aligned.ptr, n_frames, fb)
-            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
-                          _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device),
-                          _brush_paint(None, {}, height, width, dt, device,
-                                       _composite_render(stack, dc_opts, info, lambda: [aligned.ptr + i * fb for i in range(n_frames)],
-                                                         height, width, dt, device, True)))
-            _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
+            dstack = _refined(stack, rf_opts, height, width, dt, device)
+            try:
+                out = _finish(dstack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
+                              _stereo_render(dstack, sv_opts, info, n_frames, height, width, dt, device),
+                              _brush_paint(None, {}, height, width, dt, device,
+                                           _composite_render(dstack, dc_opts, info, lambda: [aligned.ptr + i * fb for i in range(n_frames)],
+                                                             height, width, dt, device, True)))
+                _depth_map_info(dstack, dm_sigma, info, out_dev is not None, height, width, device)
+            finally:
+                _release(dstack)
             done = True
         finally:
             if not (keep_handles and done):
@@ -1107,12 +1205,16 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
             transforms = [None if i == ref_idx else (ms[i].reshape(3, 3).copy() if homography else ms[i, :6].reshape(2, 3).copy())
                           for i in range(n_frames)]
             ccs = [float(c) for c in cc]
-            out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
-                          _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device),
-                          _brush_paint(None, {}, height, width, dt, device,
-                                       _composite_render(stack, dc_opts, info, lambda: [batches.ptr + i * fb for i in range(n_frames)],
-                                                         height, width, dt, device, True)))
-            _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
+            dstack = _refined(stack, rf_opts, height, width, dt, device)
+            try:
+                out = _finish(dstack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
+                              _stereo_render(dstack, sv_opts, info, n_frames, height, width, dt, device),
+                              _brush_paint(None, {}, height, width, dt, device,
+                                           _composite_render(dstack, dc_opts, info, lambda: [batches.ptr + i * fb for i in range(n_frames)],
+                                                             height, width, dt, device, True)))
+                _depth_map_info(dstack, dm_sigma, info, out_dev is not None, height, width, device)
+            finally:
+                _release(dstack)
             done = True
         finally:
             if created is not None and not (keep_handles and done):
@@ -1214,12 +1316,16 @@ def align_and_stack_device(dev_frames, n_frames, height, width, dtype, ref_idx=-
             if filled == batch_frames:
                 flush()
         flush()
-        out = _finish(stack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
-                      _stereo_render(stack, sv_opts, info, n_frames, height, width, dt, device),
-                      _brush_paint(None, {}, height, width, dt, device,
-                                   _composite_render(stack, dc_opts, info, lambda: [batches[0].ptr + i * fb for i in range(n_frames)],
-                                                     height, width, dt, device, True)))
-        _depth_map_info(stack, dm_sigma, info, out_dev is not None, height, width, device)
+        dstack = _refined(stack, rf_opts, height, width, dt, device)
+        try:
+            out = _finish(dstack, out_dev, denoise_amount, height, width, dt, device, white_balance, unsharp,
+                          _stereo_render(dstack, sv_opts, info, n_frames, height, width, dt, device),
+                          _brush_paint(None, {}, height, width, dt, device,
+                                       _composite_render(dstack, dc_opts, info, lambda: [batches[0].ptr + i * fb for i in range(n_frames)],
+                                                         height, width, dt, device, True)))
+            _depth_map_info(dstack, dm_sigma, info, out_dev is not None, height, width, device)
+        finally:
+            _release(dstack)
         if corr is not None and info is not None:
             info["corrections"] = corr.fetch_corrections()
     finally:
@@ -1236,7 +1342,7 @@ def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constan
                        overlap=constants.DEFAULT_OVERLAP, device=0, out_dev=None, on_bunch=None, on_final=None,
                        check_running=None, stacks=None, results_buf=None, info=None, zero_copy=False, denoise_amount=0,
                        white_balance=None, unsharp=None, mosaic=None, develop=None, calibration=None, packed=False,
-                       **stack_kwargs):
+                       depth_refine=None, **stack_kwargs):
     """BASELINE config 5's two-stage flow in memory (the reference's `FocusStackBunch` followed by `FocusStack`,
     stack.py:61-113, examples/stack-from-frames): the frames are fused in bunches of `frames` with `overlap` shared
     (`get_bunches`), every bunch result is the stacker's OUTPUT type -- truncated to the input dtype exactly as the file
@@ -1266,9 +1372,11 @@ def bunches_then_stack(get_frame, n_frames, height, width, dtype, frames=constan
     on the raw samples of stage 1, ahead of both; it too stays open until this returns.  `packed`: `get_frame(i)` returns a
     `dng.DngFrame` and stage 1 pushes its packed span (`Stack.push_packed`: the file's sample bytes as they lie, unpacked on the
     device, demosaiced with the frame's own Cfa; `develop` and `calibration` apply as beside `mosaic`).  Returns the fused image (or None when `out_dev` is given) and the list of
-    bunches (frame indices)."""
+    bunches (frame indices).  `depth_refine`: the option of `align_and_stack`; this flow returns no depth map, so anything but
+    None is refused, as the option without a consumer is there."""
     from .actions import get_bunches
     _check_denoise_amount(denoise_amount)
+    _check_depth_refine(depth_refine, (height, width))     # (this flow returns no depth map: the option has no consumer here)
     if white_balance is not None or unsharp is not None:
         _check_retouch(white_balance, unsharp, dtype)
     if packed and mosaic is not None:

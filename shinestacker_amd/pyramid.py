@@ -159,11 +159,13 @@ class PyramidStack(BaseStackAlgo):
         self.num_pixel_values = None
         self.max_pixel_value = None
         self._stack = None
+        self._fused = None          # the frame the last stack returned: the guide of a refined depth map
 
     # ------------------------------------------------------------------ device handle
     def _handle(self, shape, dtype):
         """One handle per (shape, dtype); FocusStackBunch reuses the stacker for every bunch."""
         key = (tuple(shape[:2]), np.dtype(dtype))
+        self._fused = None
         if self._stack is not None and self._stack_key == key:
             self._stack.reset()
             return self._stack
@@ -191,15 +193,26 @@ class PyramidStack(BaseStackAlgo):
             self._stack = None
 
     # ------------------------------------------------------------------ depth map (depth_out.py; no reference counterpart)
-    def depth_map(self, sigma=depth_out.PYRAMID_SIGMA, dev_ptr=None):
+    def depth_map(self, sigma=depth_out.PYRAMID_SIGMA, dev_ptr=None, refine=None):
         """The frame in focus at each pixel of the last focus_stack / focus_stack_arrays: the level-0 winner index, smoothed
         with the winner's energy as the weight (sigma 0: the index itself), H x W float32 in frame numbers [0, N - 1].  With
         `dev_ptr` (H x W float32 of device memory) the map is written there and nothing is returned.  Reads the stack's state
-        only; RuntimeError before any stack."""
+        only; RuntimeError before any stack.
+
+        refine: None, or {"radius": 1 .. 32, "eps": 1e-9 .. 1e3} (depth_out.check_refine): the map is then refined against the
+        fused frame this stacker returned -- the edge-aware guided filter of depth_out's docstring, with the same energy as
+        the weight, clamped to the stack's frame numbers.  It works best on the unsmoothed index (sigma 0.0): a Gaussian has
+        already spread the subject's depth across the edge, and the filter cannot tell that bleed from the truth.
+        RuntimeError before a fused frame exists."""
+        refine = depth_out.check_refine(refine)
         if self._stack is None:
             raise RuntimeError("depth_map: no stack has been run yet")
         sigma = depth_out.check_sigma(sigma, (self._stack.height, self._stack.width))
-        return self._stack.depth_map(sigma, dev_ptr)
+        if refine is None:
+            return self._stack.depth_map(sigma, dev_ptr)
+        if self._fused is None:
+            raise RuntimeError("depth_map: refine needs the fused frame, and no stack has finished yet")
+        return depth_out.refined_from_host_guide(self._stack, sigma, dev_ptr, refine, self._fused, self.device)
 
     # ------------------------------------------------------------------ the steps, one at a time (pyramid.py:24-148)
     # The reference's public methods of the same names, on NumPy arrays, run on the GPU.  They always use the reference's
@@ -350,7 +363,8 @@ class PyramidStack(BaseStackAlgo):
             if flags:
                 from .dng import check_ljpeg_status
                 check_ljpeg_status(f"{filenames[0]} .. {filenames[-1]}", [flags])
-        return stack.finish()
+        self._fused = stack.finish()
+        return self._fused
 
     def _push_raw(self, stack, frame):
         """one DngFrame into the stack under self.raw.  Without a lens: Stack.push_packed.  With one (the push has no lens
@@ -471,4 +485,5 @@ class PyramidStack(BaseStackAlgo):
                 stack.push_mosaic(fr, mosaic, develop=develop)
             if self.process is not None:
                 self._step(i + n)
-        return stack.finish()
+        self._fused = stack.finish()
+        return self._fused
