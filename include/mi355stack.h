@@ -1242,6 +1242,56 @@ MI_API int mi_feat_aligner_tap(mi_feat_aligner_t fa, int frame_slot, int what, i
 MI_API int mi_feat_aligner_stats(mi_feat_aligner_t fa, uint64_t* waits, uint64_t* launches);
 MI_API int mi_feat_aligner_destroy(mi_feat_aligner_t fa);
 
+/* ---- baseline JPEG frames in: Huffman decode, inverse DCT, upsampling and colour on the device (kernels_jpeg.hpp) ----
+ * The host reads the file's headers (jpeg.read) into one mi_jpeg_t, which always lies in HOST memory, and finds the restart
+ * intervals: `offsets` holds n_intervals + 1 uint32 offsets into the span, offsets[i] the first data byte of interval i and
+ * offsets[n_intervals] the end of the scan; an interval's bytes run to the next offset and end earlier at a marker (FF
+ * followed by anything but 00).  The span is uploaded as it lies in the file.  Interval i decodes exactly min(dri, MCUs left)
+ * MCUs from MCU i * dri on, in scan order, blocks within an MCU in T.81 order, predictors 0 at its start.  Per component the
+ * coefficient plane is its padded block grid, mcus_y * v rows of mcus_x * h blocks of 64 int16 in natural order; the planes
+ * of components 0, 1, 2 follow each other (mi_jpeg_coef_count int16 in all).  The render dequantises, runs the 13-bit
+ * "slow integer" inverse DCT, upsamples chroma with the triangle filters on the component cropped to its own size, converts
+ * YCbCr to BGR (a grey frame: the plane three times) and writes height x width x 3 uint8.  tests/jpeg_restatement.py states
+ * all of it in Python.  One status word per interval, the MI_JPEG_* bits ORed; a flagged interval's blocks are unspecified
+ * and every one is written inside the plane, all other intervals are exact. */
+typedef struct mi_jpeg {
+    int32_t width, height;  /* 1 .. 65535 each                                                          */
+    int32_t ncomp;          /* 1 (grey) or 3 (YCbCr)                                                    */
+    int32_t hmax, vmax;     /* the first component's sampling: (1,1), (2,1) or (2,2); (1,1) at ncomp 1  */
+    int32_t dri;            /* MCUs per restart interval, 1 .. MI_JPEG_MAX_DRI                          */
+    int32_t n_intervals;    /* ceil(MCUs / dri)                                                         */
+    int32_t reserved;
+    uint8_t tq[4];          /* per component: its quantisation table, 0 .. 3                            */
+    uint8_t td[4];          /* ... its DC table, 0 or 1                                                 */
+    uint8_t ta[4];          /* ... its AC table, 0 or 1                                                 */
+    uint8_t pad[4];
+    uint8_t counts[4][16];  /* tables DC 0, DC 1, AC 0, AC 1: the number of codes of length 1 .. 16     */
+    uint8_t values[4][256]; /* ... their symbols in code order                                          */
+    uint8_t quant[4][64];   /* the quantisation tables in natural order, entries 1 .. 255               */
+} mi_jpeg_t;                /* 1392 bytes */
+#define MI_JPEG_NOCODE 1u   /* status bit 0: a 16-bit prefix matched no code                      */
+#define MI_JPEG_OVERRUN 2u  /* status bit 1: bits were taken from beyond the interval's end       */
+#define MI_JPEG_RUN 4u      /* status bit 2: a run carried the coefficient index past 63          */
+#define MI_JPEG_MAX_DRI 8192 /* one wavefront walks an interval serially: at most the MCU row of a picture 65 535 wide */
+/* Checks, each MI_ERR_INVALID naming the argument before any device call: null span, offsets, jpeg, output; span_bytes in
+ * [1, 2^32); the fields of `jpeg` in the ranges above, n_intervals equal to ceil(MCUs / dri), every table a component
+ * selects non-empty, counts that fit the code space with at most 256 values, DC symbols <= 15, quant entries >= 1; where the
+ * offsets lie in host memory: non-decreasing and inside the span.  dev_span, dev_offsets and dev_status must be 4-byte
+ * aligned, dev_coef 16-byte, dev_scratch 256-byte with at least mi_jpeg_scratch_bytes.  The _device forms enqueue on
+ * `stream` and do not wait; dev_status (one word per interval) may be null.  The host forms upload, run, download and wait,
+ * and return MI_OK with the flags in status_out (may be null). */
+MI_API int mi_jpeg_coef_count(const mi_jpeg_t* jpeg, size_t* count);
+MI_API int mi_jpeg_scratch_bytes(const mi_jpeg_t* jpeg, size_t* bytes);
+MI_API int mi_jpeg_coefficients_device(int device, void* stream, const void* dev_span, size_t span_bytes, const uint32_t* dev_offsets,
+                                       const mi_jpeg_t* jpeg, int16_t* dev_coef, uint32_t* dev_status);
+MI_API int mi_jpeg_coefficients(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
+                                int16_t* host_coef, uint32_t* status_out);
+MI_API int mi_jpeg_decode_device(int device, void* stream, const void* dev_span, size_t span_bytes, const uint32_t* dev_offsets,
+                                 const mi_jpeg_t* jpeg, void* dev_scratch, size_t scratch_bytes, uint8_t* dev_out,
+                                 uint32_t* dev_status);
+MI_API int mi_jpeg_decode(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
+                          uint8_t* host_out, uint32_t* status_out);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

@@ -152,6 +152,23 @@ def ljpeg_flag_text(flags):
     return ", ".join(t for b, t in LJPEG_FLAG_NAMES.items() if flags & b) or "no flag"
 
 
+class JpegStruct(C.Structure):
+    """mi_jpeg_t: what the kernels see of a baseline JPEG frame, read from its headers (jpeg.read); host memory"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hmax", C.c_int32), ("vmax", C.c_int32),
+                ("dri", C.c_int32), ("n_intervals", C.c_int32), ("reserved", C.c_int32), ("tq", C.c_uint8 * 4), ("td", C.c_uint8 * 4),
+                ("ta", C.c_uint8 * 4), ("pad", C.c_uint8 * 4), ("counts", (C.c_uint8 * 16) * 4), ("values", (C.c_uint8 * 256) * 4),
+                ("quant", (C.c_uint8 * 64) * 4)]
+
+
+JPEG_NOCODE, JPEG_OVERRUN, JPEG_RUN = 1, 2, 4
+JPEG_FLAG_NAMES = {JPEG_NOCODE: "a 16-bit prefix matched no Huffman code", JPEG_OVERRUN: "the data ended before the interval's last block",
+                   JPEG_RUN: "a run carried the coefficient index past 63"}
+
+
+def jpeg_flag_text(flags):
+    return ", ".join(t for b, t in JPEG_FLAG_NAMES.items() if flags & b) or "no flag"
+
+
 class DepthMapParams(C.Structure):
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32),
                 ("map_type", C.c_int32), ("energy", C.c_int32), ("kernel_size", C.c_int32),
@@ -424,6 +441,14 @@ SIGNATURES = {
     "mi_feat_aligner_tap": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "mi_feat_aligner_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mi_feat_aligner_destroy": (C.c_int, [C.c_void_p]),
+    "mi_jpeg_coef_count": (C.c_int, [C.POINTER(JpegStruct), C.POINTER(C.c_size_t)]),
+    "mi_jpeg_scratch_bytes": (C.c_int, [C.POINTER(JpegStruct), C.POINTER(C.c_size_t)]),
+    "mi_jpeg_coefficients_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(JpegStruct), C.c_void_p,
+                                              C.c_void_p]),
+    "mi_jpeg_coefficients": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(JpegStruct), C.c_void_p, C.c_void_p]),
+    "mi_jpeg_decode_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(JpegStruct), C.c_void_p,
+                                        C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mi_jpeg_decode": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(JpegStruct), C.c_void_p, C.c_void_p]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }

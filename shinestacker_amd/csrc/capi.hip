@@ -35,6 +35,7 @@
 #include "kernels_steps.hpp"
 #include "kernels_lens.hpp"
 #include "kernels_finish.hpp"
+#include "kernels_jpeg.hpp"
 
 using namespace mi;
 
@@ -2381,6 +2382,146 @@ int mi_raw_ljpeg3(int device, const void* host_span, size_t span_bytes, const mi
         (rc = mi_raw_ljpeg3_device(device, nullptr, span, span_bytes, seg, layout, table, out, status)))
         return rc;
     if (status_out && (rc = tmp.download(status_out, status, nseg * sizeof(uint32_t)))) return rc;
+    return tmp.download(host_out, out, nb);
+}
+
+// ---- baseline JPEG frames (kernels_jpeg.hpp): the descriptor lies in host memory and is checked here, whole
+static int jpeg_check(const mi_jpeg_t* J) {
+    if (!J) return fail(MI_ERR_INVALID, "null jpeg");
+    if (J->width < 1 || J->width > 65535 || J->height < 1 || J->height > 65535)
+        return fail(MI_ERR_INVALID, "jpeg width and height must be in [1, 65535] (got %d x %d)", J->width, J->height);
+    if (J->ncomp != 1 && J->ncomp != 3) return fail(MI_ERR_INVALID, "jpeg ncomp must be 1 or 3 (got %d)", J->ncomp);
+    const bool samp = (J->hmax == 1 && J->vmax == 1) || (J->ncomp == 3 && J->hmax == 2 && (J->vmax == 1 || J->vmax == 2));
+    if (!samp) return fail(MI_ERR_INVALID, "jpeg hmax, vmax must be (1,1), or (2,1) or (2,2) at ncomp 3 (got (%d,%d))", J->hmax, J->vmax);
+    const jpeg::Geom g = jpeg::geom(*J);
+    if (J->dri < 1 || J->dri > MI_JPEG_MAX_DRI) return fail(MI_ERR_INVALID, "jpeg dri must be in [1, %d] (got %d)", MI_JPEG_MAX_DRI, J->dri);
+    const long long want = ((long long)g.n_mcus + J->dri - 1) / J->dri;
+    if (J->n_intervals != want)
+        return fail(MI_ERR_INVALID, "jpeg n_intervals must be ceil(%d MCUs / dri %d) = %lld (got %d)", g.n_mcus, J->dri, want, J->n_intervals);
+    bool used[4] = {false, false, false, false};
+    for (int c = 0; c < J->ncomp; ++c) {
+        if (J->tq[c] > 3) return fail(MI_ERR_INVALID, "jpeg tq[%d] must be in [0, 3] (got %d)", c, J->tq[c]);
+        if (J->td[c] > 1) return fail(MI_ERR_INVALID, "jpeg td[%d] must be 0 or 1 (got %d)", c, J->td[c]);
+        if (J->ta[c] > 1) return fail(MI_ERR_INVALID, "jpeg ta[%d] must be 0 or 1 (got %d)", c, J->ta[c]);
+        used[J->td[c]] = used[2 + J->ta[c]] = true;
+        for (int k = 0; k < 64; ++k)
+            if (J->quant[J->tq[c]][k] < 1) return fail(MI_ERR_INVALID, "jpeg quant[%d][%d] must be >= 1", J->tq[c], k);
+    }
+    for (int t = 0; t < 4; ++t) {
+        uint32_t code = 0, total = 0;
+        for (int l = 1; l <= 16; ++l) {
+            code += J->counts[t][l - 1];
+            total += J->counts[t][l - 1];
+            if (code > (1u << l)) return fail(MI_ERR_INVALID, "jpeg counts[%d] overflow the code space at length %d", t, l);
+            code <<= 1;
+        }
+        if (total > 256 || (used[t] && total < 1))
+            return fail(MI_ERR_INVALID, "jpeg counts[%d] must sum to %d .. 256 (got %u)", t, used[t] ? 1 : 0, total);
+        if (t < 2)
+            for (uint32_t k = 0; k < total; ++k)
+                if (J->values[t][k] > 15) return fail(MI_ERR_INVALID, "jpeg values[%d][%u] must be <= 15 in a DC table (got %d)", t, k, J->values[t][k]);
+    }
+    return MI_OK;
+}
+static int jpeg_args_check(const void* span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* J, const void* out) {
+    if (!span) return fail(MI_ERR_INVALID, "null span");
+    if (!offsets) return fail(MI_ERR_INVALID, "null offsets");
+    int rc = jpeg_check(J);
+    if (rc) return rc;
+    if (!out) return fail(MI_ERR_INVALID, "null output");
+    if (span_bytes < 1 || span_bytes >= (1ull << 32))
+        return fail(MI_ERR_INVALID, "span_bytes must be in [1, 2^32) (got %llu)", (unsigned long long)span_bytes);
+    return MI_OK;
+}
+static int jpeg_offsets_check(size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* J) {
+    for (int i = 0; i <= J->n_intervals; ++i) {
+        if (offsets[i] > span_bytes)
+            return fail(MI_ERR_INVALID, "offsets[%d] = %u lies outside the span of %llu bytes", i, offsets[i], (unsigned long long)span_bytes);
+        if (i && offsets[i] < offsets[i - 1]) return fail(MI_ERR_INVALID, "offsets[%d] = %u lies in front of offsets[%d] = %u", i, offsets[i], i - 1, offsets[i - 1]);
+    }
+    return MI_OK;
+}
+
+int mi_jpeg_coef_count(const mi_jpeg_t* jpeg, size_t* count) {
+    int rc = jpeg_check(jpeg);
+    if (rc) return rc;
+    if (!count) return fail(MI_ERR_INVALID, "null count");
+    *count = jpeg::geom(*jpeg).nblocks * 64;
+    return MI_OK;
+}
+// the coefficients (int16), then the sample planes (uint8)
+int mi_jpeg_scratch_bytes(const mi_jpeg_t* jpeg, size_t* bytes) {
+    int rc = jpeg_check(jpeg);
+    if (rc) return rc;
+    if (!bytes) return fail(MI_ERR_INVALID, "null bytes");
+    *bytes = jpeg::geom(*jpeg).nblocks * 192;
+    return MI_OK;
+}
+
+int mi_jpeg_coefficients_device(int device, void* stream, const void* dev_span, size_t span_bytes, const uint32_t* dev_offsets,
+                                const mi_jpeg_t* jpeg, int16_t* dev_coef, uint32_t* dev_status) {
+    int rc = jpeg_args_check(dev_span, span_bytes, dev_offsets, jpeg, dev_coef);
+    if (rc) return rc;
+    if ((uintptr_t)dev_span & 3) return fail(MI_ERR_INVALID, "dev_span must be 4-byte aligned");
+    if ((uintptr_t)dev_offsets & 3) return fail(MI_ERR_INVALID, "dev_offsets must be 4-byte aligned");
+    if ((uintptr_t)dev_coef & 15) return fail(MI_ERR_INVALID, "dev_coef must be 16-byte aligned");
+    if ((uintptr_t)dev_status & 3) return fail(MI_ERR_INVALID, "dev_status must be 4-byte aligned");
+    MI_HIP(hipSetDevice(device));
+    jpeg_entropy_launch((hipStream_t)stream, dev_span, span_bytes, dev_offsets, *jpeg, dev_coef, dev_status);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_jpeg_decode_device(int device, void* stream, const void* dev_span, size_t span_bytes, const uint32_t* dev_offsets,
+                          const mi_jpeg_t* jpeg, void* dev_scratch, size_t scratch_bytes, uint8_t* dev_out, uint32_t* dev_status) {
+    int rc = jpeg_args_check(dev_span, span_bytes, dev_offsets, jpeg, dev_out);
+    if (rc) return rc;
+    if (!dev_scratch) return fail(MI_ERR_INVALID, "null scratch");
+    const size_t nblocks = jpeg::geom(*jpeg).nblocks;
+    if (scratch_bytes < nblocks * 192)
+        return fail(MI_ERR_INVALID, "scratch_bytes must be >= %llu (got %llu)", (unsigned long long)(nblocks * 192), (unsigned long long)scratch_bytes);
+    if ((uintptr_t)dev_scratch & 255) return fail(MI_ERR_INVALID, "dev_scratch must be 256-byte aligned");
+    int16_t* coef = (int16_t*)dev_scratch;
+    if ((rc = mi_jpeg_coefficients_device(device, stream, dev_span, span_bytes, dev_offsets, jpeg, coef, dev_status))) return rc;
+    jpeg_render_launch((hipStream_t)stream, *jpeg, coef, (uint8_t*)dev_scratch + nblocks * 128, dev_out);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_jpeg_coefficients(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
+                         int16_t* host_coef, uint32_t* status_out) {
+    int rc = jpeg_args_check(host_span, span_bytes, offsets, jpeg, host_coef);
+    if (rc || (rc = jpeg_offsets_check(span_bytes, offsets, jpeg))) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t nb = jpeg::geom(*jpeg).nblocks * 128, ns = (size_t)jpeg->n_intervals * sizeof(uint32_t);
+    DevScratch tmp(nullptr);
+    void* span = nullptr;
+    uint32_t *off = nullptr, *status = nullptr;
+    int16_t* coef = nullptr;
+    if ((rc = tmp.upload(&span, host_span, span_bytes)) || (rc = tmp.upload(&off, offsets, ns + sizeof(uint32_t))) ||
+        (rc = tmp.alloc(&coef, nb)) || (rc = tmp.alloc(&status, ns)) ||
+        (rc = mi_jpeg_coefficients_device(device, nullptr, span, span_bytes, off, jpeg, coef, status)))
+        return rc;
+    if (status_out && (rc = tmp.download(status_out, status, ns))) return rc;
+    return tmp.download(host_coef, coef, nb);
+}
+
+int mi_jpeg_decode(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
+                   uint8_t* host_out, uint32_t* status_out) {
+    int rc = jpeg_args_check(host_span, span_bytes, offsets, jpeg, host_out);
+    if (rc || (rc = jpeg_offsets_check(span_bytes, offsets, jpeg))) return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t nscratch = jpeg::geom(*jpeg).nblocks * 192, ns = (size_t)jpeg->n_intervals * sizeof(uint32_t);
+    const size_t nb = (size_t)jpeg->height * jpeg->width * 3;
+    DevScratch tmp(nullptr);
+    void *span = nullptr, *scratch = nullptr;
+    uint32_t *off = nullptr, *status = nullptr;
+    uint8_t* out = nullptr;
+    if ((rc = tmp.upload(&span, host_span, span_bytes)) || (rc = tmp.upload(&off, offsets, ns + sizeof(uint32_t))) ||
+        (rc = tmp.alloc(&scratch, nscratch)) || (rc = tmp.alloc(&out, nb)) || (rc = tmp.alloc(&status, ns)) ||
+        (rc = mi_jpeg_decode_device(device, nullptr, span, span_bytes, off, jpeg, scratch, nscratch, out, status)))
+        return rc;
+    if (status_out && (rc = tmp.download(status_out, status, ns))) return rc;
     return tmp.download(host_out, out, nb);
 }
 

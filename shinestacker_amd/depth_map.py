@@ -37,8 +37,9 @@ class DepthMapStack(BaseStackAlgo):
                  kernel_size=constants.DEFAULT_DM_KERNEL_SIZE, blur_size=constants.DEFAULT_DM_BLUR_SIZE,
                  smooth_size=constants.DEFAULT_DM_SMOOTH_SIZE, temperature=constants.DEFAULT_DM_TEMPERATURE,
                  levels=constants.DEFAULT_DM_LEVELS, float_type=constants.DEFAULT_DM_FLOAT, *, device=0,
-                 decode_threads=8):
+                 decode_threads=8, jpeg=None):
         super().__init__("depth map", 2, float_type)
+        self._set_jpeg(jpeg)      # (keyword-only extension: BaseStackAlgo._set_jpeg)
         self.map_type = map_type
         self.energy = energy
         self.kernel_size = kernel_size
@@ -161,14 +162,29 @@ class DepthMapStack(BaseStackAlgo):
         n = len(filenames)
         metadata = None
         dmap = None
-        for i, (img_path, decoded) in enumerate(self._decode_ahead(filenames)):
-            self.print_message(f": reading file (1/2) {img_path.split('/')[-1]}")
-            img, metadata, updated = self.read_image_and_update_metadata(
-                img_path, metadata, decoded.result() if decoded is not None else None)
-            if updated:
-                dmap = self._handle(metadata[0], metadata[1])
-            dmap.push_frame(img)
-            self._step(i)
+        self.skipped = []
+        try:
+            for i, (img_path, decoded) in enumerate(self._decode_ahead(filenames)):
+                self.print_message(f": reading file (1/2) {img_path.split('/')[-1]}")
+                if self.jpeg is None:
+                    img = decoded.result() if decoded is not None else None
+                else:
+                    frame, img = self._jpeg_take(img_path, decoded)
+                    if frame is not None:       # decoded on the device
+                        metadata, updated = self._jpeg_metadata(frame, metadata)
+                        if updated:
+                            dmap = self._handle(metadata[0], metadata[1])
+                        self._jpeg_push(frame, dmap.push_frame_device,
+                                        lambda: _lib.check(_lib.load().mi_device_synchronize(self.device)))
+                        self._step(i)
+                        continue
+                img, metadata, updated = self.read_image_and_update_metadata(img_path, metadata, img)
+                if updated:
+                    dmap = self._handle(metadata[0], metadata[1])
+                dmap.push_frame(img)
+                self._step(i)
+        finally:
+            self._jpeg_release()
         self._check_energy()
         self._check_map()
         # the second loop of the reference (:94-115) re-reads and blends; that work is one device call

@@ -2,7 +2,8 @@
 
 Same contract as the reference's read_img / write_img: extension dispatch, jpg ->
 8-bit, tif/tiff/png -> stored depth, arrays are H x W x 3 **BGR** like cv2.imread.
-Codecs are not a GPU target: OpenCV is used when it is
+Codecs are not a GPU target -- but the stackers' `jpeg=` option exists
+(jpeg.py: baseline JPEG files with restart intervals decoded on the device); here OpenCV is used when it is
 installed, otherwise Pillow (8-bit) plus two small codecs for the 16-bit depths
 Pillow cannot hold as RGB: baseline TIFF (uncompressed strips -- what the
 reference writes with IMWRITE_TIFF_COMPRESSION=1) and 16-bit PNG (zlib; all five

@@ -40,6 +40,13 @@ def _cyan(msg):
     return f"\033[36m{msg}\033[0m"
 
 
+class _HostDecoded:
+    """a `.jpg` that jpeg.read refused under jpeg="auto": the frame the host decoded in its place (or None), and the reason"""
+
+    def __init__(self, img, reason):
+        self.img, self.reason = img, reason
+
+
 class BaseStackAlgo:
     """Plug-in base shared by stackers (reference base_stack_algo.py:9-42)."""
 
@@ -79,10 +86,75 @@ class BaseStackAlgo:
         return img, metadata, updated
 
     def _read_file(self, path):
-        """with `raw=` set: a `.dng` path is parsed by dng.read (the header only: a DngFrame whose span is the file's mapping),
-        every other path is decoded as ever"""
-        from . import dng
-        return dng.read(path) if dng.is_dng(path) else read_img(path)
+        """with `raw=` set: a `.dng` path is parsed by dng.read (the header only: a DngFrame whose span is the file's mapping);
+        with `jpeg=` set: a `.jpg` / `.jpeg` path is parsed by jpeg.read (the header only: a JpegFrame) -- under "auto" a file
+        it refuses is decoded on the host and comes back as a _HostDecoded with the reason; every other path is decoded as
+        ever.  Runs on the decode-ahead pool: it touches nothing of the stacker."""
+        if getattr(self, "raw", None) is not None:
+            from . import dng
+            if dng.is_dng(path):
+                return dng.read(path)
+        mode = getattr(self, "jpeg", None)
+        if mode is not None:
+            from . import jpeg
+            if jpeg.is_jpeg(path):
+                try:
+                    return jpeg.read(path)
+                except InvalidOptionError as e:
+                    if mode != "auto":
+                        raise
+                    return _HostDecoded(read_img(path), str(e))
+        return read_img(path)
+
+    def _set_jpeg(self, mode):
+        """jpeg (keyword-only extension): None -- every file is decoded on the host, as ever; "device" -- every `.jpg` /
+        `.jpeg` path is parsed on the decode-ahead pool (jpeg.read), its scan is uploaded as it lies in the file and decoded
+        on the device (csrc/kernels_jpeg.hpp), and a file jpeg.read refuses raises; "auto" -- such a file is decoded on the
+        host instead and (path, reason) is kept in `self.skipped`."""
+        if mode is not None:
+            from .jpeg import check_mode
+            check_mode(mode)
+        self.jpeg = mode
+        self.skipped = []
+        self._jpeg_pusher = None
+
+    def _jpeg_take(self, img_path, decoded):
+        """with `jpeg=` set, what became of a file: (JpegFrame, None), or (None, the frame the host decoded).  A file refused
+        under "auto" is noted in `skipped` here, by the consumer: the list is in file order and holds only files that reached
+        the stack.  The file is read once; one that no decoder reads raises as read_image_and_update_metadata does."""
+        res = decoded.result() if decoded is not None else self._read_file(img_path)
+        if isinstance(res, _HostDecoded):
+            self.skipped.append((img_path, res.reason))
+            res = res.img
+        if res is None:
+            raise ImageLoadError(img_path)
+        return (None, res) if isinstance(res, np.ndarray) else (res, None)
+
+    def _jpeg_push(self, frame, push_device, drain):
+        """one JpegFrame through jpeg.Pusher (span up, kernels into one of two device buffers, `push_device(ptr)`); `drain`
+        is the handle's own wait, called before a buffer is written again"""
+        if self._jpeg_pusher is None:
+            from .jpeg import Pusher
+            self._jpeg_pusher = Pusher(self.device)
+        self._jpeg_pusher.push(frame, push_device, drain)
+
+    def _jpeg_release(self):
+        """after a stack, however it ended: the device buffers of the `jpeg=` route"""
+        if self._jpeg_pusher is not None:
+            _lib.load().mi_device_synchronize(self.device)      # the handle's reads of the buffers, ahead of their release
+            self._jpeg_pusher.close()
+            self._jpeg_pusher = None
+
+    @staticmethod
+    def _jpeg_metadata(frame, metadata):
+        """read_image_and_update_metadata for a JpegFrame: (metadata, updated), the same errors"""
+        if metadata is None:
+            return (frame.shape, frame.dtype), True
+        if frame.shape != tuple(metadata[0][:2]):
+            raise ShapeError(metadata[0], frame.shape)
+        if frame.dtype != metadata[1]:
+            raise BitDepthError(metadata[1], frame.dtype)
+        return metadata, False
 
     def _decode_ahead(self, filenames):
         """(path, future-or-None) in file order.  With decode_threads > 1 the files are decoded on a
@@ -90,7 +162,7 @@ class BaseStackAlgo:
         takes the host far longer to decode than the GPU needs to fuse it.  Errors surface in order,
         at the file that caused them, as in the sequential loop (pyramid.py:155-169)."""
         n = int(self.decode_threads or 0)
-        reader = read_img if getattr(self, "raw", None) is None else self._read_file
+        reader = read_img if getattr(self, "raw", None) is None and getattr(self, "jpeg", None) is None else self._read_file
         if n <= 1 or len(filenames) <= 1:
             for p in filenames:
                 yield p, None
@@ -122,8 +194,9 @@ class PyramidStack(BaseStackAlgo):
                  kernel_size=constants.DEFAULT_PY_KERNEL_SIZE,
                  gen_kernel=constants.DEFAULT_PY_GEN_KERNEL,
                  float_type=constants.DEFAULT_PY_FLOAT, *, device=0, use_fma=True,
-                 impl=_lib.IMPL_AUTO, batch_frames=0, decode_threads=8, arith=None, raw=None):
+                 impl=_lib.IMPL_AUTO, batch_frames=0, decode_threads=8, arith=None, raw=None, jpeg=None):
         super().__init__("pyramid", 2, float_type)
+        self._set_jpeg(jpeg)
         # raw (keyword-only extension): a dng.Raw -- focus_stack then takes `.dng` paths: each is parsed on the decode-ahead
         # pool (dng.read), its packed samples are uploaded as they lie in the file and unpacked, demosaiced and developed on
         # the device (Stack.push_packed).  None: a `.dng` path is an unknown extension, as ever.
@@ -320,6 +393,13 @@ class PyramidStack(BaseStackAlgo):
     def focus_stack(self, filenames):
         """pyramid.py:150-179.  `filenames`: sorted list of image paths."""
         _lib.require_device()
+        self.skipped = []
+        try:
+            return self._focus_stack(filenames)
+        finally:
+            self._jpeg_release()
+
+    def _focus_stack(self, filenames):
         n = len(filenames)
         metadata = None
         stack = None
@@ -345,8 +425,19 @@ class PyramidStack(BaseStackAlgo):
                 self._push_raw(stack, frame)
                 self._step(i)
                 continue
-            img, metadata, updated = self.read_image_and_update_metadata(
-                img_path, metadata, decoded.result() if decoded is not None else None)
+            if self.jpeg is None:
+                img = decoded.result() if decoded is not None else None
+            else:
+                frame, img = self._jpeg_take(img_path, decoded)
+                if frame is not None:       # decoded on the device
+                    metadata, updated = self._jpeg_metadata(frame, metadata)
+                    if updated:
+                        self._set_dtype(metadata[1])
+                        stack = self._handle(metadata[0], metadata[1])
+                    self._jpeg_push(frame, lambda ptr: stack.push_frames_device(ptr, 1), stack.sync)
+                    self._step(i)
+                    continue
+            img, metadata, updated = self.read_image_and_update_metadata(img_path, metadata, img)
             if updated:
                 self._set_dtype(metadata[1])
                 stack = self._handle(metadata[0], metadata[1])
