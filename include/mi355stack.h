@@ -1258,7 +1258,7 @@ typedef struct mi_jpeg {
     int32_t width, height;  /* 1 .. 65535 each                                                          */
     int32_t ncomp;          /* 1 (grey) or 3 (YCbCr)                                                    */
     int32_t hmax, vmax;     /* the first component's sampling: (1,1), (2,1) or (2,2); (1,1) at ncomp 1  */
-    int32_t dri;            /* MCUs per restart interval, 1 .. MI_JPEG_MAX_DRI                          */
+    int32_t dri;            /* MCUs per restart interval, 1 .. MI_JPEG_MAX_DRI (mi_jpeg_split_*: 1 .. MCUs) */
     int32_t n_intervals;    /* ceil(MCUs / dri)                                                         */
     int32_t reserved;
     uint8_t tq[4];          /* per component: its quantisation table, 0 .. 3                            */
@@ -1291,6 +1291,41 @@ MI_API int mi_jpeg_decode_device(int device, void* stream, const void* dev_span,
                                  uint32_t* dev_status);
 MI_API int mi_jpeg_decode(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
                           uint8_t* host_out, uint32_t* status_out);
+
+/* ---- the split entropy decoder (kernels_jpeg_split.hpp): restart intervals of any length, a scan in one piece included ----
+ * The same frames, checks and outputs as the entry points above, with one difference in `jpeg`: dri may be anything from 1 to
+ * the number of MCUs, so a file WITHOUT a restart interval is passed as dri = MCUs, n_intervals = 1.  Every interval is cut into
+ * subsequences of sub_bytes bytes, each walked by a lane of its own from a guessed decoder state; the guesses are repaired --
+ * inside a workgroup of 256 lanes in LDS, across workgroups in up to max_rounds launches -- until every lane starts where its
+ * predecessor stopped, which makes the result exact (jpeg_sync_core.hpp; tests/jpeg_split_restatement.py states it in Python).
+ * Photographs settle in no round or one; an interval whose rounds were too few reports MI_JPEG_UNSYNCED and nothing else, and
+ * its blocks are unspecified.  The _device forms enqueue on `stream` and never wait, so they may report that bit; the host
+ * forms wait anyway, run once more with every round (workgroups - 1) when they find it, and never return it.
+ * A truncated or corrupt interval is deterministic: its walk ends at the first symbol that would start at or beyond the end
+ * of its data; MI_JPEG_OVERRUN is set when a block of the interval is then incomplete or missing, or when a symbol took bits
+ * from beyond the end; coefficients not reached are 0 and DC differences not reached are 0 (the serial walker above goes on
+ * reading zeros instead: a flagged interval's blocks are unspecified there too).
+ * Still refused, by jpeg.read: progressive and arithmetic-coded files, 12-bit samples, CMYK / RGB components, several scans,
+ * fill bytes inside the scan.
+ * Checks beyond those above: sub_bytes 0 (the default, 128) or 8, 16, 32, 64, 128; max_rounds 0 (the default, 8) or a count;
+ * a null `opt` means both defaults; dev_scratch 256-byte aligned with at least mi_jpeg_split_scratch_bytes (for the same
+ * span_bytes and opt; both device forms take the same size). */
+typedef struct {
+    uint32_t sub_bytes;
+    uint32_t max_rounds;
+} mi_jpeg_split_t;
+#define MI_JPEG_UNSYNCED 8u /* status bit 3 (split decoder, device forms only): the rounds enqueued were too few */
+MI_API int mi_jpeg_split_scratch_bytes(const mi_jpeg_t* jpeg, size_t span_bytes, const mi_jpeg_split_t* opt, size_t* bytes);
+MI_API int mi_jpeg_split_coefficients_device(int device, void* stream, const void* dev_span, size_t span_bytes,
+                                             const uint32_t* dev_offsets, const mi_jpeg_t* jpeg, const mi_jpeg_split_t* opt,
+                                             void* dev_scratch, size_t scratch_bytes, int16_t* dev_coef, uint32_t* dev_status);
+MI_API int mi_jpeg_split_coefficients(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets,
+                                      const mi_jpeg_t* jpeg, const mi_jpeg_split_t* opt, int16_t* host_coef, uint32_t* status_out);
+MI_API int mi_jpeg_split_decode_device(int device, void* stream, const void* dev_span, size_t span_bytes, const uint32_t* dev_offsets,
+                                       const mi_jpeg_t* jpeg, const mi_jpeg_split_t* opt, void* dev_scratch, size_t scratch_bytes,
+                                       uint8_t* dev_out, uint32_t* dev_status);
+MI_API int mi_jpeg_split_decode(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
+                                const mi_jpeg_split_t* opt, uint8_t* host_out, uint32_t* status_out);
 
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,

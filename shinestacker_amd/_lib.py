@@ -160,9 +160,16 @@ class JpegStruct(C.Structure):
                 ("quant", (C.c_uint8 * 64) * 4)]
 
 
-JPEG_NOCODE, JPEG_OVERRUN, JPEG_RUN = 1, 2, 4
+class JpegSplitStruct(C.Structure):
+    """mi_jpeg_split_t: the split decoder's options; 0 means the default (128 bytes a subsequence, 8 rounds)"""
+    _fields_ = [("sub_bytes", C.c_uint32), ("max_rounds", C.c_uint32)]
+
+
+JPEG_NOCODE, JPEG_OVERRUN, JPEG_RUN, JPEG_UNSYNCED = 1, 2, 4, 8
+JPEG_SPLIT_ALL_ROUNDS = 0xFFFFFFFF      # max_rounds: as many rounds as the scan has workgroups, less one
 JPEG_FLAG_NAMES = {JPEG_NOCODE: "a 16-bit prefix matched no Huffman code", JPEG_OVERRUN: "the data ended before the interval's last block",
-                   JPEG_RUN: "a run carried the coefficient index past 63"}
+                   JPEG_RUN: "a run carried the coefficient index past 63",
+                   JPEG_UNSYNCED: "the split decoder's rounds were too few"}
 
 
 def jpeg_flag_text(flags):
@@ -449,6 +456,15 @@ SIGNATURES = {
     "mi_jpeg_decode_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(JpegStruct), C.c_void_p,
                                         C.c_size_t, C.c_void_p, C.c_void_p]),
     "mi_jpeg_decode": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(JpegStruct), C.c_void_p, C.c_void_p]),
+    "mi_jpeg_split_scratch_bytes": (C.c_int, [C.POINTER(JpegStruct), C.c_size_t, C.POINTER(JpegSplitStruct), C.POINTER(C.c_size_t)]),
+    "mi_jpeg_split_coefficients_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(JpegStruct),
+                                                    C.POINTER(JpegSplitStruct), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mi_jpeg_split_coefficients": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(JpegStruct), C.POINTER(JpegSplitStruct),
+                                             C.c_void_p, C.c_void_p]),
+    "mi_jpeg_split_decode_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(JpegStruct),
+                                              C.POINTER(JpegSplitStruct), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mi_jpeg_split_decode": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(JpegStruct), C.POINTER(JpegSplitStruct),
+                                       C.c_void_p, C.c_void_p]),
     "mi_synth_frames_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_uint32]),
 }

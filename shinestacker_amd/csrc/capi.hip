@@ -36,6 +36,7 @@
 #include "kernels_lens.hpp"
 #include "kernels_finish.hpp"
 #include "kernels_jpeg.hpp"
+#include "kernels_jpeg_split.hpp"
 
 using namespace mi;
 
@@ -2386,7 +2387,8 @@ int mi_raw_ljpeg3(int device, const void* host_span, size_t span_bytes, const mi
 }
 
 // ---- baseline JPEG frames (kernels_jpeg.hpp): the descriptor lies in host memory and is checked here, whole
-static int jpeg_check(const mi_jpeg_t* J) {
+// (split: the entry points of kernels_jpeg_split.hpp, which take an interval of any length)
+static int jpeg_check(const mi_jpeg_t* J, bool split = false) {
     if (!J) return fail(MI_ERR_INVALID, "null jpeg");
     if (J->width < 1 || J->width > 65535 || J->height < 1 || J->height > 65535)
         return fail(MI_ERR_INVALID, "jpeg width and height must be in [1, 65535] (got %d x %d)", J->width, J->height);
@@ -2394,7 +2396,8 @@ static int jpeg_check(const mi_jpeg_t* J) {
     const bool samp = (J->hmax == 1 && J->vmax == 1) || (J->ncomp == 3 && J->hmax == 2 && (J->vmax == 1 || J->vmax == 2));
     if (!samp) return fail(MI_ERR_INVALID, "jpeg hmax, vmax must be (1,1), or (2,1) or (2,2) at ncomp 3 (got (%d,%d))", J->hmax, J->vmax);
     const jpeg::Geom g = jpeg::geom(*J);
-    if (J->dri < 1 || J->dri > MI_JPEG_MAX_DRI) return fail(MI_ERR_INVALID, "jpeg dri must be in [1, %d] (got %d)", MI_JPEG_MAX_DRI, J->dri);
+    const int max_dri = split ? g.n_mcus : MI_JPEG_MAX_DRI;
+    if (J->dri < 1 || J->dri > max_dri) return fail(MI_ERR_INVALID, "jpeg dri must be in [1, %d] (got %d)", max_dri, J->dri);
     const long long want = ((long long)g.n_mcus + J->dri - 1) / J->dri;
     if (J->n_intervals != want)
         return fail(MI_ERR_INVALID, "jpeg n_intervals must be ceil(%d MCUs / dri %d) = %lld (got %d)", g.n_mcus, J->dri, want, J->n_intervals);
@@ -2423,10 +2426,11 @@ static int jpeg_check(const mi_jpeg_t* J) {
     }
     return MI_OK;
 }
-static int jpeg_args_check(const void* span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* J, const void* out) {
+static int jpeg_args_check(const void* span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* J, const void* out,
+                           bool split = false) {
     if (!span) return fail(MI_ERR_INVALID, "null span");
     if (!offsets) return fail(MI_ERR_INVALID, "null offsets");
-    int rc = jpeg_check(J);
+    int rc = jpeg_check(J, split);
     if (rc) return rc;
     if (!out) return fail(MI_ERR_INVALID, "null output");
     if (span_bytes < 1 || span_bytes >= (1ull << 32))
@@ -2523,6 +2527,120 @@ int mi_jpeg_decode(int device, const void* host_span, size_t span_bytes, const u
         return rc;
     if (status_out && (rc = tmp.download(status_out, status, ns))) return rc;
     return tmp.download(host_out, out, nb);
+}
+
+// ---- the split entropy decoder (kernels_jpeg_split.hpp): the same checks, an interval of any length
+static int jpeg_split_opt(const mi_jpeg_split_t* opt, uint32_t* sub, uint32_t* rounds) {
+    *sub = opt && opt->sub_bytes ? opt->sub_bytes : jpeg::SPLIT_SUB_DEFAULT;
+    *rounds = opt && opt->max_rounds ? opt->max_rounds : jpeg::SPLIT_ROUNDS_DEFAULT;
+    if (*sub != 8 && *sub != 16 && *sub != 32 && *sub != 64 && *sub != 128)
+        return fail(MI_ERR_INVALID, "split sub_bytes must be 0, 8, 16, 32, 64 or 128 (got %u)", *sub);
+    return MI_OK;
+}
+static size_t jpeg_split_bytes(const mi_jpeg_t* J, size_t span_bytes, uint32_t sub, uint32_t rounds) {
+    const size_t nblocks = jpeg::geom(*J).nblocks;
+    return nblocks * 192 + jpeg::split_layout(span_bytes, sub, rounds, *J, nblocks).words * sizeof(uint32_t);
+}
+
+int mi_jpeg_split_scratch_bytes(const mi_jpeg_t* jpeg, size_t span_bytes, const mi_jpeg_split_t* opt, size_t* bytes) {
+    int rc = jpeg_check(jpeg, true);
+    if (rc) return rc;
+    if (span_bytes < 1 || span_bytes >= (1ull << 32))
+        return fail(MI_ERR_INVALID, "span_bytes must be in [1, 2^32) (got %llu)", (unsigned long long)span_bytes);
+    uint32_t sub, rounds;
+    if ((rc = jpeg_split_opt(opt, &sub, &rounds))) return rc;
+    if (!bytes) return fail(MI_ERR_INVALID, "null bytes");
+    *bytes = jpeg_split_bytes(jpeg, span_bytes, sub, rounds);
+    return MI_OK;
+}
+
+// the checks of both device forms; `out`: the coefficients or the frame
+static int jpeg_split_device_check(const void* dev_span, size_t span_bytes, const uint32_t* dev_offsets, const mi_jpeg_t* jpeg,
+                                   const mi_jpeg_split_t* opt, const void* dev_scratch, size_t scratch_bytes, const void* out,
+                                   const uint32_t* dev_status, uint32_t* sub, uint32_t* rounds) {
+    int rc = jpeg_args_check(dev_span, span_bytes, dev_offsets, jpeg, out, true);
+    if (rc || (rc = jpeg_split_opt(opt, sub, rounds))) return rc;
+    if (!dev_scratch) return fail(MI_ERR_INVALID, "null scratch");
+    const size_t need = jpeg_split_bytes(jpeg, span_bytes, *sub, *rounds);
+    if (scratch_bytes < need)
+        return fail(MI_ERR_INVALID, "scratch_bytes must be >= %llu (got %llu)", (unsigned long long)need, (unsigned long long)scratch_bytes);
+    if ((uintptr_t)dev_scratch & 255) return fail(MI_ERR_INVALID, "dev_scratch must be 256-byte aligned");
+    if ((uintptr_t)dev_span & 3) return fail(MI_ERR_INVALID, "dev_span must be 4-byte aligned");
+    if ((uintptr_t)dev_offsets & 3) return fail(MI_ERR_INVALID, "dev_offsets must be 4-byte aligned");
+    if ((uintptr_t)dev_status & 3) return fail(MI_ERR_INVALID, "dev_status must be 4-byte aligned");
+    return MI_OK;
+}
+
+int mi_jpeg_split_coefficients_device(int device, void* stream, const void* dev_span, size_t span_bytes, const uint32_t* dev_offsets,
+                                      const mi_jpeg_t* jpeg, const mi_jpeg_split_t* opt, void* dev_scratch, size_t scratch_bytes,
+                                      int16_t* dev_coef, uint32_t* dev_status) {
+    uint32_t sub, rounds;
+    int rc = jpeg_split_device_check(dev_span, span_bytes, dev_offsets, jpeg, opt, dev_scratch, scratch_bytes, dev_coef, dev_status, &sub, &rounds);
+    if (rc) return rc;
+    if ((uintptr_t)dev_coef & 15) return fail(MI_ERR_INVALID, "dev_coef must be 16-byte aligned");
+    MI_HIP(hipSetDevice(device));
+    uint32_t* words = (uint32_t*)((uint8_t*)dev_scratch + jpeg::geom(*jpeg).nblocks * 192);
+    jpeg_split_launch((hipStream_t)stream, dev_span, span_bytes, dev_offsets, *jpeg, sub, rounds, words, dev_coef, dev_status);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_jpeg_split_decode_device(int device, void* stream, const void* dev_span, size_t span_bytes, const uint32_t* dev_offsets,
+                                const mi_jpeg_t* jpeg, const mi_jpeg_split_t* opt, void* dev_scratch, size_t scratch_bytes,
+                                uint8_t* dev_out, uint32_t* dev_status) {
+    uint32_t sub, rounds;
+    int rc = jpeg_split_device_check(dev_span, span_bytes, dev_offsets, jpeg, opt, dev_scratch, scratch_bytes, dev_out, dev_status, &sub, &rounds);
+    if (rc) return rc;
+    int16_t* coef = (int16_t*)dev_scratch;
+    if ((rc = mi_jpeg_split_coefficients_device(device, stream, dev_span, span_bytes, dev_offsets, jpeg, opt, dev_scratch, scratch_bytes, coef,
+                                                dev_status)))
+        return rc;
+    jpeg_render_launch((hipStream_t)stream, *jpeg, coef, (uint8_t*)dev_scratch + jpeg::geom(*jpeg).nblocks * 128, dev_out);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+// both host forms: upload, run, look at the status words, run once more with every round where they say the rounds were too
+// few, download
+static int jpeg_split_host(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
+                           const mi_jpeg_split_t* opt, int16_t* host_coef, uint8_t* host_out, uint32_t* status_out) {
+    int rc = jpeg_args_check(host_span, span_bytes, offsets, jpeg, host_coef ? (const void*)host_coef : (const void*)host_out, true);
+    uint32_t sub, rounds;
+    if (rc || (rc = jpeg_split_opt(opt, &sub, &rounds)) || (rc = jpeg_offsets_check(span_bytes, offsets, jpeg))) return rc;
+    if ((rc = open_device(device))) return rc;
+    const mi_jpeg_split_t full{sub, 0xffffffffu};
+    const size_t nblocks = jpeg::geom(*jpeg).nblocks, ns = (size_t)jpeg->n_intervals * sizeof(uint32_t);
+    const size_t nscratch = jpeg_split_bytes(jpeg, span_bytes, sub, full.max_rounds), nb = (size_t)jpeg->height * jpeg->width * 3;
+    DevScratch tmp(nullptr);
+    void *span = nullptr, *scratch = nullptr;
+    uint32_t *off = nullptr, *status = nullptr;
+    uint8_t* out = nullptr;
+    if ((rc = tmp.upload(&span, host_span, span_bytes)) || (rc = tmp.upload(&off, offsets, ns + sizeof(uint32_t))) ||
+        (rc = tmp.alloc(&scratch, nscratch)) || (rc = tmp.alloc(&status, ns)) || (host_out && (rc = tmp.alloc(&out, nb))))
+        return rc;
+    std::vector<uint32_t> words((size_t)jpeg->n_intervals);
+    const mi_jpeg_split_t first{sub, rounds};
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        const mi_jpeg_split_t* o = attempt ? &full : &first;
+        rc = host_out ? mi_jpeg_split_decode_device(device, nullptr, span, span_bytes, off, jpeg, o, scratch, nscratch, out, status)
+                      : mi_jpeg_split_coefficients_device(device, nullptr, span, span_bytes, off, jpeg, o, scratch, nscratch, (int16_t*)scratch, status);
+        if (rc || (rc = tmp.download(words.data(), status, ns))) return rc;
+        bool unsynced = false;
+        for (uint32_t w : words) unsynced = unsynced || (w & MI_JPEG_UNSYNCED);
+        if (!unsynced) break;
+    }
+    if (status_out) memcpy(status_out, words.data(), ns);
+    return host_out ? tmp.download(host_out, out, nb) : tmp.download(host_coef, scratch, nblocks * 128);
+}
+
+int mi_jpeg_split_coefficients(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
+                               const mi_jpeg_split_t* opt, int16_t* host_coef, uint32_t* status_out) {
+    return jpeg_split_host(device, host_span, span_bytes, offsets, jpeg, opt, host_coef, nullptr, status_out);
+}
+
+int mi_jpeg_split_decode(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
+                         const mi_jpeg_split_t* opt, uint8_t* host_out, uint32_t* status_out) {
+    return jpeg_split_host(device, host_span, span_bytes, offsets, jpeg, opt, nullptr, host_out, status_out);
 }
 
 // the part of mi_stack_push_packed and mi_stack_push_ljpeg behind the span's checks

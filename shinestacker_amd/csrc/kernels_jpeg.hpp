@@ -9,7 +9,7 @@
 //                  one interval per MCU row, a few hundred in all -- fewer than the chip has wave slots, so every interval
 //                  gets a wave of its own either way -- and 64 walkers in one wave would run each other's
 //                  data-dependent branches (the code-length search, the end of block) under masks.  raw_ljpeg made the
-//                  same choice for its tiles.  The other 63 lanes idle: decode INSIDE an interval is the step not built.
+//                  same choice for its tiles.  The other 63 lanes idle: decode INSIDE an interval is kernels_jpeg_split.hpp.
 //   jpeg_idct      one block per lane: dequantise, the 13-bit "slow integer" inverse DCT (columns descaled by 11, rows by
 //                  18, both with rounding), + 128, clip; in int64 throughout, as the restatement computes it, so that it
 //                  holds for every int16 coefficient and every table entry.  Writes the component's padded sample plane.

@@ -37,9 +37,9 @@ class DepthMapStack(BaseStackAlgo):
                  kernel_size=constants.DEFAULT_DM_KERNEL_SIZE, blur_size=constants.DEFAULT_DM_BLUR_SIZE,
                  smooth_size=constants.DEFAULT_DM_SMOOTH_SIZE, temperature=constants.DEFAULT_DM_TEMPERATURE,
                  levels=constants.DEFAULT_DM_LEVELS, float_type=constants.DEFAULT_DM_FLOAT, *, device=0,
-                 decode_threads=8, jpeg=None):
+                 decode_threads=8, jpeg=None, jpeg_split=False):
         super().__init__("depth map", 2, float_type)
-        self._set_jpeg(jpeg)      # (keyword-only extension: BaseStackAlgo._set_jpeg)
+        self._set_jpeg(jpeg, jpeg_split)      # (keyword-only extensions: BaseStackAlgo._set_jpeg)
         self.map_type = map_type
         self.energy = energy
         self.kernel_size = kernel_size

@@ -11,8 +11,13 @@ What is decoded: SOF0 (and SOF1 with 8-bit precision, Huffman coded), one interl
 sampling (1,1), (2,1) or (2,2) with chroma (1,1), 8-bit quantisation tables, DC and AC tables 0 and 1, a restart interval,
 and a colour space libjpeg's rule reads as YCbCr or grey (JFIF: YCbCr; else an Adobe segment with transform 1; else component
 ids 1, 2, 3).  Everything else is refused by `read` with InvalidOptionError, naming the marker and the value found, before
-any device call -- among it files WITHOUT a restart interval, whose single interval would be one serial walk, and
+any device call -- among it, by default, files WITHOUT a restart interval, whose single interval would be one serial walk, and
 files whose interval is longer than MAX_DRI MCUs (the MCU row of a picture 65 535 wide), for the same reason.
+
+`read(path, split="needed")` takes those two kinds of file as well and marks them (`JpegFrame.split`) for the split decoder
+(csrc/kernels_jpeg_split.hpp), which cuts an interval of any length into subsequences, decodes them on many lanes at once and
+repairs the lanes' guesses until the result is exact; `split="always"` sends every file there.  Still refused either way:
+progressive and arithmetic-coded files, 12-bit samples, CMYK and RGB components, several scans, fill bytes inside the scan.
 
 EXIF orientation is reported (`JpegFrame.orientation`) and not applied, as the Pillow branch of read_img leaves it.
 """
@@ -26,6 +31,7 @@ from .errors import ImageLoadError, InvalidOptionError
 
 EXTENSIONS = ("jpg", "jpeg")
 MODES = (None, "device", "auto")
+SPLIT = (None, "needed", "always")
 MAX_DRI = 8192      # MI_JPEG_MAX_DRI: MCUs in the longest interval that is decoded
 _ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42,
            49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
@@ -48,9 +54,12 @@ def check_mode(mode):
 class JpegFrame:
     """What `read` found.  shape (H, W), dtype uint8, ncomp 1 or 3, sampling (hmax, vmax), dri (MCUs per restart interval),
     span (the scan's bytes, a view of the file's mapping), offsets (uint32, n_intervals + 1, into the span), desc (the
-    _lib.JpegStruct the kernels take), orientation (the EXIF tag, 1 when absent; not applied)."""
+    _lib.JpegStruct the kernels take), orientation (the EXIF tag, 1 when absent; not applied).  split: whether the frame goes to
+    the split decoder (read's `split=`); then dri is 0 for a file without a restart interval, desc.dri the MCU count and there
+    is one interval.  split_options: (sub_bytes, max_rounds) for that decoder, 0 for the library's default."""
 
-    def __init__(self, path, shape, ncomp, sampling, dri, span, offsets, desc, orientation, keep):
+    def __init__(self, path, shape, ncomp, sampling, dri, span, offsets, desc, orientation, keep, split=False):
+        self.split, self.split_options = split, (0, 0)
         self.path, self.shape, self.dtype = path, shape, np.dtype(np.uint8)
         self.ncomp, self.sampling, self.dri = ncomp, sampling, dri
         self.span, self.offsets, self.desc, self.orientation = span, offsets, desc, orientation
@@ -82,10 +91,14 @@ def _exif_orientation(tiff):
     return 1
 
 
-def read(path):
+def read(path, split=None):
     """The headers of a baseline JPEG file -> JpegFrame; InvalidOptionError for everything the device decoder does not take
-    (the module docstring lists it), RuntimeError when the file does not exist, as read_img."""
+    (the module docstring lists it), RuntimeError when the file does not exist, as read_img.  split: None -- a file without a
+    restart interval, or with one longer than MAX_DRI, is refused; "needed" -- such a file is taken and marked for the split
+    decoder; "always" -- every file is."""
     import os
+    if split not in SPLIT:
+        raise InvalidOptionError("split", split, 'None, "needed" or "always" is expected')
     path = str(path)
     if not os.path.isfile(path):
         raise RuntimeError("File does not exist: " + path)
@@ -210,10 +223,10 @@ def read(path):
         for cls, name, t in ((0, "Td", scan[c][1]), (1, "Ta", scan[c][2])):
             if t > 1 or (cls, t) not in tables or not tables[(cls, t)][1]:
                 raise _refuse(path, f"SOS {name}", t, f"component {c} selects a Huffman table the file does not define (0 and 1 are decoded)")
-    if dri < 1:
+    if dri < 1 and split is None:
         raise _refuse(path, "DRI", "none" if dri == 0 else dri,
                       "no restart interval: the scan is one serial walk, which the device decoder does not take")
-    if dri > MAX_DRI:
+    if dri > MAX_DRI and split is None:
         raise _refuse(path, "DRI", dri, f"a restart interval of more than {MAX_DRI} MCUs, the longest MCU row a JPEG can have: "
                                         "one wavefront walks an interval serially, and a picture in one piece is what is not decoded")
     # the intervals: FF followed by anything but 00
@@ -236,9 +249,11 @@ def read(path):
         k = int(wrong[0])
         raise _refuse(path, f"RST{int(mk[k]) - 0xD0}", f"byte {scan_off + int(cand[k])}", f"restart markers out of sequence: RST{k % 8} is expected")
     n_mcus = -(-width // (8 * hmax)) * -(-height // (8 * vmax))
-    n_int = -(-n_mcus // dri)
+    to_split = split == "always" or (split == "needed" and (dri < 1 or dri > MAX_DRI))
+    per = min(dri, n_mcus) if dri >= 1 else n_mcus      # (an interval longer than the picture is the picture)
+    n_int = -(-n_mcus // per)
     if e + 1 != n_int:
-        raise _refuse(path, "restart intervals", e + 1, f"{n_mcus} MCUs at DRI {dri} make {n_int}")
+        raise _refuse(path, "restart intervals", e + 1, f"{n_mcus} MCUs at DRI {dri if dri >= 1 else 'none'} make {n_int}")
     end = int(cand[e])
     if end >= 1 << 32:
         raise _refuse(path, "scan", end, "a scan of 4 GiB or more")
@@ -248,7 +263,7 @@ def read(path):
     offsets[n_int] = end
     span = body[:max(end, 1)]
     d = _lib.JpegStruct()
-    d.width, d.height, d.ncomp, d.hmax, d.vmax, d.dri, d.n_intervals = width, height, nf, hmax, vmax, dri, n_int
+    d.width, d.height, d.ncomp, d.hmax, d.vmax, d.dri, d.n_intervals = width, height, nf, hmax, vmax, per if to_split else dri, n_int
     for c in range(nf):
         d.tq[c], d.td[c], d.ta[c] = comps[c][3], scan[c][1], scan[c][2]
     for (cls, t), (counts, values) in tables.items():
@@ -260,7 +275,7 @@ def read(path):
     for t in range(4):
         for i in range(64):
             d.quant[t][i] = int(quant[t][i]) if t in quant else 1
-    return JpegFrame(path, (height, width), nf, (hmax, vmax), dri, span, offsets, d, orientation, mm)
+    return JpegFrame(path, (height, width), nf, (hmax, vmax), dri, span, offsets, d, orientation, mm, to_split)
 
 
 def check_status(path, status):
@@ -277,16 +292,30 @@ def _span(frame):
     return np.ascontiguousarray(frame.span)
 
 
+def _split_opt(frame, max_rounds=None):
+    o = _lib.JpegSplitStruct()
+    o.sub_bytes, o.max_rounds = frame.split_options
+    if max_rounds is not None:
+        o.max_rounds = max_rounds
+    return o
+
+
 def coefficients(frame, device=0):
-    """(per component its (rows of blocks, blocks a row, 64) int16 plane, the uint32 status words): the entropy kernel alone"""
+    """(per component its (rows of blocks, blocks a row, 64) int16 plane, the uint32 status words): the entropy kernel alone
+    (jpeg_entropy, or the split decoder's passes where frame.split says so)"""
     _lib.require_device()
     n = _lib.C.c_size_t()
     _lib.check(_lib.load().mi_jpeg_coef_count(_lib.C.byref(frame.desc), _lib.C.byref(n)))
     coef = np.empty(n.value, np.int16)
     status = np.zeros(frame.n_intervals, np.uint32)
     span = _span(frame)
-    _lib.check(_lib.load().mi_jpeg_coefficients(device, span.ctypes.data, span.nbytes, frame.offsets.ctypes.data, _lib.C.byref(frame.desc),
-                                                coef.ctypes.data, status.ctypes.data))
+    if frame.split:
+        _lib.check(_lib.load().mi_jpeg_split_coefficients(device, span.ctypes.data, span.nbytes, frame.offsets.ctypes.data,
+                                                          _lib.C.byref(frame.desc), _lib.C.byref(_split_opt(frame)), coef.ctypes.data,
+                                                          status.ctypes.data))
+    else:
+        _lib.check(_lib.load().mi_jpeg_coefficients(device, span.ctypes.data, span.nbytes, frame.offsets.ctypes.data,
+                                                    _lib.C.byref(frame.desc), coef.ctypes.data, status.ctypes.data))
     out, at = [], 0
     for shape in frame.coef_shapes():
         k = shape[0] * shape[1] * 64
@@ -303,8 +332,13 @@ def decode(frame, device=0, status=False):
     out = np.empty((h, w, 3), np.uint8)
     st = np.zeros(frame.n_intervals, np.uint32)
     span = _span(frame)
-    _lib.check(_lib.load().mi_jpeg_decode(device, span.ctypes.data, span.nbytes, frame.offsets.ctypes.data, _lib.C.byref(frame.desc),
-                                          out.ctypes.data, st.ctypes.data))
+    if frame.split:
+        _lib.check(_lib.load().mi_jpeg_split_decode(device, span.ctypes.data, span.nbytes, frame.offsets.ctypes.data,
+                                                    _lib.C.byref(frame.desc), _lib.C.byref(_split_opt(frame)), out.ctypes.data,
+                                                    st.ctypes.data))
+    else:
+        _lib.check(_lib.load().mi_jpeg_decode(device, span.ctypes.data, span.nbytes, frame.offsets.ctypes.data, _lib.C.byref(frame.desc),
+                                              out.ctypes.data, st.ctypes.data))
     if status:
         return out, st
     check_status(frame.path, st)
@@ -330,7 +364,11 @@ class Slot:
                 self.buf.free()
             self.buf = _lib.DeviceBuffer(need, self.device)
         nb = _lib.C.c_size_t()
-        _lib.check(_lib.load().mi_jpeg_scratch_bytes(_lib.C.byref(frame.desc), _lib.C.byref(nb)))
+        if frame.split:     # (room for every round: a frame that reports UNSYNCED is decoded again in the same slot)
+            _lib.check(_lib.load().mi_jpeg_split_scratch_bytes(_lib.C.byref(frame.desc), span.nbytes,
+                                                               _lib.C.byref(_split_opt(frame, _lib.JPEG_SPLIT_ALL_ROUNDS)), _lib.C.byref(nb)))
+        else:
+            _lib.check(_lib.load().mi_jpeg_scratch_bytes(_lib.C.byref(frame.desc), _lib.C.byref(nb)))
         if self.scratch is None or self.scratch.nbytes < nb.value:
             if self.scratch is not None:
                 self.scratch.free()
@@ -349,23 +387,42 @@ class Slot:
         self.buf = self.scratch = None
 
 
-def decode_device(frame, dev_out, slot=None, device=0, stream=None):
+def decode_device(frame, dev_out, slot=None, device=0, stream=None, max_rounds=None, loaded=False):
     """Upload the frame's span into `slot` (a Slot; a new one when None) and enqueue the kernels on `stream`: `dev_out`
     (device pointer, H x W x 3 uint8) holds the BGR frame once they have run.  Does not wait for them.  Returns the slot: it
-    owns the buffers the kernels read, and `slot.status()` gives the status words after a wait."""
+    owns the buffers the kernels read, and `slot.status()` gives the status words after a wait.  A frame with `split` set
+    goes through the split decoder, with `max_rounds` in place of its own option where given; its status words may then
+    hold JPEG_UNSYNCED (`settle`).  loaded: the slot holds this frame's span already."""
     _lib.require_device()
     slot = Slot(device) if slot is None else slot
-    slot.load(frame)
-    _lib.check(_lib.load().mi_jpeg_decode_device(device, stream, slot.buf.ptr, slot.span_bytes, slot.buf.ptr + slot.off_at,
-                                                 _lib.C.byref(frame.desc), slot.scratch.ptr, slot.scratch.nbytes, dev_out,
-                                                 slot.buf.ptr + slot.status_at))
+    if not loaded:
+        slot.load(frame)
+    if frame.split:
+        _lib.check(_lib.load().mi_jpeg_split_decode_device(device, stream, slot.buf.ptr, slot.span_bytes, slot.buf.ptr + slot.off_at,
+                                                           _lib.C.byref(frame.desc), _lib.C.byref(_split_opt(frame, max_rounds)),
+                                                           slot.scratch.ptr, slot.scratch.nbytes, dev_out, slot.buf.ptr + slot.status_at))
+    else:
+        _lib.check(_lib.load().mi_jpeg_decode_device(device, stream, slot.buf.ptr, slot.span_bytes, slot.buf.ptr + slot.off_at,
+                                                     _lib.C.byref(frame.desc), slot.scratch.ptr, slot.scratch.nbytes, dev_out,
+                                                     slot.buf.ptr + slot.status_at))
     return slot
 
 
-def frames_device(paths, dev_out, device=0):
-    """Read the n JPEG files (equal shape), upload their spans and decode them side by side into `dev_out` (device pointer,
-    n x H x W x 3 uint8): exactly what pipeline.align_and_stack_device(dev_frames, ...) takes, as dng.frames_device does for
-    raw files.  Waits for the device; a flagged file raises ImageLoadError.  Returns (H, W, dtype)."""
+def settle(frame, dev_out, slot, device=0):
+    """After a wait for decode_device's kernels: the status words -- and where the split decoder says its rounds were too few
+    (JPEG_UNSYNCED), the frame decoded once more from the slot with every round, waited for, and those words"""
+    st = slot.status()
+    if frame.split and (st & _lib.JPEG_UNSYNCED).any():
+        decode_device(frame, dev_out, slot, device, None, _lib.JPEG_SPLIT_ALL_ROUNDS, loaded=True)
+        _lib.check(_lib.load().mi_device_synchronize(device))
+        st = slot.status()
+    return st
+
+
+def frames_device(paths, dev_out, device=0, split=None):
+    """Read the n JPEG files (equal shape; `split` as in read), upload their spans and decode them side by side into `dev_out`
+    (device pointer, n x H x W x 3 uint8): exactly what pipeline.align_and_stack_device(dev_frames, ...) takes, as
+    dng.frames_device does for raw files.  Waits for the device; a flagged file raises ImageLoadError.  Returns (H, W, dtype)."""
     if len(paths) == 0:
         raise ValueError("no files")
     _lib.require_device()
@@ -374,7 +431,7 @@ def frames_device(paths, dev_out, device=0):
     first = None
     try:
         for i, p in enumerate(paths):
-            frame = read(p)
+            frame = read(p, split)
             if first is None:
                 first = frame
             elif frame.shape != first.shape:
@@ -382,15 +439,15 @@ def frames_device(paths, dev_out, device=0):
             k = i & 1
             if pending[k] is not None:      # the slot's last decode: wait, then look at its status
                 _lib.check(_lib.load().mi_device_synchronize(device))
-                check_status(pending[k], slots[k].status())
+                check_status(pending[k][0].path, settle(*pending[k], slots[k], device))
                 pending[k] = None
             h, w = frame.shape
             decode_device(frame, dev_out + i * h * w * 3, slots[k], device)
-            pending[k] = p
+            pending[k] = (frame, dev_out + i * h * w * 3)
         _lib.check(_lib.load().mi_device_synchronize(device))
         for k in (0, 1):
             if pending[k] is not None:
-                check_status(pending[k], slots[k].status())
+                check_status(pending[k][0].path, settle(*pending[k], slots[k], device))
     finally:
         _lib.load().mi_device_synchronize(device)
         for s in slots:
@@ -419,7 +476,7 @@ class Pusher:
             self.bgr[k] = _lib.DeviceBuffer(h * w * 3, self.device)
         slot = decode_device(frame, self.bgr[k].ptr, self.slots[k], self.device)
         _lib.check(_lib.load().mi_device_synchronize(self.device))       # the null stream's kernels, ahead of the handle's
-        check_status(frame.path, slot.status())
+        check_status(frame.path, settle(frame, self.bgr[k].ptr, slot, self.device))
         push_device(self.bgr[k].ptr)
         self.k += 1
 

@@ -99,22 +99,29 @@ class BaseStackAlgo:
             from . import jpeg
             if jpeg.is_jpeg(path):
                 try:
-                    return jpeg.read(path)
+                    return jpeg.read(path, "needed" if getattr(self, "jpeg_split", False) else None)
                 except InvalidOptionError as e:
                     if mode != "auto":
                         raise
                     return _HostDecoded(read_img(path), str(e))
         return read_img(path)
 
-    def _set_jpeg(self, mode):
+    def _set_jpeg(self, mode, split=False):
         """jpeg (keyword-only extension): None -- every file is decoded on the host, as ever; "device" -- every `.jpg` /
         `.jpeg` path is parsed on the decode-ahead pool (jpeg.read), its scan is uploaded as it lies in the file and decoded
         on the device (csrc/kernels_jpeg.hpp), and a file jpeg.read refuses raises; "auto" -- such a file is decoded on the
-        host instead and (path, reason) is kept in `self.skipped`."""
+        host instead and (path, reason) is kept in `self.skipped`.  jpeg_split: True -- files without a restart interval, or
+        with one longer than jpeg.MAX_DRI, are taken too (jpeg.read(split="needed")) and go through the split decoder
+        (csrc/kernels_jpeg_split.hpp); False -- they are refused, as ever."""
         if mode is not None:
             from .jpeg import check_mode
             check_mode(mode)
+        if split not in (False, True):
+            raise InvalidOptionError("jpeg_split", split, "True or False is expected")
+        if split and mode is None:
+            raise InvalidOptionError("jpeg_split", split, 'jpeg="device" or "auto" is expected with it')
         self.jpeg = mode
+        self.jpeg_split = bool(split)
         self.skipped = []
         self._jpeg_pusher = None
 
@@ -194,9 +201,10 @@ class PyramidStack(BaseStackAlgo):
                  kernel_size=constants.DEFAULT_PY_KERNEL_SIZE,
                  gen_kernel=constants.DEFAULT_PY_GEN_KERNEL,
                  float_type=constants.DEFAULT_PY_FLOAT, *, device=0, use_fma=True,
-                 impl=_lib.IMPL_AUTO, batch_frames=0, decode_threads=8, arith=None, raw=None, jpeg=None):
+                 impl=_lib.IMPL_AUTO, batch_frames=0, decode_threads=8, arith=None, raw=None, jpeg=None,
+                 jpeg_split=False):
         super().__init__("pyramid", 2, float_type)
-        self._set_jpeg(jpeg)
+        self._set_jpeg(jpeg, jpeg_split)
         # raw (keyword-only extension): a dng.Raw -- focus_stack then takes `.dng` paths: each is parsed on the decode-ahead
         # pool (dng.read), its packed samples are uploaded as they lie in the file and unpacked, demosaiced and developed on
         # the device (Stack.push_packed).  None: a `.dng` path is an unknown extension, as ever.
