@@ -1327,6 +1327,53 @@ MI_API int mi_jpeg_split_decode_device(int device, void* stream, const void* dev
 MI_API int mi_jpeg_split_decode(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
                                 const mi_jpeg_split_t* opt, uint8_t* host_out, uint32_t* status_out);
 
+/* ---- the split path of the lossless-JPEG decoder (kernels_ljpeg_split.hpp): decode INSIDE a segment ----
+ * mi_raw_ljpeg gives one segment to one wavefront, whose first lane walks every symbol; a file in long strips, or written as
+ * one strip, is then bound by one serial walk.  The split path cuts every segment (mi_ljpeg_seg_t: one or two components, every
+ * predictor, every precision) into subsequences of sub_bytes bytes, walks each on a lane of its own from a guessed decoder
+ * state -- the bit position and the component -- and repairs the guesses, inside a workgroup of 256 lanes in LDS and across
+ * workgroups in up to max_rounds launches, until every lane starts where its predecessor stopped: the differences are then
+ * exact, and prefix sums mod 2^16 (predictor 1: down the first columns, then along every row, all rows at once; predictors 2
+ * to 7: one wavefront per segment) turn them into samples (ljpeg_sync_core.hpp; tests/ljpeg_split_restatement.py states it in
+ * Python).  Descriptors, layout, crop, table, shift and output are exactly mi_raw_ljpeg's, and so is every unflagged segment.
+ * Three-component streams (mi_ljpeg_seg3_t, mi_raw_ljpeg3) stay on the serial kernel: the step deliberately left for later.
+ * Status: the bits of mi_raw_ljpeg, with these differences.  MI_LJPEG_OVERRUN: the data ended before the segment's last
+ * sample, or a sample took bits from beyond the end; the walk stops there and samples not reached have difference 0 (the
+ * serial kernel goes on reading zeros: a flagged segment's samples are unspecified in both).  MI_LJPEG_UNDECODED: as
+ * mi_raw_ljpeg, and the segment is NOT written (as mi_raw_ljpeg3); also set where descriptors in device memory overlap so far
+ * that they hold more subsequences than span_bytes / sub_bytes + segments.  MI_LJPEG_UNSYNCED: the rounds enqueued were too
+ * few -- the segment reports that bit and nothing else, and its samples are unspecified.
+ * `opt` is mi_jpeg_split_t: sub_bytes 0 (the default, 128) or 8, 16, 32, 64, 128; max_rounds 0 for the default or a count.  The
+ * default is 8 where the descriptors lie only on the device (the _device forms, which enqueue on `stream`, never wait and may
+ * report MI_LJPEG_UNSYNCED); where they lie in host memory it is the exact bound -- the largest number of workgroups any one
+ * segment's lanes touch, minus 1 -- which never leaves a segment unsynced (rounds not needed return at once).  The host forms
+ * upload, run and wait, run once more with the exact bound when a given max_rounds left a segment unsynced, and never return
+ * that bit.  Checks: those of mi_raw_ljpeg[_device], those of mi_jpeg_split_* for `opt` and the scratch (null, too small -- the
+ * message names the size --, 256-byte alignment; mi_ljpeg_split_scratch_bytes for the same layout, span_bytes and opt), and
+ * segments x seg_height x seg_width below 2^32.
+ * mi_ljpeg_split_differences[_device] is the tap for tests: the difference plane -- seg_height x seg_width uint16 per segment,
+ * in segment order, unreached samples 0 -- and the status words, with no prediction. */
+#define MI_LJPEG_UNSYNCED 8u    /* status bit 3 (split path, device forms only): the rounds enqueued were too few */
+MI_API int mi_ljpeg_split_scratch_bytes(const mi_raw_layout_t* layout, size_t span_bytes, const mi_jpeg_split_t* opt, size_t* bytes);
+MI_API int mi_raw_ljpeg_split_device(int device, void* stream, const void* dev_span, size_t span_bytes, const mi_ljpeg_seg_t* dev_segs,
+                                     const mi_raw_layout_t* layout, const uint16_t* dev_table, const mi_jpeg_split_t* opt,
+                                     void* dev_scratch, size_t scratch_bytes, void* dev_out, uint32_t* dev_status);
+MI_API int mi_raw_ljpeg_split(int device, const void* host_span, size_t span_bytes, const mi_ljpeg_seg_t* segs,
+                              const mi_raw_layout_t* layout, const uint16_t* host_table, const mi_jpeg_split_t* opt, void* host_out,
+                              uint32_t* status_out);
+MI_API int mi_ljpeg_split_differences_device(int device, void* stream, const void* dev_span, size_t span_bytes,
+                                             const mi_ljpeg_seg_t* dev_segs, const mi_raw_layout_t* layout, const mi_jpeg_split_t* opt,
+                                             void* dev_scratch, size_t scratch_bytes, uint16_t* dev_plane, uint32_t* dev_status);
+MI_API int mi_ljpeg_split_differences(int device, const void* host_span, size_t span_bytes, const mi_ljpeg_seg_t* segs,
+                                      const mi_raw_layout_t* layout, const mi_jpeg_split_t* opt, uint16_t* host_plane,
+                                      uint32_t* status_out);
+/* The stack: with `opt` set (it holds until replaced, or cleared with null, as mi_stack_set_site_correction does),
+ * mi_stack_push_ljpeg and one-sample compressed mi_stack_push_linear frames go through the split path, always with the exact
+ * round bound from their host descriptors (opt->max_rounds is not looked at: a stack never sees MI_LJPEG_UNSYNCED); three-sample
+ * linear frames keep going to raw_ljpeg3.  The stage owns one scratch, grown on demand -- the decode kernels of all frames run
+ * in order on the handle's stream.  mi_stack_ljpeg_status keeps ORing the flags; everything behind the decode is unchanged. */
+MI_API int mi_stack_set_ljpeg_split(mi_stack_t* s, const mi_jpeg_split_t* opt);
+
 /* ---- synthetic stack generator, device side ---- */
 MI_API int mi_synth_frames_device(int device, void* dev_out, int dtype, int height, int width,
                            int first_frame, int n_frames, int stack_size, uint32_t seed);

@@ -142,10 +142,11 @@ LJPEG_SEG_DTYPE = np.dtype([("scan_off", "<u4"), ("scan_bytes", "<u4"), ("x", "<
 LJPEG_SEG3_DTYPE = np.dtype([("scan_off", "<u4"), ("scan_bytes", "<u4"), ("x", "<i4"), ("y", "<i4"), ("ncomp", "u1"), ("predictor", "u1"),
                              ("precision", "u1"), ("reserved", "u1"), ("counts", "u1", (3, 16)), ("values", "u1", (3, 17)),
                              ("pad", "u1", (9,))])
-LJPEG_NOCODE, LJPEG_OVERRUN, LJPEG_UNDECODED = 1, 2, 4
+LJPEG_NOCODE, LJPEG_OVERRUN, LJPEG_UNDECODED, LJPEG_UNSYNCED = 1, 2, 4, 8
 LJPEG_MAX_LINE = 24576
 LJPEG_FLAG_NAMES = {LJPEG_NOCODE: "a 16-bit prefix matched no Huffman code", LJPEG_OVERRUN: "the data ended before the last sample",
-                    LJPEG_UNDECODED: "a descriptor the decoder does not take"}
+                    LJPEG_UNDECODED: "a descriptor the decoder does not take",
+                    LJPEG_UNSYNCED: "the split path's rounds were too few"}
 
 
 def ljpeg_flag_text(flags):
@@ -163,6 +164,20 @@ class JpegStruct(C.Structure):
 class JpegSplitStruct(C.Structure):
     """mi_jpeg_split_t: the split decoder's options; 0 means the default (128 bytes a subsequence, 8 rounds)"""
     _fields_ = [("sub_bytes", C.c_uint32), ("max_rounds", C.c_uint32)]
+
+
+def ljpeg_split_options(split):
+    """the split path's options (kernels_ljpeg_split.hpp) as a JpegSplitStruct, or None where `split` switches it off:
+    False / None -- off; True -- the defaults; {"sub_bytes": 0 | 8 | 16 | 32 | 64 | 128, "max_rounds": 0 | a count}"""
+    if split is None or split is False:
+        return None
+    if split is True:
+        return JpegSplitStruct(0, 0)
+    if isinstance(split, JpegSplitStruct):
+        return split
+    if not isinstance(split, dict) or set(split) - {"sub_bytes", "max_rounds"}:
+        raise ValueError(f'ljpeg split: False, True or a dict with "sub_bytes" and "max_rounds" is expected (got {split!r})')
+    return JpegSplitStruct(int(split.get("sub_bytes", 0)), int(split.get("max_rounds", 0)))
 
 
 JPEG_NOCODE, JPEG_OVERRUN, JPEG_RUN, JPEG_UNSYNCED = 1, 2, 4, 8
@@ -425,6 +440,16 @@ SIGNATURES = {
                                       C.POINTER(CfaStruct), C.POINTER(CalibStruct), C.POINTER(DevelopStruct), C.c_void_p, C.c_int,
                                       C.c_int]),
     "mi_stack_ljpeg_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "mi_ljpeg_split_scratch_bytes": (C.c_int, [C.POINTER(RawLayoutStruct), C.c_size_t, C.POINTER(JpegSplitStruct), C.POINTER(C.c_size_t)]),
+    "mi_raw_ljpeg_split_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p,
+                                            C.POINTER(JpegSplitStruct), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mi_raw_ljpeg_split": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct), C.c_void_p,
+                                     C.POINTER(JpegSplitStruct), C.c_void_p, C.c_void_p]),
+    "mi_ljpeg_split_differences_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct),
+                                                    C.POINTER(JpegSplitStruct), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "mi_ljpeg_split_differences": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RawLayoutStruct),
+                                             C.POINTER(JpegSplitStruct), C.c_void_p, C.c_void_p]),
+    "mi_stack_set_ljpeg_split": (C.c_int, [C.c_void_p, C.POINTER(JpegSplitStruct)]),
     "mi_feat_gray_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mi_feat_gray": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mi_feat_score_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -948,6 +973,14 @@ class Stack:
             return entry(self._h, span.ctypes.data, span.nbytes, segs.ctypes.data, int(compressed), C.byref(L),
                          None if table is None else table.ctypes.data, C.byref(ls), None if d is None else C.byref(d), pinned)
         self._push_host(push, span, zero_copy)
+
+    def set_ljpeg_split(self, split):
+        """Send every later lossless-JPEG push of this handle (push_packed of a compressed frame of one or two components)
+        through the split path -- decode inside a segment, kernels_ljpeg_split.hpp -- or (False / None) back to the serial
+        kernel.  `split`: False, True or {"sub_bytes": ..., "max_rounds": ...} (ljpeg_split_options; the handle always
+        enqueues the exact round bound).  It holds until it is replaced or cleared; the result is the same either way."""
+        opt = ljpeg_split_options(split)
+        check(load().mi_stack_set_ljpeg_split(self._h, None if opt is None else C.byref(opt)))
 
     def ljpeg_status(self):
         """the status flags (LJPEG_NOCODE, LJPEG_OVERRUN, ...) of every lossless-JPEG frame pushed since the last call, ORed:

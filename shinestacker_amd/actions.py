@@ -210,6 +210,10 @@ class FrameDirectory:
         if not isinstance(frame, dng.DngFrame):
             return frame
         stacker = getattr(self, "stack_algo", None)
+        if self.raw.ljpeg_split:
+            return dng.develop(frame, develop=self.raw.develop, lens=self.raw.lens, calibration=self.raw.calibration,
+                               corrections=self.raw.corrections, finish=self.raw.finish, split=self.raw.ljpeg_split,
+                               device=getattr(stacker, "device", getattr(self, "device", 0)))
         if self.raw.finish is not None:
             return dng.develop(frame, develop=self.raw.develop, lens=self.raw.lens, calibration=self.raw.calibration,
                                corrections=self.raw.corrections, finish=self.raw.finish,

@@ -37,6 +37,7 @@
 #include "kernels_finish.hpp"
 #include "kernels_jpeg.hpp"
 #include "kernels_jpeg_split.hpp"
+#include "kernels_ljpeg_split.hpp"
 
 using namespace mi;
 
@@ -2641,6 +2642,137 @@ int mi_jpeg_split_coefficients(int device, const void* host_span, size_t span_by
 int mi_jpeg_split_decode(int device, const void* host_span, size_t span_bytes, const uint32_t* offsets, const mi_jpeg_t* jpeg,
                          const mi_jpeg_split_t* opt, uint8_t* host_out, uint32_t* status_out) {
     return jpeg_split_host(device, host_span, span_bytes, offsets, jpeg, opt, nullptr, host_out, status_out);
+}
+
+// ---- the split path of the lossless-JPEG decoder (kernels_ljpeg_split.hpp): mi_raw_ljpeg's checks, and mi_jpeg_split_*'s for
+// `opt` and the scratch
+static int ljpeg_split_size_check(const mi_raw_layout_t* L) {
+    if ((uint64_t)unpack_nsegs(*L) * (uint64_t)L->seg_height * (uint64_t)L->seg_width >= (1ull << 32))
+        return fail(MI_ERR_INVALID, "layout segments x seg_height x seg_width must be below 2^32 for the split path");
+    return MI_OK;
+}
+static size_t ljpeg_split_bytes(const mi_raw_layout_t* L, size_t span_bytes, uint32_t sub, uint32_t rounds) {
+    return ljpeg::split_layout(*L, span_bytes, sub, rounds).words * sizeof(uint32_t);
+}
+
+int mi_ljpeg_split_scratch_bytes(const mi_raw_layout_t* layout, size_t span_bytes, const mi_jpeg_split_t* opt, size_t* bytes) {
+    static const uint16_t some = 0;     // (the layout's own checks: what stands for the buffers is not looked at)
+    int rc = raw_layout_check(&some, span_bytes, (const uint32_t*)&some, layout, &some, &some);
+    uint32_t sub, rounds;
+    if (rc || (rc = ljpeg_split_size_check(layout)) || (rc = jpeg_split_opt(opt, &sub, &rounds))) return rc;
+    if (!bytes) return fail(MI_ERR_INVALID, "null bytes");
+    *bytes = ljpeg_split_bytes(layout, span_bytes, sub, rounds);
+    return MI_OK;
+}
+
+// the checks of both device forms; `out`: the mosaic or the difference plane
+static int ljpeg_split_device_check(const void* dev_span, size_t span_bytes, const mi_ljpeg_seg_t* dev_segs, const mi_raw_layout_t* layout,
+                                    const uint16_t* dev_table, const mi_jpeg_split_t* opt, const void* dev_scratch, size_t scratch_bytes,
+                                    const void* out, const uint32_t* dev_status, uint32_t* sub, uint32_t* rounds) {
+    int rc = ljpeg_layout_check(dev_span, span_bytes, dev_segs, layout, dev_table, out);
+    if (rc || (rc = ljpeg_split_size_check(layout)) || (rc = jpeg_split_opt(opt, sub, rounds))) return rc;
+    if (!dev_scratch) return fail(MI_ERR_INVALID, "null scratch");
+    const size_t need = ljpeg_split_bytes(layout, span_bytes, *sub, *rounds);
+    if (scratch_bytes < need)
+        return fail(MI_ERR_INVALID, "scratch_bytes must be >= %llu (got %llu)", (unsigned long long)need, (unsigned long long)scratch_bytes);
+    if ((uintptr_t)dev_scratch & 255) return fail(MI_ERR_INVALID, "dev_scratch must be 256-byte aligned");
+    if ((uintptr_t)dev_span & 3) return fail(MI_ERR_INVALID, "dev_span must be 4-byte aligned");
+    if ((uintptr_t)dev_segs & 15) return fail(MI_ERR_INVALID, "dev_segs must be 16-byte aligned");
+    if ((uintptr_t)dev_status & 3) return fail(MI_ERR_INVALID, "dev_status must be 4-byte aligned");
+    return MI_OK;
+}
+
+// both device forms behind their checks; `rounds` as given (0: round 0 alone)
+static int ljpeg_split_run(int device, void* stream, const void* dev_span, size_t span_bytes, const mi_ljpeg_seg_t* dev_segs,
+                           const mi_raw_layout_t* layout, const uint16_t* dev_table, uint32_t sub, uint32_t rounds, void* dev_scratch,
+                           void* dev_out, uint16_t* dev_plane, uint32_t* dev_status) {
+    MI_HIP(hipSetDevice(device));
+    ljpeg_split_launch((hipStream_t)stream, dev_span, span_bytes, dev_segs, *layout, dev_table, sub, rounds, (uint32_t*)dev_scratch, dev_out,
+                       dev_plane, dev_status, nullptr);
+    MI_HIP(hipGetLastError());
+    return MI_OK;
+}
+
+int mi_raw_ljpeg_split_device(int device, void* stream, const void* dev_span, size_t span_bytes, const mi_ljpeg_seg_t* dev_segs,
+                              const mi_raw_layout_t* layout, const uint16_t* dev_table, const mi_jpeg_split_t* opt, void* dev_scratch,
+                              size_t scratch_bytes, void* dev_out, uint32_t* dev_status) {
+    uint32_t sub, rounds;
+    int rc = ljpeg_split_device_check(dev_span, span_bytes, dev_segs, layout, dev_table, opt, dev_scratch, scratch_bytes, dev_out, dev_status,
+                                      &sub, &rounds);
+    if (rc) return rc;
+    if ((uintptr_t)dev_out & (dtype_size(layout->dtype) - 1)) return fail(MI_ERR_INVALID, "dev_out must be aligned to its samples");
+    return ljpeg_split_run(device, stream, dev_span, span_bytes, dev_segs, layout, dev_table, sub, rounds, dev_scratch, dev_out, nullptr, dev_status);
+}
+
+int mi_ljpeg_split_differences_device(int device, void* stream, const void* dev_span, size_t span_bytes, const mi_ljpeg_seg_t* dev_segs,
+                                      const mi_raw_layout_t* layout, const mi_jpeg_split_t* opt, void* dev_scratch, size_t scratch_bytes,
+                                      uint16_t* dev_plane, uint32_t* dev_status) {
+    static const uint16_t no_table = 0;     // (the table is not applied to differences; the layout may name one)
+    uint32_t sub, rounds;
+    int rc = ljpeg_split_device_check(dev_span, span_bytes, dev_segs, layout, &no_table, opt, dev_scratch, scratch_bytes, dev_plane, dev_status,
+                                      &sub, &rounds);
+    if (rc) return rc;
+    if ((uintptr_t)dev_plane & 1) return fail(MI_ERR_INVALID, "dev_plane must be 2-byte aligned");
+    return ljpeg_split_run(device, stream, dev_span, span_bytes, dev_segs, layout, nullptr, sub, rounds, dev_scratch, nullptr, dev_plane, dev_status);
+}
+
+// both host forms: upload, run, look at the status words, run once more with the exact bound where they say the rounds were
+// too few, download.  max_rounds 0: the exact bound at once.
+static int ljpeg_split_host(int device, const void* host_span, size_t span_bytes, const mi_ljpeg_seg_t* segs, const mi_raw_layout_t* layout,
+                            const uint16_t* host_table, const mi_jpeg_split_t* opt, void* host_out, uint16_t* host_plane, uint32_t* status_out) {
+    static const uint16_t no_table = 0;
+    int rc = ljpeg_layout_check(host_span, span_bytes, segs, layout, host_out ? host_table : &no_table,
+                                host_out ? (const void*)host_out : (const void*)host_plane);
+    uint32_t sub, rounds;
+    if (rc || (rc = ljpeg_split_size_check(layout)) || (rc = jpeg_split_opt(opt, &sub, &rounds)) ||
+        (rc = ljpeg_segs_check(span_bytes, segs, layout)))
+        return rc;
+    if ((rc = open_device(device))) return rc;
+    const size_t nb = (size_t)layout->height * layout->width * dtype_size(layout->dtype);
+    const size_t nseg = (size_t)unpack_nsegs(*layout), ns = nseg * sizeof(uint32_t);
+    const size_t np = nseg * (size_t)layout->seg_height * layout->seg_width * sizeof(uint16_t);
+    const uint32_t exact = ljpeg::split_exact_rounds(segs, nseg, span_bytes, sub);
+    const uint32_t first = opt && opt->max_rounds ? opt->max_rounds : exact;
+    const size_t nscratch = ljpeg_split_bytes(layout, span_bytes, sub, 0xffffffffu);
+    DevScratch tmp(nullptr);
+    void *span = nullptr, *out = nullptr, *scratch = nullptr;
+    mi_ljpeg_seg_t* seg = nullptr;
+    uint16_t *table = nullptr, *plane = nullptr;
+    uint32_t* status = nullptr;
+    if ((rc = tmp.upload(&span, host_span, span_bytes)) || (rc = tmp.upload(&seg, segs, nseg * sizeof(mi_ljpeg_seg_t))) ||
+        (host_out && layout->table_len > 0 && (rc = tmp.upload(&table, host_table, (size_t)layout->table_len * sizeof(uint16_t)))) ||
+        (host_out && (rc = tmp.alloc(&out, nb))) || (host_plane && (rc = tmp.alloc(&plane, np))) || (rc = tmp.alloc(&scratch, nscratch)) ||
+        (rc = tmp.alloc(&status, ns)))
+        return rc;
+    std::vector<uint32_t> words(nseg);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if ((rc = ljpeg_split_run(device, nullptr, span, span_bytes, seg, layout, table, sub, attempt ? exact : first, scratch, out, plane, status)) ||
+            (rc = tmp.download(words.data(), status, ns)))
+            return rc;
+        bool unsynced = false;
+        for (uint32_t w : words) unsynced = unsynced || (w & MI_LJPEG_UNSYNCED);
+        if (!unsynced) break;
+    }
+    if (status_out) memcpy(status_out, words.data(), ns);
+    return host_out ? tmp.download(host_out, out, nb) : tmp.download(host_plane, plane, np);
+}
+
+int mi_raw_ljpeg_split(int device, const void* host_span, size_t span_bytes, const mi_ljpeg_seg_t* segs, const mi_raw_layout_t* layout,
+                       const uint16_t* host_table, const mi_jpeg_split_t* opt, void* host_out, uint32_t* status_out) {
+    return ljpeg_split_host(device, host_span, span_bytes, segs, layout, host_table, opt, host_out, nullptr, status_out);
+}
+
+int mi_ljpeg_split_differences(int device, const void* host_span, size_t span_bytes, const mi_ljpeg_seg_t* segs, const mi_raw_layout_t* layout,
+                               const mi_jpeg_split_t* opt, uint16_t* host_plane, uint32_t* status_out) {
+    return ljpeg_split_host(device, host_span, span_bytes, segs, layout, nullptr, opt, nullptr, host_plane, status_out);
+}
+
+int mi_stack_set_ljpeg_split(mi_stack_t* s, const mi_jpeg_split_t* opt) {
+    int rc = check_handle(s);
+    if (rc) return rc;
+    uint32_t sub = 0, rounds = 0;
+    if (opt && (rc = jpeg_split_opt(opt, &sub, &rounds))) return rc;
+    return mosaic_set_ljpeg_split(s, opt != nullptr, sub);
 }
 
 // the part of mi_stack_push_packed and mi_stack_push_ljpeg behind the span's checks

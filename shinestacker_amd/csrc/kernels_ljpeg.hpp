@@ -58,11 +58,13 @@
 // candidates are the dependent LDS byte reads of the refill (two per source byte, the second for the stuffing test), the
 // lookup and the difference arithmetic, all under a one-lane mask.  That the wave's part -- staging, prediction, stores -- is
 // small is arithmetic, not measurement: a few thousand wave instructions a tile against 65 536 serial walks.  The decode is 38
-// times the span's upload: a stack of compressed frames is bound by the decode, not by the link.  The step not built is decode
-// INSIDE a segment (self-synchronising sub-sequences: many lanes start at guessed bit positions and converge on the true
-// symbol boundaries), which would put the other 63 lanes on the walk.  A leaner walker (dword reads of the ring, the stuffing
-// removed by the wave after all, a wider lookup that also yields short differences) may be a cheaper step before it; which of
-// these pays is for a counter run to say.
+// times the span's upload: a stack of compressed frames is bound by the decode, not by the link.  Decode INSIDE a segment
+// (self-synchronising sub-sequences: many lanes start at guessed bit positions and converge on the true symbol boundaries) is
+// kernels_ljpeg_split.hpp, an option beside this kernel for segments of one and two components: measured there, 50 MP in
+// tiles 33.2 -> 16.1 ms, in strips of 64 rows 212 -> 54.0 ms, as one strip 18.9 s -> 0.26 s (docs/studies.md).  Three-component
+// streams (raw_ljpeg3 below) stay on this walker: the step deliberately left for later.  A leaner walker (dword reads of the
+// ring, the stuffing removed by the wave after all, a wider lookup that also yields short differences) is still not built;
+// whether it pays is for a counter run to say.
 #pragma once
 #include <type_traits>
 

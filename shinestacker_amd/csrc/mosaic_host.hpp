@@ -13,7 +13,8 @@
 //               mi_stack_wait_uploads); pageable ones go through a ring of pinned bounce buffers (PinRing, copy_rows).
 //   kernels     frame_kernels, on s->stream behind evCopied[slot], into frame `pending` of `bgr`: raw_unpack or raw_ljpeg
 //               (packed spans; the latter ORs every segment's status flags into `ljstatus`, which mi_stack_ljpeg_status reads
-//               and clears), the bad-site kernels and mosaic_site_correct (site corrections), calibration, the defect kernel,
+//               and clears; with mi_stack_set_ljpeg_split the split path's kernels stand in for raw_ljpeg and share ONE scratch
+//               of the stage, which is safe because all of them run here, in order), the bad-site kernels and mosaic_site_correct (site corrections), calibration, the defect kernel,
 //               the (developed) demosaic -- all but the last in place on slot[slot].  evSlotFree[slot] follows them, and the
 //               copy stream waits for it before it overwrites any of the slot's buffers.  The kernels are a twelfth of the
 //               copy's time; on the copy stream they would run in the low class behind another handle's level kernels and
@@ -43,6 +44,7 @@
 #include "kernels_demosaic.hpp"
 #include "kernels_linear.hpp"
 #include "kernels_ljpeg.hpp"
+#include "kernels_ljpeg_split.hpp"
 #include "kernels_sitecorr.hpp"
 #include "kernels_unpack.hpp"
 
@@ -120,6 +122,12 @@ struct MosaicStage {
     size_t meta_cap = 0;
     PinRing ppin;                             // bounce buffers of spans that are not pinned
     uint32_t* ljstatus = nullptr;             // lossless-JPEG spans: every frame's status flags ORed (in s->allocs)
+    // the split path (mi_stack_set_ljpeg_split): one scratch for every frame -- the decode kernels of all frames run in order on
+    // s->stream --, owned by the stage and grown on demand; lj_rounds is the frame's exact bound, from its host descriptors
+    bool lj_split = false;
+    uint32_t lj_sub = 0, lj_rounds = 0;
+    void* lj_scratch = nullptr;
+    size_t lj_scratch_cap = 0;
     // linear frames (mi_stack_push_linear): the unpacked H x W x spp samples; they belong to the stage and grow as pslot does
     void* lslot[NSLOT] = {};
     size_t lslot_cap = 0;
@@ -344,6 +352,7 @@ inline void mosaic_destroy(mi_stack* s) {
         if (m->pslot[i]) (void)hipFree(m->pslot[i]);
         if (m->lslot[i]) (void)hipFree(m->lslot[i]);
     }
+    if (m->lj_scratch) (void)hipFree(m->lj_scratch);    // (s->stream was waited for above: a split frame came as a packed span)
     for (int i = 0; i < MosaicStage::NUP; ++i)
         if (m->evUp[i]) (void)hipEventDestroy(m->evUp[i]);
     for (int i = 0; i < MosaicStage::NSLOT; ++i) {
@@ -492,6 +501,9 @@ inline void frame_kernels(hipStream_t st, const mi_stack* s, const MosaicFrame& 
         if (pk.ljseg3)
             ljpeg3_launch(st, ps, pk.span_bytes, (const mi_ljpeg_seg3_t*)(ps + at.seg_at), *pk.layout, (const uint16_t*)(ps + at.table_at), slot,
                           nullptr, m->ljstatus);
+        else if (pk.ljseg && m->lj_split)
+            ljpeg_split_launch(st, ps, pk.span_bytes, (const mi_ljpeg_seg_t*)(ps + at.seg_at), *pk.layout, (const uint16_t*)(ps + at.table_at),
+                               m->lj_sub, m->lj_rounds, (uint32_t*)m->lj_scratch, slot, nullptr, nullptr, m->ljstatus);
         else if (pk.ljseg)
             ljpeg_launch(st, ps, pk.span_bytes, (const mi_ljpeg_seg_t*)(ps + at.seg_at), *pk.layout, (const uint16_t*)(ps + at.table_at), slot,
                          nullptr, m->ljstatus);
@@ -536,6 +548,29 @@ inline int linear_reserve(mi_stack* s, int spp) {
     return set_realloc(m->lslot, nslot, &m->lslot_cap, need, false);
 }
 
+// the split path's scratch for this frame, and its exact round bound.  Growing waits for s->stream first: the decode kernels
+// of earlier frames, the scratch's only users, run there.
+inline int ljpeg_split_reserve(mi_stack* s, const PackedSrc& pk) {
+    MosaicStage* m = mstage(s);
+    uint64_t samples = (uint64_t)pk.nseg * (uint64_t)pk.layout->seg_height * (uint64_t)pk.layout->seg_width;
+    if (samples >= (1ull << 32)) return fail(MI_ERR_INVALID, "layout segments x seg_height x seg_width must be below 2^32 for the split path");
+    m->lj_rounds = ljpeg::split_exact_rounds(pk.ljseg, (size_t)pk.nseg, pk.span_bytes, m->lj_sub);
+    const size_t need = ljpeg::split_layout(*pk.layout, pk.span_bytes, m->lj_sub, m->lj_rounds).words * sizeof(uint32_t);
+    if (need <= m->lj_scratch_cap) return MI_OK;
+    MI_HIP(hipStreamSynchronize(s->stream));
+    return set_realloc(&m->lj_scratch, 1, &m->lj_scratch_cap, need, false);
+}
+
+// mi_stack_set_ljpeg_split behind its checks: holds until replaced or cleared
+inline int mosaic_set_ljpeg_split(mi_stack* s, bool on, uint32_t sub) {
+    int rc;
+    if (!on && !mstage(s)) return MI_OK;
+    if (!mstage(s) && (rc = mosaic_create(s))) return rc;
+    mstage(s)->lj_split = on;
+    mstage(s)->lj_sub = sub;
+    return MI_OK;
+}
+
 // One raw host frame: stage it, start its upload and its kernels, return.
 inline int mosaic_push(mi_stack* s, const MosaicFrame& f) {
     TiledState* t = tstate(s);
@@ -554,6 +589,7 @@ inline int mosaic_push(mi_stack* s, const MosaicFrame& f) {
         if ((rc = dev_alloc(s, (void**)&m->ljstatus, sizeof(uint32_t)))) return rc;
         MI_HIP(hipMemsetAsync(m->ljstatus, 0, sizeof(uint32_t), s->stream));
     }
+    if (pk && pk->ljseg && m->lj_split && (rc = ljpeg_split_reserve(s, *pk))) return rc;
     if (s->p.impl != MI_IMPL_TILED) {
         // float-64 and MI_IMPL_SIMPLE handles: upload, kernels, push, wait -- one frame at a time on the handle's stream
         char* ps = (char*)m->pslot[0];

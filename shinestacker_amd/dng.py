@@ -253,12 +253,17 @@ class Raw:
                  the site corrections, crop and orientation are the last stage: the stack, its depth map and everything
                  derived from them come out in the finished geometry.
 
+    ljpeg_split  False: lossless-JPEG files are decoded one segment a wavefront (raw_ljpeg); True, or {"sub_bytes": ...,
+                 "max_rounds": ...}: by the split path, which decodes inside a segment (csrc/kernels_ljpeg_split.hpp) -- the
+                 same samples, sooner for files in long strips or one strip.  Three-sample LinearRaw files keep going to
+                 raw_ljpeg3, silently: the same result.
+
     LinearRaw files of a folder take the same options where they mean something (develop, lens, finish); `calibration`, a
     `develop` with defect sites and a SiteCorrections object are per CFA site and raise InvalidOptionError at such a file
     (`check_linear_options`), "auto" records what the file carries as skipped.
     """
 
-    def __init__(self, develop="auto", lens="auto", calibration=None, corrections=None, finish=None):
+    def __init__(self, develop="auto", lens="auto", calibration=None, corrections=None, finish=None, ljpeg_split=False):
         from .demosaic import check_calibration, check_develop
         from .lens import check_lens
         if not (isinstance(develop, str) and develop == "auto") and develop is not None:
@@ -271,11 +276,17 @@ class Raw:
             check_corrections(corrections)
         if not (isinstance(finish, str) and finish == "auto") and finish is not None:
             check_finish(finish)
+        try:
+            _lib.ljpeg_split_options(ljpeg_split)
+        except (TypeError, ValueError) as e:
+            raise InvalidOptionError("ljpeg_split", ljpeg_split, str(e))
         self.develop, self.lens, self.calibration, self.corrections, self.finish = develop, lens, calibration, corrections, finish
+        self.ljpeg_split = ljpeg_split if ljpeg_split else False
 
     def __repr__(self):
         tail = "" if self.corrections is None else f", corrections={self.corrections!r}"
         tail += "" if self.finish is None else f", finish={self.finish!r}"
+        tail += "" if not self.ljpeg_split else f", ljpeg_split={self.ljpeg_split!r}"
         return f"Raw(develop={self.develop!r}, lens={self.lens!r}, calibration={self.calibration!r}{tail})"
 
     def corrections_for(self, frame):
@@ -1538,8 +1549,10 @@ def check_linear_options(frame, calibration=None, corrections=None, develop=None
     return fin
 
 
-def unpack(frame, device=0, corrections=None, finish=None):
+def unpack(frame, device=0, corrections=None, finish=None, split=False):
     """The cropped H x W mosaic of a DngFrame as a NumPy array of its dtype: span up, raw_unpack or raw_ljpeg, mosaic down.
+    `split`: False, True or {"sub_bytes": ..., "max_rounds": ...} -- a lossless-JPEG frame of one or two components is decoded
+    by the split path (csrc/kernels_ljpeg_split.hpp: the same samples); anything else ignores it.
     A lossless-JPEG frame one of whose streams did not decode raises ImageLoadError.  `corrections`: None, "auto" (the
     frame's own) or a SiteCorrections, applied to the unpacked mosaic (demosaic.correct_sites).  `finish`: None, "auto" or
     a Finish -- its VIGNETTE only, behind the corrections (demosaic.radial_gain; no lens follows here: the table is the
@@ -1549,19 +1562,44 @@ def unpack(frame, device=0, corrections=None, finish=None):
     if _check_frame(frame).linear is not None:
         check_linear_options(frame, corrections=corrections, finish=finish)
         h, w = frame.shape
-        return _unpack_plane(frame, device).reshape((h, w, 3) if frame.layout.spp == 3 else (h, w))
+        return _unpack_plane(frame, device, split).reshape((h, w, 3) if frame.layout.spp == 3 else (h, w))
     fin = resolve_finish(_check_frame(frame), finish)
     if fin is not None and fin.vignette is not None:
         from .demosaic import radial_gain
-        return radial_gain(unpack(frame, device, corrections), frame.cfa, fin.vignette, device=device)
+        return radial_gain(unpack(frame, device, corrections, split=split), frame.cfa, fin.vignette, device=device)
     sc = resolve_corrections(_check_frame(frame), corrections)
     if sc is not None:
         from .demosaic import correct_sites
-        return correct_sites(unpack(frame, device), frame.cfa, sc, device=device)
-    return _unpack_plane(frame, device)
+        return correct_sites(unpack(frame, device, split=split), frame.cfa, sc, device=device)
+    return _unpack_plane(frame, device, split)
 
 
-def _unpack_plane(frame, device):
+def takes_split(layout, split):
+    """whether `split` sends this layout through the split path: lossless JPEG of one or two components"""
+    return bool(split) and layout.compression == 7 and layout.spp != 3
+
+
+def split_options(layout, span_bytes, split):
+    """(the JpegSplitStruct a device form is called with, the scratch bytes it needs) for a layout whose descriptors lie in
+    host memory too: max_rounds 0 becomes the exact bound -- the largest number of workgroups of 256 subsequences any one
+    segment's lanes touch, minus 1 -- so that the device form never leaves a segment unsynced"""
+    opt = _lib.ljpeg_split_options(split)
+    opt = _lib.JpegSplitStruct(opt.sub_bytes, opt.max_rounds)
+    if opt.max_rounds == 0:
+        sub = opt.sub_bytes or 128
+        off = layout.segments["scan_off"].astype(np.int64)
+        length = np.clip(np.minimum(layout.segments["scan_bytes"].astype(np.int64), int(span_bytes) - off), 0, None)
+        lanes = np.maximum(1, -(-length // sub))
+        last = np.cumsum(lanes) - 1
+        first = last - lanes + 1
+        opt.max_rounds = int((last // 256 - first // 256).max())      # (0 asks for the default: rounds not needed return at once)
+    nbytes = _lib.C.c_size_t(0)
+    L = layout.struct()
+    _lib.check(_lib.load().mi_ljpeg_split_scratch_bytes(_lib.C.byref(L), int(span_bytes), _lib.C.byref(opt), _lib.C.byref(nbytes)))
+    return opt, int(nbytes.value)
+
+
+def _unpack_plane(frame, device, split=False):
     """layout.height x layout.width samples of the frame's span (a mosaic; of a LinearRaw frame the H x (W spp) samples)"""
     lay = _check_frame(frame).layout
     _lib.require_device()
@@ -1570,6 +1608,13 @@ def _unpack_plane(frame, device):
     span = host_span(frame)
     if lay.compression == 7:
         status = np.zeros(len(lay.segments), np.uint32)
+        if takes_split(lay, split):
+            opt = _lib.ljpeg_split_options(split)
+            _lib.check(_lib.load().mi_raw_ljpeg_split(device, span.ctypes.data, span.nbytes, lay.segments.ctypes.data, _lib.C.byref(L),
+                                                      None if lay.table is None else lay.table.ctypes.data, _lib.C.byref(opt),
+                                                      out.ctypes.data, status.ctypes.data))
+            check_ljpeg_status(frame.path, status)
+            return out
         entry = _lib.load().mi_raw_ljpeg3 if lay.spp == 3 else _lib.load().mi_raw_ljpeg
         _lib.check(entry(device, span.ctypes.data, span.nbytes, lay.segments.ctypes.data, _lib.C.byref(L),
                                             None if lay.table is None else lay.table.ctypes.data, out.ctypes.data, status.ctypes.data))
@@ -1590,13 +1635,23 @@ def check_ljpeg_status(path, status):
         raise ImageLoadError(path, f"lossless JPEG: {where} did not decode (status {int(status[k])}: {_lib.ljpeg_flag_text(int(status[k]))})")
 
 
-def unpack_device(layout, dev_span, span_bytes, dev_offsets, dev_table, dev_out, device=0, stream=None, dev_status=None):
+def unpack_device(layout, dev_span, span_bytes, dev_offsets, dev_table, dev_out, device=0, stream=None, dev_status=None, split=False,
+                  dev_scratch=None):
     """raw_unpack on buffers resident in HBM: the span (`span_bytes` of it, 4-byte aligned), the uint32 segment offsets, the
     uint16 table (or None) -> `dev_out`, layout.height x layout.width samples.  Queued on `stream`, not waited for.  A
     lossless-JPEG layout: `dev_offsets` holds its descriptors (layout.segments, 16-byte aligned) and raw_ljpeg runs, which
-    leaves one status word per segment at `dev_status` (or None)."""
+    leaves one status word per segment at `dev_status` (or None).  `split` (False, True or a dict, as `unpack` takes it) sends
+    a lossless-JPEG layout of one or two components through the split path: `dev_scratch` is then a _lib.DeviceBuffer of at
+    least split_options(layout, span_bytes, split)[1] bytes, which the queued kernels use until they are through."""
     _lib.require_device()
     L = layout.struct()
+    if takes_split(layout, split):
+        opt, need = split_options(layout, span_bytes, split)
+        if dev_scratch is None or dev_scratch.nbytes < need:
+            raise InvalidOptionError("dev_scratch", dev_scratch, f"the split path needs a DeviceBuffer of at least {need} bytes")
+        _lib.check(_lib.load().mi_raw_ljpeg_split_device(device, stream, dev_span, int(span_bytes), dev_offsets, _lib.C.byref(L), dev_table,
+                                                         _lib.C.byref(opt), dev_scratch.ptr, dev_scratch.nbytes, dev_out, dev_status))
+        return
     if layout.compression == 7:     # (three samples per pixel: mi_ljpeg_seg3_t descriptors and raw_ljpeg3)
         entry = _lib.load().mi_raw_ljpeg3_device if layout.spp == 3 else _lib.load().mi_raw_ljpeg_device
         _lib.check(entry(device, stream, dev_span, int(span_bytes), dev_offsets, _lib.C.byref(L), dev_table, dev_out, dev_status))
@@ -1605,10 +1660,13 @@ def unpack_device(layout, dev_span, span_bytes, dev_offsets, dev_table, dev_out,
 
 
 class _Staged:
-    """a frame's span, offsets (or lossless-JPEG descriptors and status words) and table in one device buffer"""
+    """a frame's span, offsets (or lossless-JPEG descriptors and status words) and table in one device buffer; with `split`
+    (as `unpack` takes it) the split path's scratch too, in a buffer of its own (`free` releases both)"""
 
-    def __init__(self, frame, device):
+    def __init__(self, frame, device, split=False):
         lay = frame.layout
+        self.split = split if takes_split(lay, split) else False
+        self.scratch = None
         segs = lay.segments if lay.compression == 7 else lay.offsets
         self.path, self.nseg = frame.path, len(segs)
         self.seg_at = (frame.span.nbytes + 255) & ~255
@@ -1622,8 +1680,24 @@ class _Staged:
             self.buf.upload(lay.table, self.table_at)
         self.span_bytes = frame.span.nbytes
         self.table = None if lay.table is None else self.buf.ptr + self.table_at
+        if self.split:
+            try:
+                self.scratch = _lib.DeviceBuffer(split_options(lay, self.span_bytes, self.split)[1], device)
+            except Exception:
+                self.buf.free()
+                raise
+            span_free = self.buf.free
+
+            def free():         # (callers release `buf`: the scratch goes with it)
+                span_free()
+                self.scratch.free()
+            self.buf.free = free
 
     def unpack_into(self, layout, dev_out, device, stream=None):
+        if self.split:
+            unpack_device(layout, self.buf.ptr, self.span_bytes, self.buf.ptr + self.seg_at, self.table, dev_out, device, stream, self.status,
+                          split=self.split, dev_scratch=self.scratch)
+            return
         unpack_device(layout, self.buf.ptr, self.span_bytes, self.buf.ptr + self.seg_at, self.table, dev_out, device, stream, self.status)
 
     def check_status(self):
@@ -1650,12 +1724,16 @@ def _resolve(frame, develop, lens):
     return develop, lens
 
 
-def develop(frame, develop="auto", lens="auto", calibration=None, device=0, corrections=None, finish=None):
+def develop(frame, develop="auto", lens="auto", calibration=None, device=0, corrections=None, finish=None, split=False):
     """A DngFrame -> H x W x 3 BGR of its dtype: unpack, then `debayer` with the frame's own Cfa.  `develop`, `lens`: "auto"
     takes frame.develop / frame.lens, None switches the step off, an object overrides it.  `calibration`: a
     demosaic.Calibration applied to the unpacked mosaic first.  `corrections`: None, "auto" or a SiteCorrections -- the
     file's site corrections, ahead of the calibration.  `finish`: None, "auto" or a Finish -- the vignette gain behind the
-    corrections, crop and orientation last: the result is then H' x W' x 3 (`DngFrame.finished_shape`)."""
+    corrections, crop and orientation last: the result is then H' x W' x 3 (`DngFrame.finished_shape`).  `split`: as `unpack`
+    takes it."""
+    if split:
+        mosaic = unpack(_check_frame(frame), device, split=split)
+        return _develop_unpacked(frame, mosaic, develop, lens, calibration, device, corrections, finish)
     dev, ln = _resolve(_check_frame(frame), develop, lens)
     if frame.linear is not None:    # no mosaic: the samples straight into linear_develop; crop and orientation apply
         fin = check_linear_options(frame, calibration, corrections, dev, finish)
@@ -1674,13 +1752,32 @@ def develop(frame, develop="auto", lens="auto", calibration=None, device=0, corr
     return debayer(unpack(frame, device), frame.cfa, develop=dev, device=device, calibration=calibration, lens=ln)
 
 
-def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None, device=0, corrections=None, finish=None):
+def _develop_unpacked(frame, mosaic, develop, lens, calibration, device, corrections, finish):
+    """`develop` behind the unpack: `mosaic` is what unpack(frame, device) returns, decoded by whichever path"""
+    dev, ln = _resolve(frame, develop, lens)
+    if frame.linear is not None:
+        fin = check_linear_options(frame, calibration, corrections, dev, finish)
+        return develop_linear(mosaic, frame.linear, develop=dev, lens=ln, finish=fin, device=device)
+    sc = resolve_corrections(frame, corrections)
+    fin = resolve_finish(frame, finish)
+    if fin is not None:
+        try:
+            return debayer(mosaic, frame.cfa, develop=dev, device=device, calibration=calibration, lens=ln, corrections=sc, finish=fin)
+        finally:
+            if fin is frame.finish:
+                fin.close()
+    if sc is not None:
+        return debayer(mosaic, frame.cfa, develop=dev, device=device, calibration=calibration, lens=ln, corrections=sc)
+    return debayer(mosaic, frame.cfa, develop=dev, device=device, calibration=calibration, lens=ln)
+
+
+def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None, device=0, corrections=None, finish=None, split=False):
     """Read the n DNG files (equal cropped shape and dtype), upload their spans and unpack and demosaic them side by side
     into `dev_out` (device pointer, n x H x W x 3 of their dtype): exactly what pipeline.align_and_stack_device(dev_frames,
     ...) takes, as demosaic.debayer_frames_device does for mosaics.  Waits for the device.  Returns (H, W, dtype).
     `corrections`: None, "auto" (each file's own) or a SiteCorrections, applied in place behind the unpack.
     `finish`: None, "auto" (each file's own) or a Finish: the frames in `dev_out` are then n x H' x W' x 3, the finished
-    shape, which every file must share, and (H', W', dtype) is returned."""
+    shape, which every file must share, and (H', W', dtype) is returned.  `split`: as `unpack` takes it."""
     if len(paths) == 0:
         raise ValueError("no files")
     _lib.require_device()
@@ -1716,7 +1813,7 @@ def frames_device(paths, dev_out, develop="auto", lens="auto", calibration=None,
                 out_bytes = out_shape[0] * out_shape[1] * 3 * frame.dtype.itemsize
                 if fin is not None and fscratch is None:
                     fscratch = _lib.DeviceBuffer(frame_bytes, device)
-            up = _Staged(frame, device)
+            up = _Staged(frame, device, split) if split else _Staged(frame, device)
             try:
                 up.unpack_into(frame.layout, stage.ptr, device)
                 sc = None if frame.linear is not None else resolve_corrections(frame, corrections)

@@ -471,6 +471,8 @@ class PyramidStack(BaseStackAlgo):
         A finish (dng.Finish: vignette, crop, orientation) takes the same route: unpack, debayer, [lens], finish, push -- the
         handle was created with the finished shape."""
         raw = self.raw
+        if raw.ljpeg_split:     # (the handle holds it: set again for every file, which costs nothing)
+            stack.set_ljpeg_split(raw.ljpeg_split)
         dev, ln = raw.develop_for(frame), raw.lens_for(frame)
         if dev is not None and dev is frame.develop:     # files of one camera share one Develop: one tone table on the device
             dev = self._raw_develops.setdefault(dev.matrix_q, dev)
@@ -489,7 +491,7 @@ class PyramidStack(BaseStackAlgo):
         from .dng import _Staged
         h, w = frame.shape
         nb = h * w * frame.dtype.itemsize
-        up = _Staged(frame, self.device)
+        up = _Staged(frame, self.device, raw.ljpeg_split) if raw.ljpeg_split else _Staged(frame, self.device)
         mosaic, bgr, scratch = (_lib.DeviceBuffer(nb, self.device), _lib.DeviceBuffer(3 * nb, self.device),
                                 _lib.DeviceBuffer(3 * nb, self.device))
         fscratch = None if fin is None else _lib.DeviceBuffer(3 * nb, self.device)
@@ -533,7 +535,7 @@ class PyramidStack(BaseStackAlgo):
         nb = h * w * frame.dtype.itemsize
         up, bufs = None, []
         try:
-            up = _Staged(frame, self.device)
+            up = _Staged(frame, self.device, raw.ljpeg_split) if raw.ljpeg_split else _Staged(frame, self.device)
             bufs += [_lib.DeviceBuffer(frame.layout.spp * nb, self.device), _lib.DeviceBuffer(3 * nb, self.device)]
             bufs += [_lib.DeviceBuffer(3 * nb, self.device) for opt in (ln, fin) if opt is not None]
             up.unpack_into(frame.layout, bufs[0].ptr, self.device)

@@ -38,6 +38,8 @@ def two_stage(args):
     `--ljpeg` (with `--mosaic --packed BITS`): stage 1 a further time from the same samples as lossless-JPEG spans
     (`mi_stack_push_ljpeg`: 256 x 256 tiles, two components, predictor 1, written by tools/ljpeg_encode.py; decoded on the device
     by raw_ljpeg), in turns with the packed and the mosaic runs; the handles' decode status is asserted to be 0.
+    `--split` (with `--ljpeg`): the compressed stage 1 once more with the split path set on the handles (decode inside a
+    segment), in turns with the serial kernel on the same spans.
     `--sitecorr` (with `--mosaic --packed BITS`): the packed stage 1 with site corrections (dng.SiteCorrections: black deltas
     and four 17 x 13 gain maps) set on every stage-1 handle, in turns with the packed run without them.
     `--calibrate` (with `--mosaic`): stage 1 from the mosaics with a `Calibration` (a master dark and a master flat; the gain
@@ -282,6 +284,27 @@ def two_stage(args):
                 for s_ in stacks:
                     s_.sync()
                     assert s_.ljpeg_status() == 0
+                if args.split:
+                    # the compressed run once more with the split path set on every stage-1 handle (decode inside a segment,
+                    # kernels_ljpeg_split.hpp), in turns with the serial kernel on the same spans
+                    def run_split():
+                        for s_ in stacks:
+                            s_.set_ljpeg_split(True)
+                        try:
+                            return run_ljpeg()
+                        finally:
+                            for s_ in stacks:
+                                s_.set_ljpeg_split(False)
+                    run_split()
+                    with_sp, with_l2 = [], []
+                    for _ in range(3):
+                        with_sp.append(run_split())
+                        with_l2.append(run_ljpeg())
+                    for s_ in stacks:
+                        s_.sync()
+                        assert s_.ljpeg_status() == 0
+                    developed.update({"ljpeg_split_stage1_seconds": with_sp, "ljpeg_stage1_seconds_in_turns_with_split": with_l2,
+                                      "ljpeg_split_over_ljpeg_stage1": float(np.median(with_sp) / np.median(with_l2))})
                 developed.update({"ljpeg_stage1_seconds": with_l, "packed_stage1_seconds_in_turns": with_p2,
                                   "mosaic_stage1_seconds_in_turns_with_ljpeg": without2,
                                   "ljpeg_over_packed_stage1": float(np.median(with_l) / np.median(with_p2)),
@@ -336,6 +359,9 @@ def main():
                          "device), in turns with the mosaic run on the same samples")
     ap.add_argument("--ljpeg", action="store_true",
                     help="with --two-stage --mosaic --packed BITS: stage 1 from lossless-JPEG spans of the same samples as well")
+    ap.add_argument("--split", action="store_true",
+                    help="with --two-stage --mosaic --packed BITS --ljpeg: the compressed stage 1 once more through the split path "
+                         "(Stack.set_ljpeg_split), in turns with the serial kernel")
     ap.add_argument("--pageable", action="store_true", help="host frames in ordinary (pageable) memory: the bounce-copy path")
     args = ap.parse_args()
     if args.two_stage:
