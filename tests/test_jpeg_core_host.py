@@ -2,7 +2,9 @@
 decoder that meet untrusted bytes -- compiled for the host into tools/jpeg_core_check.cpp with the address and
 undefined-behaviour sanitizers and run, as a child process, over every stream of the case table, short ones included, and
 over seeded corruptions of them: it prints what tests/jpeg_restatement.py computes, status words and coefficients, and the
-sanitizers stay silent.  The sanitizer runtimes are linked statically, so the program does not care what else the process
+sanitizers stay silent.  The same on the corpus of tests/jpeg_mutants.py: every distinct accepted mutant that jpeg.read takes
+with its restart intervals (some 4 000: changed tables, sizes, quantisation selectors, DRI values and restart layouts among
+them, before any of them is given to the GPU).  The sanitizer runtimes are linked statically, so the program does not care what else the process
 loads and the child inherits the environment as it is.  Where no compiler links them the program is built plain."""
 import os
 import shutil
@@ -111,3 +113,32 @@ def test_the_core_equals_the_restatement_on_every_stream(program, tmp_path):
         for s in want[:len(h["offsets"]) - 1]:
             flags |= s
     assert flags == R.NOCODE | R.OVERRUN | R.RUN
+
+
+def test_the_core_equals_the_restatement_on_the_mutants(program, tmp_path):
+    """every distinct (headers, scan bytes) of the corpus that jpeg.read accepts at split=None, of at most
+    jpeg_mutants.MAX_SAMPLES samples: status words and every coefficient, flagged intervals included"""
+    import jpeg_mutants as M
+    exe, sanitized = program
+    print("sanitizers:", sanitized)
+    todo = {}
+    for o in M.outcomes():
+        if o.serial and o.restate:
+            todo.setdefault(o.key(), o)
+    todo = list(todo.values())
+    assert len(todo) >= 3000
+    dump = tmp_path / "mutants.txt"
+    dump.write_text("\n".join(_record(o.data, M.restated(o).h) for o in todo) + "\n")
+    res = subprocess.run([exe, str(dump)], capture_output=True, text=True, timeout=900)
+    assert res.returncode == 0, (sanitized, res.stderr[-3000:])
+    assert res.stderr == "", res.stderr[-3000:]
+    got = res.stdout.splitlines()
+    assert len(got) == len(todo)
+    flags, flagged = 0, 0
+    for line, o in zip(got, todo):
+        planes, status = M.restated(o).serial
+        want = " ".join(map(str, status.tolist() + np.concatenate([p.reshape(-1) for p in planes]).tolist()))
+        assert " ".join(line.split()) == want, o.recipe
+        flags |= int(np.bitwise_or.reduce(status))
+        flagged += bool(status.any())
+    assert flags == R.NOCODE | R.OVERRUN | R.RUN and flagged >= 1500, (flags, flagged)

@@ -3,7 +3,8 @@ meet untrusted bytes -- compiled for the host into tools/jpeg_split_check.cpp wi
 sanitizers and run, as a child process, over every stream of tests/jpeg_split_cases.py, short ones included, and over
 seeded corruptions of them, the lanes emulated one after the other as kernels_jpeg_split.hpp runs them: it prints what
 tests/jpeg_split_restatement.py computes -- status words, coefficients, and every subsequence's exit from its cold state and
-from its true entry -- and the sanitizers stay silent.  The sanitizer runtimes are linked statically, so the program does not
+from its true entry -- and the sanitizers stay silent.  The same on the corpus of tests/jpeg_mutants.py: every distinct accepted
+mutant, files with and without restart intervals, before any of them is given to the GPU.  The sanitizer runtimes are linked statically, so the program does not
 care what else the process loads and the child inherits the environment as it is.  Where no compiler links them the program
 is built plain."""
 import os
@@ -137,3 +138,46 @@ def test_the_core_equals_the_restatement_on_every_stream(program, tmp_path, sub)
             flags |= s
     assert flags == S.NOCODE | S.OVERRUN | S.RUN and compared_cold > len(streams)
     assert differ > 0 or sub == 128
+
+
+LANES_EVERY = 1         # of the mutants, every how-manieth has its subsequences' exits restated and compared as well
+
+
+@pytest.mark.parametrize("sub", [8, 16, 128])
+def test_the_core_equals_the_restatement_on_the_mutants(program, tmp_path, sub):
+    """every distinct (headers, scan bytes) of the corpus that jpeg.read accepts, of at most jpeg_mutants.MAX_SAMPLES samples:
+    status words, every coefficient and every subsequence's two exits, flagged intervals included"""
+    import jpeg_mutants as M
+    exe, sanitized = program
+    print("sanitizers:", sanitized)
+    todo = {}
+    for o in M.outcomes():
+        if o.accepted and o.restate:
+            todo.setdefault(o.key(), o)
+    todo = list(todo.values())
+    assert len(todo) >= 6000
+    dump = tmp_path / "mutants.txt"
+    dump.write_text("\n".join(_record(o.data, M.restated(o).h) for o in todo) + "\n")
+    res = subprocess.run([exe, str(dump), str(sub)], capture_output=True, text=True, timeout=1800)
+    assert res.returncode == 0, (sanitized, res.stderr[-3000:])
+    assert res.stderr == "", res.stderr[-3000:]
+    got = res.stdout.split("\n")
+    assert len(got) == 2 * len(todo) + 1
+    flags, flagged, compared = 0, 0, 0
+    for i, o in enumerate(todo):
+        r = M.restated(o)
+        planes, status = r.split
+        want = " ".join(map(str, status.tolist() + np.concatenate([p.reshape(-1) for p in planes]).tolist()))
+        assert " ".join(got[2 * i].split()) == want, o.recipe
+        flags |= int(np.bitwise_or.reduce(status))
+        flagged += bool(status.any())
+        if i % LANES_EVERY == 0:
+            words = list(map(int, got[2 * i + 1].split()))
+            lanes = S.lanes_of(o.data, r.h, sub)
+            assert len(words) == 4 * len(lanes), o.recipe
+            for j, ((iv, lo, hi, last), (cold, true)) in enumerate(zip(lanes, S.exits(o.data, r.h, sub))):
+                assert words[4 * j + 2:4 * j + 4] == _packed(*true), (o.recipe, j)
+                if lo <= iv.end:
+                    assert words[4 * j:4 * j + 2] == _packed(*cold), (o.recipe, j)
+                    compared += 1
+    assert flags == S.NOCODE | S.OVERRUN | S.RUN and flagged >= 2500 and compared > len(todo) // LANES_EVERY, (flags, flagged, compared)

@@ -3,7 +3,10 @@ that meet untrusted bytes -- compiled for the host into tools/ljpeg_split_check.
 sanitizers and run, as a child process, over every segment of tests/ljpeg_split_cases.py, short streams included, and over
 seeded corruptions of them, the lanes emulated one after the other as kernels_ljpeg_split.hpp runs them: it prints what
 tests/ljpeg_split_restatement.py computes -- the status word, the differences, and every subsequence's exit from its cold state
-and from its true entry -- and the sanitizers stay silent.  The sanitizer runtimes are linked statically, so the program does
+and from its true entry -- and the sanitizers stay silent.  The same on the corrupt files of tests/dng_mutants.py: every segment
+of every one- and two-component mutant that dng.read accepts (changed precisions, predictors and DHT counts, `dht-move`,
+markers in the middle of a tile, data that ends early, spans declared short), which until now reached the serial core only.
+The sanitizer runtimes are linked statically, so the program does
 not care what else the process loads and the child inherits the environment as it is.  Where no compiler links them the
 program is built plain."""
 import os
@@ -112,3 +115,53 @@ def test_the_core_equals_the_restatement_on_every_segment(program, segments, tmp
         flags |= status
     assert flags == S.NOCODE | S.OVERRUN
     assert differ > 0
+
+
+@pytest.mark.parametrize("sub", [8, 128])
+def test_the_core_equals_the_restatement_on_the_mutants(program, tmp_path, sub):
+    """The corrupt files of tests/dng_mutants.py, deduplicated as test_ljpeg_core_host.py does it: every segment of every one- and
+    two-component mutant that dng.read accepts, of every restated base, whose descriptors or span differ from the base's, the
+    data as the descriptor states it; a frame once per dng_mutants key, a segment once per record.  The status word, every
+    difference and every subsequence's two exits equal the restatement's, and the sanitizers stay silent."""
+    import dng_mutants as M
+    exe, sanitized = program
+    print("sanitizers:", sanitized)
+    frames, records, todo = set(), set(), []
+    with M._no_collection():
+        for o in M.outcomes():
+            if not o.accepted or not o.base.restate:
+                continue
+            lay = o.frame.layout
+            if lay.compression != 7 or lay.spp == 3 or not M.changed(o) or o.key() in frames:
+                continue
+            frames.add(o.key())
+            for k, seg in enumerate(S.segments_of(o.frame.span, lay)):
+                record = _record(seg, lay.segments[k])
+                if record not in records:
+                    records.add(record)
+                    todo.append((o.recipe, k, seg, record))
+    print(f"{len(frames)} accepted frames, {len(todo)} distinct segments")
+    assert len(frames) >= 3000, len(frames)
+    dump = tmp_path / "mutants.txt"
+    dump.write_text("\n".join(t[3] for t in todo) + "\n")
+    res = subprocess.run([exe, str(dump), str(sub)], capture_output=True, text=True, timeout=1800)
+    assert res.returncode == 0, (sanitized, res.stderr[-3000:])
+    assert res.stderr == "", res.stderr[-3000:]
+    got = res.stdout.split("\n")
+    assert len(got) == 2 * len(todo) + 1
+    flagged = {S.NOCODE: 0, S.OVERRUN: 0}
+    for i, (recipe, k, seg, _) in enumerate(todo):
+        diff, status = S.differences(seg)
+        first = np.array(got[2 * i].split(), np.int64)
+        assert first[0] == status, (recipe, k)
+        assert np.array_equal(first[1:], diff.reshape(-1)), (recipe, k)
+        words = list(map(int, got[2 * i + 1].split()))
+        lanes = S.exits([seg], sub)
+        assert len(words) == 4 * len(lanes), (recipe, k)
+        for j, (cold, true) in enumerate(lanes):
+            assert words[4 * j + 2:4 * j + 4] == _packed(*true), (recipe, k, j)
+            if j * sub <= seg.data.end:
+                assert words[4 * j:4 * j + 2] == _packed(*cold), (recipe, k, j)
+        for bit in flagged:
+            flagged[bit] += bool(status & bit)
+    assert min(flagged.values()) >= 300, flagged
