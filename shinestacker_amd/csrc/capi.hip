@@ -2532,8 +2532,8 @@ int mi_jpeg_decode(int device, const void* host_span, size_t span_bytes, const u
 
 // ---- the split entropy decoder (kernels_jpeg_split.hpp): the same checks, an interval of any length
 static int jpeg_split_opt(const mi_jpeg_split_t* opt, uint32_t* sub, uint32_t* rounds) {
-    *sub = opt && opt->sub_bytes ? opt->sub_bytes : jpeg::SPLIT_SUB_DEFAULT;
-    *rounds = opt && opt->max_rounds ? opt->max_rounds : jpeg::SPLIT_ROUNDS_DEFAULT;
+    *sub = opt && opt->sub_bytes ? opt->sub_bytes : split::SUB_DEFAULT;
+    *rounds = opt && opt->max_rounds ? opt->max_rounds : split::ROUNDS_DEFAULT;
     if (*sub != 8 && *sub != 16 && *sub != 32 && *sub != 64 && *sub != 128)
         return fail(MI_ERR_INVALID, "split sub_bytes must be 0, 8, 16, 32, 64 or 128 (got %u)", *sub);
     return MI_OK;

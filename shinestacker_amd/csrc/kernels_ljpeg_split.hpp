@@ -1,13 +1,11 @@
 // kernels_ljpeg_split.hpp -- the second entropy path of the lossless-JPEG decoder: a segment (mi_ljpeg_seg_t: one or two
 // components, every predictor, every precision) of ANY length, a file written as one strip included, decoded on many lanes at
-// once and exactly.  ljpeg_sync_core.hpp has the transition, jpeg_sync_core.hpp the scheme's reasoning; the definition is
-// tests/ljpeg_split_restatement.py, held bit for bit.  Tables, descriptors, layout, crop, linearisation table, shift and
-// output are exactly raw_ljpeg's (kernels_ljpeg.hpp), and so is the result.  No reference counterpart.
+// once and exactly.  ljpeg_sync_core.hpp has the transition, kernels_split_common.hpp the lanes, the bytes, the rounds and the
+// frame of the write pass; the definition is tests/ljpeg_split_restatement.py, held bit for bit.  Tables, descriptors, layout,
+// crop, linearisation table, shift and output are exactly raw_ljpeg's (kernels_ljpeg.hpp), and so is the result.  No reference
+// counterpart.  The scaffold's units are the segments.
 //
 // Deliberately left for later: three-component streams (mi_ljpeg_seg3_t, raw_ljpeg3) stay on the serial kernel.
-//
-// The segments' subsequences -- sub_bytes bytes each, counted segment after segment, at least one per segment -- are the
-// lanes, 256 consecutive ones a workgroup ("group"); a segment may cover many groups and a group many segments.
 //
 //   ljpeg_split_prep      per segment (one workgroup): its subsequence count (from the descriptor, clamped to the span), its
 //                         status word, its tables in canonical form and their lookup over the next 10 bits in scratch --
@@ -15,25 +13,13 @@
 //                         the host forms refuse (ncomp outside 1 and 2, a bad predictor or precision, a width that is no
 //                         multiple of ncomp, predictors 2 to 7 wider than MI_LJPEG_MAX_LINE) sets MI_LJPEG_UNDECODED: the
 //                         segment keeps one lane that walks nothing, and NOTHING of it is written (as raw_ljpeg3 does).
-//                         seg_scan then gives every segment its first lane; a lane finds its segment by bisection.
-//   ljpeg_split_round     round 0: every lane walks its subsequence from its cold state, then the group iterates in LDS -- a
-//                         lane takes a new exit when its predecessor's changed -- until no lane changes, at most 256 times.
-//                         Round r > 0: the group's first lane takes the exit its predecessor group left in round r - 1 (two
-//                         boundary arrays, written in alternation, so no group reads what another writes in the same launch)
-//                         and the group converges again; a group whose entry did not change returns before it stages a byte.
-//                         A round returns at once when the round before it changed no boundary.  After r rounds the first
-//                         r + 1 groups of a segment are exact, so groups - 1 rounds always suffice.
-//                         Two components: a cold lane falls into step with the true BIT position quickly and has the
-//                         COMPONENT right half of the time -- with two similar tables the wrong one decodes just as well --,
-//                         so a lane walks from its entry and from the entry with the other component, keeps both exits (the
-//                         second in `alts`, across rounds too), and a predecessor that flips its component costs a swap, not
-//                         a walk: the repair of a whole group is then 256 cheap iterations at worst, not 256 walks.  This
-//                         changes no result -- a memo of the same function.
-//   ljpeg_split_write     every lane walks once more from its predecessor's stored exit, its first sample given by the
-//                         segmented scan of the sample counts, and writes the differences mod 2^16 of the samples below its
-//                         segment's quota (rows x columns) into the difference plane, seg_h x seg_w uint16 per segment,
-//                         zeroed beforehand.  Status bits come from this pass alone.  A lane whose walk does not reproduce its
-//                         stored exit sets MI_LJPEG_UNSYNCED: the rounds were too few.
+//                         seg_scan then gives every segment its first lane.
+//   ljpeg_split_round     the scaffold's rounds.  Two components: the state's table selection is the COMPONENT, and a lane
+//                         keeps the scaffold's second exit, from the entry with the other component.
+//   ljpeg_split_write     the scaffold's write pass: a lane's first sample is given by the segmented scan of the sample
+//                         counts, and it writes the differences mod 2^16 of the samples below its segment's quota (rows x
+//                         columns) into the difference plane, seg_h x seg_w uint16 per segment, zeroed beforehand.  A lane
+//                         whose walk does not reproduce its stored exit sets MI_LJPEG_UNSYNCED.
 //   ljpeg_split_columns   predictor 1: a scan down each segment's first ncomp columns from 2^(P-1), in place (one wave per
 //   ljpeg_split_rows      segment); then one wave per segment ROW, in chunks of ROW_CHUNK = 512 samples with a carry: a
 //                         per-component inclusive scan mod 2^16 -- after the column pass a row is a plain scan with carry 0 --
@@ -45,57 +31,40 @@
 //                         states.  A segment whose lanes were cut off (descriptors that overlap: more subsequences than the
 //                         span has bytes for) reports MI_LJPEG_UNDECODED.
 //
-// Bytes: as kernels_jpeg_split.hpp -- a group's 256 * sub_bytes bytes and 24 more, from its first lane's first byte on, are
-// staged into LDS with coalesced dword loads, padded by 4 bytes every 128; a byte outside the stage (segments out of file
-// order, gaps, headers between small tiles) is read from the span.  No workgroup ever waits for another.  Bounded by
-// construction: every byte index is checked against the segment, every segment against the span, every lane against the
-// arrays' lengths, every sample index against the quota and every store against the crop (ljpeg_store, the one write path).
-// A corrupt stream costs status bits and nothing else.
+// Segments out of file order, gaps and headers between small tiles put bytes outside a group's stage.  Every sample index is
+// checked against the quota and every store against the crop (ljpeg_store, the one write path).  A corrupt stream costs status
+// bits and nothing else.
 #pragma once
 #include "common.hpp"
-#include "kernels_jpeg_split.hpp"
 #include "kernels_ljpeg.hpp"
+#include "kernels_split_common.hpp"
 #include "ljpeg_sync_core.hpp"
 
 namespace mi {
 
 namespace ljpeg {
-constexpr int SPLIT_GROUP = 256;            // lanes a workgroup
-constexpr uint32_t SPLIT_SUB_DEFAULT = 128, SPLIT_ROUNDS_DEFAULT = 8;
-constexpr uint32_t SPLIT_OVERSHOOT = 24;    // bytes staged behind the group's last subsequence: a symbol reads at most 11
 constexpr int ROW_PER_LANE = 8, ROW_CHUNK = LANES * ROW_PER_LANE, ROWS_PER_BLOCK = 4;
 constexpr int SPLIT_LUT = 2 << SYNC_LUT_BITS;   // lookup entries a segment
 static_assert(SYNC_LUT_BITS == LUT_BITS, "one lookup width");
 
-inline size_t split_lanes(size_t span_bytes, uint32_t sub, size_t nseg) { return (span_bytes + sub - 1) / sub + nseg; }
-
 // the scratch, in words
 struct SplitLayout {
-    size_t nseg, lanes, groups, rounds, samples;
-    size_t incl, exits, alts, counts, gentry, bnd, flags, stat, tmp, huff, lut, plane, words;
+    split::Layout S;
+    size_t nseg, samples;
+    size_t stat, tmp, huff, lut, plane, words;
 };
 inline SplitLayout split_layout(const mi_raw_layout_t& R, size_t span_bytes, uint32_t sub, uint32_t max_rounds) {
     SplitLayout L{};
     L.nseg = (size_t)unpack_nsegs(R);
-    L.lanes = split_lanes(span_bytes, sub, L.nseg);
-    L.groups = (L.lanes + SPLIT_GROUP - 1) / SPLIT_GROUP;
-    L.rounds = L.groups > 1 ? (max_rounds < L.groups - 1 ? max_rounds : L.groups - 1) : 0;
     L.samples = L.nseg * (size_t)R.seg_height * (size_t)R.seg_width;
-    size_t at = 0;
-    auto take = [&](size_t words) { const size_t o = at; at += (words + 63) & ~(size_t)63; return o; };
-    L.incl = take(L.nseg);
-    L.exits = take(2 * L.lanes);
-    L.alts = take(2 * L.lanes);
-    L.counts = take(L.lanes);
-    L.gentry = take(2 * L.groups);
-    L.bnd = take(4 * L.groups);
-    L.flags = take(L.rounds + 2);
+    split::Take take;
+    L.S = split::layout(take, span_bytes, sub, max_rounds, L.nseg, true);
     L.stat = take(L.nseg);
-    L.tmp = take(segscan::tmp_words(L.lanes > L.nseg ? L.lanes : L.nseg));
+    L.tmp = take(segscan::tmp_words(L.S.lanes > L.nseg ? L.S.lanes : L.nseg));
     L.huff = take((2 * L.nseg * sizeof(Huff) + 3) / 4);
     L.lut = take(L.nseg * SPLIT_LUT / 2);
     L.plane = take((L.samples + 1) / 2);
-    L.words = at;
+    L.words = take.at;
     return L;
 }
 
@@ -105,7 +74,7 @@ inline uint32_t split_exact_rounds(const mi_ljpeg_seg_t* segs, size_t nseg, size
     uint64_t at = 0, most = 1;
     for (size_t k = 0; k < nseg; ++k) {
         const uint64_t n = sync_nsub(sync_data_len(segs[k].scan_off, segs[k].scan_bytes, (uint32_t)span_bytes), sub);
-        const uint64_t groups = (at + n - 1) / SPLIT_GROUP - at / SPLIT_GROUP + 1;
+        const uint64_t groups = (at + n - 1) / split::GROUP - at / split::GROUP + 1;
         most = groups > most ? groups : most;
         at += n;
     }
@@ -114,18 +83,12 @@ inline uint32_t split_exact_rounds(const mi_ljpeg_seg_t* segs, size_t nseg, size
 
 struct SplitArgs {
     LjpegArgs L;            // the span, the descriptors, the table, the output, the geometry: raw_ljpeg's
-    uint32_t* incl;         // per segment: lanes of it and of every segment before it (seg_scan of the counts)
-    uint2* exits;           // per lane: its exit state and sample count (sync_pack)
-    uint2* alts;            // per lane: its exit from the entry with the other component
-    uint32_t* counts;       // per lane: its sample count, bit 31 on a segment's first lane; scanned before the write pass
-    uint2* gentry;          // per group: the entry its first lane last walked from
-    uint2* bnd;             // two arrays of one exit per group
-    uint32_t* flags;        // per round: a boundary changed
+    split::Args S;          // the span again and the scaffold's arrays; counts are samples, `alts` the other component's exits
     uint32_t* stat;
     Huff* huff;             // per segment: two tables
     uint16_t* lut;          // per segment: SPLIT_LUT entries
     uint16_t* plane;        // the differences: seg_h * seg_w per segment
-    uint32_t nseg, sub, lanes, groups;
+    uint32_t nseg;
 };
 
 // what a descriptor says, checked: `ok` false where the host forms refuse it
@@ -147,74 +110,51 @@ __device__ inline SplitSeg split_seg(const SplitArgs& A, uint32_t k) {
     return G;
 }
 
-// a lane's place: its segment and the bytes of its subsequence
-struct SplitLane {
-    bool active, first, last;
-    uint32_t k, o0, len, lo, hi, nc;
-};
-__device__ inline SplitLane split_lane(const SplitArgs& A, uint32_t g) {
-    SplitLane P{};
-    const uint32_t n = A.nseg;
-    const uint32_t total = A.incl[n - 1] & segscan::MASK;
-    uint32_t lo = 0, hi = n - 1;        // the first segment whose inclusive count exceeds g (bisection: trip count log2 n)
-    for (int it = 0; it < 32; ++it) {
-        if (lo >= hi) break;
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if ((A.incl[mid] & segscan::MASK) > g) hi = mid;
-        else lo = mid + 1;
-    }
-    P.k = lo;
-    const uint32_t before = lo ? A.incl[lo - 1] & segscan::MASK : 0u;
-    const SplitSeg G = split_seg(A, lo);
-    P.o0 = G.o0; P.len = G.len; P.nc = (uint32_t)G.nc;
-    const uint32_t nsub = sync_nsub(G.len, A.sub);
-    const uint32_t j = g - before;
-    P.active = G.ok && g < total && g < A.lanes && g >= before && j < nsub;
-    P.first = j == 0;
-    P.last = j == nsub - 1;
-    P.lo = P.active ? j * A.sub : 0u;
-    P.hi = min(P.lo + A.sub, P.len);
-    return P;
-}
-
-// the segment's bytes: from the group's stage in LDS where they lie in it, else from the span (i < len: inside the span)
-struct SplitBytes {
-    const uint8_t* stage;
-    const uint8_t* span;
-    uint32_t o0, base, staged;      // the segment's first byte, the stage's first byte (both in the span), bytes staged
-    __device__ uint32_t byte(uint32_t i) const {
-        const uint32_t a = o0 + i, d = a - base;
-        return d < staged ? stage[jpeg::split_stage_index(d)] : span[a];
-    }
+// a lane's place and its segment's components
+struct SplitLane : split::Lane {
+    uint32_t nc;
 };
 
-// the group's bytes into LDS, from its first lane's first byte (4-byte aligned down)
-__device__ inline void split_stage(const SplitArgs& A, const SplitLane& P, uint8_t* stage, uint32_t* shared_base, uint32_t& base, uint32_t& staged) {
-    const int t = (int)threadIdx.x;
-    if (t == 0) *shared_base = min(P.o0 < A.L.span_bytes ? P.o0 + min(P.lo, A.L.span_bytes - P.o0) : A.L.span_bytes, A.L.span_bytes) & ~3u;
-    __syncthreads();
-    base = *shared_base;
-    const uint32_t want = SPLIT_GROUP * A.sub + SPLIT_OVERSHOOT + 4;
-    staged = min(want, A.L.span_bytes - base);
-    for (uint32_t d = 4u * t; d < staged; d += 4u * SPLIT_GROUP) {
-        uint32_t w;
-        if (d + 4 <= staged) {
-            w = *(const uint32_t*)(A.L.span + base + d);
-        } else {
-            w = 0;
-            for (uint32_t k = 0; k < 3; ++k)
-                if (d + k < staged) w |= (uint32_t)A.L.span[base + d + k] << (8 * k);
+// what the scaffold's bodies ask of a decoder (kernels_split_common.hpp)
+struct SplitDecoder {
+    static constexpr bool TWO = true;
+    static constexpr uint32_t ENDED = 1u << 4, ALT_VALID = 1u << 5;
+    using Lane = SplitLane;
+    const SplitArgs& A;
+    struct Walker {
+        const Lane& P;
+        const split::StagedBytes& src;
+        const SyncTabs& T;
+        uint32_t max_symbols;
+        __device__ bool two() const { return P.nc == 2; }
+        __device__ static uint2 other(uint2 e) { return make_uint2(e.x, e.y ^ 8u); }     // the same place, the other component
+        __device__ uint2 cold() const {
+            const SyncState c = sync_cold(src, P.len, P.lo);
+            return make_uint2(c.p, sync_pack(c, 0));
         }
-        *(uint32_t*)(stage + jpeg::split_stage_index(d)) = w;
+        template <class Emit>
+        __device__ uint2 walk(uint2 e, Emit& emit) const {
+            SyncState s = P.first ? sync_start(0) : sync_unpack(e.x, e.y);
+            uint32_t n = 0;
+            sync_lane(src, P.len, P.hi, P.last, max_symbols, T, s, n, emit);
+            return make_uint2(s.end ? 0u : s.p, sync_pack(s, n));
+        }
+    };
+    __device__ Lane lane(uint32_t g) const {
+        Lane P{};
+        SplitSeg G{};
+        static_cast<split::Lane&>(P) = split::place_lane(A.S.incl, A.nseg, g, A.S.lanes, A.S.sub, [&](uint32_t k, uint32_t& o0, uint32_t& len) {
+            G = split_seg(A, k);
+            o0 = G.o0;
+            len = G.len;
+            return G.ok;
+        });
+        P.nc = (uint32_t)G.nc;
+        return P;
     }
-    __syncthreads();
-}
-
-__device__ inline SyncTabs split_tabs(const SplitArgs& A, const SplitLane& P) {
-    return SyncTabs{A.huff + 2 * (size_t)P.k, A.lut + (size_t)P.k * SPLIT_LUT, P.nc};
-}
-__device__ inline bool same2(uint2 a, uint2 b) { return a.x == b.x && a.y == b.y; }
-__device__ inline bool is_end(uint2 e) { return (e.y >> 4) & 1u; }
+    __device__ void prepare() const {}      // (the tables are in scratch: ljpeg_split_prep)
+    __device__ SyncTabs tabs_of(const Lane& P) const { return SyncTabs{A.huff + 2 * (size_t)P.k, A.lut + (size_t)P.k * SPLIT_LUT, P.nc}; }
+};
 }  // namespace ljpeg
 
 // one workgroup per segment
@@ -222,13 +162,13 @@ __global__ __launch_bounds__(256) void ljpeg_split_prep(ljpeg::SplitArgs A, uint
     using namespace ljpeg;
     const uint32_t k = blockIdx.x, t = threadIdx.x;
     if (k == 0)
-        for (uint32_t i = t; i < n_flags; i += 256) A.flags[i] = 0;
+        for (uint32_t i = t; i < n_flags; i += 256) A.S.flags[i] = 0;
     const SplitSeg G = split_seg(A, k);
     const mi_ljpeg_seg_t& S = A.L.segs[k];
     Huff* h = A.huff + 2 * (size_t)k;
     if (t < 2) huff_build(h[t], S.counts[t], S.values[t]);
     if (t == 0) {
-        A.incl[k] = sync_nsub(G.len, A.sub) | (k == 0 ? segscan::HEAD : 0u);
+        A.S.incl[k] = sync_nsub(G.len, A.S.sub) | (k == 0 ? segscan::HEAD : 0u);
         A.stat[k] = G.ok ? 0u : MI_LJPEG_UNDECODED;
     }
     __syncthreads();
@@ -241,126 +181,8 @@ __global__ __launch_bounds__(256) void ljpeg_split_prep(ljpeg::SplitArgs A, uint
 }
 
 __global__ __launch_bounds__(256) void ljpeg_split_round(ljpeg::SplitArgs A, uint32_t round) {
-    using namespace ljpeg;
     extern __shared__ __align__(16) uint8_t stage[];
-    __shared__ uint2 ex[SPLIT_GROUP];
-    __shared__ uint32_t chg[SPLIT_GROUP];
-    __shared__ uint32_t shared_base, go;
-    if (round > 0 && A.flags[round - 1] == 0) return;      // the round before changed no boundary: nothing can change
-    const int t = (int)threadIdx.x;
-    const uint32_t grp = blockIdx.x, g = grp * SPLIT_GROUP + t;
-    const SplitLane P = split_lane(A, g);
-    const uint2 ended = make_uint2(0u, 1u << 4);
-    uint2 e0 = make_uint2(0, 0);        // lane 0: the entry from outside the group
-    uint2 en = ended;                   // the entry this lane last walked from; `ax`: its exit from en with the other component
-    bool need = false;
-    if (round > 0) {
-        if (t == 0) {
-            e0 = grp ? A.bnd[(size_t)((round - 1) & 1) * A.groups + grp - 1] : ended;
-            e0.y &= 0xffffu;
-            en = A.gentry[grp];
-            need = P.active && !P.first && grp > 0 && !same2(e0, en);
-            go = need ? 1u : 0u;
-        }
-        __syncthreads();
-        if (!go) {          // this group's entry is what it was: its exits stand
-            if (t == SPLIT_GROUP - 1) A.bnd[(size_t)(round & 1) * A.groups + grp] = A.bnd[(size_t)((round - 1) & 1) * A.groups + grp];
-            return;
-        }
-    }
-    uint32_t base, staged;
-    split_stage(A, P, stage, &shared_base, base, staged);
-    const SyncTabs T = split_tabs(A, P);
-    const SplitBytes src{stage, A.L.span, P.o0, base, staged};
-    const uint32_t max_symbols = 8 * A.sub;
-    const bool two = P.nc == 2;
-    SyncNoEmit none;
-
-    // a walk from `e`, packed
-    auto walk = [&](uint2 e) {
-        SyncState s = P.first ? sync_start(0) : sync_unpack(e.x, e.y);
-        uint32_t n = 0;
-        sync_lane(src, P.len, P.hi, P.last, max_symbols, T, s, n, none);
-        return make_uint2(s.end ? 0u : s.p, sync_pack(s, n));
-    };
-    const auto other = [](uint2 e) { return make_uint2(e.x, e.y ^ 8u); };     // the same place, the other component
-    uint2 cur, ax;
-    bool axv = false;
-    if (round == 0) {
-        const SyncState c = sync_cold(src, P.len, P.lo);
-        const uint2 cold = make_uint2(c.p, sync_pack(c, 0));
-        cur = P.active ? walk(cold) : ended;
-        ax = cur;
-        en = cold;
-        if (t == 0) {
-            e0 = cold;
-            A.gentry[grp] = cold;
-            if (grp == 0) A.flags[0] = 1;
-            if (P.active && !P.first && two) {
-                ax = walk(other(cold));
-                axv = true;
-            }
-        }
-        need = P.active && !P.first && t > 0;
-        ex[t] = cur;
-    } else {
-        cur = g < A.lanes ? A.exits[g] : ended;
-        ax = g < A.lanes ? A.alts[g] : ended;
-        axv = (ax.y & 32u) != 0;        // (bit 5: the second exit is there)
-        ax.y &= ~32u;
-        ex[t] = cur;
-        if (t == 0 && need) A.gentry[grp] = e0;
-    }
-    chg[t] = 0;
-    __syncthreads();
-    if (round > 0 && t > 0) {
-        en = ex[t - 1];
-        en.y &= 0xffffu;
-    }
-    for (int it = 0; it < SPLIT_GROUP; ++it) {      // (a change moves on by one lane or more an iteration)
-        bool c = false;
-        uint2 nw = cur;
-        if (need) {
-            uint2 e = e0;
-            if (t > 0) {
-                e = ex[t - 1];
-                e.y &= 0xffffu;
-            }
-            if (same2(e, en)) {
-                nw = cur;
-            } else if (two && axv && !is_end(e) && !is_end(en) && same2(e, other(en))) {
-                nw = ax;
-                ax = cur;
-            } else {
-                nw = walk(e);
-                axv = two && !is_end(e);
-                ax = axv ? walk(other(e)) : nw;
-            }
-            en = e;
-            c = !same2(nw, cur);
-        }
-        __syncthreads();
-        if (c) {
-            ex[t] = nw;
-            cur = nw;
-        }
-        chg[t] = c ? 1u : 0u;
-        __syncthreads();
-        need = P.active && !P.first && t > 0 && chg[t - 1] != 0;
-        if (!__syncthreads_or(need ? 1 : 0)) break;
-    }
-    if (g < A.lanes) {
-        A.exits[g] = cur;
-        A.alts[g] = axv ? make_uint2(ax.x, ax.y | 32u) : cur;
-        A.counts[g] = (P.active ? cur.y >> 16 : 0u) | (P.first || !P.active ? segscan::HEAD : 0u);
-    }
-    if (t == SPLIT_GROUP - 1) {
-        if (round > 0) {
-            const uint2 was = A.bnd[(size_t)((round - 1) & 1) * A.groups + grp];
-            if (!same2(was, cur)) atomicOr(A.flags + round, 1u);
-        }
-        A.bnd[(size_t)(round & 1) * A.groups + grp] = cur;
-    }
+    split::round_body(ljpeg::SplitDecoder{A}, A.S, round, stage);
 }
 
 // what the write pass does with a symbol
@@ -379,32 +201,12 @@ struct LjpegSplitWriter {
 };
 
 __global__ __launch_bounds__(256) void ljpeg_split_write(ljpeg::SplitArgs A) {
-    using namespace ljpeg;
     extern __shared__ __align__(16) uint8_t stage[];
-    __shared__ uint32_t shared_base;
-    const int t = (int)threadIdx.x;
-    const uint32_t g = blockIdx.x * SPLIT_GROUP + t;
-    const SplitLane P = split_lane(A, g);
-    uint32_t base, staged;
-    split_stage(A, P, stage, &shared_base, base, staged);
-    if (!P.active) return;
-    const SyncTabs T = split_tabs(A, P);
-    const SplitBytes src{stage, A.L.span, P.o0, base, staged};
-    const uint2 stored = A.exits[g];
-    SyncState s = sync_start(0);
-    if (!P.first) {
-        const uint2 e = A.exits[g - 1];
-        s = sync_unpack(e.x, e.y);
-    }
-    const SplitSeg G = split_seg(A, P.k);
-    const uint32_t quota = (uint32_t)G.rows * (uint32_t)A.L.seg_w;      // (rows <= seg_h: inside the segment's part of the plane)
-    LjpegSplitWriter wr{A.plane + (size_t)P.k * A.L.seg_h * A.L.seg_w, ((A.counts[g] & segscan::MASK) - (stored.y >> 16)) & segscan::MASK,
-                        quota, 0u};
-    uint32_t n = 0;
-    sync_lane(src, P.len, P.hi, P.last, 8 * A.sub, T, s, n, wr);
-    const uint2 now = make_uint2(s.end ? 0u : s.p, sync_pack(s, n));
-    if (!same2(now, stored)) wr.status |= ST_UNSYNCED;
-    if (wr.status) atomicOr(A.stat + P.k, wr.status);
+    split::write_body(ljpeg::SplitDecoder{A}, A.S, stage, A.stat, [&](const ljpeg::SplitDecoder::Walker& W, uint32_t first_sample) {
+        // (rows <= seg_h: inside the segment's part of the plane)
+        const uint32_t quota = (uint32_t)ljpeg::split_seg(A, W.P.k).rows * (uint32_t)A.L.seg_w;
+        return LjpegSplitWriter{A.plane + (size_t)W.P.k * A.L.seg_h * A.L.seg_w, first_sample, quota, 0u};
+    });
 }
 
 // predictor 1, first pass: one wave per segment scans down the first ncomp columns from the seed, in place
@@ -570,7 +372,7 @@ __global__ __launch_bounds__(256) void ljpeg_split_status(ljpeg::SplitArgs A) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= A.nseg) return;
     uint32_t st = A.stat[k];
-    if ((A.incl[k] & segscan::MASK) > A.lanes) st |= MI_LJPEG_UNDECODED;      // (descriptors that overlap: lanes were cut off)
+    if ((A.S.incl[k] & segscan::MASK) > A.S.lanes) st |= MI_LJPEG_UNDECODED;      // (descriptors that overlap: lanes were cut off)
     if (st & ljpeg::ST_UNSYNCED) st = ljpeg::ST_UNSYNCED;
     if (A.L.status) A.L.status[k] = st;
     if (A.L.status_or && st) atomicOr(A.L.status_or, st);
@@ -590,21 +392,20 @@ inline void ljpeg_split_launch(hipStream_t st, const void* span, size_t span_byt
     A.L.h = R.height; A.L.w = R.width; A.L.crop_y = R.crop_y; A.L.crop_x = R.crop_x; A.L.image_h = R.image_height;
     A.L.seg_h = R.seg_height; A.L.seg_w = R.seg_width; A.L.nsx = unpack_nsx(R); A.L.tiled = R.tiled;
     A.L.shift = R.shift; A.L.table_len = R.table_len;
-    A.incl = words + L.incl; A.exits = (uint2*)(words + L.exits); A.alts = (uint2*)(words + L.alts); A.counts = words + L.counts;
-    A.gentry = (uint2*)(words + L.gentry); A.bnd = (uint2*)(words + L.bnd); A.flags = words + L.flags; A.stat = words + L.stat;
-    A.huff = (Huff*)(words + L.huff); A.lut = (uint16_t*)(words + L.lut);
+    A.S = split::bind(L.S, words, span, span_bytes, sub);
+    A.stat = words + L.stat; A.huff = (Huff*)(words + L.huff); A.lut = (uint16_t*)(words + L.lut);
     A.plane = plane_out ? plane_out : (uint16_t*)(words + L.plane);
-    A.nseg = (uint32_t)L.nseg; A.sub = sub; A.lanes = (uint32_t)L.lanes; A.groups = (uint32_t)L.groups;
+    A.nseg = (uint32_t)L.nseg;
     uint32_t* tmp = words + L.tmp;
-    const unsigned ns = (unsigned)L.nseg, nflags = (unsigned)L.rounds + 2;
-    const size_t lds = jpeg::split_stage_bytes(sub);
+    const unsigned ns = (unsigned)L.nseg, nflags = (unsigned)L.S.rounds + 2;
+    const size_t lds = split::stage_bytes(sub);
     (void)hipMemsetAsync(A.plane, 0, L.samples * sizeof(uint16_t), st);
     hipLaunchKernelGGL(ljpeg_split_prep, dim3(ns), dim3(256), 0, st, A, nflags);
-    segscan::launch(st, A.incl, ns, tmp);
-    for (uint32_t r = 0; r <= (uint32_t)L.rounds; ++r)
-        hipLaunchKernelGGL(ljpeg_split_round, dim3((unsigned)L.groups), dim3(SPLIT_GROUP), lds, st, A, r);
-    segscan::launch(st, A.counts, L.lanes, tmp);
-    hipLaunchKernelGGL(ljpeg_split_write, dim3((unsigned)L.groups), dim3(SPLIT_GROUP), lds, st, A);
+    segscan::launch(st, A.S.incl, ns, tmp);
+    for (uint32_t r = 0; r <= (uint32_t)L.S.rounds; ++r)
+        hipLaunchKernelGGL(ljpeg_split_round, dim3((unsigned)L.S.groups), dim3(split::GROUP), lds, st, A, r);
+    segscan::launch(st, A.S.counts, L.S.lanes, tmp);
+    hipLaunchKernelGGL(ljpeg_split_write, dim3((unsigned)L.S.groups), dim3(split::GROUP), lds, st, A);
     if (!plane_out) {
         const size_t rows = L.nseg * (size_t)R.seg_height;
         const dim3 rgrid((unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK));

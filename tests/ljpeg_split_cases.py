@@ -12,7 +12,7 @@ import numpy as np
 import ljpeg_cases as LC
 import ljpeg_split_restatement as S
 
-GROUP, ROW_CHUNK = 256, 512         # ljpeg:: SPLIT_GROUP and ROW_CHUNK of csrc/kernels_ljpeg_split.hpp
+GROUP, ROW_CHUNK = 256, 512         # split::GROUP of csrc/kernels_split_common.hpp, ljpeg::ROW_CHUNK of csrc/kernels_ljpeg_split.hpp
 SUBS = (8, 128)
 
 # one-code tables of different lengths: component 0 "0", component 1 "00", both category 0
